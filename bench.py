@@ -24,12 +24,8 @@ _ROOT = os.path.dirname(os.path.abspath(__file__))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-# HIP backs its streams with a few hardware queues (GPU_MAX_HW_QUEUES, default 4 per priority); streams that share one run their
-# kernels in order.  This process keeps several in flight -- scan stream, stage stream, the process group's collective stream,
-# torch's own -- and with 4 queues the collective of the N > 1 step lands behind the scans for some stream-creation orders: the
-# one-rank RCCL step measured 0.84-0.88 of the plain step with 4 and 8 queues, 0.98 with 16 and 32 (profiles/
-# r4_e_hw_queues.txt).  Must be set before the HIP runtime initialises (torch is imported in main()).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The number of hardware queues HIP backs its streams with is left to the environment: the script does not raise it (the
+# record names the value it ran with, config.hip_hw_queues).
 
 import numpy as np  # noqa: E402
 
@@ -120,6 +116,35 @@ def compact_line(full: dict, side_path) -> dict:
     out["device"] = full.get("device")
     out["details"] = side_path
     return out
+
+
+DUMP_BYTES_CAP = 60 * 2 ** 20   # --dump-outputs: the arrays' bytes in all (the .npy headers stay well under the 64 MB bound)
+DUMP_SEED = 20240601            # the fixed seed of the pair sample when the whole output is larger than the cap
+
+
+def dump_outputs(out_dir: str, arrays: dict, note) -> None:
+    """--dump-outputs: writes what the last timed step delivered as out_dir/<name>.npy.  `arrays` maps a name to a host array
+    whose rows are stereo pairs; integer tables go out as float32 (every entry is an index or count below 2^24: exact), the
+    float64 disparities as they are.  When all rows are over DUMP_BYTES_CAP, the same seeded sample of pairs is taken from
+    every array (pair_index.npy names them), so that two builds given the same arguments write comparable files."""
+    conv = {k: (v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    n_rows = min(v.shape[0] for v in conv.values())
+    per_row = sum(v[:1].nbytes * (v.shape[0] // n_rows) for v in conv.values()) + 8      # + the float64 pair index
+    keep = max(1, min(n_rows, DUMP_BYTES_CAP // per_row))
+    if keep < n_rows:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n_rows, size=keep, replace=False))
+    else:
+        idx = np.arange(n_rows)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pair_index.npy"), idx.astype(np.float64))
+    total = idx.size * 8
+    for k, v in conv.items():
+        # (N > 1: the gathered table holds every rank's pairs; the sample takes the same pairs of each rank's shard)
+        sel = np.concatenate([idx + r * n_rows for r in range(v.shape[0] // n_rows)])
+        a = np.ascontiguousarray(v[sel])
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        total += a.nbytes
+    note(f"outputs of the last timed step: {len(conv) + 1} arrays, {idx.size} of {n_rows} pairs, {total / 2 ** 20:.1f} MiB -> {out_dir}")
 
 
 def oracle_tables(stream, n_orb, n_lbd, nnr_p, nnr_l, threads=None):
@@ -427,6 +452,9 @@ def main():
     ap.add_argument("--full-json", default=None, metavar="PATH",
                     help="where the FULL record goes (secondary records, distributions, notes); default gpurun_out/bench_full.json. "
                          "stdout carries one compact line of the contract's keys")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (match tables and counts, stereo-gate tables, "
+                         "disparities and counts; a fixed sample of pairs above 60 MiB) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--launch-check", action="store_true",
                     help="(tests) after the self-launch: a gloo rendezvous of the ranks and ONE JSON line from rank 0 -- no GPU work")
     args = ap.parse_args()
@@ -614,6 +642,24 @@ def main():
         scan_ms, fin_ms, runs = scan_ms + a_, fin_ms + b_, runs + n_
         p_.set_profiling(False)
     note(f"timed {args.steps} steps in {elapsed:.4f}s; scan {scan_ms / max(runs, 1):.3f} ms/launch")
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the buffers step k_last wrote, as run_steps() picks them: the gather's buffer k % nbuf (the table as gathered on the
+        # root), a batch of the rotation (its one buffer), the matcher's buffer k % n_buffers, or the one buffer of run()
+        k_last = args.warmup + args.steps - 1
+        if pg is not None:
+            m_, b_ = bm, k_last % pg.pipe.nbuf
+        elif overlap and nbatch > 1:
+            m_, b_ = ([bm] + extra_bms)[k_last % nbatch], 0
+        elif overlap:
+            m_, b_ = bm, k_last % len(bm.plans)
+        else:
+            m_, b_ = bm, 0
+        dumped = {"match_table": (pg.gathered(b_) if pg is not None else m_.tables[b_]).cpu().numpy(),
+                  "match_counts": m_.count_bufs[b_].cpu().numpy()}
+        if gates is not None:
+            dumped.update(stereo_table=m_.stereo_tabs[b_].cpu().numpy(), stereo_disp=m_.stereo_disps[b_].cpu().numpy(),
+                          stereo_counts=m_.stereo_cnts[b_].cpu().numpy())
+        dump_outputs(args.dump_outputs, dumped, note)
     # the same K steps over ONE repeated batch (round 2's stepping): how much of the number is cache residency
     repeated = None
     if nbatch > 1:

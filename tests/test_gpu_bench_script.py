@@ -158,3 +158,37 @@ def test_bench_strong_scaling_flag_at_one_rank(tmp_path):
     line, d = _run(["--no-cpu-baseline", "--no-secondary", "--scaling", "strong"], tmp_path, pairs=32)
     assert line["scaling"] == "strong" and line["config"]["pairs_per_step_all_gpus"] == 32
     assert d["scaling"] == "strong" and d["config"]["pairs_per_gpu_per_step"] == 32 and d["config"]["pairs_per_step_all_gpus"] == 32
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step delivered, as float32 / float64 .npy files, the same from run to run.
+    With one warm-up step and four timed ones over the rotation of three batches the last step is step 4, batch 1 -- not the
+    batch of buffer 0 -- and its dumped table must be that batch's oracle table."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from plslam_amd import synth
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs-per-gpu", "24",
+               "--n-orb", "192", "--n-lbd", "40", "--no-cpu-baseline", "--no-secondary", "--full-json", str(tmp_path / "full.json"),
+               "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert res.returncode == 0, res.stderr[-3000:]
+        line, _ = _check_line(res.stdout, tmp_path)
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert files == sorted(f"{k}.npy" for k in ("pair_index", "match_table", "match_counts", "stereo_table", "stereo_disp",
+                                                    "stereo_counts"))
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 2 ** 20
+        dumps.append({f[:-4]: np.load(out / f) for f in files})
+    for k, v in dumps[0].items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.array_equal(v, dumps[1][k], equal_nan=True), k
+    d = dumps[0]
+    assert np.array_equal(d["pair_index"], np.arange(24)) and d["match_table"].shape == (24, 2 * 192 + 2 * 40)
+    st1 = synth.stereo_stream(24, 192, 40, seed=synth.SEED0 + 7919, first_pair=0)
+    ref, _ = bench.oracle_tables(st1, 192, 40, 0.75, 0.75)
+    assert np.array_equal(d["match_table"], ref.astype(np.float32))
+    assert d["match_counts"].shape == (24, 4) and d["stereo_table"].shape == (24, 192 + 40)

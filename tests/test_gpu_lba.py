@@ -418,6 +418,9 @@ def test_lba_plan_device_resident_iteration_and_gba_blocks(ctx):
     torch.cuda.synchronize()
     dX = torch.from_numpy(X2).to(torch.device("cuda", 0))
     assert plslam_amd.capi._hip_memcpy_dtod(st["Xw"], dX.data_ptr(), X2.nbytes) == 0
+    # a device-to-device hipMemcpy may return before the copy is done, and the plan's stream does not wait for the null
+    # stream (it is created non-blocking): wait for the update before the plan reads it
+    torch.cuda.synchronize()
     e_res = big.iterate_resident()
     b_res = big.blocks()
     e_up, _ = big.iterate_dev(lm["T_kf_w"], X2, lm["Lw"], want_g=False)

@@ -40,7 +40,7 @@ extern "C" {
 
 /* 2: plslam_match_problem grew (keep_prior, reserved: 56 bytes), plslam_lba_plan_iterate's flags became a bit mask, options
  * "mfma_form" 3/4 and "exact_second"; 3 (round 4): "mfma_form" 5 (the default), "post_fuse", plslam_match_plan_key_state;
- * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available.
+ * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available; additive within 5: the plslam_bow_* bag-of-words entry points.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -850,6 +850,85 @@ typedef struct plslam_gather_step {
 } plslam_gather_step;
 int plslam_match_plan_step_gather(plslam_match_plan* plan, const plslam_gather_step* step);
 int plslam_match_plan_gather_sync(plslam_match_plan* plan);
+
+/* ---- Bag of words: DBoW2 vocabulary transform and the keyframe confusion matrix (bow.hip) ----------------------------------
+ * Replaces the bag-of-words step of MapHandler::addKeyFrame (src/mapHandler.cpp:196-201 -> insertKFBowVector{P,L,PL},
+ * :3007-3128): TemplatedVocabulary<FORB>::transform (3rdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1046-1100,
+ * :1198-1240) and L1Scoring::score (src/DBoW2/ScoringObject.cpp:23-67) against every earlier keyframe.
+ * Results are bit-identical to the reference's double arithmetic (fixed fold orders, DESIGN.md section "Bag of words"). */
+
+/* DBoW2's enums (3rdparty/DBoW2/include/DBoW2/BowVector.h:29-55) */
+enum { PLSLAM_BOW_TF_IDF = 0, PLSLAM_BOW_TF = 1, PLSLAM_BOW_IDF = 2, PLSLAM_BOW_BINARY = 3 };
+enum { PLSLAM_BOW_L1_NORM = 0 };   /* the only scoring supported; the others get PLSLAM_ENOTSUP */
+/* largest descriptor set of one transform / one modality of one keyframe (PLSLAM_ERANGE beyond it) */
+#define PLSLAM_BOW_MAX_SET 16384
+
+/* the records of TemplatedVocabulary::load (TemplatedVocabulary.h:1437-1485), in FILE order */
+typedef struct plslam_bow_node {
+    int32_t node_id, parent_id;     /* 1..n_nodes, 0..n_nodes (0 = the root, which has no record) */
+    double weight;
+    uint8_t descriptor[32];         /* FORB::fromString's 32 bytes */
+} plslam_bow_node;
+typedef struct plslam_bow_word {
+    int32_t word_id, node_id;       /* 0..n_words-1, 1..n_nodes */
+} plslam_bow_word;
+typedef struct plslam_bow_vocab_desc {
+    int32_t k, L, scoring_type, weighting_type;
+    int32_t n_nodes, n_words;
+    const plslam_bow_node* nodes;
+    const plslam_bow_word* words;
+} plslam_bow_vocab_desc;
+typedef struct plslam_bow_vocab plslam_bow_vocab;
+
+/* Copies the vocabulary to the device.  Children keep the order in which their records appear (load()'s push_back): the
+ * descent keeps the FIRST child of that list on a distance tie.  PLSLAM_EINVAL (with plslam_last_error()) for ids out of
+ * range, a duplicate node or word id, a parent that is not a node, a cycle, a leaf without a word, an empty vocabulary;
+ * PLSLAM_ENOTSUP for a scoring other than PLSLAM_BOW_L1_NORM.  The vocabulary belongs to ctx and must be destroyed first. */
+int plslam_bow_vocab_create(plslam_ctx* ctx, const plslam_bow_vocab_desc* desc, plslam_bow_vocab** out);
+void plslam_bow_vocab_destroy(plslam_bow_vocab* voc);
+
+/* TemplatedVocabulary::transform of `nsets` descriptor sets (set s = rows offsets[s] .. offsets[s+1]-1 of desc, every set at
+ * most PLSLAM_BOW_MAX_SET rows, else PLSLAM_ERANGE).  Per descriptor: word_id / word_weight of the leaf it descends to (stopped
+ * words included).  Per set: the BowVector after normalize(L1) as ascending word ids and weights at bow_word / bow_weight
+ * + offsets[s], bow_len[s] entries.  Any output pointer but bow_len may be NULL. */
+int plslam_bow_transform(plslam_bow_vocab* voc, const uint8_t* desc, const int32_t* offsets, int32_t nsets,
+                         int32_t* word_id, double* word_weight, int32_t* bow_word, double* bow_weight, int32_t* bow_len);
+/* Device pointers, enqueued on `stream` (NULL = the context's stream), no synchronisation.  total = offsets[nsets] and
+ * max_set (>= every set's size, <= PLSLAM_BOW_MAX_SET) come from the caller; a set longer than max_set gets bow_len = -1.
+ * word_weight may be NULL; the other outputs are required (total / total / total / nsets entries).  desc 16-byte aligned. */
+int plslam_bow_transform_dev(plslam_bow_vocab* voc, const uint8_t* desc, const int32_t* offsets, int32_t nsets, int32_t total,
+                             int32_t max_set, int32_t* word_id, double* word_weight, int32_t* bow_word, double* bow_weight,
+                             int32_t* bow_len, void* stream);
+
+/* the per-keyframe inputs of insertKFBowVectorPL's combination (src/mapHandler.cpp:3063-3098): vector_stdv lives in stvo-pl,
+ * so the caller computes std_pt / std_ls */
+typedef struct plslam_bow_pl_stats {
+    int32_t n_pt, n_ls;
+    double std_pt, std_ls;
+} plslam_bow_pl_stats;
+typedef struct plslam_bow_db plslam_bow_db;
+
+/* The keyframe BowVectors on the device.  vocab_p / vocab_l: either may be NULL, which selects insertKFBowVectorL / P; both
+ * set = insertKFBowVectorPL (src/mapHandler.cpp:196-201).  capacity_hint: keyframes to reserve for (grows by itself). */
+int plslam_bow_db_create(plslam_ctx* ctx, plslam_bow_vocab* vocab_p, plslam_bow_vocab* vocab_l, int32_t capacity_hint,
+                         plslam_bow_db** out);
+void plslam_bow_db_destroy(plslam_bow_db* db);
+/* insertKFBowVector{P,L,PL}(kf) for kf_idx: transforms the keyframe's left descriptors, stores the vectors, and writes
+ * conf_row[i] = score(new, i) for every i < kf_idx with alive[i] != 0 (= map_keyframes[i] != NULL; each such i must have been
+ * inserted), and conf_row[kf_idx] = score(new, new).  Other entries are left untouched.  The inputs of an absent modality are
+ * ignored; stats is read in PL mode only.  One launch sequence (3 kernels) and one synchronisation. */
+int plslam_bow_db_insert(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t n_pdesc, const uint8_t* ldesc,
+                         int32_t n_ldesc, const plslam_bow_pl_stats* stats, const uint8_t* alive, double* conf_row);
+/* Device pointers for pdesc / ldesc / alive / conf_row (kf_idx + 1 entries each); stats is a host struct.  Enqueued on the
+ * context's stream, no synchronisation; an alive entry that was never inserted is left untouched. */
+int plslam_bow_db_insert_dev(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t n_pdesc, const uint8_t* ldesc,
+                             int32_t n_ldesc, const plslam_bow_pl_stats* stats, const uint8_t* alive, double* conf_row);
+/* *n = 1 + the largest keyframe index inserted (0 when empty) */
+int plslam_bow_db_size(plslam_bow_db* db, int32_t* n);
+/* Throughput form: out[q * n + i] (n = plslam_bow_db_size) = the value plslam_bow_db_insert would have written at i with
+ * queries[q] as the new keyframe (its stored PL stats), for every stored keyframe i; NaN where i was never inserted.
+ * Every query must have been inserted. */
+int plslam_bow_db_score(plslam_bow_db* db, const int32_t* queries, int32_t nq, double* out);
 
 #ifdef __cplusplus
 }

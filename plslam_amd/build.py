@@ -22,7 +22,7 @@ OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 # the product: what AUTO can pick (K1i and its merge kernel, K1f for column-split plans, the popcount kernels) and every
 # other row of SURVEY section 8
 SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_mfma_i.hip", "lba.hip", "lba_assemble.hip",
-           "map2kf.hip", "lbd.hip", "median_desc.hip", "match_grid.hip", "stereo_gates.hip", "pose_gn.hip", "lbd_float.hip",
+           "map2kf.hip", "lbd.hip", "median_desc.hip", "match_grid.hip", "stereo_gates.hip", "pose_gn.hip", "lbd_float.hip", "bow.hip",
            "capi.hip"]
 # earlier generations of the matrix-core scan, reachable only through the context option "mfma_form" (1 = K1e, 3 = K1g,
 # 4 = K1h -- whose scan kernel sits behind the same macro in hamming_mfma_h.hip): cross-checks for the tests and A/B baselines

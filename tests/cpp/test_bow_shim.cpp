@@ -1,0 +1,96 @@
+// Exercises plslam_amd/host/dbow_voc.hpp the way MapHandler uses DBoW2 (src/mapHandler.cpp:38-41 vocabulary load,
+// :196-201 -> insertKFBowVector{P,L,PL}, :3007-3128): replays a keyframe run from a fixture written by
+// tests/test_gpu_bow_shim.py and compares the whole conf_matrix bit for bit with the restatement's (tests/dbow_ref.py).
+// Built and run on a GPU box.  Usage: test_bow_shim <fixture>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "../../plslam_amd/host/dbow_voc.hpp"
+
+namespace {
+struct Reader {
+    std::vector<char> b;
+    size_t o = 0;
+    template <class T> T get() { T v; std::memcpy(&v, &b[o], sizeof(T)); o += sizeof(T); return v; }
+    template <class T> std::vector<T> arr(size_t n) { std::vector<T> v(n); if (n) std::memcpy(v.data(), &b[o], n * sizeof(T)); o += n * sizeof(T); return v; }
+};
+struct Rows {                                   // a cv::Mat descriptor block stand-in (rows, ptr<uchar>())
+    const uint8_t* data;
+    int rows;
+    template <class T> const T* ptr() const { return reinterpret_cast<const T*>(data); }
+};
+}  // namespace
+
+int main(int argc, char** argv)
+{
+    if (argc < 2) return 2;
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    Reader r;
+    std::fseek(f, 0, SEEK_END);
+    r.b.resize((size_t)std::ftell(f));
+    std::fseek(f, 0, SEEK_SET);
+    if (std::fread(r.b.data(), 1, r.b.size(), f) != r.b.size()) return 2;
+    std::fclose(f);
+    const int mode = r.get<int32_t>(), nkf = r.get<int32_t>();
+    plslam_ctx* ctx = nullptr;
+    PlslamBow::check(plslam_ctx_create(0, &ctx), "plslam_ctx_create");
+    std::vector<plslam_bow_node> nodes[2];
+    std::vector<plslam_bow_word> words[2];
+    plslam_bow_vocab_desc desc[2];
+    for (int m = 0; m < 2; ++m) {
+        desc[m].k = r.get<int32_t>();
+        desc[m].L = r.get<int32_t>();
+        desc[m].scoring_type = PLSLAM_BOW_L1_NORM;
+        desc[m].weighting_type = r.get<int32_t>();
+        desc[m].n_nodes = r.get<int32_t>();
+        desc[m].n_words = r.get<int32_t>();
+        nodes[m] = r.arr<plslam_bow_node>((size_t)desc[m].n_nodes);
+        words[m] = r.arr<plslam_bow_word>((size_t)desc[m].n_words);
+        desc[m].nodes = nodes[m].data();
+        desc[m].words = words[m].data();
+    }
+    int fails = 0;
+    {
+        PlslamBow::Vocabulary vp(ctx, desc[0]), vl(ctx, desc[1]);
+        PlslamBow::KFBowDatabase db(ctx, (mode & 1) ? &vp : nullptr, (mode & 2) ? &vl : nullptr, 8);
+        std::vector<std::vector<double>> conf((size_t)nkf, std::vector<double>((size_t)nkf, std::nan("")));
+        std::vector<const int*> map_keyframes((size_t)nkf, nullptr);
+        static const int live = 1;
+        for (int k = 0; k < nkf; ++k) {
+            const int n_p = r.get<int32_t>(), n_l = r.get<int32_t>(), n_pt = r.get<int32_t>(), n_ls = r.get<int32_t>();
+            const double std_pt = r.get<double>(), std_ls = r.get<double>();
+            const std::vector<uint8_t> pd = r.arr<uint8_t>((size_t)n_p * 32), ld = r.arr<uint8_t>((size_t)n_l * 32);
+            const std::vector<uint8_t> alive = r.arr<uint8_t>((size_t)nkf);
+            for (int i = 0; i < nkf; ++i) map_keyframes[i] = alive[i] ? &live : nullptr;
+            const Rows P{pd.data(), n_p}, L{ld.data(), n_l};
+            if (mode == 3) db.insertKFBowVectorPL(k, P, L, n_pt, n_ls, std_pt, std_ls, map_keyframes, conf);
+            else if (mode == 1) db.insertKFBowVectorP(k, P, map_keyframes, conf);
+            else db.insertKFBowVectorL(k, L, map_keyframes, conf);
+            if (k == 0 && mode == 1 && n_p > 0) {
+                // Vocabulary::transform over a vector of 1-row descriptors + the one-pair score reproduce the self score
+                std::vector<Rows> feats;
+                for (int i = 0; i < n_p; ++i) feats.push_back(Rows{pd.data() + 32 * (size_t)i, 1});
+                std::map<unsigned int, double> v;
+                vp.transform(feats, v);
+                const double s = PlslamBow::Vocabulary::score(v, v);
+                if (std::memcmp(&s, &conf[0][0], 8) != 0) { std::printf("FAIL self score %.17g vs %.17g\n", s, conf[0][0]); ++fails; }
+            }
+        }
+        const std::vector<double> want = r.arr<double>((size_t)nkf * nkf);
+        for (int i = 0; i < nkf; ++i)
+            for (int j = 0; j < nkf; ++j) {
+                const double a = conf[i][j], b = want[(size_t)i * nkf + j];
+                const bool same = (std::isnan(a) && std::isnan(b)) || std::memcmp(&a, &b, 8) == 0;
+                if (!same && fails++ < 10) std::printf("FAIL conf[%d][%d] = %.17g, want %.17g\n", i, j, a, b);
+            }
+        std::printf("mode %d, %d keyframes: %d mismatches\n", mode, nkf, fails);
+    }
+    plslam_ctx_destroy(ctx);
+    if (fails) return 1;
+    std::printf("all checks passed\n");
+    return 0;
+}

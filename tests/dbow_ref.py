@@ -1,0 +1,166 @@
+"""Plain-Python restatement of the DBoW2 code PL-SLAM runs on every keyframe (test infrastructure, never imported by the
+product).  Python floats are IEEE doubles and every fold below runs in the reference's order, so the results are
+bit-identical to it.  References are to the pl-slam tree (3rdparty/DBoW2, src/mapHandler.cpp)."""
+from __future__ import annotations
+
+import math
+
+TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
+
+
+def forb_distance(a: bytes, b: bytes) -> int:
+    """FORB::distance, src/DBoW2/FORB.cpp:78-101: popcount of a XOR b over the 32 bytes."""
+    return (int.from_bytes(a, "little") ^ int.from_bytes(b, "little")).bit_count()
+
+
+class Vocab:
+    """TemplatedVocabulary::load, TemplatedVocabulary.h:1437-1485: node records in file order, each appended to its
+    parent's children list (m_nodes[pid].children.push_back(nid), :1470); words point at nodes (:1476-1484)."""
+
+    def __init__(self, voc):
+        self.weighting = int(voc.weighting_type)
+        n = voc.nodes.shape[0]
+        self.children = [[] for _ in range(n + 1)]
+        self.desc = [b""] * (n + 1)
+        self.weight = [0.0] * (n + 1)
+        self.word_id = [None] * (n + 1)
+        raw = voc.nodes["descriptor"].tobytes()
+        for r, (nid, pid, w) in enumerate(zip(voc.nodes["node_id"].tolist(), voc.nodes["parent_id"].tolist(),
+                                              voc.nodes["weight"].tolist())):
+            self.weight[nid] = w
+            self.children[pid].append(nid)
+            self.desc[nid] = raw[32 * r:32 * r + 32]
+        for wid, nid in zip(voc.words["word_id"].tolist(), voc.words["node_id"].tolist()):
+            self.word_id[nid] = wid
+        self.n_words = voc.words.shape[0]
+
+    def transform_one(self, feature: bytes):
+        """transform(feature, word_id, weight), TemplatedVocabulary.h:1198-1240: from the root, the child with the smallest
+        distance, strict '<' over the children list (the first one wins a tie), until a leaf."""
+        final_id = 0
+        while True:
+            nodes = self.children[final_id]
+            final_id = nodes[0]
+            best_d = forb_distance(feature, self.desc[final_id])
+            for nid in nodes[1:]:
+                d = forb_distance(feature, self.desc[nid])
+                if d < best_d:
+                    best_d = d
+                    final_id = nid
+            if not self.children[final_id]:
+                break
+        return self.word_id[final_id], self.weight[final_id]
+
+    def transform(self, features):
+        """transform(features, BowVector&), TemplatedVocabulary.h:1046-1100 with L1Scoring (mustNormalize -> L1): returns
+        the BowVector as a dict, its keys unordered (read it through sorted_items) and the per-feature (word, weight)."""
+        v = {}
+        per = []
+        if self.n_words == 0:
+            return v, per
+        for f in features:
+            wid, w = self.transform_one(bytes(f))
+            per.append((wid, w))
+            if w > 0:                                   # :1074 / :1093 -- not stopped
+                if self.weighting in (TF, TF_IDF):
+                    add_weight(v, wid, w)
+                else:
+                    add_if_not_exist(v, wid, w)
+        normalize_l1(v)
+        return v, per
+
+
+def add_weight(v: dict, wid: int, w: float) -> None:
+    """BowVector::addWeight, src/DBoW2/BowVector.cpp:33-45"""
+    if wid in v:
+        v[wid] += w
+    else:
+        v[wid] = w
+
+
+def add_if_not_exist(v: dict, wid: int, w: float) -> None:
+    """BowVector::addIfNotExist, BowVector.cpp:49-57"""
+    if wid not in v:
+        v[wid] = w
+
+
+def sorted_items(v: dict):
+    """std::map<WordId, WordValue> iteration order: ascending word id"""
+    return sorted(v.items())
+
+
+def normalize_l1(v: dict) -> None:
+    """BowVector::normalize(L1), BowVector.cpp:62-84: the norm summed over fabs in map (ascending id) order; divide only when
+    norm > 0"""
+    norm = 0.0
+    for _, w in sorted_items(v):
+        norm += math.fabs(w)
+    if norm > 0.0:
+        for wid in list(v):
+            v[wid] = v[wid] / norm
+
+
+def l1_score(v1: dict, v2: dict) -> float:
+    """L1Scoring::score, src/DBoW2/ScoringObject.cpp:23-67: the iterator walk with lower_bound jumps visits exactly the common
+    words in ascending id order; score += fabs(vi - wi) - fabs(vi) - fabs(wi); then -score / 2.0"""
+    score = 0.0
+    for wid in sorted(v1.keys() & v2.keys()):
+        vi, wi = v1[wid], v2[wid]
+        score += math.fabs(vi - wi) - math.fabs(vi) - math.fabs(wi)
+    score = -score / 2.0
+    return score
+
+
+def pl_combine(score_p: float, score_l: float, n_pt: int, n_ls: int, std_pt: float, std_ls: float) -> float:
+    """insertKFBowVectorPL's combination, src/mapHandler.cpp:3093-3106 (int -> double conversions as C++ makes them)"""
+    std_pl = std_ls + std_pt
+    n_pl = n_pt + n_ls
+    score = 0.0
+    try:
+        score += (score_p * n_pt + score_l * n_ls) / n_pl
+    except ZeroDivisionError:
+        score += _ieee_div(score_p * n_pt + score_l * n_ls, float(n_pl))
+    try:
+        score += (score_p * std_pt + score_l * std_ls) / std_pl
+    except ZeroDivisionError:
+        score += _ieee_div(score_p * std_pt + score_l * std_ls, std_pl)
+    return score
+
+
+def _ieee_div(a: float, b: float) -> float:
+    """a / b for b == +-0.0 as IEEE 754 gives it (Python raises instead)"""
+    if math.isnan(a) or a == 0.0:
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+class MapBow:
+    """MapHandler's keyframe BowVectors and conf_matrix: insertKFBowVector{P,L,PL}, src/mapHandler.cpp:3007-3128.
+    voc_p / voc_l: Vocab or None (the mode of :196-201)."""
+
+    def __init__(self, voc_p, voc_l, n):
+        self.voc_p, self.voc_l = voc_p, voc_l
+        self.conf = [[math.nan] * n for _ in range(n)]
+        self.bow_p, self.bow_l = {}, {}
+
+    def insert(self, kf_idx, pdesc, ldesc, alive, stats=None):
+        """alive[i] = map_keyframes[i] != NULL; stats = (n_pt, n_ls, std_pt, std_ls) in PL mode"""
+        if self.voc_p is not None:
+            self.bow_p[kf_idx] = self.voc_p.transform(pdesc)[0]
+        if self.voc_l is not None:
+            self.bow_l[kf_idx] = self.voc_l.transform(ldesc)[0]
+        for i in list(range(kf_idx)) + [kf_idx]:
+            if i < kf_idx and not alive[i]:
+                continue
+            s = self.pair(kf_idx, i, stats)
+            self.conf[kf_idx][i] = s
+            self.conf[i][kf_idx] = s
+
+    def pair(self, q, i, stats=None):
+        if self.voc_p is not None and self.voc_l is not None:                    # :3093-3106 / :3108-3127
+            sp = l1_score(self.bow_p[q], self.bow_p[i])
+            sl = l1_score(self.bow_l[q], self.bow_l[i])
+            return pl_combine(sp, sl, *stats)
+        if self.voc_p is not None:                                               # :3014-3027
+            return l1_score(self.bow_p[q], self.bow_p[i])
+        return l1_score(self.bow_l[q], self.bow_l[i])                            # :3040-3053

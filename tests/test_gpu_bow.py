@@ -1,0 +1,300 @@
+"""GPU tests of the bag-of-words entry points (plslam_bow_*, bow.hip) against the plain-Python restatement of DBoW2 and
+MapHandler::insertKFBowVector* (tests/dbow_ref.py).  Every double is compared bit for bit (float64 viewed as uint64; NaN
+matches NaN)."""
+import numpy as np
+import pytest
+
+import plslam_amd
+from plslam_amd import bow
+from plslam_amd.capi import EINVAL, ENOTSUP, ERANGE, BOW_MAX_SET, PlslamError
+from tests import dbow_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits_equal(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint64), b[~nb].view(np.uint64))
+
+
+def _ragged(sets):
+    off = np.zeros(len(sets) + 1, np.int32)
+    off[1:] = np.cumsum([len(s) for s in sets])
+    d = np.concatenate([np.asarray(s, np.uint8).reshape(-1, 32) for s in sets]) if sets else np.zeros((0, 32), np.uint8)
+    return d, off
+
+
+def _check_transform(gv, rv, sets):
+    d, off = _ragged(sets)
+    word, weight, bword, bweight, blen = gv.transform(d, off)
+    for s, feats in enumerate(sets):
+        v, per = rv.transform(feats)
+        a, b = off[s], off[s + 1]
+        assert [p[0] for p in per] == word[a:b].tolist(), f"set {s}: words"
+        assert _bits_equal([p[1] for p in per], weight[a:b]), f"set {s}: node weights"
+        items = R.sorted_items(v)
+        assert blen[s] == len(items), f"set {s}: BowVector length"
+        assert bword[a:a + blen[s]].tolist() == [w for w, _ in items], f"set {s}: BowVector words"
+        assert _bits_equal(bweight[a:a + blen[s]], [x for _, x in items]), f"set {s}: BowVector weights"
+    return word, blen
+
+
+def _sets(rng, voc, sizes, near=0.7):
+    out = []
+    for n in sizes:
+        k = int(round(n * near))
+        s = np.concatenate([bow.near_leaf_descriptors(rng, voc, k), rng.integers(0, 256, (n - k, 32), dtype=np.uint8)])
+        out.append(s[rng.permutation(n)])
+    return out
+
+
+@pytest.mark.parametrize("weighting", [R.TF_IDF, R.TF, R.IDF, R.BINARY])
+def test_transform_matches_the_restatement(ctx, weighting):
+    """Unbalanced tree (1..k children, leaves at any depth), stopped words, node ids and word ids permuted."""
+    rng = np.random.default_rng(10 + weighting)
+    v = bow.synth_vocabulary(rng, k=6, L=5, weighting=weighting, irregular=True, shuffle_ids=True, permute_words=True,
+                             stop_frac=0.15)
+    gv = plslam_amd.BowVocabulary(ctx, v)
+    rv = R.Vocab(v)
+    sets = _sets(rng, v, [0, 1, 37, 300, 2, 0, 999, 64, 65])
+    word, _ = _check_transform(gv, rv, sets)
+    w = dict(zip(v.words["word_id"].tolist(), v.words["node_id"].tolist()))
+    nw = dict(zip(v.nodes["node_id"].tolist(), v.nodes["weight"].tolist()))
+    assert any(nw[w[x]] == 0.0 for x in word.tolist()), "no stopped word was hit"
+    gv.close()
+
+
+def _tie_vocab(rng):
+    """Every parent's second child carries its first child's descriptor, and node ids are shuffled: a tie is resolved by
+    the children-list (file) order, which is not the id order."""
+    v = bow.synth_vocabulary(rng, k=4, L=4, shuffle_ids=True, permute_words=True)
+    pid = v.nodes["parent_id"]
+    starts = np.flatnonzero(np.r_[True, pid[1:] != pid[:-1]])
+    for s in starts:
+        if s + 1 < pid.size and pid[s + 1] == pid[s]:
+            v.nodes["descriptor"][s + 1] = v.nodes["descriptor"][s]
+    return v
+
+
+def test_ties_follow_the_children_list_order(ctx):
+    rng = np.random.default_rng(21)
+    v = _tie_vocab(rng)
+    rv = R.Vocab(v)
+    feats = bow.near_leaf_descriptors(rng, v, 400, flip_log2=6)
+    # the restatement does meet ties whose first child has the larger id
+    seen = 0
+    for f in feats[:100]:
+        node = 0
+        while rv.children[node]:
+            ch = rv.children[node]
+            d = [R.forb_distance(bytes(f), rv.desc[c]) for c in ch]
+            m = min(d)
+            tied = [c for c, x in zip(ch, d) if x == m]
+            seen += len(tied) > 1 and tied[0] > min(tied)
+            node = tied[0]
+    assert seen > 0
+    gv = plslam_amd.BowVocabulary(ctx, v)
+    _check_transform(gv, rv, [feats[:200], feats[200:]])
+    # the same vocabulary with every parent's records in reverse order: other winners, still the restatement's
+    pid = v.nodes["parent_id"]
+    starts = list(np.flatnonzero(np.r_[True, pid[1:] != pid[:-1]])) + [pid.size]
+    perm = np.concatenate([np.arange(a, b)[::-1] for a, b in zip(starts[:-1], starts[1:])])
+    v2 = bow.Vocabulary(v.k, v.L, v.scoring_type, v.weighting_type, v.nodes[perm], v.words)
+    gv2 = plslam_amd.BowVocabulary(ctx, v2)
+    w1 = gv.transform(feats, [0, len(feats)])[0]
+    w2, _ = _check_transform(gv2, R.Vocab(v2), [feats])
+    assert not np.array_equal(w1, w2)
+    gv.close()
+    gv2.close()
+
+
+def test_set_size_limit(ctx):
+    rng = np.random.default_rng(31)
+    v = bow.synth_vocabulary(rng, k=5, L=4, weighting=R.TF_IDF)
+    gv = plslam_amd.BowVocabulary(ctx, v)
+    big = _sets(rng, v, [BOW_MAX_SET])[0]
+    _check_transform(gv, R.Vocab(v), [big[:1], big, np.zeros((0, 32), np.uint8)])
+    over = np.concatenate([big, big[:1]])
+    with pytest.raises(PlslamError) as e:
+        gv.transform(over, [0, over.shape[0]])
+    assert e.value.code == ERANGE
+    gv.close()
+
+
+def test_full_size_vocabulary(ctx):
+    """k = 10, L = 6 (1.1 M nodes): one keyframe's 1500 ORB + 200 LBD descriptors, most of them near leaves."""
+    rng = np.random.default_rng(41)
+    v = bow.synth_vocabulary(rng, k=10, L=6, weighting=R.TF_IDF)
+    gv = plslam_amd.BowVocabulary(ctx, v)
+    sets = _sets(rng, v, [1500, 200], near=0.8)
+    _check_transform(gv, R.Vocab(v), sets)
+    gv.close()
+
+
+def _dev(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
+def test_transform_dev_equals_host(ctx):
+    import torch
+    rng = np.random.default_rng(51)
+    v = bow.synth_vocabulary(rng, k=6, L=4, weighting=R.TF, irregular=True, stop_frac=0.1)
+    gv = plslam_amd.BowVocabulary(ctx, v)
+    sets = _sets(rng, v, [100, 0, 1, 513])
+    d, off = _ragged(sets)
+    host = gv.transform(d, off)
+    total = d.shape[0]
+    dd, doff = _dev(torch, d), _dev(torch, off)
+    outs = [torch.empty(total, dtype=torch.int32, device="cuda"), torch.empty(total, dtype=torch.float64, device="cuda"),
+            torch.empty(total, dtype=torch.int32, device="cuda"), torch.empty(total, dtype=torch.float64, device="cuda"),
+            torch.empty(len(sets), dtype=torch.int32, device="cuda")]
+    gv.transform_dev(dd.data_ptr(), doff.data_ptr(), len(sets), total, 513, *[o.data_ptr() for o in outs])
+    torch.cuda.synchronize()
+    got = [o.cpu().numpy() for o in outs]
+    blen = host[4]
+    assert np.array_equal(got[0], host[0]) and _bits_equal(got[1], host[1]) and np.array_equal(got[4], blen)
+    for s in range(len(sets)):
+        a = off[s]
+        assert np.array_equal(got[2][a:a + blen[s]], host[2][a:a + blen[s]])
+        assert _bits_equal(got[3][a:a + blen[s]], host[3][a:a + blen[s]])
+    # a set longer than the caller's bound gets no vector
+    gv.transform_dev(dd.data_ptr(), doff.data_ptr(), len(sets), total, 100, *[o.data_ptr() for o in outs])
+    torch.cuda.synchronize()
+    assert outs[4].cpu().numpy().tolist() == [blen[0], blen[1], blen[2], -1]
+    gv.close()
+
+
+def _run(rng, vp, vl, n_kf, places=12):
+    """A keyframe run: descriptors drawn around a few 'places' (so that keyframes share words), some keyframes empty, PL
+    stats including n_pt = n_ls = 0 and std_pt = std_ls = 0 (0/0 -> NaN), and keyframes that die along the way."""
+    pool_p = [bow.near_leaf_descriptors(rng, vp, 120) for _ in range(places)] if vp else None
+    pool_l = [bow.near_leaf_descriptors(rng, vl, 40) for _ in range(places)] if vl else None
+    death = np.where(rng.random(n_kf) < 0.2, rng.integers(0, n_kf, n_kf), n_kf + 1)
+    kfs = []
+    for k in range(n_kf):
+        pl = int(rng.integers(0, places))
+        np_, nl_ = int(rng.integers(20, 120)), int(rng.integers(5, 40))
+        if k % 37 == 5:
+            np_ = 0
+        if k % 41 == 7:
+            nl_ = 0
+        pd = pool_p[pl][rng.choice(120, np_)] if vp else np.zeros((0, 32), np.uint8)
+        ld = pool_l[pl][rng.choice(40, nl_)] if vl else np.zeros((0, 32), np.uint8)
+        if vp:
+            pd = np.concatenate([pd, rng.integers(0, 256, (5, 32), dtype=np.uint8)])
+        stats = (int(rng.integers(0, 300)), int(rng.integers(0, 60)), float(rng.uniform(0, 200)), float(rng.uniform(0, 200)))
+        if k == 3:
+            stats = (0, 0, 0.0, 0.0)
+        alive = (death[:k] > k).astype(np.uint8)
+        kfs.append((pd, ld, stats, alive))
+    return kfs
+
+
+@pytest.mark.parametrize("mode", ["P", "L", "PL"])
+def test_insert_reproduces_the_conf_matrix(ctx, mode):
+    """200 keyframes through plslam_bow_db_insert (capacity hint 4: the database grows) = MapHandler's conf_matrix."""
+    import torch
+    rng = np.random.default_rng({"P": 61, "L": 62, "PL": 63}[mode])
+    vp = bow.synth_vocabulary(rng, k=6, L=4, weighting=R.TF_IDF, stop_frac=0.05) if "P" in mode else None
+    vl = bow.synth_vocabulary(rng, k=5, L=3, weighting=R.IDF, irregular=True) if "L" in mode else None
+    n_kf = 200
+    kfs = _run(rng, vp, vl, n_kf)
+    ref = R.MapBow(R.Vocab(vp) if vp else None, R.Vocab(vl) if vl else None, n_kf)
+    gp = plslam_amd.BowVocabulary(ctx, vp) if vp else None
+    gl = plslam_amd.BowVocabulary(ctx, vl) if vl else None
+    db = plslam_amd.BowDatabase(ctx, gp, gl, capacity_hint=4)
+    dbd = plslam_amd.BowDatabase(ctx, gp, gl, capacity_hint=0)
+    conf = np.full((n_kf, n_kf), np.nan)
+    conf_dev = torch.full((n_kf, n_kf), float("nan"), dtype=torch.float64, device="cuda")
+    for k, (pd, ld, stats, alive) in enumerate(kfs):
+        ref.insert(k, pd, ld, alive, stats)
+        row = conf[k].copy()
+        db.insert(k, pd, ld, stats, alive, row)
+        conf[k, :k + 1] = row[:k + 1]
+        conf[:k, k] = np.where(alive.astype(bool), row[:k], conf[:k, k])
+        # the device-pointer twin on a second database
+        dp, dl = _dev(torch, pd.reshape(-1, 32)), _dev(torch, ld.reshape(-1, 32))
+        da = _dev(torch, np.r_[alive, np.uint8(1)])
+        dbd.insert_dev(k, dp.data_ptr() if pd.shape[0] else 0, pd.shape[0], dl.data_ptr() if ld.shape[0] else 0,
+                       ld.shape[0], stats, da.data_ptr(), conf_dev[k].data_ptr())
+        torch.cuda.synchronize()
+    want = np.array(ref.conf)
+    assert _bits_equal(conf, want), np.argwhere(~((conf.view(np.uint64) == want.view(np.uint64)) |
+                                                   (np.isnan(conf) & np.isnan(want))))[:5]
+    got_dev = conf_dev.cpu().numpy()
+    # the device row holds what insert wrote at [k, :k+1]; the column half is the host's mirror
+    tri = np.tril(np.ones((n_kf, n_kf), bool))
+    assert _bits_equal(np.where(tri, got_dev, np.nan), np.where(tri, want, np.nan))
+    assert db.size == n_kf
+    # plslam_bow_db_score: each keyframe as the query against every stored one = the rows insert wrote
+    out = db.score(np.arange(n_kf))
+    assert out.shape == (n_kf, n_kf)
+    for q, (_, _, _, alive) in enumerate(kfs):
+        cols = np.r_[np.flatnonzero(alive), q]
+        assert _bits_equal(out[q, cols], want[q, cols]), q
+    for d in (db, dbd):
+        d.close()
+    for g in (gp, gl):
+        if g:
+            g.close()
+
+
+def test_score_marks_keyframes_never_inserted(ctx):
+    rng = np.random.default_rng(71)
+    vp = bow.synth_vocabulary(rng, k=4, L=3)
+    gp = plslam_amd.BowVocabulary(ctx, vp)
+    db = plslam_amd.BowDatabase(ctx, gp, None)
+    d = bow.near_leaf_descriptors(rng, vp, 50)
+    db.insert(0, d[:20])
+    db.insert(3, d[20:], alive=np.array([1, 0, 0], np.uint8))
+    out = db.score([0, 3])
+    assert out.shape == (2, 4) and np.isnan(out[:, 1:3]).all() and not np.isnan(out[:, [0, 3]]).any()
+    with pytest.raises(PlslamError) as e:
+        db.score([1])
+    assert e.value.code == EINVAL
+    with pytest.raises(PlslamError) as e:                # alive but never inserted
+        db.insert(4, d[:5], alive=np.array([1, 1, 0, 1], np.uint8))
+    assert e.value.code == EINVAL
+    db.close()
+    gp.close()
+
+
+def _tiny():
+    nodes = np.zeros(3, plslam_amd.capi.BOW_NODE_DTYPE)
+    nodes["node_id"], nodes["parent_id"], nodes["weight"] = [1, 2, 3], [0, 0, 1], [0.0, 1.0, 2.0]
+    words = np.zeros(2, plslam_amd.capi.BOW_WORD_DTYPE)
+    words["word_id"], words["node_id"] = [0, 1], [2, 3]
+    return bow.Vocabulary(2, 2, 0, 0, nodes, words)
+
+
+def _variant(**kw):
+    v = _tiny()
+    v.nodes, v.words = v.nodes.copy(), v.words.copy()
+    for key, f in kw.items():
+        f(v)
+    return v
+
+
+@pytest.mark.parametrize("name,voc,code", [
+    ("valid", _tiny(), 0),
+    ("id out of range", _variant(a=lambda v: v.nodes["node_id"].__setitem__(2, 4)), EINVAL),
+    ("duplicate node id", _variant(a=lambda v: v.nodes["node_id"].__setitem__(2, 2)), EINVAL),
+    ("parent not a node", _variant(a=lambda v: v.nodes["parent_id"].__setitem__(2, 7)), EINVAL),
+    ("cycle", _variant(a=lambda v: v.nodes["parent_id"].__setitem__(0, 3)), EINVAL),
+    ("leaf without word", _variant(a=lambda v: v.words.__setitem__("node_id", [2, 1])), EINVAL),
+    ("word id out of range", _variant(a=lambda v: v.words["word_id"].__setitem__(1, 5)), EINVAL),
+    ("empty", bow.Vocabulary(2, 2, 0, 0, np.zeros(0, plslam_amd.capi.BOW_NODE_DTYPE),
+                             np.zeros(0, plslam_amd.capi.BOW_WORD_DTYPE)), EINVAL),
+    ("L2 scoring", bow.Vocabulary(2, 2, 1, 0, _tiny().nodes, _tiny().words), ENOTSUP),
+])
+def test_vocabulary_validation(ctx, name, voc, code):
+    if code == 0:
+        plslam_amd.BowVocabulary(ctx, voc).close()
+        return
+    with pytest.raises(PlslamError) as e:
+        plslam_amd.BowVocabulary(ctx, voc)
+    assert e.value.code == code, name
+    assert "bow vocabulary" in str(e.value)

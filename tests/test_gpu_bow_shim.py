@@ -1,0 +1,57 @@
+"""Builds and runs the C++ bag-of-words shim test (plslam_amd/host/dbow_voc.hpp) on the GPU: it replays a keyframe run from a
+fixture written here and must reproduce the restatement's conf_matrix (tests/dbow_ref.py) bit for bit."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import plslam_amd
+from plslam_amd import bow
+from tests import dbow_ref as R
+from tests.test_gpu_bow import _run
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _compile(tmp):
+    exe = os.path.join(tmp, "test_bow_shim")
+    lib = os.path.dirname(plslam_amd.LIB_PATH)
+    subprocess.run([shutil.which("g++") or "g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "cpp", "test_bow_shim.cpp"),
+                    "-I" + os.path.join(ROOT, "include"), "-L" + lib, "-lplslam_hip", "-Wl,-rpath," + lib,
+                    "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-o", exe], check=True)
+    return exe
+
+
+def _fixture(path, mode, n_kf, seed):
+    rng = np.random.default_rng(seed)
+    vp = bow.synth_vocabulary(rng, k=6, L=4, weighting=R.TF_IDF, stop_frac=0.05)
+    vl = bow.synth_vocabulary(rng, k=5, L=3, weighting=R.TF, irregular=True, shuffle_ids=True)
+    kfs = _run(rng, vp if mode & 1 else None, vl if mode & 2 else None, n_kf)
+    ref = R.MapBow(R.Vocab(vp) if mode & 1 else None, R.Vocab(vl) if mode & 2 else None, n_kf)
+    parts = [np.array([mode, n_kf], np.int32)]
+    for v in (vp, vl):
+        parts += [np.array([v.k, v.L, v.weighting_type, v.nodes.shape[0], v.words.shape[0]], np.int32), v.nodes, v.words]
+    for k, (pd, ld, stats, alive) in enumerate(kfs):
+        ref.insert(k, pd, ld, alive, stats)
+        row_alive = np.zeros(n_kf, np.uint8)
+        row_alive[:k] = alive
+        parts += [np.array([pd.shape[0], ld.shape[0], stats[0], stats[1]], np.int32), np.array(stats[2:], np.float64),
+                  np.ascontiguousarray(pd, np.uint8), np.ascontiguousarray(ld, np.uint8), row_alive]
+    parts.append(np.array(ref.conf, np.float64))
+    with open(path, "wb") as f:
+        for p in parts:
+            f.write(np.ascontiguousarray(p).tobytes())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [1, 2, 3])
+def test_bow_shim_reproduces_the_conf_matrix(tmp_path, mode):
+    exe = _compile(str(tmp_path))
+    fx = str(tmp_path / "run.bin")
+    _fixture(fx, mode, 60, 90 + mode)
+    res = subprocess.run([exe, fx], capture_output=True, text=True, timeout=300)
+    print(res.stdout[-2000:], res.stderr[-2000:])
+    assert res.returncode == 0, res.stdout[-2000:]
+    assert "all checks passed" in res.stdout

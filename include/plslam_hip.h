@@ -40,7 +40,8 @@ extern "C" {
 
 /* 2: plslam_match_problem grew (keep_prior, reserved: 56 bytes), plslam_lba_plan_iterate's flags became a bit mask, options
  * "mfma_form" 3/4 and "exact_second"; 3 (round 4): "mfma_form" 5 (the default), "post_fuse", plslam_match_plan_key_state;
- * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available; additive within 5: the plslam_bow_* bag-of-words entry points.
+ * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available; additive within 5: the plslam_bow_* bag-of-words entry points; the loop-closure check plslam_loop_closure_verify[_dev] /
+ * plslam_relpose_robust_gn with plslam_lc_params / plslam_lc_keyframe / plslam_lc_result.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -929,6 +930,88 @@ int plslam_bow_db_size(plslam_bow_db* db, int32_t* n);
  * queries[q] as the new keyframe (its stored PL stats), for every stored keyframe i; NaN where i was never inserted.
  * Every query must have been inserted. */
 int plslam_bow_db_score(plslam_bow_db* db, const int32_t* queries, int32_t nq, double* out);
+
+/* ---- K25: loop-closure verification (MapHandler::isLoopClosure + computeRelativePoseRobustGN) ------------------------ */
+/* src/mapHandler.cpp:3192-3300 and :3566-3957 in one call: the two StVO::match problems between the keyframes' left
+ * descriptors, the correspondences in i1 order, the inlier-ratio gate, the two-stage robust pose-only Gauss-Newton (the
+ * 6 x 6 solve restates Eigen's ColPivHouseholderQR), the outlier pass, and the five-way decision.  See DESIGN.md,
+ * "Loop-closure verification", for every reference quirk kept. */
+#define PLSLAM_LC_MAX_FEATURES 16384      /* per kind and keyframe (n_pt, n_ls); larger -> PLSLAM_ERANGE */
+#define PLSLAM_LC_MAX_ITERS 10000         /* max_iters and max_iters_ref each; larger or negative -> PLSLAM_EINVAL */
+
+typedef struct plslam_lc_params {
+    plslam_cam cam;                 /* the stereo camera (MapHandler::cam; fx, fy, cx, cy are read)                 */
+    double homog_th;                /* stvo Config::homogTh()                                                      */
+    float min_ratio_12_p;           /* SlamConfig::minRatio12P()                                                   */
+    float min_ratio_12_l;           /* SlamConfig::minRatio12L()                                                   */
+    int32_t mutual;                 /* stvo Config::bestLRMatches() (StVO::match's cross check)                     */
+    int32_t has_points, has_lines;  /* SlamConfig::hasPoints() / hasLines()                                        */
+    int32_t max_iters;              /* SlamConfig::maxIters()     (stage 1)                                        */
+    int32_t max_iters_ref;          /* SlamConfig::maxItersRef()  (stage 2)                                        */
+    int32_t reserved;
+    double lc_inlier_ratio;         /* SlamConfig::lcInlierRatio() (percent)                                       */
+    double lc_res;                  /* SlamConfig::lcRes()                                                         */
+    double lc_unc;                  /* SlamConfig::lcUnc()                                                         */
+    double lc_inl;                  /* SlamConfig::lcInl()  (computed and reported; the decision ignores it, :3903) */
+    double lc_trs;                  /* SlamConfig::lcTrs()                                                         */
+    double lc_rot;                  /* SlamConfig::lcRot()  (degrees)                                              */
+} plslam_lc_params;
+
+/* one keyframe's stereo features (kf->stereo_frame): row i of every array is stereo_pt[i] / stereo_ls[i] */
+typedef struct plslam_lc_keyframe {
+    const uint8_t* pdesc;           /* n_pt x 32: pdesc_l                                      */
+    const double* P;                /* n_pt x 3:  stereo_pt[i]->P                              */
+    const double* pl;               /* n_pt x 2:  stereo_pt[i]->pl                             */
+    const int32_t* pt_idx;          /* n_pt:      stereo_pt[i]->idx (-1 allowed); NULL = all -1 */
+    int32_t n_pt;
+    int32_t n_ls;
+    const uint8_t* ldesc;           /* n_ls x 32: ldesc_l                                      */
+    const double* sPeP;             /* n_ls x 6:  stereo_ls[i]->sP, ->eP                       */
+    const double* le;               /* n_ls x 3:  stereo_ls[i]->le                             */
+    const int32_t* ls_idx;          /* n_ls:      stereo_ls[i]->idx; NULL = all -1             */
+} plslam_lc_keyframe;
+
+typedef struct plslam_lc_result {
+    int32_t is_lc;                  /* isLoopClosure's return value                                             */
+    int32_t gn_ran;                 /* the inlier-ratio gate passed and computeRelativePoseRobustGN ran         */
+    int32_t common_pt, common_ls;   /* match() counts = correspondences (rows of pt_corr / ls_corr)             */
+    int32_t n_pt_inliers, n_ls_inliers;   /* inlier flags after the outlier pass                                */
+    int32_t iters_1, iters_2;       /* systems assembled in stage 1 / stage 2                                   */
+    int32_t ok_res, ok_unc, ok_inl, ok_trs, ok_rot;   /* the five tests (ok_inl as computed, before :3903)     */
+    int32_t reserved;
+    double inl_ratio_pt, inl_ratio_ls;   /* :3273-3274 (NaN where a keyframe has no features of the kind)       */
+    double e;                       /* the last assembled system's normalised error                             */
+    double cov_eig;                 /* largest eigenvalue of H^-1                                               */
+    double ratio_inliers, t, r;
+    double x_inc[6];                /* logmap_se3(T_inc)                                                        */
+    double T_inc[16];               /* row-major                                                                */
+    double pose_inc[6];             /* logmap_se3(inverse_se3(expmap_se3(x_inc))) when is_lc, else 0            */
+    double H[36], g[6];             /* the last assembled system (row-major H)                                  */
+    int64_t clk_total, clk_serial;  /* diagnostics: K25's time, and its one-lane part (solve, update, decision),
+                                       in ticks of the 100 MHz wall clock                                       */
+} plslam_lc_result;
+
+/* Host pointers, one synchronisation.  pt_corr: kf0.n_pt x 4 capacity; row k (k < common_pt) = (kf0.pt_idx[i1], i1,
+ * kf1.pt_idx[i2], i2) for the k-th match in i1 order (lc_pt_idx before the decision); pt_inlier[k] = its flag after the
+ * outlier pass.  ls_corr / ls_inlier likewise with kf0.n_ls rows.  The reference's outputs are: lc_pt_idx = rows with
+ * pt_inlier set if is_lc, all common_pt rows otherwise (and likewise for lines).  Any of the four may be NULL.
+ * EINVAL: NULL inputs, negative sizes, max_iters / max_iters_ref outside [0, PLSLAM_LC_MAX_ITERS];
+ * ERANGE: a feature count over PLSLAM_LC_MAX_FEATURES. */
+int plslam_loop_closure_verify(plslam_ctx* ctx, const plslam_lc_params* params, const plslam_lc_keyframe* kf0,
+                               const plslam_lc_keyframe* kf1, plslam_lc_result* result, int32_t* pt_corr, uint8_t* pt_inlier,
+                               int32_t* ls_corr, uint8_t* ls_inlier);
+/* Device pointers throughout (the keyframe arrays, result, and the four outputs, which must not be NULL where the kind has
+ * rows); params and the two keyframe records are host structs.  Enqueued behind `stream` (NULL = the context's stream),
+ * no synchronisation; the result is in device memory when `stream` reaches this point. */
+int plslam_loop_closure_verify_dev(plslam_ctx* ctx, const plslam_lc_params* params, const plslam_lc_keyframe* kf0,
+                                   const plslam_lc_keyframe* kf1, plslam_lc_result* result, int32_t* pt_corr,
+                                   uint8_t* pt_inlier, int32_t* ls_corr, uint8_t* ls_inlier, void* stream);
+/* computeRelativePoseRobustGN (:3566-3957) alone on the caller's correspondences (lc_points / lc_lines, all inlier on
+ * entry): P npt x 3, pl_obs npt x 2, sPeP nls x 6, le_obs nls x 3.  Host pointers, one synchronisation; the params' match
+ * and gate fields are ignored.  common_pt / common_ls = npt / nls; inl_ratio_* are 0; pt_inlier / ls_inlier may be NULL. */
+int plslam_relpose_robust_gn(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
+                             int32_t npt, const double* sPeP, const double* le_obs, int32_t nls, plslam_lc_result* result,
+                             uint8_t* pt_inlier, uint8_t* ls_inlier);
 
 #ifdef __cplusplus
 }

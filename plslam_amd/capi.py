@@ -55,10 +55,13 @@ ABI_SYMBOLS = (
     "plslam_bow_vocab_create", "plslam_bow_vocab_destroy", "plslam_bow_transform", "plslam_bow_transform_dev",
     "plslam_bow_db_create", "plslam_bow_db_destroy", "plslam_bow_db_insert", "plslam_bow_db_insert_dev", "plslam_bow_db_size",
     "plslam_bow_db_score",
+    "plslam_loop_closure_verify", "plslam_loop_closure_verify_dev", "plslam_relpose_robust_gn",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
 BOW_MAX_SET = 16384      # include/plslam_hip.h: PLSLAM_BOW_MAX_SET
+LC_MAX_FEATURES = 16384  # include/plslam_hip.h: PLSLAM_LC_MAX_FEATURES
+LC_MAX_ITERS = 10000     # include/plslam_hip.h: PLSLAM_LC_MAX_ITERS
 
 
 class Cam(C.Structure):
@@ -130,6 +133,40 @@ class BowVocabDesc(C.Structure):
 class BowPlStats(C.Structure):
     """plslam_bow_pl_stats"""
     _fields_ = [("n_pt", C.c_int32), ("n_ls", C.c_int32), ("std_pt", C.c_double), ("std_ls", C.c_double)]
+
+
+class LcParams(C.Structure):
+    """plslam_lc_params (plslam_amd.loop_closure.params() builds one from the shipped configuration)"""
+    _fields_ = [("cam", Cam), ("homog_th", C.c_double), ("min_ratio_12_p", C.c_float), ("min_ratio_12_l", C.c_float),
+                ("mutual", C.c_int32), ("has_points", C.c_int32), ("has_lines", C.c_int32), ("max_iters", C.c_int32),
+                ("max_iters_ref", C.c_int32), ("reserved", C.c_int32), ("lc_inlier_ratio", C.c_double),
+                ("lc_res", C.c_double), ("lc_unc", C.c_double), ("lc_inl", C.c_double), ("lc_trs", C.c_double),
+                ("lc_rot", C.c_double)]
+
+
+class LcKeyframe(C.Structure):
+    """plslam_lc_keyframe"""
+    _fields_ = [("pdesc", C.c_void_p), ("P", C.c_void_p), ("pl", C.c_void_p), ("pt_idx", C.c_void_p), ("n_pt", C.c_int32),
+                ("n_ls", C.c_int32), ("ldesc", C.c_void_p), ("sPeP", C.c_void_p), ("le", C.c_void_p), ("ls_idx", C.c_void_p)]
+
+
+class LcResult(C.Structure):
+    """plslam_lc_result"""
+    _fields_ = [(n, C.c_int32) for n in ("is_lc", "gn_ran", "common_pt", "common_ls", "n_pt_inliers", "n_ls_inliers", "iters_1",
+                                          "iters_2", "ok_res", "ok_unc", "ok_inl", "ok_trs", "ok_rot", "reserved")] + \
+              [(n, C.c_double) for n in ("inl_ratio_pt", "inl_ratio_ls", "e", "cov_eig", "ratio_inliers", "t", "r")] + \
+              [("x_inc", C.c_double * 6), ("T_inc", C.c_double * 16), ("pose_inc", C.c_double * 6), ("H", C.c_double * 36),
+               ("g", C.c_double * 6), ("clk_total", C.c_int64), ("clk_serial", C.c_int64)]
+
+    def as_dict(self):
+        """the record as plain Python values / numpy arrays (T_inc 4 x 4, H 6 x 6)"""
+        d = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            d[name] = np.ctypeslib.as_array(v).copy() if not isinstance(v, (int, float)) else v
+        d["T_inc"] = d["T_inc"].reshape(4, 4)
+        d["H"] = d["H"].reshape(6, 6)
+        return d
 
 
 # plslam_bow_node / plslam_bow_word as numpy records
@@ -319,6 +356,11 @@ def load() -> C.CDLL:
     L.plslam_bow_db_insert_dev.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(BowPlStats), vp, vp]
     L.plslam_bow_db_size.argtypes = [vp, C.POINTER(i32)]
     L.plslam_bow_db_score.argtypes = [vp, vp, i32, vp]
+    L.plslam_loop_closure_verify.argtypes = [vp, C.POINTER(LcParams), C.POINTER(LcKeyframe), C.POINTER(LcKeyframe),
+                                             C.POINTER(LcResult), vp, vp, vp, vp]
+    L.plslam_loop_closure_verify_dev.argtypes = [vp, C.POINTER(LcParams), C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), vp,
+                                                 vp, vp, vp, vp, vp]
+    L.plslam_relpose_robust_gn.argtypes = [vp, C.POINTER(LcParams), vp, vp, i32, vp, vp, i32, C.POINTER(LcResult), vp, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("plslam_strerror", "plslam_last_error", "plslam_ctx_destroy",
@@ -487,6 +529,63 @@ class Context:
                                                  P.shape[0], _p(S), _p(lo), _p(li), S.shape[0], _p(H), _p(g), _p(e), _p(n)),
                "plslam_pose_gn_accumulate")
         return H, g, float(e[0]), (int(n[0]), int(n[1]))
+
+    # ---- K25: loop-closure verification (MapHandler::isLoopClosure) --------------------------------------------------
+    @staticmethod
+    def _lc_kf_arrays(kf):
+        """the host arrays of one keyframe dict (pdesc, P, pl, pt_idx, ldesc, sPeP, le, ls_idx), contiguous and typed"""
+        out = {"pdesc": _arr(kf["pdesc"], np.uint8, (-1, 32)), "P": _arr(kf["P"], np.float64, (-1, 3)),
+               "pl": _arr(kf["pl"], np.float64, (-1, 2)), "ldesc": _arr(kf["ldesc"], np.uint8, (-1, 32)),
+               "sPeP": _arr(kf["sPeP"], np.float64, (-1, 6)), "le": _arr(kf["le"], np.float64, (-1, 3))}
+        for k in ("pt_idx", "ls_idx"):
+            out[k] = None if kf.get(k) is None else _arr(kf[k], np.int32)
+        n_pt, n_ls = out["pdesc"].shape[0], out["ldesc"].shape[0]
+        for k, n in (("P", n_pt), ("pl", n_pt), ("pt_idx", n_pt), ("sPeP", n_ls), ("le", n_ls), ("ls_idx", n_ls)):
+            if out[k] is not None and out[k].shape[0] != n:
+                raise ValueError(f"keyframe array {k} has {out[k].shape[0]} rows, its descriptors {n}")
+        return out
+
+    @staticmethod
+    def _lc_kf_record(a):
+        # a: the arrays of _lc_kf_arrays (host) or of device tensors' addresses; the caller keeps them alive across the call
+        return LcKeyframe(_p(a["pdesc"]), _p(a["P"]), _p(a["pl"]), _p(a["pt_idx"]), a["P"].shape[0], a["sPeP"].shape[0],
+                          _p(a["ldesc"]), _p(a["sPeP"]), _p(a["le"]), _p(a["ls_idx"]))
+
+    def loop_closure_verify(self, params, kf0, kf1):
+        """isLoopClosure(kf0, kf1) -> (result dict, pt_corr[common_pt, 4], pt_inlier, ls_corr[common_ls, 4], ls_inlier).
+        kf0 / kf1: dicts with pdesc, P, pl, pt_idx (or None), ldesc, sPeP, le, ls_idx (or None)."""
+        a0, a1 = self._lc_kf_arrays(kf0), self._lc_kf_arrays(kf1)
+        r0, r1 = self._lc_kf_record(a0), self._lc_kf_record(a1)
+        n0p, n0l = a0["P"].shape[0], a0["sPeP"].shape[0]
+        pc, pi = np.zeros((n0p, 4), np.int32), np.zeros(n0p, np.uint8)
+        lc, li = np.zeros((n0l, 4), np.int32), np.zeros(n0l, np.uint8)
+        res = LcResult()
+        _check(self._L.plslam_loop_closure_verify(self._h, C.byref(params), C.byref(r0), C.byref(r1), C.byref(res), _p(pc),
+                                                  _p(pi), _p(lc), _p(li)), "plslam_loop_closure_verify")
+        d = res.as_dict()
+        return d, pc[:d["common_pt"]], pi[:d["common_pt"]].astype(bool), lc[:d["common_ls"]], li[:d["common_ls"]].astype(bool)
+
+    def loop_closure_verify_dev(self, params, kf0_dev, kf1_dev, result_ptr, pt_corr_ptr, pt_inlier_ptr, ls_corr_ptr,
+                                ls_inlier_ptr, stream=None):
+        """Device-pointer form.  kf0_dev / kf1_dev: dicts of device addresses (ints) for pdesc, P, pl, pt_idx, ldesc, sPeP, le,
+        ls_idx plus the counts n_pt, n_ls; result_ptr: device memory of sizeof(LcResult) bytes.  Enqueued behind `stream`
+        (None = the context's stream), no synchronisation."""
+        recs = [LcKeyframe(*(C.c_void_p(k.get(n) or 0) for n in ("pdesc", "P", "pl", "pt_idx")), int(k["n_pt"]), int(k["n_ls"]),
+                           *(C.c_void_p(k.get(n) or 0) for n in ("ldesc", "sPeP", "le", "ls_idx"))) for k in (kf0_dev, kf1_dev)]
+        _check(self._L.plslam_loop_closure_verify_dev(self._h, C.byref(params), C.byref(recs[0]), C.byref(recs[1]),
+                                                      C.c_void_p(result_ptr), C.c_void_p(pt_corr_ptr), C.c_void_p(pt_inlier_ptr),
+                                                      C.c_void_p(ls_corr_ptr), C.c_void_p(ls_inlier_ptr),
+                                                      C.c_void_p(stream or 0)), "plslam_loop_closure_verify_dev")
+
+    def relpose_robust_gn(self, params, P, pl_obs, sPeP, le_obs):
+        """computeRelativePoseRobustGN on given correspondences -> (result dict, pt_inlier, ls_inlier)"""
+        P, po = _arr(P, np.float64, (-1, 3)), _arr(pl_obs, np.float64, (-1, 2))
+        S, lo = _arr(sPeP, np.float64, (-1, 6)), _arr(le_obs, np.float64, (-1, 3))
+        pi, li = np.zeros(P.shape[0], np.uint8), np.zeros(S.shape[0], np.uint8)
+        res = LcResult()
+        _check(self._L.plslam_relpose_robust_gn(self._h, C.byref(params), _p(P), _p(po), P.shape[0], _p(S), _p(lo), S.shape[0],
+                                                C.byref(res), _p(pi), _p(li)), "plslam_relpose_robust_gn")
+        return res.as_dict(), pi.astype(bool), li.astype(bool)
 
     def stereo_point_gate(self, m12, kp_l, kp_r, max_dist_epip, min_disp):
         """StereoFrame::matchStereoPoints gates -> (stereo_12, disp, n_stereo)."""

@@ -791,6 +791,14 @@ int match_problems_on_ctx_stream(plslam_ctx* ctx, const plslam_match_problem* pr
     if (r == PLSLAM_ENOTSUP && n1_dev0) return r;            // (not an error: the caller has another form; no message)
     return r ? r : plan_run(ctx->host_plan, ctx->stream, ctx->stream);
 }
+
+int match_problems_lc(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob)
+{
+    if (!ctx->lc_plan) ctx->lc_plan = new (std::nothrow) plslam_match_plan();
+    PLSLAM_REQUIRE(ctx->lc_plan != nullptr, PLSLAM_ENOMEM);
+    const int r = plan_build(ctx, probs, nprob, ctx->lc_plan);
+    return r ? r : plan_run(ctx->lc_plan, ctx->stream, ctx->stream);
+}
 }  // namespace plslam
 
 // ---------------------------------------------------------------------------------------------
@@ -864,6 +872,13 @@ void plslam_ctx_destroy(plslam_ctx* ctx)
         ctx->host_plan->free_all();
         delete ctx->host_plan;
     }
+    if (ctx->lc_plan) {
+        ctx->lc_plan->free_all();
+        delete ctx->lc_plan;
+    }
+    ctx->lc_in.release(); ctx->lc_out.release(); ctx->lc_tab.release();
+    for (hipEvent_t& e : ctx->lc_ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

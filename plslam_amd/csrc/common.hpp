@@ -141,9 +141,16 @@ struct plslam_ctx {
     plslam::HostBuf pin_misc;                       // host-built tables of the map-level drivers (map2kf.hip)
     plslam::LineRing lbd_ring;                      // line records of the last plslam_lbd_compute* calls
     struct plslam_match_plan* host_plan = nullptr;  // reused by the host-pointer match entry points
+    struct plslam_match_plan* lc_plan = nullptr;    // the loop-closure check's two match problems (loop_closure.hip)
+    plslam::DevBuf lc_in, lc_out, lc_tab;           // ... its keyframe image, its outputs, its match tables
+    hipEvent_t lc_ev[2] = {nullptr, nullptr};       // ... its fences with a caller's stream (the _dev form)
 };
 
 namespace plslam {
+
+// the loop-closure check's match problems (device pointers) as one plan on the context's stream: ctx->lc_plan, whose
+// buffers only grow and whose tables are staged in pageable memory (capi.hip)
+int match_problems_lc(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob);
 
 // Pointers read from launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction (it counts on
 // lgkmcnt as well as vmcnt, and cannot take a scalar base).  Kernels spell the address space out at the point of use:

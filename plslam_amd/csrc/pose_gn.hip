@@ -14,44 +14,12 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "pose_gn_dev.hpp"
 
 namespace plslam {
 namespace {
 
 constexpr int GN_THREADS = 256;
-constexpr int GN_TERMS = 21 + 6 + 1;       // upper triangle of H, g, e
-
-struct GnCam { double fx, fy, cx, cy; };
-
-__device__ __forceinline__ double dmaxd(double a, double b) { return a < b ? b : a; }   // std::max
-
-__device__ __forceinline__ void xform(const double* T, const double* X, double o[3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = (T[4 * i] * X[0] + T[4 * i + 1] * X[1] + T[4 * i + 2] * X[2]) + T[4 * i + 3];
-}
-
-__device__ __forceinline__ void jac6(double fgz2, double a, double b, double gx, double gy, double gz, double J[6])
-{
-    J[0] = +fgz2 * a * gz;
-    J[1] = +fgz2 * b * gz;
-    J[2] = -fgz2 * (gx * a + gy * b);
-    J[3] = -fgz2 * (gx * gy * a + gy * gy * b + gz * gz * b);
-    J[4] = +fgz2 * (gx * gx * a + gz * gz * a + gx * gy * b);
-    J[5] = +fgz2 * (gx * gz * b - gy * gz * a);
-}
-
-__device__ __forceinline__ void accumulate(double acc[GN_TERMS], const double J[6], double r, double w)
-{
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) acc[k++] += J[i] * J[j] * w;     // (J J^T) w, evaluated as Eigen does: product, then * w
-#pragma unroll
-    for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r * w;
-    acc[27] += r * r * w;
-}
 
 __global__ void __launch_bounds__(GN_THREADS)
 k_pose_gn(GnCam K, double th, const double* __restrict__ T, const double* __restrict__ P, const double* __restrict__ pl_obs,
@@ -71,35 +39,18 @@ k_pose_gn(GnCam K, double th, const double* __restrict__ T, const double* __rest
     int np = 0, nl = 0;
     for (int32_t i = tid; i < npt; i += GN_THREADS) {
         if (!pt_inlier[i]) continue;
-        double G[3], J[6];
-        xform(Tm, P + 3 * (size_t)i, G);
-        const double u = K.cx + K.fx * G[0] / G[2], v = K.cy + K.fy * G[1] / G[2];
-        const double dx = u - pl_obs[2 * (size_t)i], dy = v - pl_obs[2 * (size_t)i + 1];
-        const double r = sqrt(dx * dx + dy * dy);
-        const double fgz2 = K.fx / dmaxd(th, G[2] * G[2]);
-        jac6(fgz2, dx, dy, G[0], G[1], G[2], J);
-        const double den = dmaxd(th, r);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) J[k] = J[k] / den;
-        accumulate(ap, J, r, 1.0 / (1.0 + r * r));
+        const double X[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
+        gn_point_row(K, th, Tm, X, pl_obs[2 * (size_t)i], pl_obs[2 * (size_t)i + 1], ap);
         ++np;
     }
     for (int32_t i = tid; i < nls; i += GN_THREADS) {
         if (!ls_inlier[i]) continue;
-        double S[3], E[3], Js[6], Je[6], J[6];
-        xform(Tm, sPeP + 6 * (size_t)i, S);
-        xform(Tm, sPeP + 6 * (size_t)i + 3, E);
-        const double su = K.cx + K.fx * S[0] / S[2], sv = K.cy + K.fy * S[1] / S[2];
-        const double eu = K.cx + K.fx * E[0] / E[2], ev = K.cy + K.fy * E[1] / E[2];
-        const double lx = le_obs[3 * (size_t)i], ly = le_obs[3 * (size_t)i + 1], lz = le_obs[3 * (size_t)i + 2];
-        const double ds = lx * su + ly * sv + lz, de = lx * eu + ly * ev + lz;
-        const double r = sqrt(ds * ds + de * de);
-        jac6(K.fx / dmaxd(th, S[2] * S[2]), lx, ly, S[0], S[1], S[2], Js);
-        jac6(K.fx / dmaxd(th, E[2] * E[2]), lx, ly, E[0], E[1], E[2], Je);
-        const double den = dmaxd(th, r);
+        double SE[6], l[3];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) J[k] = (Js[k] * ds + Je[k] * de) / den;
-        accumulate(al, J, r, 1.0 / (1.0 + r * r));
+        for (int k = 0; k < 6; ++k) SE[k] = sPeP[6 * (size_t)i + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) l[k] = le_obs[3 * (size_t)i + k];
+        gn_line_row(K, th, Tm, SE, l, al);
         ++nl;
     }
     __syncthreads();

@@ -1,0 +1,122 @@
+"""Loop-closure verification (K25, MapHandler::isLoopClosure): the parameter record with the shipped configuration's values,
+and a seeded synthetic keyframe pair with known correspondences and a known relative pose."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import synth
+from .capi import Cam, LcParams
+
+# config/config/config.yaml (SlamConfig) and the stvo-pl Config it loads (homog_th, min_ratio_12_*, best_lr_matches)
+DEFAULTS = dict(homog_th=1e-7, min_ratio_12_p=0.75, min_ratio_12_l=0.75, mutual=1, has_points=1, has_lines=1, max_iters=5,
+                max_iters_ref=10, lc_inlier_ratio=30.0, lc_res=1.5, lc_unc=0.01, lc_inl=0.3, lc_trs=1.5, lc_rot=35.0)
+KITTI_ITERS = dict(max_iters=100, max_iters_ref=100)     # config/config/config_kitti.yaml:49-50
+
+
+def params(cam=None, **over) -> LcParams:
+    """plslam_lc_params with DEFAULTS, overridden by keyword; cam: a Cam, or a dict of fx, fy, cx, cy (default EuRoC)"""
+    d = dict(DEFAULTS)
+    unknown = set(over) - set(d)
+    if unknown:
+        raise KeyError(f"unknown loop-closure parameters: {sorted(unknown)}")
+    d.update(over)
+    if cam is None:
+        cam = synth.EUROC
+    if not isinstance(cam, Cam):
+        cam = Cam(cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam.get("b", 0.0), cam.get("width", 0), cam.get("height", 0))
+    p = LcParams()
+    p.cam = cam
+    for k, v in d.items():
+        setattr(p, k, v)
+    return p
+
+
+def params_dict(p: LcParams) -> dict:
+    return {k: getattr(p, k) for k in DEFAULTS}
+
+
+def _project(cam, X):
+    return np.stack([cam["cx"] + cam["fx"] * X[:, 0] / X[:, 2], cam["cy"] + cam["fy"] * X[:, 1] / X[:, 2]], axis=1)
+
+
+def _disk(rng, n, radius):
+    a = rng.uniform(0, 2 * np.pi, n)
+    r = radius * np.sqrt(rng.uniform(0, 1, n))
+    return np.stack([r * np.cos(a), r * np.sin(a)], axis=1)
+
+
+def keyframe_pair(seed, n_pt=1500, n_ls=200, pose=(0.05, -0.03, 0.10, 0.01, -0.02, 0.015), keep_frac=0.7, flip_p=0.08,
+                  outlier_frac=0.1, noise_px=0.5, outlier_px=(12.0, 40.0), cam=None):
+    """Two keyframes whose features partly observe the same scene.  kf0 holds n_pt points (P in kf0's frame, 2-20 m deep)
+    and n_ls segments; kf1's descriptors are synth.noisy_copy of kf0's (keep_frac true rows with flip_p bit flips, the
+    rest fresh distractors), and a true row's observation is the projection of T * X (T = expmap(pose), kf0 -> kf1) with
+    noise inside a disk of noise_px.  outlier_frac of the true rows are moved by outlier_px (a range) instead.  A point
+    observation is pl; a line's is le, the normalised line through its projected end points.  Returns (kf0, kf1, truth)."""
+    cam = cam or synth.EUROC
+    rng = np.random.Generator(np.random.PCG64(seed))
+    T = synth.se3_exp(np.asarray(pose, np.float64))
+    W, Hh = cam.get("width", 752), cam.get("height", 480)
+
+    def scene(n):
+        uv = np.stack([rng.uniform(40, W - 40, n), rng.uniform(40, Hh - 40, n)], axis=1)
+        z = rng.uniform(2.0, 20.0, n)
+        return np.stack([(uv[:, 0] - cam["cx"]) * z / cam["fx"], (uv[:, 1] - cam["cy"]) * z / cam["fy"], z], axis=1)
+
+    def xf(X):
+        return X @ T[:3, :3].T + T[:3, 3]
+
+    kf0, kf1, truth = {}, {}, {"T": T, "pose": np.asarray(pose, np.float64)}
+    # points
+    P = scene(n_pt)
+    d0 = synth.random_desc(rng, n_pt)
+    if n_pt:
+        d1, perm, fresh = synth.noisy_copy(rng, d0, keep_frac, flip_p)
+    else:
+        d1, perm, fresh = d0.copy(), np.zeros(0, np.int64), np.zeros(0, bool)
+    pl = _project(cam, xf(P[perm])) + _disk(rng, n_pt, noise_px) if n_pt else np.zeros((0, 2))
+    out = (~fresh) & (rng.random(n_pt) < outlier_frac)
+    if out.any():
+        pl[out] += _ring(rng, int(out.sum()), *outlier_px)
+    pl[fresh] = np.stack([rng.uniform(0, W, int(fresh.sum())), rng.uniform(0, Hh, int(fresh.sum()))], axis=1)
+    kf0.update(pdesc=d0, P=P, pt_idx=np.arange(n_pt, dtype=np.int32) + 1000)
+    kf1.update(pdesc=d1, pl=pl, pt_idx=np.arange(n_pt, dtype=np.int32) + 5000)
+    truth.update(pt_src=np.where(fresh, -1, perm), pt_out=out)
+    kf0["pl"] = _project(cam, P)
+    kf1["P"] = xf(P[perm]) if n_pt else np.zeros((0, 3))
+    # lines
+    S, E = scene(n_ls), scene(n_ls)
+    l0 = synth.random_desc(rng, n_ls)
+    if n_ls:
+        l1, lperm, lfresh = synth.noisy_copy(rng, l0, keep_frac, flip_p)
+    else:
+        l1, lperm, lfresh = l0.copy(), np.zeros(0, np.int64), np.zeros(0, bool)
+    s1 = _project(cam, xf(S[lperm])) + _disk(rng, n_ls, noise_px) if n_ls else np.zeros((0, 2))
+    e1 = _project(cam, xf(E[lperm])) + _disk(rng, n_ls, noise_px) if n_ls else np.zeros((0, 2))
+    lout = (~lfresh) & (rng.random(n_ls) < outlier_frac)
+    if lout.any():                     # moved across the segment: a shift along it would leave the line in place
+        dvec = e1[lout] - s1[lout]
+        nrm = np.stack([-dvec[:, 1], dvec[:, 0]], axis=1) / np.linalg.norm(dvec, axis=1)[:, None]
+        sh = nrm * (rng.uniform(*outlier_px, int(lout.sum())) * rng.choice([-1.0, 1.0], int(lout.sum())))[:, None]
+        s1[lout] += sh
+        e1[lout] += sh
+    nf = int(lfresh.sum())
+    s1[lfresh] = np.stack([rng.uniform(0, W, nf), rng.uniform(0, Hh, nf)], axis=1)
+    e1[lfresh] = np.stack([rng.uniform(0, W, nf), rng.uniform(0, Hh, nf)], axis=1)
+    le = np.cross(np.c_[s1, np.ones(n_ls)], np.c_[e1, np.ones(n_ls)]) if n_ls else np.zeros((0, 3))
+    if n_ls:
+        le = le / np.sqrt(le[:, 0] ** 2 + le[:, 1] ** 2)[:, None]
+    kf0.update(ldesc=l0, sPeP=np.c_[S, E], ls_idx=np.arange(n_ls, dtype=np.int32) + 2000)
+    kf1.update(ldesc=l1, le=le, ls_idx=np.arange(n_ls, dtype=np.int32) + 7000)
+    kf0["le"] = np.zeros((n_ls, 3))
+    kf1["sPeP"] = np.c_[xf(S[lperm]), xf(E[lperm])] if n_ls else np.zeros((0, 6))
+    truth.update(ls_src=np.where(lfresh, -1, lperm), ls_out=lout)
+    for kf in (kf0, kf1):
+        for k, w in (("pdesc", 32), ("P", 3), ("pl", 2), ("ldesc", 32), ("sPeP", 6), ("le", 3)):
+            kf[k] = np.ascontiguousarray(np.asarray(kf[k]).reshape(-1, w), dtype=np.uint8 if "desc" in k else np.float64)
+    return kf0, kf1, truth
+
+
+def _ring(rng, n, r0, r1):
+    a = rng.uniform(0, 2 * np.pi, n)
+    r = rng.uniform(r0, r1, n)
+    return np.stack([r * np.cos(a), r * np.sin(a)], axis=1)

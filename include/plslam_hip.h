@@ -41,7 +41,8 @@ extern "C" {
 /* 2: plslam_match_problem grew (keep_prior, reserved: 56 bytes), plslam_lba_plan_iterate's flags became a bit mask, options
  * "mfma_form" 3/4 and "exact_second"; 3 (round 4): "mfma_form" 5 (the default), "post_fuse", plslam_match_plan_key_state;
  * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available; additive within 5: the plslam_bow_* bag-of-words entry points; the loop-closure check plslam_loop_closure_verify[_dev] /
- * plslam_relpose_robust_gn with plslam_lc_params / plslam_lc_keyframe / plslam_lc_result.
+ * plslam_relpose_robust_gn with plslam_lc_params / plslam_lc_keyframe / plslam_lc_result; the global bundle adjustment
+ * plslam_gba_plan_create / plslam_gba_optimize / plslam_gba_plan_destroy and plslam_dense_ldlt_solve.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1012,6 +1013,64 @@ int plslam_loop_closure_verify_dev(plslam_ctx* ctx, const plslam_lc_params* para
 int plslam_relpose_robust_gn(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
                              int32_t npt, const double* sPeP, const double* le_obs, int32_t nls, plslam_lc_result* result,
                              uint8_t* pt_inlier, uint8_t* ls_inlier);
+
+/* ---- K26-K39: global bundle adjustment (MapHandler::globalBundleAdjustment + levMarquardtOptimizationGBA,
+ * src/mapHandler.cpp:1995-2099, :2101-2703) ---------------------------------------------------------------------------
+ * The rows and blocks of every pass are the LBA plan's: the first pass reads the stored T_kf_w of every keyframe (:2136,
+ * :2246) and writes the pose x line cross blocks transposed in both triangles (:2349-2350, PLSLAM_LBA_COMPAT_GBA); every
+ * later pass gives the points of an optimised keyframe expmap_se3(X) (:2411-2416) but the lines the STORED T_kf_w and both
+ * end points from one stride-3 block (:2520-2523, PLSLAM_LBA_COMPAT_ITER_PASS), and writes the correct block J_l J_p^T into
+ * the lower triangle, the only one SimplicialLDLT reads (:2628-2629).  The LBA text spells the iteration pass's homogTh as the
+ * literal 1e-7 where the GBA reads SlamConfig::homogTh(): the plan refuses any other homog_th (PLSLAM_EINVAL).
+ * The solve is the Schur complement on the covisible keyframe blocks plus a dense fp64 L D L^T of the 6 nkf x 6 nkf reduced
+ * camera system on the device.  A landmark block that is not positive definite after damping contributes nothing and gets a
+ * zero step (counted: n_singular) where the reference's full-system SimplicialLDLT would carry non-finite values; pivots of
+ * the reduced system that are zero or not finite are counted (n_bad_pivots), not repaired.
+ *   plslam_gba_plan_create  n_map_kf keyframe slots (map indices), nkf optimised keyframes (kf_list[k] = map index of local
+ *                           keyframe k: every non-null keyframe but kf_idx 0, :2001-2013), npt / nls landmarks, and the
+ *                           observation lists as the reference builds them (:2017-2092): pt_obs / ls_obs are Vector6i rows
+ *                           (landmark map index, landmark local index, observation index, keyframe map index, keyframe local
+ *                           index or -1, inlier flag), pt_obs_uv n x 2 / ls_l_obs n x 3 the observations themselves.
+ *                           EINVAL: nkf above PLSLAM_GBA_MAX_KEYFRAMES (S alone takes 4.8 GB there), homog_th != 1e-7,
+ *                           indices out of range, sizes that overflow the plan's 32-bit element offsets.
+ *   plslam_gba_optimize     the LM loop (:2101-2672): lambda = lambda_lba_lm * trunc(max |H(i,i)|) (`int Hmax`, :2359), the
+ *                           first solve always applied, then up to max_iters_lba - 1 passes with the reference's tests.  Its err
+ *                           is divided by Npt_obs + Nls_obs, which are never incremented (:2121, :2230): +inf (NaN for a zero
+ *                           sum) on every pass, so every step is taken and lambda grows by lambda_lba_k after each solve; the
+ *                           stops are numeric_limits<double>::epsilon() (:2637, :2667).  In: the stored T_kf_w (n_map_kf x 16),
+ *                           x_kf (nkf x 6, the keyframes' x_kf_w), Xw (npt x 3), Lw (nls x 6).  Out: x_kf_out (nkf x 6),
+ *                           T_out (nkf x 16, expmap_se3 of x_kf_out: what the write-back stores, :2674-2680; may be NULL),
+ *                           Xw_out, Lw_out.  trace (may be NULL) receives one record per solve: max(max_iters_lba, 1) entries.
+ *                           Per solve only the err and ||DX||^2 scalars cross to the host.
+ *   plslam_dense_ldlt_solve the device L D L^T alone: A (n x n, row-major, host; its LOWER triangle is read), b, x (n);
+ *                           *n_bad_pivots (may be NULL) counts zero / non-finite pivots. */
+#define PLSLAM_GBA_MAX_KEYFRAMES 4096
+#define PLSLAM_GBA_STOP_MAX_ITERS 0    /* the loop ran out (iters == max_iters_lba)                                  */
+#define PLSLAM_GBA_STOP_ERR 1          /* abs(err - err_prev) < eps || err < eps, before the solve (:2637)            */
+#define PLSLAM_GBA_STOP_DX 2           /* DX.norm() < eps, after the solve (:2667)                                    */
+typedef struct plslam_gba_plan plslam_gba_plan;
+typedef struct plslam_gba_solve {
+    double lambda;                     /* the damping this solve used                                              */
+    double err_raw, err;               /* the pass's sum of r^2 w, and err as the reference normalises it           */
+    double dx_norm;                    /* ||DX|| over all N unknowns                                               */
+    int32_t n_singular, n_bad_pivots;  /* landmark blocks not positive definite; zero / non-finite pivots of S      */
+    int32_t accepted, reserved;        /* the step was applied (err <= err_prev, or the first solve)                */
+} plslam_gba_solve;
+typedef struct plslam_gba_result {
+    int32_t iters;                     /* the reference's `iters` when the loop ends                                */
+    int32_t n_solves, stop_reason, reserved;
+    double err, err_prev, lambda;      /* the loop's variables when it ends                                         */
+    double hmax;                       /* max |H(i,i)| of the first pass (before the truncation)                    */
+} plslam_gba_result;
+int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf,
+                           const int32_t* kf_list, int32_t npt, int32_t nls, const int32_t* pt_obs, const double* pt_obs_uv,
+                           int32_t n_pt_obs, const int32_t* ls_obs, const double* ls_l_obs, int32_t n_ls_obs,
+                           plslam_gba_plan** out);
+int plslam_gba_optimize(plslam_gba_plan* plan, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba,
+                        const double* T_kf_w, const double* x_kf, const double* Xw, const double* Lw, double* x_kf_out,
+                        double* T_out, double* Xw_out, double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result);
+void plslam_gba_plan_destroy(plslam_gba_plan* plan);
+int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots);
 
 #ifdef __cplusplus
 }

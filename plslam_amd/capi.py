@@ -56,12 +56,27 @@ ABI_SYMBOLS = (
     "plslam_bow_db_create", "plslam_bow_db_destroy", "plslam_bow_db_insert", "plslam_bow_db_insert_dev", "plslam_bow_db_size",
     "plslam_bow_db_score",
     "plslam_loop_closure_verify", "plslam_loop_closure_verify_dev", "plslam_relpose_robust_gn",
+    "plslam_gba_plan_create", "plslam_gba_optimize", "plslam_gba_plan_destroy", "plslam_dense_ldlt_solve",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
 BOW_MAX_SET = 16384      # include/plslam_hip.h: PLSLAM_BOW_MAX_SET
 LC_MAX_FEATURES = 16384  # include/plslam_hip.h: PLSLAM_LC_MAX_FEATURES
 LC_MAX_ITERS = 10000     # include/plslam_hip.h: PLSLAM_LC_MAX_ITERS
+GBA_MAX_KEYFRAMES = 4096  # include/plslam_hip.h: PLSLAM_GBA_MAX_KEYFRAMES
+GBA_STOP_MAX_ITERS, GBA_STOP_ERR, GBA_STOP_DX = 0, 1, 2
+
+
+class GbaSolve(C.Structure):
+    """plslam_gba_solve: one record per solve of plslam_gba_optimize"""
+    _fields_ = [("lambda_", C.c_double), ("err_raw", C.c_double), ("err", C.c_double), ("dx_norm", C.c_double),
+                ("n_singular", C.c_int32), ("n_bad_pivots", C.c_int32), ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GbaResult(C.Structure):
+    """plslam_gba_result"""
+    _fields_ = [("iters", C.c_int32), ("n_solves", C.c_int32), ("stop_reason", C.c_int32), ("reserved", C.c_int32),
+                ("err", C.c_double), ("err_prev", C.c_double), ("lambda_", C.c_double), ("hmax", C.c_double)]
 
 
 class Cam(C.Structure):
@@ -361,13 +376,18 @@ def load() -> C.CDLL:
     L.plslam_loop_closure_verify_dev.argtypes = [vp, C.POINTER(LcParams), C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), vp,
                                                  vp, vp, vp, vp, vp]
     L.plslam_relpose_robust_gn.argtypes = [vp, C.POINTER(LcParams), vp, vp, i32, vp, vp, i32, C.POINTER(LcResult), vp, vp]
+    L.plslam_gba_plan_create.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(vp)]
+    L.plslam_gba_optimize.argtypes = [vp, f64, f64, i32] + [vp] * 8 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)]
+    L.plslam_gba_plan_destroy.argtypes = [vp]
+    L.plslam_gba_plan_destroy.restype = None
+    L.plslam_dense_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32)]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("plslam_strerror", "plslam_last_error", "plslam_ctx_destroy",
                         "plslam_match_plan_destroy", "plslam_lba_plan_destroy", "plslam_grid_plan_destroy",
                         "plslam_match_pipeline_destroy", "plslam_pinned_alloc", "plslam_pinned_free",
                         "plslam_grid_pair_capacity", "plslam_grid_pair_capacity_bound", "plslam_bow_vocab_destroy",
-                        "plslam_bow_db_destroy"):
+                        "plslam_bow_db_destroy", "plslam_gba_plan_destroy"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -1394,3 +1414,66 @@ def _hip_memcpy_dtod(dst: int, src: int, nbytes: int) -> int:
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipMemcpy.restype = C.c_int
     return hip.hipMemcpy(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 3)      # hipMemcpyDeviceToDevice
+
+
+class GbaPlan:
+    """plslam_gba_plan: the global bundle adjustment of the reference (levMarquardtOptimizationGBA) over one map.
+
+    pt_obs / ls_obs: the reference's Vector6i rows (n, 6) -- landmark map index, landmark local index, observation index,
+    keyframe map index, keyframe local index (-1: keyframe 0), inlier flag; pt_uv (n, 2) / ls_l (n, 3) the observations;
+    kf_list[k]: the map index of optimised keyframe k."""
+
+    def __init__(self, ctx: Context, cam: Cam, n_map_kf, kf_list, npt, nls, pt_obs, pt_uv, ls_obs, ls_l, homog_th=1e-7):
+        self._L = ctx._L
+        self._ctx = ctx
+        kl = _arr(kf_list, np.int32, (-1,))
+        po, lo = _arr(pt_obs, np.int32, (-1, 6)), _arr(ls_obs, np.int32, (-1, 6))
+        uv, ll = _arr(pt_uv, np.float64, (-1, 2)), _arr(ls_l, np.float64, (-1, 3))
+        self.dims = (int(n_map_kf), kl.shape[0], int(npt), int(nls))
+        self._h = None
+        h = C.c_void_p()
+        _check(self._L.plslam_gba_plan_create(ctx.handle, C.byref(cam), float(homog_th), int(n_map_kf), kl.shape[0], _p(kl),
+                                              int(npt), int(nls), _p(po), _p(uv), po.shape[0], _p(lo), _p(ll), lo.shape[0],
+                                              C.byref(h)), "plslam_gba_plan_create")
+        self._h = h
+
+    def optimize(self, T_kf_w, x_kf, Xw, Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15) -> dict:
+        """The LM loop -> dict(x_kf (nkf, 6), T (nkf, 4, 4), Xw (npt, 3), Lw (nls, 6), trace (one dict per solve), iters,
+        n_solves, stop_reason, err, err_prev, lam, hmax)."""
+        n_map, nkf, npt, nls = self.dims
+        T = _arr(T_kf_w, np.float64, (n_map, 16))
+        x = _arr(x_kf, np.float64, (nkf, 6))
+        X, Lm = _arr(Xw, np.float64, (npt, 3)), _arr(Lw, np.float64, (nls, 6))
+        xo, To, Xo, Lo = np.empty((nkf, 6)), np.empty((nkf, 4, 4)), np.empty((npt, 3)), np.empty((nls, 6))
+        tr = (GbaSolve * max(int(max_iters), 1))()
+        res = GbaResult()
+        _check(self._L.plslam_gba_optimize(self._h, float(lambda_lm), float(lambda_k), int(max_iters), _p(T), _p(x), _p(X),
+                                           _p(Lm), _p(xo), _p(To), _p(Xo), _p(Lo), tr, C.byref(res)), "plslam_gba_optimize")
+        trace = [dict(lam=t.lambda_, err_raw=t.err_raw, err=t.err, dx_norm=t.dx_norm, n_singular=t.n_singular,
+                      n_bad_pivots=t.n_bad_pivots, accepted=bool(t.accepted)) for t in tr[:res.n_solves]]
+        return dict(x_kf=xo, T=To, Xw=Xo, Lw=Lo, trace=trace, iters=res.iters, n_solves=res.n_solves,
+                    stop_reason=res.stop_reason, err=res.err, err_prev=res.err_prev, lam=res.lambda_, hmax=res.hmax)
+
+    def close(self) -> None:
+        # a plan is destroyed before its context: once the context is closed the handle is only dropped
+        if self._h is not None and self._h.value and self._ctx.handle:
+            self._L.plslam_gba_plan_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dense_ldlt_solve(ctx: Context, A, b):
+    """plslam_dense_ldlt_solve: x with (the lower triangle of A, mirrored) x = b on the device -> (x, number of zero /
+    non-finite pivots)."""
+    A = _arr(A, np.float64)
+    n = A.shape[0]
+    assert A.shape == (n, n)
+    bb = _arr(b, np.float64, (n,))
+    x, nb = np.empty(n), C.c_int32(0)
+    _check(ctx._L.plslam_dense_ldlt_solve(ctx.handle, n, _p(A), _p(bb), _p(x), C.byref(nb)), "plslam_dense_ldlt_solve")
+    return x, int(nb.value)

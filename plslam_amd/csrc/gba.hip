@@ -1,0 +1,939 @@
+// gba.hip -- the global bundle adjustment of the reference (MapHandler::globalBundleAdjustment + levMarquardtOptimizationGBA,
+// src/mapHandler.cpp:1995-2099, :2101-2703) on the device, on top of the LBA plan's public device-block API.
+//
+// The rows, H and g of every pass are the LBA plan's (plslam_lba_plan_iterate_dev / _iterate_resident: PLSLAM_LBA_COMPAT_GBA on
+// the first pass, PLSLAM_LBA_COMPAT_ITER_PASS on every later one -- DESIGN.md section 5).  What this file adds is the solve that
+// scales to the whole map:
+//   K26 k_gba_hmax             max |H(i,i)| over all N diagonal entries (the first pass's Hmax, :2359-2364)
+//   K27 k_gba_landmarks<DL>    a lane per landmark: Vj' = Vj + lambda diag(Vj), its inverse (Gauss-Jordan, no pivoting: a pivot
+//                              that is not positive makes the landmark singular -- no contribution, zero step), tj = Vj'^-1 gj
+//   K28 k_gba_cross<DL>        a lane per observation of an optimised keyframe: Y_o = Vj'^-1 W_o
+//   K29 k_gba_pairs            a workgroup per ragged chunk (<= 64 observation pairs of one covisible block, one kind): the
+//                              chunk's sum of W_o1^T Y_o2, pair after pair
+//   K30 k_gba_blocks           a workgroup per covisible block (k1 >= k2): S(k1,k2) = [H_pose + lambda diag]delta - chunk sums
+//   K31 k_gba_rhs              a workgroup per keyframe: b_k = g_k - sum_o W_o^T t_lm(o)
+//   K32 k_ldlt_diag            one workgroup: L D L^T of the 32 x 32 diagonal tile (pivots that are zero / not finite counted)
+//   K33 k_ldlt_panel           a workgroup per row tile below it: L_ik = A_ik L_kk^-T D^-1 (and X_ik = L_ik D kept)
+//   K34 k_ldlt_update          a workgroup per lower tile of the trailing matrix: A_ij -= X_ik L_jk^T on v_mfma_f64_16x16x4_f64
+//   K35 k_ldlt_fwd             per tile column: L y = b (+ the D scaling), the rows below updated in parallel
+//   K36 k_ldlt_bwd             per tile row, last first: L^T x = z, the rows above updated in parallel
+//   K37 k_gba_backsub<DL>      a lane per landmark: dxj = Vj'^-1 (gj - sum_o W_o dp[kf(o)]), X += dx when the step is taken
+//   K38 k_gba_pose             a lane per optimised keyframe: x <- logmap(expmap(x) inverse(expmap(dp))), its estimate slot
+//   K39 k_gba_stats            ||DX||^2 over all N unknowns, singular landmarks, bad pivots: 24 bytes for the host
+// Every sum has a fixed shape (no floating-point atomics): two runs give the same bits.  Phases are ordered by kernel
+// boundaries only -- no grid barrier, no device-scope fence.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "common.hpp"
+#include "se3_dev.hpp"
+
+namespace plslam {
+namespace {
+
+constexpr int GBA_CHUNK = 64;   // observation pairs per chunk of K29
+constexpr int LT = 32;          // LDL^T tile edge
+typedef double dvec4_t __attribute__((ext_vector_type(4)));
+
+struct GbaStats {               // what crosses to the host per solve
+    double dx_sumsq;
+    int32_t n_singular, n_bad_pivots;
+};
+struct GbaBlock { int32_t k1, k2, c0, c1; };          // covisible block (k1 >= k2) and its chunk range
+struct GbaChunk { int32_t blk, line, p0, np; };       // chunk: block, kind (1 = lines), first pair, pair count
+
+// ---- K26 ----------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_gba_hmax(const double* __restrict__ Hp, int32_t nkf, const double* __restrict__ Hpt, int32_t npt, const double* __restrict__ Hls,
+           int32_t nls, double* __restrict__ out)
+{
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    const int64_t n1 = 6 * (int64_t)nkf, n2 = n1 + 3 * (int64_t)npt, n3 = n2 + 6 * (int64_t)nls;
+    double m = 0.0;
+    for (int64_t i = t; i < n3; i += 256) {
+        double v;
+        if (i < n1) v = Hp[(i / 6) * 36 + (i % 6) * 7];
+        else if (i < n2) v = Hpt[((i - n1) / 3) * 9 + ((i - n1) % 3) * 4];
+        else v = Hls[((i - n2) / 6) * 36 + ((i - n2) % 6) * 7];
+        v = fabs(v);
+        if (v > m) m = v;            // a NaN diagonal never wins the comparison (as in the reference's test)
+    }
+    red[t] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s && red[t + s] > red[t]) red[t] = red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) out[0] = red[0];
+}
+
+// ---- K27 ----------------------------------------------------------------------------------------------------------------
+template <int DL>
+__global__ void __launch_bounds__(256)
+k_gba_landmarks(const double* __restrict__ H, const double* __restrict__ g, int32_t nlm, double lambda, double* __restrict__ Vinv,
+                double* __restrict__ tv, int32_t* __restrict__ sing)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= nlm) return;
+    double A[DL][DL], I[DL][DL];
+#pragma unroll
+    for (int a = 0; a < DL; ++a)
+#pragma unroll
+        for (int b = 0; b < DL; ++b) {
+            const double h = H[(size_t)j * DL * DL + a * DL + b];
+            A[a][b] = a == b ? h + lambda * h : h;
+            I[a][b] = a == b ? 1.0 : 0.0;
+        }
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < DL; ++c) {
+        const double piv = A[c][c];
+        ok = ok && piv > 0.0;
+        const double ip = 1.0 / (piv > 0.0 ? piv : 1.0);
+#pragma unroll
+        for (int b = 0; b < DL; ++b) { A[c][b] *= ip; I[c][b] *= ip; }
+#pragma unroll
+        for (int a = 0; a < DL; ++a) {
+            if (a == c) continue;
+            const double f = A[a][c];
+#pragma unroll
+            for (int b = 0; b < DL; ++b) { A[a][b] -= f * A[c][b]; I[a][b] -= f * I[c][b]; }
+        }
+    }
+    double gj[DL];
+#pragma unroll
+    for (int a = 0; a < DL; ++a) gj[a] = g[(size_t)j * DL + a];
+#pragma unroll
+    for (int a = 0; a < DL; ++a) {
+        double acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < DL; ++b) {
+            const double v = ok ? I[a][b] : 0.0;
+            Vinv[(size_t)j * DL * DL + a * DL + b] = v;
+            acc += v * gj[b];
+        }
+        tv[(size_t)j * DL + a] = acc;
+    }
+    sing[j] = ok ? 0 : 1;
+}
+
+// ---- K28: Y_o = Vinv_j W_o (DL x 6), for the observations of optimised keyframes ------------------------------------------------
+template <int DL>
+__global__ void __launch_bounds__(256)
+k_gba_cross(const int32_t* __restrict__ lm, const int32_t* __restrict__ kf, int32_t nobs, const double* __restrict__ Vinv,
+            const double* __restrict__ W, double* __restrict__ Y)
+{
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= nobs || kf[o] < 0) return;
+    const int j = lm[o];
+    double V[DL * DL], w[DL * 6];
+#pragma unroll
+    for (int i = 0; i < DL * DL; ++i) V[i] = Vinv[(size_t)j * DL * DL + i];
+#pragma unroll
+    for (int i = 0; i < DL * 6; ++i) w[i] = W[(size_t)o * DL * 6 + i];
+#pragma unroll
+    for (int x = 0; x < DL; ++x)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            double acc = 0.0;
+#pragma unroll
+            for (int y = 0; y < DL; ++y) acc += V[x * DL + y] * w[y * 6 + b];
+            Y[(size_t)o * DL * 6 + x * 6 + b] = acc;
+        }
+}
+
+// ---- K29: a chunk's sum of W_o1^T Y_o2 -----------------------------------------------------------------------------------
+template <int DL>
+__device__ __forceinline__ void gba_pair_product(const double* __restrict__ W, const double* __restrict__ Y, int o1, int o2,
+                                                 double* __restrict__ out /* LDS, [36] with stride GBA_CHUNK */)
+{
+    double w1[DL * 6], y2[DL * 6];
+#pragma unroll
+    for (int i = 0; i < DL * 6; ++i) { w1[i] = W[(size_t)o1 * DL * 6 + i]; y2[i] = Y[(size_t)o2 * DL * 6 + i]; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            double acc = 0.0;
+#pragma unroll
+            for (int x = 0; x < DL; ++x) acc += w1[x * 6 + a] * y2[x * 6 + b];
+            out[(a * 6 + b) * GBA_CHUNK] = acc;
+        }
+}
+
+__global__ void __launch_bounds__(GBA_CHUNK)
+k_gba_pairs(const GbaChunk* __restrict__ chunks, const int2* __restrict__ pairs, const double* __restrict__ W_pt,
+            const double* __restrict__ Y_pt, const double* __restrict__ W_ls, const double* __restrict__ Y_ls,
+            double* __restrict__ part)
+{
+    __shared__ double prod[36 * GBA_CHUNK];
+    const GbaChunk c = chunks[blockIdx.x];
+    const int i = threadIdx.x;
+    if (i < c.np) {
+        const int2 q = pairs[c.p0 + i];
+        if (c.line) gba_pair_product<6>(W_ls, Y_ls, q.x, q.y, prod + i);
+        else gba_pair_product<3>(W_pt, Y_pt, q.x, q.y, prod + i);
+    }
+    __syncthreads();
+    if (i < 36) {
+        double s = 0.0;
+        for (int p = 0; p < c.np; ++p) s += prod[i * GBA_CHUNK + p];    // pair after pair, in list order
+        part[(size_t)blockIdx.x * 36 + i] = s;
+    }
+}
+
+// ---- K30: S(k1,k2) = [H_pose + lambda diag] delta(k1,k2) - sum of its chunks, lower blocks only ---------------------------------
+__global__ void __launch_bounds__(64)
+k_gba_blocks(const GbaBlock* __restrict__ blocks, const double* __restrict__ part, const double* __restrict__ Hp, double lambda,
+             double* __restrict__ S, int64_t ld)
+{
+    const GbaBlock B = blocks[blockIdx.x];
+    const int e = threadIdx.x;
+    if (e >= 36) return;
+    const int a = e / 6, b = e % 6;
+    double v = 0.0;
+    if (B.k1 == B.k2) {
+        const double h = Hp[(size_t)B.k1 * 36 + e];
+        v = a == b ? h + lambda * h : h;
+    }
+    for (int c = B.c0; c < B.c1; ++c) v -= part[(size_t)c * 36 + e];
+    S[(6 * (int64_t)B.k1 + a) * ld + 6 * (int64_t)B.k2 + b] = v;
+}
+
+// the padding of the matrix beyond n: identity, so that every tile is full
+__global__ void __launch_bounds__(256)
+k_pad_diag(double* __restrict__ S, int64_t ld, int32_t n, int32_t npad)
+{
+    const int i = n + blockIdx.x * 256 + threadIdx.x;
+    if (i < npad) S[(int64_t)i * ld + i] = 1.0;
+}
+
+// ---- K31: b_k = g_k - sum over the keyframe's observations of W_o^T t_lm(o) ---------------------------------------------------
+template <int DL>
+__device__ __forceinline__ void gba_rhs_term(const double* __restrict__ W, const double* __restrict__ tv, int o, int j, double (&acc)[6])
+{
+    double t[DL];
+#pragma unroll
+    for (int x = 0; x < DL; ++x) t[x] = tv[(size_t)j * DL + x];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int x = 0; x < DL; ++x) s += W[(size_t)o * DL * 6 + x * 6 + a] * t[x];
+        acc[a] += s;
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_gba_rhs(const int32_t* __restrict__ kp_ptr, const int32_t* __restrict__ kp_obs, const int32_t* __restrict__ kl_ptr,
+          const int32_t* __restrict__ kl_obs, const int32_t* __restrict__ pt_lm, const int32_t* __restrict__ ls_lm,
+          const double* __restrict__ W_pt, const double* __restrict__ t_pt, const double* __restrict__ W_ls,
+          const double* __restrict__ t_ls, const double* __restrict__ g, double* __restrict__ b)
+{
+    __shared__ double red[6][64];
+    const int k = blockIdx.x, i = threadIdx.x;
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int q = kp_ptr[k] + i; q < kp_ptr[k + 1]; q += 64) { const int o = kp_obs[q]; gba_rhs_term<3>(W_pt, t_pt, o, pt_lm[o], acc); }
+    for (int q = kl_ptr[k] + i; q < kl_ptr[k + 1]; q += 64) { const int o = kl_obs[q]; gba_rhs_term<6>(W_ls, t_ls, o, ls_lm[o], acc); }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) red[a][i] = acc[a];
+    __syncthreads();
+    for (int s = 32; s > 0; s >>= 1) {
+        if (i < s)
+#pragma unroll
+            for (int a = 0; a < 6; ++a) red[a][i] += red[a][i + s];
+        __syncthreads();
+    }
+    if (i < 6) b[6 * (size_t)k + i] = g[6 * (size_t)k + i] - red[i][0];
+}
+
+// ---- K32-K34: right-looking blocked L D L^T of the lower triangle, in place (strict lower: L, diagonal: D) --------------------
+__global__ void __launch_bounds__(256)
+k_ldlt_diag(double* __restrict__ S, int64_t ld, int32_t k, int32_t* __restrict__ badp)
+{
+    __shared__ double A[LT][LT + 1];
+    __shared__ double col[LT];
+    const int t = threadIdx.x;
+    double* T0 = S + (int64_t)k * LT * ld + (int64_t)k * LT;
+    for (int e = t; e < LT * LT; e += 256) {
+        const int i = e / LT, c = e % LT;
+        A[i][c] = c <= i ? T0[(int64_t)i * ld + c] : 0.0;     // the lower triangle only
+    }
+    int bad = 0;
+    for (int j = 0; j < LT; ++j) {
+        __syncthreads();
+        const double d = A[j][j];
+        if (t == 0 && !(d != 0.0 && isfinite(d))) ++bad;
+        if (t > j && t < LT) { const double l = A[t][j] / d; col[t] = l; A[t][j] = l; }
+        __syncthreads();
+        for (int e = t; e < LT * LT; e += 256) {
+            const int i = e / LT, c = e % LT;
+            if (c > j && i >= c) A[i][c] -= col[i] * (d * col[c]);
+        }
+    }
+    __syncthreads();
+    for (int e = t; e < LT * LT; e += 256) {
+        const int i = e / LT, c = e % LT;
+        if (c <= i) T0[(int64_t)i * ld + c] = A[i][c];
+    }
+    if (t == 0) badp[k] = bad;
+}
+
+// row tile i = k + 1 + blockIdx.x: X = A_ik L_kk^-T (forward over the columns), L_ik = X D^-1; X goes to the panel buffer
+__global__ void __launch_bounds__(64)
+k_ldlt_panel(double* __restrict__ S, int64_t ld, int32_t k, double* __restrict__ P)
+{
+    __shared__ double Lk[LT][LT + 1];
+    const int r = threadIdx.x;
+    const int64_t i0 = (int64_t)(k + 1 + blockIdx.x) * LT;
+    const double* Tk = S + (int64_t)k * LT * ld + (int64_t)k * LT;
+    for (int e = r; e < LT * LT; e += 64) Lk[e / LT][e % LT] = Tk[(int64_t)(e / LT) * ld + e % LT];
+    __syncthreads();
+    if (r >= LT) return;
+    double* row = S + (i0 + r) * ld + (int64_t)k * LT;
+    double x[LT];
+#pragma unroll
+    for (int c = 0; c < LT; ++c) x[c] = row[c];
+#pragma unroll
+    for (int j = 0; j < LT; ++j) {
+        double s = x[j];
+#pragma unroll
+        for (int p = 0; p < j; ++p) s -= x[p] * Lk[j][p];
+        x[j] = s;
+    }
+    double* prow = P + (i0 + r) * LT;
+#pragma unroll
+    for (int j = 0; j < LT; ++j) {
+        prow[j] = x[j];
+        row[j] = x[j] / Lk[j][j];
+    }
+}
+
+// lower tile (i, j), k < j <= i: A_ij -= X_ik L_jk^T.  Four waves, one 16 x 16 quadrant each, eight MFMA steps of k = 4.
+// v_mfma_f64_16x16x4_f64: A[row lane&15][k lane>>4], B[k lane>>4][col lane&15], D[row (lane>>4) + 4 q][col lane&15].
+__global__ void __launch_bounds__(256)
+k_ldlt_update(double* __restrict__ S, int64_t ld, int32_t k, const double* __restrict__ P)
+{
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj > ti) return;
+    __shared__ double Xs[LT][LT + 1], Ls[LT][LT + 1];
+    const int64_t i0 = (int64_t)(k + 1 + ti) * LT, j0 = (int64_t)(k + 1 + tj) * LT;
+    const int t = threadIdx.x;
+    for (int e = t; e < LT * LT; e += 256) {
+        const int r = e / LT, c = e % LT;
+        Xs[r][c] = P[(i0 + r) * LT + c];
+        Ls[r][c] = S[(j0 + r) * ld + (int64_t)k * LT + c];
+    }
+    __syncthreads();
+    const int w = t >> 6, lane = t & 63;
+    const int r0 = (w >> 1) * 16, c0 = (w & 1) * 16;
+    dvec4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < LT / 4; ++s) {
+        const double a = Xs[r0 + (lane & 15)][4 * s + (lane >> 4)];
+        const double b = Ls[c0 + (lane & 15)][4 * s + (lane >> 4)];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+    }
+    double* C = S + (i0 + r0) * ld + j0 + c0 + (lane & 15);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) C[(int64_t)((lane >> 4) + 4 * q) * ld] -= acc[q];
+}
+
+// ---- K35 / K36: the triangular solves.  Launch k of the forward solve: every workgroup solves L_kk y_k = w_k (w_k is final:
+// only tiles below k change in this launch); workgroup 0 writes z_k = y_k / d_k, workgroup t > 0 updates w_(k+t) -= L y_k. ------
+__global__ void __launch_bounds__(64)
+k_ldlt_fwd(const double* __restrict__ S, int64_t ld, int32_t k, double* __restrict__ w, double* __restrict__ z)
+{
+    __shared__ double Ls[LT][LT + 1];
+    __shared__ double ys[LT];
+    const int r = threadIdx.x;
+    const int64_t k0 = (int64_t)k * LT;
+    for (int e = r; e < LT * LT; e += 64) Ls[e / LT][e % LT] = S[(k0 + e / LT) * ld + k0 + e % LT];
+    __syncthreads();
+    double y = r < LT ? w[k0 + r] : 0.0;
+    for (int j = 0; j < LT; ++j) {
+        const double yj = __shfl(y, j);
+        if (r > j && r < LT) y -= Ls[r][j] * yj;
+    }
+    if (r < LT) ys[r] = y;
+    const int64_t i0 = (int64_t)(k + blockIdx.x) * LT;
+    if (blockIdx.x == 0) {
+        if (r < LT) z[k0 + r] = y / Ls[r][r];
+        return;
+    }
+    __syncthreads();
+    for (int e = r; e < LT * LT; e += 64) Ls[e / LT][e % LT] = S[(i0 + e / LT) * ld + k0 + e % LT];
+    __syncthreads();
+    if (r < LT) {
+        double acc = 0.0;
+        for (int c = 0; c < LT; ++c) acc += Ls[r][c] * ys[c];
+        w[i0 + r] -= acc;
+    }
+}
+
+// launch k of the backward solve (k descending): L_kk^T x_k = u_k; workgroup k writes x_k, workgroup j < k updates
+// u_j -= L_kj^T x_k
+__global__ void __launch_bounds__(64)
+k_ldlt_bwd(const double* __restrict__ S, int64_t ld, int32_t k, double* __restrict__ u, double* __restrict__ x)
+{
+    __shared__ double Ls[LT][LT + 1];
+    __shared__ double xs[LT];
+    const int c = threadIdx.x;
+    const int64_t k0 = (int64_t)k * LT;
+    for (int e = c; e < LT * LT; e += 64) Ls[e / LT][e % LT] = S[(k0 + e / LT) * ld + k0 + e % LT];
+    __syncthreads();
+    double v = c < LT ? u[k0 + c] : 0.0;
+    for (int r = LT - 1; r >= 0; --r) {
+        const double xr = __shfl(v, r);
+        if (c < r) v -= Ls[r][c] * xr;
+    }
+    if (c < LT) xs[c] = v;
+    const int j = blockIdx.x;
+    if (j == k) {
+        if (c < LT) x[k0 + c] = v;
+        return;
+    }
+    const int64_t j0 = (int64_t)j * LT;
+    __syncthreads();
+    for (int e = c; e < LT * LT; e += 64) Ls[e / LT][e % LT] = S[(k0 + e / LT) * ld + j0 + e % LT];
+    __syncthreads();
+    if (c < LT) {
+        double acc = 0.0;
+        for (int r = 0; r < LT; ++r) acc += Ls[r][c] * xs[r];
+        u[j0 + c] -= acc;
+    }
+}
+
+// ---- K37: landmark steps ----------------------------------------------------------------------------------------------------
+template <int DL>
+__global__ void __launch_bounds__(256)
+k_gba_backsub(const int32_t* __restrict__ lm_ptr, const int32_t* __restrict__ lm_obs, const int32_t* __restrict__ kf,
+              int32_t nlm, const double* __restrict__ W, const double* __restrict__ Vinv, const double* __restrict__ g,
+              const double* __restrict__ dp, int32_t apply, double* __restrict__ X, double* __restrict__ part)
+{
+    __shared__ double red[256];
+    const int t = threadIdx.x, j = blockIdx.x * 256 + t;
+    double ss = 0.0;
+    if (j < nlm) {
+        double rhs[DL];
+#pragma unroll
+        for (int x = 0; x < DL; ++x) rhs[x] = g[(size_t)j * DL + x];
+        for (int q = lm_ptr[j]; q < lm_ptr[j + 1]; ++q) {
+            const int o = lm_obs[q];
+            const int k = kf[o];
+            double d[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) d[a] = dp[6 * (size_t)k + a];
+#pragma unroll
+            for (int x = 0; x < DL; ++x) {
+                double s = 0.0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) s += W[(size_t)o * DL * 6 + x * 6 + a] * d[a];
+                rhs[x] -= s;
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < DL; ++x) {
+            double s = 0.0;
+#pragma unroll
+            for (int y = 0; y < DL; ++y) s += Vinv[(size_t)j * DL * DL + x * DL + y] * rhs[y];
+            ss += s * s;
+            if (apply) X[(size_t)j * DL + x] += s;
+        }
+    }
+    red[t] = ss;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+// ---- K38: the pose update of :2371-2377 / :2650-2655, and the estimate slot the next pass's point rows read -----------------------
+__global__ void __launch_bounds__(256)
+k_gba_pose(int32_t nkf, const double* __restrict__ dp, int32_t apply, double* __restrict__ xkf, double* __restrict__ Test,
+           double* __restrict__ part)
+{
+    __shared__ double red[256];
+    const int t = threadIdx.x, k = blockIdx.x * 256 + t;
+    double ss = 0.0;
+    if (k < nkf) {
+        double d[6], x[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { d[a] = dp[6 * (size_t)k + a]; ss += d[a] * d[a]; x[a] = xkf[6 * (size_t)k + a]; }
+        if (apply) {
+            double Tp[16], E[16], Ei[16], Tc[16];
+            expmap_se3(x, Tp);
+            expmap_se3(d, E);
+            inverse_se3(E, Ei);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    Tc[4 * i + c] = Tp[4 * i] * Ei[c] + Tp[4 * i + 1] * Ei[4 + c] + Tp[4 * i + 2] * Ei[8 + c] + Tp[4 * i + 3] * Ei[12 + c];
+            logmap_se3(Tc, x);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) xkf[6 * (size_t)k + a] = x[a];
+            expmap_se3(x, Tp);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) Test[16 * (size_t)k + i] = Tp[i];
+        }
+    }
+    red[t] = ss;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+// ---- K39 -------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_gba_stats(const double* __restrict__ part, int32_t npart, const int32_t* __restrict__ sing, int32_t nsing,
+            const int32_t* __restrict__ badp, int32_t nbad, GbaStats* __restrict__ out)
+{
+    __shared__ int32_t red[256];
+    const int t = threadIdx.x;
+    int c = 0;
+    for (int i = t; i < nsing; i += 256) c += sing[i];
+    red[t] = c;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) {
+        double ss = 0.0;
+        for (int i = 0; i < npart; ++i) ss += part[i];     // the partials in a fixed order
+        int nb = 0;
+        for (int i = 0; i < nbad; ++i) nb += badp[i];
+        out->dx_sumsq = ss;
+        out->n_singular = red[0];
+        out->n_bad_pivots = nb;
+    }
+}
+
+// ---- host side of the LDL^T: the matrix S (npad x npad, row-major, lower triangle read) is factored in place and
+// S x = b solved; w, z: npad doubles of workspace (w holds b on entry and is overwritten); P: npad x 32 doubles ------------------
+int ldlt_enqueue(double* S, int64_t npad, double* P, double* w, double* z, double* x, int32_t* badp, hipStream_t s)
+{
+    const int nt = (int)(npad / LT);
+    for (int k = 0; k < nt; ++k) {
+        hipLaunchKernelGGL(k_ldlt_diag, dim3(1), dim3(256), 0, s, S, npad, k, badp);
+        const int T = nt - k - 1;
+        if (T > 0) {
+            hipLaunchKernelGGL(k_ldlt_panel, dim3(T), dim3(64), 0, s, S, npad, k, P);
+            hipLaunchKernelGGL(k_ldlt_update, dim3(T, T), dim3(256), 0, s, S, npad, k, (const double*)P);
+        }
+    }
+    for (int k = 0; k < nt; ++k) hipLaunchKernelGGL(k_ldlt_fwd, dim3(nt - k), dim3(64), 0, s, (const double*)S, npad, k, w, z);
+    for (int k = nt - 1; k >= 0; --k) hipLaunchKernelGGL(k_ldlt_bwd, dim3(k + 1), dim3(64), 0, s, (const double*)S, npad, k, z, x);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    return PLSLAM_OK;
+}
+
+inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }
+
+}  // namespace
+}  // namespace plslam
+
+using namespace plslam;
+
+struct plslam_gba_plan {
+    plslam_ctx* ctx = nullptr;
+    plslam_lba_plan* lba = nullptr;
+    int32_t n_map = 0, nkf = 0, npt = 0, nls = 0, np = 0, nl = 0;
+    int64_t n = 0, npad = 0;
+    int32_t nblk = 0, nchunk = 0, nt = 0;
+    std::vector<int32_t> kf_list;           // map index of optimised keyframe k
+    DevBuf stat, work, Sbuf;
+    // static lists (stat)
+    size_t oBlk = 0, oChk = 0, oPair = 0, oPlm = 0, oPkf = 0, oLlm = 0, oLkf = 0, oKpp = 0, oKpo = 0, oKlp = 0, oKlo = 0,
+           oLpp = 0, oLpo = 0, oLlp = 0, oLlo = 0;
+    // per-iteration arrays (work)
+    size_t oVp = 0, oTp = 0, oVl = 0, oTl = 0, oSp = 0, oSl = 0, oYp = 0, oYl = 0, oPart = 0, oP = 0, oW = 0, oZ = 0, oDp = 0,
+           oBad = 0, oSsPart = 0, oStats = 0, oHmax = 0, oX = 0;
+    int32_t nss = 0;                         // partials of ||DX||^2: pose workgroups, point workgroups, line workgroups
+};
+
+namespace {
+
+int gba_fail(plslam_gba_plan* G, int rc)
+{
+    if (G->lba) plslam_lba_plan_destroy(G->lba);
+    G->stat.release(); G->work.release(); G->Sbuf.release();
+    delete G;
+    return rc;
+}
+
+// one damped solve on the blocks the LBA plan left on the device: Schur complement, LDL^T, landmark and pose steps, stats
+int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t s)
+{
+    plslam_lba_blocks B;
+    plslam_lba_state st;
+    int rc;
+    if ((rc = plslam_lba_plan_device_blocks(G->lba, &B)) || (rc = plslam_lba_plan_device_state(G->lba, &st))) return rc;
+    char* d = G->stat.as<char>();
+    char* wk = G->work.as<char>();
+    auto I32 = [&](size_t o) { return (const int32_t*)(d + o); };
+    auto D = [&](size_t o) { return (double*)(wk + o); };
+    double* S = G->Sbuf.as<double>();
+    const int32_t nkf = G->nkf, npt = G->npt, nls = G->nls;
+    const double* g_pt = B.g + 6 * (size_t)nkf;
+    const double* g_ls = g_pt + 3 * (size_t)npt;
+    if (npt)
+        hipLaunchKernelGGL(k_gba_landmarks<3>, dim3((npt + 255) / 256), dim3(256), 0, s, B.H_pt, g_pt, npt, lambda, D(G->oVp),
+                           D(G->oTp), (int32_t*)(wk + G->oSp));
+    if (nls)
+        hipLaunchKernelGGL(k_gba_landmarks<6>, dim3((nls + 255) / 256), dim3(256), 0, s, B.H_ls, g_ls, nls, lambda, D(G->oVl),
+                           D(G->oTl), (int32_t*)(wk + G->oSl));
+    if (G->np)
+        hipLaunchKernelGGL(k_gba_cross<3>, dim3((G->np + 255) / 256), dim3(256), 0, s, I32(G->oPlm), I32(G->oPkf), G->np,
+                           (const double*)D(G->oVp), B.W_pt, D(G->oYp));
+    if (G->nl)
+        hipLaunchKernelGGL(k_gba_cross<6>, dim3((G->nl + 255) / 256), dim3(256), 0, s, I32(G->oLlm), I32(G->oLkf), G->nl,
+                           (const double*)D(G->oVl), B.W_ls, D(G->oYl));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)G->npad * (size_t)G->npad * 8, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(D(G->oW), 0, (size_t)G->npad * 8, s));
+    if (G->nchunk)
+        hipLaunchKernelGGL(k_gba_pairs, dim3(G->nchunk), dim3(GBA_CHUNK), 0, s, (const GbaChunk*)(d + G->oChk),
+                           (const int2*)(d + G->oPair), B.W_pt, (const double*)D(G->oYp), B.W_ls, (const double*)D(G->oYl),
+                           D(G->oPart));
+    hipLaunchKernelGGL(k_gba_blocks, dim3(G->nblk), dim3(64), 0, s, (const GbaBlock*)(d + G->oBlk), (const double*)D(G->oPart),
+                       B.H_pose, lambda, S, G->npad);
+    if (G->npad > G->n)
+        hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, G->npad, (int32_t)G->n, (int32_t)G->npad);
+    hipLaunchKernelGGL(k_gba_rhs, dim3(nkf), dim3(64), 0, s, I32(G->oKpp), I32(G->oKpo), I32(G->oKlp), I32(G->oKlo), I32(G->oPlm),
+                       I32(G->oLlm), B.W_pt, (const double*)D(G->oTp), B.W_ls, (const double*)D(G->oTl), B.g, D(G->oW));
+    if ((rc = ldlt_enqueue(S, G->npad, D(G->oP), D(G->oW), D(G->oZ), D(G->oDp), (int32_t*)(wk + G->oBad), s))) return rc;
+    const int nwp = (npt + 255) / 256, nwl = (nls + 255) / 256, nwk = (nkf + 255) / 256;
+    double* part = D(G->oSsPart);
+    hipLaunchKernelGGL(k_gba_pose, dim3(nwk), dim3(256), 0, s, nkf, (const double*)D(G->oDp), (int32_t)apply, D(G->oX),
+                       st.T_kf_w + 16 * (size_t)G->n_map, part);
+    if (npt)
+        hipLaunchKernelGGL(k_gba_backsub<3>, dim3(nwp), dim3(256), 0, s, I32(G->oLpp), I32(G->oLpo), I32(G->oPkf), npt, B.W_pt,
+                           (const double*)D(G->oVp), g_pt, (const double*)D(G->oDp), (int32_t)apply, st.Xw, part + nwk);
+    if (nls)
+        hipLaunchKernelGGL(k_gba_backsub<6>, dim3(nwl), dim3(256), 0, s, I32(G->oLlp), I32(G->oLlo), I32(G->oLkf), nls, B.W_ls,
+                           (const double*)D(G->oVl), g_ls, (const double*)D(G->oDp), (int32_t)apply, st.Lw, part + nwk + nwp);
+    // the singular flags of points and lines lie back to back (oSp, oSl carved contiguously)
+    hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)part, nwk + nwp + nwl, (const int32_t*)(wk + G->oSp),
+                       npt + nls, (const int32_t*)(wk + G->oBad), G->nt, (GbaStats*)(wk + G->oStats));
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    return PLSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf, const int32_t* kf_list, int32_t npt, int32_t nls, const int32_t* pt_obs,
+                           const double* pt_obs_uv, int32_t n_pt_obs, const int32_t* ls_obs, const double* ls_l_obs,
+                           int32_t n_ls_obs, plslam_gba_plan** out)
+{
+    PLSLAM_REQUIRE(ctx && K && out && n_map_kf >= 0 && nkf >= 1 && npt >= 0 && nls >= 0 && n_pt_obs >= 0 && n_ls_obs >= 0,
+                   PLSLAM_EINVAL);
+    *out = nullptr;
+    PLSLAM_REQUIRE(nkf <= PLSLAM_GBA_MAX_KEYFRAMES && kf_list, PLSLAM_EINVAL);
+    // the iteration pass's line rows are the LBA plan's COMPAT_ITER_PASS rows only where homogTh is the literal they spell
+    PLSLAM_REQUIRE(homog_th == 1e-7, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(n_pt_obs == 0 || (pt_obs && pt_obs_uv), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(n_ls_obs == 0 || (ls_obs && ls_l_obs), PLSLAM_EINVAL);
+    // 32-bit addressing: observation blocks (DL x 6 doubles each), landmark blocks and pair lists are indexed with int32
+    PLSLAM_REQUIRE((int64_t)n_pt_obs * 18 < INT32_MAX && (int64_t)n_ls_obs * 36 < INT32_MAX &&
+                   (int64_t)npt * 9 < INT32_MAX && (int64_t)nls * 36 < INT32_MAX, PLSLAM_EINVAL);
+    for (int32_t k = 0; k < nkf; ++k) PLSLAM_REQUIRE(kf_list[k] >= 0 && kf_list[k] < n_map_kf, PLSLAM_EINVAL);
+    std::vector<int32_t> plm(n_pt_obs), pkf(n_pt_obs), pslot(n_pt_obs), llm(n_ls_obs), lkf(n_ls_obs), lslot(n_ls_obs);
+    // Vector6i columns: 0 landmark map index, 1 landmark local index, 2 observation index, 3 keyframe map index, 4 keyframe
+    // local index (-1: keyframe 0, not optimised), 5 inlier flag
+    for (int32_t o = 0; o < n_pt_obs; ++o) {
+        const int32_t* v = pt_obs + 6 * (size_t)o;
+        PLSLAM_REQUIRE(v[1] >= 0 && v[1] < npt && v[3] >= 0 && v[3] < n_map_kf && v[4] >= -1 && v[4] < nkf, PLSLAM_EINVAL);
+        PLSLAM_REQUIRE(v[4] < 0 || kf_list[v[4]] == v[3], PLSLAM_EINVAL);
+        plm[o] = v[1]; pkf[o] = v[4];
+        pslot[o] = v[4] >= 0 ? n_map_kf + v[4] : v[3];      // points of optimised keyframes read the estimate (:2411-2416)
+    }
+    for (int32_t o = 0; o < n_ls_obs; ++o) {
+        const int32_t* v = ls_obs + 6 * (size_t)o;
+        PLSLAM_REQUIRE(v[1] >= 0 && v[1] < nls && v[3] >= 0 && v[3] < n_map_kf && v[4] >= -1 && v[4] < nkf, PLSLAM_EINVAL);
+        PLSLAM_REQUIRE(v[4] < 0 || kf_list[v[4]] == v[3], PLSLAM_EINVAL);
+        llm[o] = v[1]; lkf[o] = v[4];
+        lslot[o] = v[3];                                     // lines always read the stored pose (:2523)
+    }
+    plslam_gba_plan* G = new (std::nothrow) plslam_gba_plan();
+    PLSLAM_REQUIRE(G != nullptr, PLSLAM_ENOMEM);
+    G->ctx = ctx; G->n_map = n_map_kf; G->nkf = nkf; G->npt = npt; G->nls = nls; G->np = n_pt_obs; G->nl = n_ls_obs;
+    G->kf_list.assign(kf_list, kf_list + nkf);
+    G->n = 6 * (int64_t)nkf;
+    G->npad = pad_to_tile(G->n);
+    G->nt = (int32_t)(G->npad / LT);
+    int rc = plslam_lba_plan_create(ctx, K, homog_th, n_map_kf + nkf, nkf, npt, nls, plm.data(), pslot.data(), pkf.data(),
+                                    pt_obs_uv, n_pt_obs, llm.data(), lslot.data(), lkf.data(), ls_l_obs, n_ls_obs, &G->lba);
+    if (rc) return gba_fail(G, rc);
+
+    // landmark -> its observations by optimised keyframes, list order; keyframe -> its observations, list order
+    auto csr = [](const std::vector<int32_t>& key, const std::vector<int32_t>& kf, int32_t nkey, std::vector<int32_t>& ptr,
+                  std::vector<int32_t>& ids) {
+        ptr.assign(nkey + 1, 0);
+        for (size_t o = 0; o < key.size(); ++o) if (kf[o] >= 0) ++ptr[key[o] + 1];
+        for (int32_t i = 0; i < nkey; ++i) ptr[i + 1] += ptr[i];
+        ids.assign(ptr[nkey], 0);
+        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+        for (size_t o = 0; o < key.size(); ++o) if (kf[o] >= 0) ids[fill[key[o]]++] = (int32_t)o;
+    };
+    std::vector<int32_t> lpp, lpo, llp, llo, kpp, kpo, klp, klo;
+    csr(plm, pkf, npt, lpp, lpo);
+    csr(llm, lkf, nls, llp, llo);
+    csr(pkf, pkf, nkf, kpp, kpo);
+    csr(lkf, lkf, nkf, klp, klo);
+
+    // covisible blocks: every ordered pair (o1, o2) of a landmark's observations with kf(o1) >= kf(o2) falls in lower block
+    // (kf(o1), kf(o2)); blocks sorted by (k1, k2), a block's point pairs before its line pairs, each in landmark order
+    struct Pr { int64_t key; int32_t line, o1, o2; };
+    std::vector<Pr> prs;
+    auto add_pairs = [&](const std::vector<int32_t>& ptr, const std::vector<int32_t>& ids, const std::vector<int32_t>& kf, int line,
+                         int32_t nlm) {
+        for (int32_t j = 0; j < nlm; ++j)
+            for (int32_t a = ptr[j]; a < ptr[j + 1]; ++a)
+                for (int32_t b = ptr[j]; b < ptr[j + 1]; ++b) {
+                    const int32_t o1 = ids[a], o2 = ids[b];
+                    if (kf[o1] >= kf[o2]) prs.push_back({(int64_t)kf[o1] * nkf + kf[o2], line, o1, o2});
+                }
+    };
+    add_pairs(lpp, lpo, pkf, 0, npt);
+    add_pairs(llp, llo, lkf, 1, nls);
+    for (int32_t k = 0; k < nkf; ++k) prs.push_back({(int64_t)k * nkf + k, 2, -1, -1});   // every diagonal block exists
+    std::stable_sort(prs.begin(), prs.end(), [](const Pr& x, const Pr& y) { return x.key != y.key ? x.key < y.key : x.line < y.line; });
+    std::vector<GbaBlock> blks;
+    std::vector<GbaChunk> chks;
+    std::vector<int2> pairs;
+    pairs.reserve(prs.size());
+    for (size_t i = 0; i < prs.size();) {
+        size_t e = i;
+        while (e < prs.size() && prs[e].key == prs[i].key) ++e;
+        GbaBlock B{(int32_t)(prs[i].key / nkf), (int32_t)(prs[i].key % nkf), (int32_t)chks.size(), 0};
+        for (size_t q = i; q < e;) {
+            if (prs[q].line == 2) { ++q; continue; }
+            size_t r = q;
+            while (r < e && prs[r].line == prs[q].line && r - q < (size_t)GBA_CHUNK) ++r;
+            chks.push_back({(int32_t)blks.size(), prs[q].line, (int32_t)pairs.size(), (int32_t)(r - q)});
+            for (size_t u = q; u < r; ++u) pairs.push_back(make_int2(prs[u].o1, prs[u].o2));
+            q = r;
+        }
+        B.c1 = (int32_t)chks.size();
+        blks.push_back(B);
+        i = e;
+    }
+    if (pairs.size() >= (size_t)INT32_MAX || chks.size() * 36 >= (size_t)INT32_MAX) return gba_fail(G, PLSLAM_EINVAL);
+    prs.clear(); prs.shrink_to_fit();
+    G->nblk = (int32_t)blks.size(); G->nchunk = (int32_t)chks.size();
+
+    Carver cs;
+    G->oBlk = cs.take(blks.size() * sizeof(GbaBlock)); G->oChk = cs.take(chks.size() * sizeof(GbaChunk) + 16);
+    G->oPair = cs.take(pairs.size() * 8 + 8);
+    G->oPlm = cs.take(plm.size() * 4 + 4); G->oPkf = cs.take(pkf.size() * 4 + 4);
+    G->oLlm = cs.take(llm.size() * 4 + 4); G->oLkf = cs.take(lkf.size() * 4 + 4);
+    G->oKpp = cs.take(kpp.size() * 4); G->oKpo = cs.take(kpo.size() * 4 + 4); G->oKlp = cs.take(klp.size() * 4);
+    G->oKlo = cs.take(klo.size() * 4 + 4); G->oLpp = cs.take(lpp.size() * 4); G->oLpo = cs.take(lpo.size() * 4 + 4);
+    G->oLlp = cs.take(llp.size() * 4); G->oLlo = cs.take(llo.size() * 4 + 4);
+    const size_t np = (size_t)n_pt_obs, nl = (size_t)n_ls_obs;
+    const int nwp = (npt + 255) / 256, nwl = (nls + 255) / 256, nwk = (nkf + 255) / 256;
+    G->nss = nwp + nwl + nwk;
+    Carver cw;
+    G->oVp = cw.take((size_t)npt * 72 + 8); G->oTp = cw.take((size_t)npt * 24 + 8);
+    G->oVl = cw.take((size_t)nls * 288 + 8); G->oTl = cw.take((size_t)nls * 48 + 8);
+    G->oSp = cw.take(0);                                  // point flags, then line flags, back to back
+    cw.off += ((size_t)npt + nls) * 4;
+    G->oSl = G->oSp + (size_t)npt * 4;
+    cw.take(8);
+    G->oYp = cw.take(np * 144 + 8); G->oYl = cw.take(nl * 288 + 8);
+    G->oPart = cw.take(chks.size() * 288 + 8);
+    G->oP = cw.take((size_t)G->npad * LT * 8); G->oW = cw.take((size_t)G->npad * 8); G->oZ = cw.take((size_t)G->npad * 8);
+    G->oDp = cw.take((size_t)G->npad * 8); G->oBad = cw.take((size_t)G->nt * 4 + 4);
+    G->oSsPart = cw.take((size_t)G->nss * 8 + 8); G->oStats = cw.take(sizeof(GbaStats)); G->oHmax = cw.take(8);
+    G->oX = cw.take((size_t)nkf * 48);
+    if ((rc = G->stat.reserve(cs.off + 256)) || (rc = G->work.reserve(cw.off + 256)) ||
+        (rc = G->Sbuf.reserve((size_t)G->npad * (size_t)G->npad * 8)))
+        return gba_fail(G, rc);
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard dg_(ctx->device);
+        hipStream_t s = ctx->stream;
+        char* d = G->stat.as<char>();
+        auto up = [&](size_t off, const void* src, size_t bytes) -> int {
+            if (bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s));
+            return PLSLAM_OK;
+        };
+        if ((rc = up(G->oBlk, blks.data(), blks.size() * sizeof(GbaBlock))) ||
+            (rc = up(G->oChk, chks.data(), chks.size() * sizeof(GbaChunk))) || (rc = up(G->oPair, pairs.data(), pairs.size() * 8)) ||
+            (rc = up(G->oPlm, plm.data(), np * 4)) || (rc = up(G->oPkf, pkf.data(), np * 4)) ||
+            (rc = up(G->oLlm, llm.data(), nl * 4)) || (rc = up(G->oLkf, lkf.data(), nl * 4)) ||
+            (rc = up(G->oKpp, kpp.data(), kpp.size() * 4)) || (rc = up(G->oKpo, kpo.data(), kpo.size() * 4)) ||
+            (rc = up(G->oKlp, klp.data(), klp.size() * 4)) || (rc = up(G->oKlo, klo.data(), klo.size() * 4)) ||
+            (rc = up(G->oLpp, lpp.data(), lpp.size() * 4)) || (rc = up(G->oLpo, lpo.data(), lpo.size() * 4)) ||
+            (rc = up(G->oLlp, llp.data(), llp.size() * 4)) || (rc = up(G->oLlo, llo.data(), llo.size() * 4))) {
+            (void)hipStreamSynchronize(s);
+            return gba_fail(G, rc);
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) return gba_fail(G, PLSLAM_EHIP);
+    }
+    *out = G;
+    return PLSLAM_OK;
+}
+
+int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba, const double* T_kf_w,
+                        const double* x_kf, const double* Xw, const double* Lw, double* x_kf_out, double* T_out, double* Xw_out,
+                        double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result)
+{
+    PLSLAM_REQUIRE(G && x_kf && x_kf_out && (G->n_map == 0 || T_kf_w) && (G->npt == 0 || (Xw && Xw_out)) &&
+                   (G->nls == 0 || (Lw && Lw_out)), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lambda_lba_k != 0.0, PLSLAM_EINVAL);
+    plslam_ctx* ctx = G->ctx;
+    DeviceGuard dg_(ctx->device);
+    const int32_t nkf = G->nkf, n_map = G->n_map;
+    const double eps = std::numeric_limits<double>::epsilon();
+    // Npt_obs / Nls_obs are never incremented (:2121, :2230): every err is divided by zero (:2356, :2635)
+    const double n_obs_counted = 0.0;
+    // pose slots: the stored T_kf_w of every keyframe, then the estimate slots -- which hold the stored poses too on the first
+    // pass (:2136: every row of the first pass reads map_keyframes[kf]->T_kf_w)
+    std::vector<double> T((size_t)(n_map + nkf) * 16);
+    if (n_map) std::memcpy(T.data(), T_kf_w, (size_t)n_map * 128);
+    for (int32_t k = 0; k < nkf; ++k) std::memcpy(&T[16 * (size_t)(n_map + k)], &T_kf_w[16 * (size_t)G->kf_list[k]], 128);
+    double err_raw = 0.0;
+    int rc = plslam_lba_plan_iterate_dev(G->lba, T.data(), Xw, Lw, PLSLAM_LBA_COMPAT_GBA, nullptr, &err_raw);
+    if (rc) return rc;
+    plslam_lba_blocks B;
+    if ((rc = plslam_lba_plan_device_blocks(G->lba, &B))) return rc;
+    hipStream_t s = (hipStream_t)B.stream;
+    char* wk = G->work.as<char>();
+    double hmax = 0.0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard dg2_(ctx->device);
+        StreamSyncOnError guard(s);
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(wk + G->oX, x_kf, (size_t)nkf * 48, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_gba_hmax, dim3(1), dim3(256), 0, s, B.H_pose, nkf, B.H_pt, G->npt, B.H_ls, G->nls,
+                           (double*)(wk + G->oHmax));
+        PLSLAM_HIP_CHECK(hipGetLastError());
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(&hmax, wk + G->oHmax, 8, hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+        guard.dismiss();
+    }
+    // int Hmax = 0.0 (:2359): the comparisons run against the truncated running maximum, so Hmax ends as trunc(max |H(i,i)|)
+    const double Hmax = std::trunc(hmax);
+    double lambda = lambda_lba_lm * Hmax, lambda_k = lambda_lba_k;
+    int32_t nsol = 0;
+    auto solve = [&](double err_raw_, double err_, bool apply, GbaStats& st) -> int {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard dg3_(ctx->device);
+        StreamSyncOnError guard(s);
+        int r = gba_solve_enqueue(G, lambda, apply, s);
+        if (r) return r;
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(&st, wk + G->oStats, sizeof(GbaStats), hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+        guard.dismiss();
+        if (trace) {
+            plslam_gba_solve& t = trace[nsol];
+            t.lambda = lambda; t.err_raw = err_raw_; t.err = err_; t.dx_norm = std::sqrt(st.dx_sumsq);
+            t.n_singular = st.n_singular; t.n_bad_pivots = st.n_bad_pivots; t.accepted = apply ? 1 : 0; t.reserved = 0;
+        }
+        ++nsol;
+        return PLSLAM_OK;
+    };
+    GbaStats st{};
+    double err = err_raw / n_obs_counted;
+    if ((rc = solve(err_raw, err, true, st))) return rc;            // the first solve is always applied (:2366-2380)
+    double err_prev = err;
+    int32_t iters, stop = PLSLAM_GBA_STOP_MAX_ITERS;
+    for (iters = 1; iters < max_iters_lba; ++iters) {
+        if ((rc = plslam_lba_plan_iterate_resident(G->lba, PLSLAM_LBA_COMPAT_ITER_PASS, &err_raw))) return rc;
+        err = err_raw / n_obs_counted;
+        if (std::fabs(err - err_prev) < eps || err < eps) { stop = PLSLAM_GBA_STOP_ERR; break; }
+        const bool accept = !(err > err_prev);
+        if ((rc = solve(err_raw, err, accept, st))) return rc;
+        if (accept) lambda *= lambda_k;
+        else lambda /= lambda_k;
+        if (std::sqrt(st.dx_sumsq) < eps) { stop = PLSLAM_GBA_STOP_DX; break; }
+        err_prev = err;
+    }
+    // the write-back (:2674-2702): T_kf_w = expmap(X) of every optimised keyframe, point3D / line3D = X
+    plslam_lba_state ls;
+    if ((rc = plslam_lba_plan_device_state(G->lba, &ls))) return rc;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard dg4_(ctx->device);
+        StreamSyncOnError guard(s);
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(x_kf_out, wk + G->oX, (size_t)nkf * 48, hipMemcpyDeviceToHost, s));
+        if (T_out)
+            PLSLAM_HIP_CHECK(hipMemcpyAsync(T_out, ls.T_kf_w + 16 * (size_t)n_map, (size_t)nkf * 128, hipMemcpyDeviceToHost, s));
+        if (G->npt) PLSLAM_HIP_CHECK(hipMemcpyAsync(Xw_out, ls.Xw, (size_t)G->npt * 24, hipMemcpyDeviceToHost, s));
+        if (G->nls) PLSLAM_HIP_CHECK(hipMemcpyAsync(Lw_out, ls.Lw, (size_t)G->nls * 48, hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+        guard.dismiss();
+    }
+    if (result) {
+        result->iters = iters; result->n_solves = nsol; result->stop_reason = stop; result->reserved = 0;
+        result->err = err; result->err_prev = err_prev; result->lambda = lambda; result->hmax = hmax;
+    }
+    return PLSLAM_OK;
+}
+
+void plslam_gba_plan_destroy(plslam_gba_plan* G)
+{
+    if (!G) return;
+    {
+        std::lock_guard<std::mutex> lk(G->ctx->mu);
+        DeviceGuard dg_(G->ctx->device);
+        (void)hipStreamSynchronize(G->ctx->stream);
+        G->stat.release(); G->work.release(); G->Sbuf.release();
+    }
+    if (G->lba) plslam_lba_plan_destroy(G->lba);
+    delete G;
+}
+
+int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots)
+{
+    PLSLAM_REQUIRE(ctx && n >= 1 && A && b && x && n <= 6 * PLSLAM_GBA_MAX_KEYFRAMES, PLSLAM_EINVAL);
+    const int64_t npad = pad_to_tile(n);
+    const int nt = (int)(npad / LT);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard dg_(ctx->device);
+    hipStream_t s = ctx->stream;
+    DevBuf buf;
+    Carver c;
+    const size_t oS = c.take((size_t)npad * npad * 8), oP = c.take((size_t)npad * LT * 8), oW = c.take((size_t)npad * 8),
+                 oZ = c.take((size_t)npad * 8), oX = c.take((size_t)npad * 8), oB = c.take((size_t)nt * 4),
+                 oR = c.take(sizeof(GbaStats));
+    int rc = buf.reserve(c.off);
+    if (rc) return rc;
+    struct Rel { DevBuf& b; hipStream_t s; ~Rel() { (void)hipStreamSynchronize(s); b.release(); } } rel{buf, s};
+    char* d = buf.as<char>();
+    double* S = (double*)(d + oS);
+    PLSLAM_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)npad * npad * 8, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d + oW, 0, (size_t)npad * 8, s));
+    PLSLAM_HIP_CHECK(hipMemcpy2DAsync(S, (size_t)npad * 8, A, (size_t)n * 8, (size_t)n * 8, n, hipMemcpyHostToDevice, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oW, b, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, npad, n, (int32_t)npad);
+    if ((rc = ldlt_enqueue(S, npad, (double*)(d + oP), (double*)(d + oW), (double*)(d + oZ), (double*)(d + oX),
+                           (int32_t*)(d + oB), s)))
+        return rc;
+    hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)nullptr, 0, (const int32_t*)nullptr, 0,
+                       (const int32_t*)(d + oB), nt, (GbaStats*)(d + oR));
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    GbaStats st{};
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(x, d + oX, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(&st, d + oR, sizeof(GbaStats), hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    if (n_bad_pivots) *n_bad_pivots = st.n_bad_pivots;
+    return PLSLAM_OK;
+}
+
+}  // extern "C"

@@ -8,8 +8,12 @@ StereoFrame's epipolar / disparity / overlap gates over the two L<->R tables -- 
 With N > 1 ranks (one per GPU, torch.distributed 'nccl' == RCCL) every rank runs its own shard of
 pairs (weak scaling) and the per-pair match tables are gathered to rank 0 inside the step.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full adds everything else this
+script measures or checks: the CPU baseline, the check of every output against the oracle, the exclusive kernel times and
+rooflines, the secondary records (other sizes, kernels and configurations) -- each of them runs after the timed steps.
+
 Prints ONE compact JSON line on rank 0 (the contract's keys, < 6 kB) and writes the full record -- secondary
-records, distributions, notes -- to gpurun_out/bench_full.json (see DESIGN.md "Measurement" for every field).
+records, distributions, notes -- to a side file (--full-json; see DESIGN.md "Measurement" for every field).
 """
 from __future__ import annotations
 
@@ -59,6 +63,81 @@ def usable_cpus() -> int:
     return max(1, n)
 
 
+INPUT_PIECE_PAIRS = 64          # make_inputs: pairs per piece of work, one restart period of synth.stereo_stream's frame chain
+_INPUTS = None                  # make_inputs: (shared mapping, per-batch array layouts, workload) -- inherited by the forked workers
+
+
+def _input_views(buf, layout):
+    return {k: np.frombuffer(buf, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape)
+            for k, (shape, dt, off) in layout.items()}
+
+
+def _make_input_piece(job):
+    """(worker) pairs [lo, hi) of batch `b`: synth's own generators over the piece, rows 1.. (and the halo, row 0, for the
+    batch's first piece) written into the shared mapping."""
+    from plslam_amd import synth
+    b, lo, hi = job
+    buf, layouts, (B, n_orb, n_lbd, first_pair, seeds, geometry) = _INPUTS
+    views = _input_views(buf, layouts[b])
+    st = synth.stereo_stream(hi - lo, n_orb, n_lbd, seed=seeds[b], first_pair=lo)
+    parts = [st, synth.stereo_geometry(st, first_pair=lo)] if geometry else [st]
+    r0 = 0 if lo == first_pair else 1
+    a = lo - first_pair
+    for part in parts:
+        for k, v in part.items():
+            views[k][a + r0:a + v.shape[0]] = v[r0:]
+
+
+def make_inputs(B, n_orb, n_lbd, first_pair, seeds, geometry, workers):
+    """The run's synthetic inputs, one batch per seed: (synth.stereo_stream(B, n_orb, n_lbd, seed, first_pair), and with
+    `geometry` synth.stereo_geometry(that stream, first_pair=first_pair), else None) -- bit for bit what those calls return,
+    generated in pieces by `workers` processes.  Every frame of the stream depends only on (seed, frame) and on its chain,
+    which restarts every 64 frames, and every frame's geometry only on (frame, its stream row): pieces cut where a chain
+    restarts are independent.  The arrays are views of one shared anonymous mapping the workers write into; they are forked
+    before this process touches the GPU (call this before torch is imported)."""
+    global _INPUTS
+    import mmap
+    F = B + 1
+    shapes = {"orb_l": ((F, n_orb, 32), np.uint8), "orb_r": ((F, n_orb, 32), np.uint8),
+              "lbd_l": ((F, n_lbd, 32), np.uint8), "lbd_r": ((F, n_lbd, 32), np.uint8),
+              "orb_rperm": ((F, n_orb), np.int32), "orb_rfresh": ((F, n_orb), np.bool_),
+              "lbd_rperm": ((F, n_lbd), np.int32), "lbd_rfresh": ((F, n_lbd), np.bool_)}
+    geo_keys = ("kp_l", "kp_r", "seg_l", "seg_r")
+    if geometry:
+        shapes.update(kp_l=((F, n_orb, 2), np.float32), kp_r=((F, n_orb, 2), np.float32),
+                      seg_l=((F, n_lbd, 4), np.float32), seg_r=((F, n_lbd, 4), np.float32))
+    layouts, off = [], 0
+    for _ in seeds:
+        lay = {}
+        for k, (shape, dt) in shapes.items():
+            lay[k] = (shape, np.dtype(dt), off)
+            off += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 64) * 64
+        layouts.append(lay)
+    buf = mmap.mmap(-1, max(off, 1))                    # MAP_SHARED | MAP_ANONYMOUS: the forked workers write into it
+    # piece boundaries: the batch's first pair, then every pair whose halo frame (pair - 1) starts a chain
+    cuts = [first_pair] + list(range(((first_pair - 1) // INPUT_PIECE_PAIRS + 1) * INPUT_PIECE_PAIRS + 1, first_pair + B,
+                                     INPUT_PIECE_PAIRS)) + [first_pair + B]
+    jobs = [(b, lo, hi) for b in range(len(seeds)) for lo, hi in zip(cuts[:-1], cuts[1:])]
+    _INPUTS = (buf, layouts, (B, n_orb, n_lbd, first_pair, tuple(seeds), geometry))
+    try:
+        workers = max(1, min(workers, len(jobs)))
+        if workers == 1:
+            for j in jobs:
+                _make_input_piece(j)
+        else:
+            import multiprocessing
+            from concurrent.futures import ProcessPoolExecutor
+            with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("fork")) as ex:
+                list(ex.map(_make_input_piece, jobs))
+    finally:
+        _INPUTS = None
+    out = []
+    for lay in layouts:
+        v = _input_views(buf, lay)
+        out.append(({k: a for k, a in v.items() if k not in geo_keys}, {k: v[k] for k in geo_keys} if geometry else None))
+    return out
+
+
 SCAN_KERNEL_SOURCES = ("common.hpp", "mfma_h_common.hpp", "hamming.hip", "hamming_mfma.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip",
                        "hamming_mfma_i.hip", "hamming_mfma_d.hip")
 
@@ -83,11 +162,10 @@ def _short(s, n=120):
 
 
 def compact_line(full: dict, side_path) -> dict:
-    """The ONE stdout line: the bench contract's keys, `roofline`, `hbm_roofline`, `cpu_baseline`, `verified` -- numbers and
-    short strings only.  Everything else of the full record (secondary records, step-time distribution, the one-batch
-    comparison, executed-instruction figures, notes) is in the side file `details`."""
+    """The ONE stdout line: the bench contract's keys and, with --full, `roofline`, `hbm_roofline`, `cpu_baseline`, `verified`
+    -- numbers and short strings only.  Everything else of the full record (secondary records, step-time distribution, the
+    one-batch comparison, executed-instruction figures, notes) is in the side file `details`."""
     c = full["config"]
-    r = full["roofline"]
     out = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data")}
     out["config"] = {"workload": _short(c["workload"], 200), "pairs_per_gpu_per_step": c["pairs_per_gpu_per_step"],
@@ -97,10 +175,11 @@ def compact_line(full: dict, side_path) -> dict:
                      "kernel_source_hash": c["kernel_source_hash"], "rccl_ranks_seen": c["rccl_ranks_seen"],
                      "gather_wire": None if c["gather_wire"] is None else {k: c["gather_wire"][k] for k in ("format", "comm")},
                      "parallelism": _short(c["parallelism"], 100)}
-    out["roofline"] = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms",
-                                             "frac_profiles", "frac_profiles_source")}
-    h = full["hbm_roofline"]
-    out["hbm_roofline"] = {k: h.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
+    if "roofline" in full:
+        r, h = full["roofline"], full["hbm_roofline"]
+        out["roofline"] = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms",
+                                                 "frac_profiles", "frac_profiles_source")}
+        out["hbm_roofline"] = {k: h.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
     out["kernel_ms"] = {k: v for k, v in full["kernel_ms"].items() if k != "note"}
     if "cpu_baseline" in full:
         b = full["cpu_baseline"]
@@ -108,7 +187,8 @@ def compact_line(full: dict, side_path) -> dict:
                                "host_logical_cpus": b.get("host_logical_cpus"), "kind": b["kind"],
                                "cores_note": f"{b['cores']} usable of {b.get('host_logical_cpus')} logical CPUs (cgroup quota)",
                                "sample": _short(b.get("sample"), 160)}
-    out["verified"] = {k: _short(v, 160) for k, v in full["verified"].items()}
+    if "verified" in full:
+        out["verified"] = {k: _short(v, 160) for k, v in full["verified"].items()}
     c4 = (full.get("secondary") or {}).get("config4_strong")
     if c4 is not None and full["n_gpus"] >= 1 and "value" in c4:
         out["config4_strong"] = {k: c4.get(k) for k in ("value", "unit", "n_gpus", "scaling", "pairs_per_gpu_per_step", "ms_per_step",
@@ -434,9 +514,14 @@ def main():
                          "sharded contiguously over the ranks (BASELINE config 4: 4096 pairs -> 512 per GPU at N = 8)")
     ap.add_argument("--batches", type=int, default=3,
                     help="N = 1: distinct input batches rotated through the timed loop (1 = the same batch every step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the check of the outputs against the oracle, the exclusive kernel "
+                         "times and rooflines, the one-repeated-batch comparison, the determinism check and the secondary records "
+                         "(other sizes, kernels and configurations; config 4 as written at N > 1).  Without it a run sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the whole-batch check it enables)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary records (tables only, popcount kernels, C5, C3) of the N = 1 line")
+                    help="--full: skip the secondary records (popcount kernels, C5, C3, ...; config 4 as written at N > 1)")
     ap.add_argument("--gather-wire", choices=("auto", "int16", "int32"), default="auto",
                     help="N > 1: wire format of the table gather (auto: both are tried for a few untimed steps, the faster one runs)")
     ap.add_argument("--force-dist", action="store_true",
@@ -480,30 +565,18 @@ def main():
     def note(msg):                                      # progress on stderr (stdout carries the JSON)
         print(f"[bench +{time.perf_counter() - T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
-    import torch
-    import torch.distributed as dist
-    import plslam_amd
     from plslam_amd import frontend, synth
-    note("imports done")
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         args.gpus = world                               # (the launcher's world size is the truth)
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    # one rank per GPU: LOCAL_RANK is the device index -- unless the launcher masks the devices per process (each then sees one)
-    ndev = torch.cuda.device_count()
-    dev_index = local_rank if local_rank < ndev else local_rank % max(ndev, 1)
-    torch.cuda.set_device(dev_index)
-    dev = torch.device("cuda", dev_index)
     use_dist = world > 1 or args.force_dist
-    if use_dist:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29531")
-        import datetime
-        # (a rank that dies leaves the others in a collective: they give up after this long instead of hanging the node)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(minutes=10))
+    overlap = not use_dist and not args.no_overlap
+    # N = 1: consecutive steps are DIFFERENT batches (round 2 alternated two plans over one batch, whose LBD sets and tables
+    # fit the 256 MB Infinity Cache): `--batches` matchers with their own descriptors, tables and plans step through the
+    # same pair of streams in rotation.  (N > 1 keeps one batch per rank: the gather pipeline owns the table buffers.)
+    nbatch = max(1, args.batches) if (overlap and not use_dist) else 1
 
     n_orb, n_lbd = args.n_orb, args.n_lbd
     if args.scaling == "strong":
@@ -515,12 +588,34 @@ def main():
     else:
         B = args.pairs_per_gpu                   # weak scaling: rank r owns pairs [r*B, (r+1)*B) of one global stream
         first_pair = rank * B
+    # every shard carries a one-pair halo (the left descriptors of the pair before its first); batch k of the rotation is
+    # seeded SEED0 + 7919 k.  Generated before torch is imported: the generator's worker processes are forked.
+    inputs = make_inputs(B, n_orb, n_lbd, first_pair, [synth.SEED0 + 7919 * k_ for k_ in range(nbatch)], not args.no_gates,
+                         max(1, usable_cpus() // world))
+    stream, geo = inputs[0]
+    note(f"synthetic stream of {B} pairs generated ({nbatch} batch(es))")
+
+    import torch
+    import torch.distributed as dist
+    import plslam_amd
+    note("imports done")
+
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    # one rank per GPU: LOCAL_RANK is the device index -- unless the launcher masks the devices per process (each then sees one)
+    ndev = torch.cuda.device_count()
+    dev_index = local_rank if local_rank < ndev else local_rank % max(ndev, 1)
+    torch.cuda.set_device(dev_index)
+    dev = torch.device("cuda", dev_index)
+    if use_dist:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29531")
+        import datetime
+        # (a rank that dies leaves the others in a collective: they give up after this long instead of hanging the node)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(minutes=10))
+
     baseline_cfg = {(800, 100): "C1-shaped (KITTI 800 ORB + 100 LBD)", (1500, 200): "C2", (4000, 600): "C5"}
     cfg_name = baseline_cfg.get((n_orb, n_lbd), "custom")
-    # every shard carries a one-pair halo (the left descriptors of the pair before its first)
-    stream = synth.stereo_stream(B, n_orb, n_lbd, seed=synth.SEED0, first_pair=first_pair)
     gates = None if args.no_gates else dict(synth.KITTI_GATES)
-    geo = None if args.no_gates else synth.stereo_geometry(stream, first_pair=first_pair)
 
     # N > 1: every rank must sit on its own GPU (a launcher that maps two ranks to one device would still "scale")
     ranks_seen = None
@@ -533,7 +628,6 @@ def main():
         ranks_seen = {"world_size": dist.get_world_size(), "distinct_devices": len(set(idents))}
         if rank == 0 and ranks_seen["distinct_devices"] != world:
             raise SystemExit(f"{world} ranks on {ranks_seen['distinct_devices']} distinct devices: {idents}")
-    note(f"synthetic stream of {B} pairs generated")
     ctx = plslam_amd.Context(dev_index)      # raises if libplslam_hip.so / a gfx950 device is missing
     for key, val in (("scan_variant", args.scan_variant), ("scan_block", args.scan_block), ("sym_rows", args.sym_rows),
                      ("group_cap", args.group_cap), ("mfma_form", args.mfma_form), ("fuse", args.fuse), ("post_workgroups", args.post_wgs)):
@@ -541,20 +635,13 @@ def main():
             ctx.set_option(key, val)
     for kv in args.opt:
         ctx.set_option(kv.split("=")[0], int(kv.split("=")[1]))
-    overlap = not use_dist and not args.no_overlap
     n_buf = max(2, args.step_streams) if (use_dist or overlap) else 1
     bm = frontend.StereoBatchMatcher(ctx, stream, nnr_p=args.nnr_p, nnr_l=args.nnr_l, mutual=True, device=dev,
                                      n_buffers=n_buf, geometry=geo, gates=gates)
     info = bm.plan.info()
     devinfo = ctx.device_info()
-    # N = 1: consecutive steps are DIFFERENT batches (round 2 alternated two plans over one batch, whose LBD sets and tables
-    # fit the 256 MB Infinity Cache): `--batches` matchers with their own descriptors, tables and plans step through the
-    # same pair of streams in rotation.  (N > 1 keeps one batch per rank: the gather pipeline owns the table buffers.)
-    nbatch = max(1, args.batches) if (overlap and not use_dist) else 1
     extra_streams, extra_bms = [], []
-    for k_ in range(1, nbatch):
-        st_k = synth.stereo_stream(B, n_orb, n_lbd, seed=synth.SEED0 + 7919 * k_, first_pair=first_pair)
-        geo_k = None if args.no_gates else synth.stereo_geometry(st_k, first_pair=first_pair)
+    for st_k, geo_k in inputs[1:]:
         extra_streams.append(st_k)
         extra_bms.append(frontend.StereoBatchMatcher(ctx, st_k, nnr_p=args.nnr_p, nnr_l=args.nnr_l, mutual=True, device=dev,
                                                      n_buffers=1, geometry=geo_k, gates=gates, streams=bm.streams))
@@ -662,7 +749,7 @@ def main():
         dump_outputs(args.dump_outputs, dumped, note)
     # the same K steps over ONE repeated batch (round 2's stepping): how much of the number is cache residency
     repeated = None
-    if nbatch > 1:
+    if args.full and nbatch > 1:
         run_steps(bm, pg, 2, 0, rotate=False)
         sync(bm, pg)
         t1 = time.perf_counter()
@@ -684,7 +771,7 @@ def main():
     # there includes the share of the GPU the other step's kernels took.  Measure the scan kernel's
     # EXCLUSIVE duration too: a few strictly serial launches, same plan, same data, HIP events.
     excl_scan_ms = excl_fin_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         p0 = bm.plans[0]
         p0.set_profiling(True)
         p0.elapsed()
@@ -701,7 +788,7 @@ def main():
     # part; rank 0's (long) verification of the headline's tables comes after it, when no collective is left.  A forced one-rank
     # group runs config 4's per-GPU shard (512 pairs) instead: the step's own overhead.
     config4 = None
-    if use_dist and not args.no_secondary:
+    if args.full and use_dist and not args.no_secondary:
         total4 = 4096 if world > 1 else 512
         note(f"config 4 as written: {total4} pairs per step over {world} rank(s) ...")
         config4 = shard_gather_record(ctx, dev, args, world, rank, total4, gather_wire["format"], gather_wire["comm"],
@@ -709,7 +796,7 @@ def main():
 
     # full-size determinism check: every output buffer was computed from the same inputs (under
     # overlap / contention), so whole tables and count arrays must be bit-identical
-    if args.steps + args.warmup >= 2:
+    if args.full and args.steps + args.warmup >= 2:
         for b_ in range(1, len(bm.tables)):
             same = torch.equal(bm.tables[0], bm.tables[b_]) and torch.equal(bm.count_bufs[0], bm.count_bufs[b_])
             if gates is not None:
@@ -721,149 +808,153 @@ def main():
 
     out = None
     if rank == 0:
-        from oracle import oracle as O
-        sl = frontend.table_slices(n_orb, n_lbd)
-        # ---- CPU baseline (N = 1 only) and, with it, the oracle's tables for the WHOLE batch --------------------------
         cpu_rec, cpu_tables = None, None
-        if world == 1 and not args.no_cpu_baseline:
-            note("cpu baseline ...")
-            cpu_rec, cpu_tables = cpu_baseline(stream, n_orb, n_lbd, args.nnr_p, args.nnr_l, args.cpu_budget_s)
-        # ---- verification of the timed output against the oracle (the checker, not the product) -----------------------
-        bufs = list(range(len(bm.tables))) if args.steps + args.warmup >= 2 else [0]
-        verified = {"match_tables": None, "stereo_gates": None}
-        if cpu_tables is not None:
-            # every pair, every problem of rank 0's batch: the table the cpu_baseline leg computed anyway
-            for b_ in bufs:
-                got = bm.tables[b_].cpu().numpy()
-                if not np.array_equal(got, cpu_tables):
-                    bad = np.argwhere(got != cpu_tables)
-                    raise SystemExit(f"bench output differs from the oracle: buffer {b_}, {len(bad)} entries, first at "
-                                     f"pair {bad[0][0]} column {bad[0][1]}")
-            verified["match_tables"] = f"all {B} pairs x 4 problems bit-exact vs the oracle ({len(bufs)} buffer(s))"
-        # N > 1 (or no CPU baseline): pair 0 and a spread of pairs of EVERY rank's table as it arrived on rank 0
-        # (through the RCCL gather, both buffers)
-        sample = frontend.spread_sample(B, 64) if cpu_tables is None else [0]
-        firsts = [frontend.shard_range(args.pairs_per_gpu, world, r_)[0] if args.scaling == "strong" else r_ * B for r_ in range(world)]
-        for b_ in bufs:
-            full = (pg.gathered(b_) if pg is not None else bm.tables[b_]).cpu().numpy()
-            bad = frontend.verify_gathered_tables(full, world if pg is not None else 1, B, n_orb, n_lbd, args.nnr_p,
-                                                  args.nnr_l, sample, lambda d1, d2, nnr: O.match(d1, d2, nnr, True)[0],
-                                                  local_stream=stream, first_pairs=firsts)
-            if bad:
-                raise SystemExit(f"bench output differs from the oracle: buffer {b_}, (rank, pair, problem) = {bad[:4]}")
-        if verified["match_tables"] is None:
-            verified["match_tables"] = (f"{len(sample)} pairs (the shard's ends + four runs spread over it) x 4 problems of EACH of "
-                                        f"{world if pg is not None else 1} rank(s) bit-exact vs the oracle ({len(bufs)} buffer(s)"
-                                        f"{', as gathered on rank 0' if pg is not None else ''})")
-        if gates is not None:
-            gsample = sorted(set(range(0, B, max(1, B // 64))) | {B - 1})
-            ref_tab = cpu_tables if cpu_tables is not None else bm.tables[0].cpu().numpy()
-            st_, sd_, sc_ = (x.cpu().numpy() for x in (bm.stereo_tabs[0], bm.stereo_disps[0], bm.stereo_cnts[0]))
-            with np.errstate(all="ignore"):
-                for i_ in gsample:
-                    ep, dp, cp = O.stereo_point_gate(ref_tab[i_, sl["orb_lr"]], geo["kp_l"][i_ + 1], geo["kp_r"][i_ + 1],
-                                                     gates["max_dist_epip"], gates["min_disp"])
-                    el, dl, cl = O.stereo_line_gate(ref_tab[i_, sl["lbd_lr"]], geo["seg_l"][i_ + 1], geo["seg_r"][i_ + 1],
-                                                    gates["min_disp"], gates["line_horiz_th"], gates["stereo_overlap_th"],
-                                                    gates["ls_min_disp_ratio"])
-                    ok = (np.array_equal(st_[i_, :n_orb], ep) and np.array_equal(st_[i_, n_orb:], el) and
-                          np.array_equal(sd_[i_, :n_orb].view(np.uint64), dp.view(np.uint64)) and
-                          np.array_equal(sd_[i_, n_orb:].view(np.uint64), dl.reshape(-1).view(np.uint64)) and
-                          sc_[i_].tolist() == [cp, cl])
-                    if not ok:
-                        raise SystemExit(f"bench stereo-gate output differs from the oracle: pair {i_}")
-            verified["stereo_gates"] = (f"{len(gsample)} pairs spread over the batch bit-exact vs the oracle (tables, "
-                                        f"disparities as raw words, counts); kept {int(sc_[:, 0].sum())} points + "
-                                        f"{int(sc_[:, 1].sum())} lines of the batch")
-        # the other batches of the rotation: whole batches when the CPU leg runs anyway, a spread of pairs otherwise
-        for k_, (eb, st_k) in enumerate(zip(extra_bms, extra_streams), start=1):
-            got = eb.tables[0].cpu().numpy()
+        verified = None
+        if args.full:
+            from oracle import oracle as O
+            sl = frontend.table_slices(n_orb, n_lbd)
+            # ---- CPU baseline (N = 1 only) and, with it, the oracle's tables for the WHOLE batch --------------------------
+            if world == 1 and not args.no_cpu_baseline:
+                note("cpu baseline ...")
+                cpu_rec, cpu_tables = cpu_baseline(stream, n_orb, n_lbd, args.nnr_p, args.nnr_l, args.cpu_budget_s)
+            # ---- verification of the timed output against the oracle (the checker, not the product) -----------------------
+            bufs = list(range(len(bm.tables))) if args.steps + args.warmup >= 2 else [0]
+            verified = {"match_tables": None, "stereo_gates": None}
             if cpu_tables is not None:
-                ref_k, _ = oracle_tables(st_k, n_orb, n_lbd, args.nnr_p, args.nnr_l)
-                if not np.array_equal(got, ref_k):
-                    bad = np.argwhere(got != ref_k)
-                    raise SystemExit(f"bench output differs from the oracle: batch {k_}, {len(bad)} entries, first at pair {bad[0][0]}")
-            else:
-                bad = frontend.verify_gathered_tables(got, 1, B, n_orb, n_lbd, args.nnr_p, args.nnr_l,
-                                                      frontend.spread_sample(B, 64),
-                                                      lambda d1, d2, nnr: O.match(d1, d2, nnr, True)[0], local_stream=st_k)
+                # every pair, every problem of rank 0's batch: the table the cpu_baseline leg computed anyway
+                for b_ in bufs:
+                    got = bm.tables[b_].cpu().numpy()
+                    if not np.array_equal(got, cpu_tables):
+                        bad = np.argwhere(got != cpu_tables)
+                        raise SystemExit(f"bench output differs from the oracle: buffer {b_}, {len(bad)} entries, first at "
+                                         f"pair {bad[0][0]} column {bad[0][1]}")
+                verified["match_tables"] = f"all {B} pairs x 4 problems bit-exact vs the oracle ({len(bufs)} buffer(s))"
+            # N > 1 (or no CPU baseline): pair 0 and a spread of pairs of EVERY rank's table as it arrived on rank 0
+            # (through the RCCL gather, both buffers)
+            sample = frontend.spread_sample(B, 64) if cpu_tables is None else [0]
+            firsts = [frontend.shard_range(args.pairs_per_gpu, world, r_)[0] if args.scaling == "strong" else r_ * B for r_ in range(world)]
+            for b_ in bufs:
+                full = (pg.gathered(b_) if pg is not None else bm.tables[b_]).cpu().numpy()
+                bad = frontend.verify_gathered_tables(full, world if pg is not None else 1, B, n_orb, n_lbd, args.nnr_p,
+                                                      args.nnr_l, sample, lambda d1, d2, nnr: O.match(d1, d2, nnr, True)[0],
+                                                      local_stream=stream, first_pairs=firsts)
                 if bad:
-                    raise SystemExit(f"bench output differs from the oracle: batch {k_}, (rank, pair, problem) = {bad[:4]}")
-        if extra_bms:
-            verified["match_tables"] += (f"; the {len(extra_bms)} other batch(es) of the rotation: " +
-                                         ("every pair" if cpu_tables is not None else "the same spread of pairs"))
-        note(f"output verified: {verified}")
+                    raise SystemExit(f"bench output differs from the oracle: buffer {b_}, (rank, pair, problem) = {bad[:4]}")
+            if verified["match_tables"] is None:
+                verified["match_tables"] = (f"{len(sample)} pairs (the shard's ends + four runs spread over it) x 4 problems of EACH of "
+                                            f"{world if pg is not None else 1} rank(s) bit-exact vs the oracle ({len(bufs)} buffer(s)"
+                                            f"{', as gathered on rank 0' if pg is not None else ''})")
+            if gates is not None:
+                gsample = sorted(set(range(0, B, max(1, B // 64))) | {B - 1})
+                ref_tab = cpu_tables if cpu_tables is not None else bm.tables[0].cpu().numpy()
+                st_, sd_, sc_ = (x.cpu().numpy() for x in (bm.stereo_tabs[0], bm.stereo_disps[0], bm.stereo_cnts[0]))
+                with np.errstate(all="ignore"):
+                    for i_ in gsample:
+                        ep, dp, cp = O.stereo_point_gate(ref_tab[i_, sl["orb_lr"]], geo["kp_l"][i_ + 1], geo["kp_r"][i_ + 1],
+                                                         gates["max_dist_epip"], gates["min_disp"])
+                        el, dl, cl = O.stereo_line_gate(ref_tab[i_, sl["lbd_lr"]], geo["seg_l"][i_ + 1], geo["seg_r"][i_ + 1],
+                                                        gates["min_disp"], gates["line_horiz_th"], gates["stereo_overlap_th"],
+                                                        gates["ls_min_disp_ratio"])
+                        ok = (np.array_equal(st_[i_, :n_orb], ep) and np.array_equal(st_[i_, n_orb:], el) and
+                              np.array_equal(sd_[i_, :n_orb].view(np.uint64), dp.view(np.uint64)) and
+                              np.array_equal(sd_[i_, n_orb:].view(np.uint64), dl.reshape(-1).view(np.uint64)) and
+                              sc_[i_].tolist() == [cp, cl])
+                        if not ok:
+                            raise SystemExit(f"bench stereo-gate output differs from the oracle: pair {i_}")
+                verified["stereo_gates"] = (f"{len(gsample)} pairs spread over the batch bit-exact vs the oracle (tables, "
+                                            f"disparities as raw words, counts); kept {int(sc_[:, 0].sum())} points + "
+                                            f"{int(sc_[:, 1].sum())} lines of the batch")
+            # the other batches of the rotation: whole batches when the CPU leg runs anyway, a spread of pairs otherwise
+            for k_, (eb, st_k) in enumerate(zip(extra_bms, extra_streams), start=1):
+                got = eb.tables[0].cpu().numpy()
+                if cpu_tables is not None:
+                    ref_k, _ = oracle_tables(st_k, n_orb, n_lbd, args.nnr_p, args.nnr_l)
+                    if not np.array_equal(got, ref_k):
+                        bad = np.argwhere(got != ref_k)
+                        raise SystemExit(f"bench output differs from the oracle: batch {k_}, {len(bad)} entries, first at pair {bad[0][0]}")
+                else:
+                    bad = frontend.verify_gathered_tables(got, 1, B, n_orb, n_lbd, args.nnr_p, args.nnr_l,
+                                                          frontend.spread_sample(B, 64),
+                                                          lambda d1, d2, nnr: O.match(d1, d2, nnr, True)[0], local_stream=st_k)
+                    if bad:
+                        raise SystemExit(f"bench output differs from the oracle: batch {k_}, (rank, pair, problem) = {bad[:4]}")
+            if extra_bms:
+                verified["match_tables"] += (f"; the {len(extra_bms)} other batch(es) of the rotation: " +
+                                             ("every pair" if cpu_tables is not None else "the same spread of pairs"))
+            note(f"output verified: {verified}")
 
         pairs_total = B * world * args.steps
-        # duration of the dominant kernel: exclusive (serial launches) for the roofline; the in-region
-        # figure (overlapped with the neighbouring step) is reported next to it
-        scan_s = excl_scan_ms / 1e3
-        achieved_gbs = info["algorithmic_bytes"] / scan_s / 1e9
         mfma = info["scan_variant"] == 4
         form = ctx.get_option("mfma_form")
         kernel_name = {4: {1: "k_scan_sym_mfma", 2: "k_scan_sym_mfma_g", 3: "k_scan_dir_mfma", 4: "k_scan_sym_mfma_h"}.get(form, "k_scan_sym_mfma_i"),
                        3: "k_scan_symmetric" + ("_r4" if info["scan_block_threads"] == 64 else ""),
                        2: "k_scan_wave_per_query", 1: "k_scan_lane_per_query"}.get(info["scan_variant"], "k_scan")
-        # HBM bytes / executed instructions of the dominant kernel per launch: PMC counters cannot be read from inside
-        # this process, so the figures come from the committed rocprofv3 passes of this same command
-        # (profiles/pmc_traffic.json) -- and ONLY when they were taken on these kernel sources (hash) and this workload.
         src_hash = kernel_source_hash()
-        wkey = f"{n_orb}+{n_lbd}:pairs{B}:{kernel_name}"
-        traffic, executed, pmc_note = None, None, "no PMC entry for these kernel sources / this workload"
-        try:
-            with open(os.path.join(_ROOT, "profiles", "pmc_traffic.json")) as f:
-                pm = json.load(f).get("entries", {}).get(wkey)
-        except OSError:
-            pm = None
-        trace_us, trace_file = None, None
-        if pm and pm.get("kernel_source_hash") == src_hash:
-            trace_us, trace_file = pm.get("trace_avg_us"), pm.get("trace_file")
-            traffic = pm["traffic_bytes_per_launch"]
-            valu_insts = pm["sq_insts_valu_per_launch"] - pm.get("sq_insts_mfma_per_launch", 0)
-            lane_ops = valu_insts * 64 / scan_s
-            executed = {"lane_ops_per_s": lane_ops, "sq_insts_valu_per_launch": valu_insts,
-                        "sq_insts_mfma_per_launch": pm.get("sq_insts_mfma_per_launch", 0),
-                        "measured_ceiling_lane_ops_per_s": pm["measured_int_valu_ceiling_lane_ops_per_s"],
-                        "frac_of_measured_ceiling": lane_ops / pm["measured_int_valu_ceiling_lane_ops_per_s"],
-                        "source": pm.get("source"),
-                        "note": "executed wave64 VALU instructions, MFMAs excluded (PMC) x 64 / exclusive scan time, against "
-                                "the issue rate measured for this integer instruction class (16 lanes/clk/SIMD)"}
-            pmc_note = pm.get("source")
-        elif pm:
-            pmc_note = "profiles/pmc_traffic.json holds this workload for OTHER kernel sources (stale): not reported"
-        timing_note = ("kernel_ms = exclusive duration (5 serial launches after the timed region, HIP events on the launch "
-                       "stream); in the timed region consecutive steps overlap on two streams, so start-to-end times there "
-                       "include the other step's share of the GPU")
-        hbm_roofline = {
-            "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel_name,
-            "kernel_ms": 1e3 * scan_s, "kernel_ms_in_timed_region": scan_ms / max(runs, 1), "timing": timing_note,
-            "algorithmic_bytes_per_launch": info["algorithmic_bytes"],
-            "note": "compulsory-byte model 32(Q+T)+16Q per directed scan; at ~17 k distance evaluations per compulsory "
-                    "kilobyte the path is compute-bound on any formulation, so this fraction is small by construction",
-        }
-        if mfma:
-            # distances come from v_mfma_scale_f32_32x32x64_f8f6f4 over fp4 +-1 codes; 256 multiply-accumulates =
-            # 512 ops per executed distance
-            mx_peak = devinfo["cu_count"] * 4 * FP4_MFMA_OPS_PER_CLK_PER_SIMD * devinfo["clock_khz"] * 1e3
-            mfma_ops = info["distance_evals"] * 512
-            roofline = {
-                "bound": "mfma", "achieved": mfma_ops / scan_s / 1e12, "peak": mx_peak / 1e12, "unit": "TFLOP/s",
-                "frac": mfma_ops / scan_s / mx_peak, "traffic": traffic, "kernel": kernel_name,
+        hbm_roofline = roofline = executed = None
+        if args.full:
+            # duration of the dominant kernel: exclusive (serial launches) for the roofline; the in-region
+            # figure (overlapped with the neighbouring step) is reported next to it
+            scan_s = excl_scan_ms / 1e3
+            achieved_gbs = info["algorithmic_bytes"] / scan_s / 1e9
+            # HBM bytes / executed instructions of the dominant kernel per launch: PMC counters cannot be read from inside
+            # this process, so the figures come from the committed rocprofv3 passes of this same command
+            # (profiles/pmc_traffic.json) -- and ONLY when they were taken on these kernel sources (hash) and this workload.
+            wkey = f"{n_orb}+{n_lbd}:pairs{B}:{kernel_name}"
+            traffic, executed, pmc_note = None, None, "no PMC entry for these kernel sources / this workload"
+            try:
+                with open(os.path.join(_ROOT, "profiles", "pmc_traffic.json")) as f:
+                    pm = json.load(f).get("entries", {}).get(wkey)
+            except OSError:
+                pm = None
+            trace_us, trace_file = None, None
+            if pm and pm.get("kernel_source_hash") == src_hash:
+                trace_us, trace_file = pm.get("trace_avg_us"), pm.get("trace_file")
+                traffic = pm["traffic_bytes_per_launch"]
+                valu_insts = pm["sq_insts_valu_per_launch"] - pm.get("sq_insts_mfma_per_launch", 0)
+                lane_ops = valu_insts * 64 / scan_s
+                executed = {"lane_ops_per_s": lane_ops, "sq_insts_valu_per_launch": valu_insts,
+                            "sq_insts_mfma_per_launch": pm.get("sq_insts_mfma_per_launch", 0),
+                            "measured_ceiling_lane_ops_per_s": pm["measured_int_valu_ceiling_lane_ops_per_s"],
+                            "frac_of_measured_ceiling": lane_ops / pm["measured_int_valu_ceiling_lane_ops_per_s"],
+                            "source": pm.get("source"),
+                            "note": "executed wave64 VALU instructions, MFMAs excluded (PMC) x 64 / exclusive scan time, against "
+                                    "the issue rate measured for this integer instruction class (16 lanes/clk/SIMD)"}
+                pmc_note = pm.get("source")
+            elif pm:
+                pmc_note = "profiles/pmc_traffic.json holds this workload for OTHER kernel sources (stale): not reported"
+            timing_note = ("kernel_ms = exclusive duration (5 serial launches after the timed region, HIP events on the launch "
+                           "stream); in the timed region consecutive steps overlap on two streams, so start-to-end times there "
+                           "include the other step's share of the GPU")
+            hbm_roofline = {
+                "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel_name,
                 "kernel_ms": 1e3 * scan_s, "kernel_ms_in_timed_region": scan_ms / max(runs, 1), "timing": timing_note,
-                "algorithmic_ops_per_launch": mfma_ops, "pmc": pmc_note,
-                # the same fraction from the COMMITTED rocprofv3 kernel trace of this command (another box, another day: boxes
-                # differ by a few per cent), when it was taken on these kernel sources
-                "frac_profiles": (mfma_ops / (trace_us * 1e-6) / mx_peak) if trace_us else None,
-                "frac_profiles_source": trace_file if trace_us else None,
-                "note": "fp4 MFMA v_mfma_f32_32x32x64_f8f6f4 (operands are the e2m1 codes of +-4 -- K1i, unscaled -- or of +-1 "
-                        "with a 2^6 block scale -- K1e..K1h; fp32 accumulation of integers below 2^24: exact); dense fp4 peak = "
-                        "CUs x 4 SIMDs x 4096 ops/clk x max clock (MI355X_MICROARCH.md measures 9099 T for the 32x32x64 "
-                        "shape); 512 ops per executed 256-bit distance (each serves both match directions).  The kernel is "
-                        "co-limited by the VALU bookkeeping that consumes the accumulators: see valu_executed",
+                "algorithmic_bytes_per_launch": info["algorithmic_bytes"],
+                "note": "compulsory-byte model 32(Q+T)+16Q per directed scan; at ~17 k distance evaluations per compulsory "
+                        "kilobyte the path is compute-bound on any formulation, so this fraction is small by construction",
             }
-        else:
-            roofline = dict(hbm_roofline, pmc=pmc_note)
+            if mfma:
+                # distances come from v_mfma_scale_f32_32x32x64_f8f6f4 over fp4 +-1 codes; 256 multiply-accumulates =
+                # 512 ops per executed distance
+                mx_peak = devinfo["cu_count"] * 4 * FP4_MFMA_OPS_PER_CLK_PER_SIMD * devinfo["clock_khz"] * 1e3
+                mfma_ops = info["distance_evals"] * 512
+                roofline = {
+                    "bound": "mfma", "achieved": mfma_ops / scan_s / 1e12, "peak": mx_peak / 1e12, "unit": "TFLOP/s",
+                    "frac": mfma_ops / scan_s / mx_peak, "traffic": traffic, "kernel": kernel_name,
+                    "kernel_ms": 1e3 * scan_s, "kernel_ms_in_timed_region": scan_ms / max(runs, 1), "timing": timing_note,
+                    "algorithmic_ops_per_launch": mfma_ops, "pmc": pmc_note,
+                    # the same fraction from the COMMITTED rocprofv3 kernel trace of this command (another box, another day: boxes
+                    # differ by a few per cent), when it was taken on these kernel sources
+                    "frac_profiles": (mfma_ops / (trace_us * 1e-6) / mx_peak) if trace_us else None,
+                    "frac_profiles_source": trace_file if trace_us else None,
+                    "note": "fp4 MFMA v_mfma_f32_32x32x64_f8f6f4 (operands are the e2m1 codes of +-4 -- K1i, unscaled -- or of +-1 "
+                            "with a 2^6 block scale -- K1e..K1h; fp32 accumulation of integers below 2^24: exact); dense fp4 peak = "
+                            "CUs x 4 SIMDs x 4096 ops/clk x max clock (MI355X_MICROARCH.md measures 9099 T for the 32x32x64 "
+                            "shape); 512 ops per executed 256-bit distance (each serves both match directions).  The kernel is "
+                            "co-limited by the VALU bookkeeping that consumes the accumulators: see valu_executed",
+                }
+            else:
+                roofline = dict(hbm_roofline, pmc=pmc_note)
         workload = (f"{cfg_name}: synthetic 752x480 stereo stream, {n_orb} ORB + {n_lbd} LBD per image, ORB+LBD L<->R and "
                     "prev<->curr, mutual + ratio (StVO::match)" +
                     ("" if gates is None else ", then StereoFrame's gates over the L<->R tables (config_kitti.yaml:25-36)") +
@@ -887,7 +978,8 @@ def main():
             "vs_baseline": None,
             "dtype": "fp4" if mfma else "u32",
             "dtype_note": ("the operand CODE of +-1 values on the matrix cores; every distance is an exact integer (fp32 accumulation "
-                           "of integers below 2^24) and every table of the timed run is compared bit for bit with the oracle's"
+                           "of integers below 2^24) and with --full every table of the timed run is compared bit for bit with "
+                           "the oracle's"
                            if mfma else "exact: XOR + popcount on 32-bit words"),
             "data": "synthetic",
             "config": {
@@ -903,17 +995,15 @@ def main():
                                ("single GPU; consecutive steps alternate two output buffers; every scan on one HIP stream, the stages behind a scan (merge, finalize, gates) on a second, high-priority one: they run under the next step's scan" if overlap
                                 else "single GPU"),
             },
-            "roofline": roofline,
-            "hbm_roofline": hbm_roofline,
-            "valu_executed": executed,
-            "kernel_ms": {"scan": excl_scan_ms, "post_scan_stages": excl_fin_ms,
-                          "scan_in_timed_region": scan_ms / max(runs, 1),
+            "kernel_ms": {"scan_in_timed_region": scan_ms / max(runs, 1),
                           "post_scan_stages_in_timed_region": fin_ms / max(runs, 1),
                           "note": "post-scan stages = column-partial merge + ratio/mutual finalize" +
                                   ("" if gates is None else " + stereo gates")},
-            "verified": verified,
             "device": devinfo["name"],
         }
+        if args.full:
+            out.update(roofline=roofline, hbm_roofline=hbm_roofline, valu_executed=executed, verified=verified)
+            out["kernel_ms"].update(scan=excl_scan_ms, post_scan_stages=excl_fin_ms)
         if cpu_rec is not None:
             out["cpu_baseline"] = cpu_rec
         if repeated is not None:
@@ -924,7 +1014,7 @@ def main():
         eb.close()
     bm.close()
     # ---- secondary records (N = 1): the other single-GPU configurations, timed by this same command ---------------------
-    if rank == 0 and world == 1 and not args.no_secondary and not use_dist:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not use_dist:
         note("secondary records ...")
         out["secondary"] = secondary_records(ctx, dev, args, note, cpu_tables if out is not None else None, streams=bm.streams)
     elif rank == 0 and config4 is not None:

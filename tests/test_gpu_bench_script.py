@@ -37,7 +37,7 @@ def _check_line(stdout, tmp_path):
 
 
 def _run(extra, tmp_path, env=None, pairs=24, n_orb=192, n_lbd=40):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
            "--pairs-per-gpu", str(pairs), "--n-orb", str(n_orb), "--n-lbd", str(n_lbd), "--full-json", str(tmp_path / "full.json")] + extra
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(env or {}))
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=e)
@@ -49,7 +49,7 @@ def test_bench_default_workload_line_is_compact(tmp_path):
     """The driver's own command shape -- default sizes (C2: 4096 pairs of 1500 ORB + 200 LBD, every secondary record) with a
     short timed region and CPU leg: the line must stay under the cap AT THIS SHAPE (round 5's was 22 kB here and came back
     `parsed: null`), carry `roofline.frac` and `cpu_baseline.value`, and name the side file holding the rest."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-budget-s", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--cpu-budget-s", "1",
            "--full-json", str(tmp_path / "full.json")]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert res.returncode == 0, res.stderr[-3000:]
@@ -133,7 +133,7 @@ def test_bench_forced_rccl_group_one_rank(tmp_path):
     torch.distributed.run (the road `python bench.py --gpus 8` takes), rank 0 prints the one line; the N > 1 stepping, the
     gather probe, the 64-pair check of the gathered tables and the config-4-as-written record all run on the one-rank group."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-gpu", "24",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-gpu", "24",
            "--n-orb", "192", "--n-lbd", "40", "--no-cpu-baseline", "--force-dist", "--full-json", str(tmp_path / "full.json")]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert res.returncode == 0, res.stderr[-3000:]
@@ -171,7 +171,7 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     dumps = []
     for run in ("a", "b"):
         out = tmp_path / run
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs-per-gpu", "24",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs-per-gpu", "24",
                "--n-orb", "192", "--n-lbd", "40", "--no-cpu-baseline", "--no-secondary", "--full-json", str(tmp_path / "full.json"),
                "--dump-outputs", str(out)]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -192,3 +192,31 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     ref, _ = bench.oracle_tables(st1, 192, 40, 0.75, 0.75)
     assert np.array_equal(d["match_table"], ref.astype(np.float32))
     assert d["match_counts"].shape == (24, 4) and d["stereo_table"].shape == (24, 192 + 40)
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the run is set-up, warm-up, timed steps, --dump-outputs and the line: the contract's keys, no
+    roofline, oracle check, CPU baseline or secondary record -- and what its last timed step computed is what the same
+    command with --full computes."""
+    import numpy as np
+    outs = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--pairs-per-gpu", "24",
+               "--n-orb", "192", "--n-lbd", "40", "--full-json", str(tmp_path / f"{mode}.json"), "--dump-outputs", str(tmp_path / mode)]
+        cmd += ["--full", "--no-cpu-baseline", "--no-secondary"] if mode == "full" else []
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0]) < LINE_CAP, res.stdout[-2000:]
+        line = json.loads(lines[0])
+        outs[mode] = (line, {f[:-4]: np.load(tmp_path / mode / f) for f in os.listdir(tmp_path / mode)})
+    line, full = outs["plain"][0], outs["full"][0]
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                         "vs_baseline", "dtype", "data", "config", "kernel_ms", "device", "details"}, sorted(line)
+    assert "roofline" in full and "verified" in full
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["higher_is_better"] is True and line["value"] == json.load(open(tmp_path / "plain.json"))["value"]
+    assert all(line[k] == full[k] for k in ("metric", "unit", "n_gpus", "dtype", "data", "config"))
+    assert "scan" not in line["kernel_ms"] and line["kernel_ms"]["scan_in_timed_region"] > 0
+    a, b = outs["plain"][1], outs["full"][1]
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)

@@ -13,8 +13,8 @@ rm -rf $O/kt_schur; rocprofv3 --kernel-trace --stats -d $O/kt_schur -o run -- py
 python $R/tools/rocpd_summary.py $(find $O/kt_schur -name "*.db" | head -1) > $O/${TAG}_lba_schur_iteration_trace.txt; rm -rf $O/kt_schur
 cat $O/${TAG}_schur.stdout >> $O/${TAG}_lba_schur_iteration_trace.txt; cat $O/${TAG}_lba_schur_iteration_trace.txt
 cd $R
-python bench.py --gpus 1 --force-dist --no-cpu-baseline > $O/${TAG}_bench_forced_dist_1rank.json 2> $O/${TAG}_bench_forced_dist_1rank.err
-python bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err
+python bench.py --full --gpus 1 --force-dist --no-cpu-baseline > $O/${TAG}_bench_forced_dist_1rank.json 2> $O/${TAG}_bench_forced_dist_1rank.err
+python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err
 python -c "
 import json
 d=json.loads(open('$O/${TAG}_bench_n1.json').readline()); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['roofline'].get('frac_profiles'), d['roofline']['traffic'])

@@ -8,7 +8,7 @@ cd $R
 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3 > $O/${TAG}_tests.txt; cat $O/${TAG}_tests.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 > $O/${TAG}_smoke.txt; cat $O/${TAG}_smoke.txt
 cp $O/lm_iteration_native.json $O/${TAG}_lm_iteration_native.json
-python bench.py --gpus 1 --force-dist --no-cpu-baseline --full-json $O/${TAG}_bench_forced_dist_1rank_full.json > $O/${TAG}_bench_forced_dist_1rank.json 2> $O/${TAG}_bench_forced_dist_1rank.err
+python bench.py --full --gpus 1 --force-dist --no-cpu-baseline --full-json $O/${TAG}_bench_forced_dist_1rank_full.json > $O/${TAG}_bench_forced_dist_1rank.json 2> $O/${TAG}_bench_forced_dist_1rank.err
 python -c "
 import json
 f=json.loads(open('$O/${TAG}_bench_forced_dist_1rank.json').readline()); print(len(json.dumps(f)), f['value'], f['ms_per_step'], f.get('config4_strong'))"

@@ -17,10 +17,10 @@ rm -rf $O/pmc_calib; rocprofv3 --pmc FETCH_SIZE -d $O/pmc_calib -o run -- /tmp/f
 python $R/tools/rocpd_summary.py $(find $O/pmc_calib -name "*.db" | head -1) > $O/${TAG}_fetch_gather_calib.txt; rm -rf $O/pmc_calib
 grep -v "^W2\|^E2\|^I2" $O/${TAG}_fetch_gather_calib.stdout | tail -8 >> $O/${TAG}_fetch_gather_calib.txt; cat $O/${TAG}_fetch_gather_calib.txt
 for x in 0 1; do
-rm -rf $O/pmc_xcd; rocprofv3 --pmc FETCH_SIZE -d $O/pmc_xcd -o run -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-secondary --batches 1 --opt post_xcd=$x > /dev/null 2>&1
+rm -rf $O/pmc_xcd; rocprofv3 --pmc FETCH_SIZE -d $O/pmc_xcd -o run -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-secondary --batches 1 --opt post_xcd=$x > /dev/null 2>&1
 python $R/tools/rocpd_summary.py $(find $O/pmc_xcd -name "*.db" | head -1) > $O/${TAG}_pmc_fetch_post_xcd$x.txt; rm -rf $O/pmc_xcd; grep -n "finalize" $O/${TAG}_pmc_fetch_post_xcd$x.txt
 done
 cd $R
-for x in 0 2 0 2; do python bench.py --no-cpu-baseline --no-secondary --steps 30 --opt post_xcd=$x 2>/dev/null | tail -1 | python -c "
+for x in 0 2 0 2; do python bench.py --full --no-cpu-baseline --no-secondary --steps 30 --opt post_xcd=$x 2>/dev/null | tail -1 | python -c "
 import json,sys; b=json.loads(sys.stdin.readline()); print('post_xcd=$x', round(b['value']), round(b['ms_per_step'],4), 'scan', round(b['kernel_ms']['scan'],4), 'stages', round(b['kernel_ms']['post_scan_stages'],4))"
 done > $O/${TAG}_post_xcd_ab.txt; cat $O/${TAG}_post_xcd_ab.txt

@@ -13,9 +13,9 @@ kt() {  # tag, command...
   python $R/tools/rocpd_summary.py $(find $O/kt_$tag -name "*.db" | head -1) > $O/${TAG}_kernel_trace_stats_$tag.txt; rm -rf $O/kt_$tag
 }
 if [ -z "$ONLY_DRIVERS" ]; then   # (ONLY_DRIVERS=1: the scan's sources are those of the last full set -- its traces and counters stand)
-kt serial python $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --batches 1
-kt overlapped python $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-secondary
-bash $R/tools/pmc_passes.sh ${TAG} python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-secondary --batches 1
+kt serial python $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --batches 1
+kt overlapped python $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-secondary
+bash $R/tools/pmc_passes.sh ${TAG} python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-overlap --no-secondary --batches 1
 cd $R && python tools/make_pmc_traffic.py ${TAG} 1500 200 4096 k_scan_sym_mfma_i 2.0 > $O/${TAG}_pmc_entry.json 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 fi
@@ -34,7 +34,7 @@ kt lba python $R/tools/lba_stream.py
 PMC_SQ_ONLY= bash $R/tools/pmc_passes.sh ${TAG}_lba python $R/tools/lba_stream.py
 fi
 fi
-cd $R && python bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err
+cd $R && python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err
 python -c "
 import json; d=json.loads(open('$O/${TAG}_bench_n1.json').readline()); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['roofline'].get('frac_profiles'), d['roofline']['traffic'], d['ms_per_step_distribution'])"
 [ -z "$ONLY_DRIVERS" ] && head -6 $O/${TAG}_kernel_trace_stats_serial.txt

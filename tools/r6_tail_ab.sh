@@ -5,7 +5,7 @@
 root=$(cd "$(dirname "$0")/.." && pwd)
 one() {  # tag, extra bench args...
   tag=$1; shift
-  python $root/bench.py --no-cpu-baseline --no-secondary --steps 30 --warmup 3 --full-json /tmp/tail_full.json "$@" > /tmp/tail_line.json 2>/tmp/tail_err.txt || { echo "$tag FAILED: $(tail -2 /tmp/tail_err.txt)"; return; }
+  python $root/bench.py --full --no-cpu-baseline --no-secondary --steps 30 --warmup 3 --full-json /tmp/tail_full.json "$@" > /tmp/tail_line.json 2>/tmp/tail_err.txt || { echo "$tag FAILED: $(tail -2 /tmp/tail_err.txt)"; return; }
   python -c "
 import json; d=json.load(open('/tmp/tail_full.json')); k=d['kernel_ms']
 print('%-22s %.0f pairs/s  step %.3f ms (median %.3f)  scan %.3f  post %.3f  scan in step %.3f  verified: %s' % ('$tag', d['value'], d['ms_per_step'], d['ms_per_step_distribution']['median'], k['scan'], k['post_scan_stages'], k['scan_in_timed_region'], str(d.get('verified'))[:60]))"

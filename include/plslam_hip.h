@@ -42,7 +42,9 @@ extern "C" {
  * "mfma_form" 3/4 and "exact_second"; 3 (round 4): "mfma_form" 5 (the default), "post_fuse", plslam_match_plan_key_state;
  * 4 (round 5): plslam_match_plan_set_wire16, the Schur step, plslam_lba_plan_host_state; 5 (round 6): plslam_lba_plan_get_landmarks, plslam_lba_plan_iterate_schur / _apply_step, plslam_lba_point_rows_dev_n / _line_rows_dev_n, plslam_match_plan_step_gather / _gather_sync, plslam_rccl_use / _rccl_available; additive within 5: the plslam_bow_* bag-of-words entry points; the loop-closure check plslam_loop_closure_verify[_dev] /
  * plslam_relpose_robust_gn with plslam_lc_params / plslam_lc_keyframe / plslam_lc_result; the global bundle adjustment
- * plslam_gba_plan_create / plslam_gba_optimize / plslam_gba_plan_destroy and plslam_dense_ldlt_solve.
+ * plslam_gba_plan_create / plslam_gba_optimize / plslam_gba_plan_destroy and plslam_dense_ldlt_solve; the loop-closure
+ * correction plslam_pgo_plan_create / plslam_pgo_optimize / plslam_pgo_plan_destroy, plslam_lc_correct_map[_dev] and
+ * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1071,6 +1073,77 @@ int plslam_gba_optimize(plslam_gba_plan* plan, double lambda_lba_lm, double lamb
                         double* T_out, double* Xw_out, double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result);
 void plslam_gba_plan_destroy(plslam_gba_plan* plan);
 int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots);
+
+/* ---- K40-K53: loop-closure correction (MapHandler::loopClosureOptimizationCovGraphG2O, src/mapHandler.cpp:4185-4410, up to
+ * loopClosureFuseLandmarks()) -------------------------------------------------------------------------------------------
+ * The pose graph: kf_curr_idx = max lc_idx[k][1]; vertices every non-NULL keyframe 0 .. kf_curr_idx, vertex 0 fixed; edges in
+ * the reference's creation order -- covisibility (i ascending, j > i ascending: full_graph[i][j] >= min_lm_ess_graph or
+ * >= min_lm_cov_graph or |i - j| == 1, measured from the stored T_kf_w), then one per LC entry (all of them, (2) == 0
+ * included).  The optimiser restates g2o's Levenberg-Marquardt over EdgeSE3 / VertexSE3 with computeInitialGuess (DESIGN.md
+ * section 5; parity unpinned).  The damped system is solved in a reverse Cuthill-McKee order by an envelope L D L^T on one
+ * workgroup; a zero or non-finite pivot rejects the trial (g2o's failed Cholmod).  Per trial only chi', dx.(lambda dx + b)
+ * and the pivot flag cross to the host.
+ *   plslam_pgo_plan_create  n_map_kf keyframe slots, kf_valid (n_map_kf, 0 = NULL), full_graph (n_map_kf^2 int32, row-major),
+ *                           lc_idx (n_lc x 3: the two keyframes and the (2) flag).  EINVAL: n_lc = 0, keyframe 0 NULL, an LC
+ *                           entry naming a NULL or out-of-range keyframe or the same keyframe twice, no active vertex, an
+ *                           active vertex without a path to vertex 0 (a singular system: a documented deviation).  ERANGE: more
+ *                           than PLSLAM_GBA_MAX_KEYFRAMES active vertices.
+ *   plslam_pgo_optimize     In: T_kf_w (n_map_kf x 16, row-major), x_kf_w (n_map_kf x 6), lc_pose (n_lc x 6).  Out, per slot:
+ *                           T_out / x_out the corrected poses (:4298-4304, :4358-4362), T_corr the correction that slot's
+ *                           landmarks take (Tkfw * inverse_se3(T_prev); the last vertex's for the slots after kf_curr_idx; the
+ *                           identity elsewhere), corrected (1 where the reference corrects).  NULL slots after kf_curr_idx are
+ *                           skipped (the reference dereferences them).  trace (trace_cap records, may be NULL with 0) receives
+ *                           one record per trial.
+ *   plslam_lc_correct_map[_dev]  :4306-4355 / :4364-4397: every corrected slot, in slot order, applies its T_corr to each valid
+ *                           landmark of its anchor list -- X (both end points of a line), med_obs_dir and every dir_list entry
+ *                           (p <- R p + t, the translation added to the directions as the reference does).  A landmark listed
+ *                           under two slots is transformed twice, in slot order.  _dev: device pointers, on `stream` (NULL:
+ *                           the context's); returns when the correction is done.
+ *   plslam_envelope_ldlt_solve  the envelope L D L^T alone, in the caller's ordering: A (n x n, row-major, host; the lower
+ *                           triangle read, its envelope = the first nonzero of every row), b, x; *n_bad_pivots (may be NULL),
+ *                           *env_width (may be NULL): max over rows of (row - first column). */
+#define PLSLAM_PGO_STOP_MAX_ITERS 0    /* max_iters_pgo iterations ran                                                */
+#define PLSLAM_PGO_STOP_TERMINATE 1    /* max_trials failed trials in one iteration, or rho == 0                      */
+typedef struct plslam_pgo_plan plslam_pgo_plan;
+typedef struct plslam_pgo_params {
+    int32_t min_lm_ess_graph, min_lm_cov_graph;   /* SlamConfig::minLMEssGraph / minLMCovGraph (75)              */
+    int32_t max_iters_pgo, max_trials;            /* SlamConfig::maxItersPGO (100); g2o's maxTrialsAfterFailure (10) */
+    double lambda_init;                           /* setUserLambdaInit (1e-10)                                     */
+} plslam_pgo_params;
+typedef struct plslam_pgo_trial {
+    int32_t iteration, trial;
+    double lambda, chi, chi_new, scale, rho;      /* chi_new = DBL_MAX after a failed factorisation; scale includes 1e-3 */
+    int32_t ok, accepted;
+} plslam_pgo_trial;
+typedef struct plslam_pgo_result {
+    int32_t iterations, trials, stop_reason;
+    int32_t n_vertices, n_active, n_edges, n_lc_edges;
+    int32_t env_width;                            /* max over rows of the reordered system of (row - first column)  */
+    int64_t env_entries;                          /* doubles in the envelope                                        */
+    double chi_initial, chi_final, lambda;        /* chi of computeInitialGuess's estimate and of the final state   */
+} plslam_pgo_result;
+typedef struct plslam_lc_landmarks {
+    int32_t n, n_anchor, n_dir;
+    const int32_t* anchor_ptr;   /* n_map_kf + 1: slot k lists anchor_idx[anchor_ptr[k] .. anchor_ptr[k+1]) (map_*_kf_idx) */
+    const int32_t* anchor_idx;   /* n_anchor landmark indices                                                               */
+    const uint8_t* valid;        /* n (0 = NULL)                                                                           */
+    double* X;                   /* n x 3 (points) or n x 6 (lines)                                                        */
+    double* med_dir;             /* n x 3                                                                                  */
+    const int32_t* dir_ptr;      /* n + 1: landmark j's dir_list is dirs[dir_ptr[j] .. dir_ptr[j+1])                       */
+    double* dirs;                /* n_dir x 3                                                                              */
+} plslam_lc_landmarks;
+int plslam_pgo_plan_create(plslam_ctx* ctx, const plslam_pgo_params* params, int32_t n_map_kf, const uint8_t* kf_valid,
+                           const int32_t* full_graph, int32_t n_lc, const int32_t* lc_idx, plslam_pgo_plan** out);
+int plslam_pgo_optimize(plslam_pgo_plan* plan, const double* T_kf_w, const double* x_kf_w, const double* lc_pose, double* T_out,
+                        double* x_out, double* T_corr, uint8_t* corrected, plslam_pgo_trial* trace, int32_t trace_cap,
+                        plslam_pgo_result* result);
+void plslam_pgo_plan_destroy(plslam_pgo_plan* plan);
+int plslam_lc_correct_map(plslam_ctx* ctx, int32_t n_map_kf, const double* T_corr, const uint8_t* corrected,
+                          const plslam_lc_landmarks* points, const plslam_lc_landmarks* lines);
+int plslam_lc_correct_map_dev(plslam_ctx* ctx, int32_t n_map_kf, const double* T_corr, const uint8_t* corrected,
+                              const plslam_lc_landmarks* points, const plslam_lc_landmarks* lines, void* stream);
+int plslam_envelope_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots,
+                               int32_t* env_width);
 
 #ifdef __cplusplus
 }

@@ -877,6 +877,7 @@ void plslam_ctx_destroy(plslam_ctx* ctx)
         delete ctx->lc_plan;
     }
     ctx->lc_in.release(); ctx->lc_out.release(); ctx->lc_tab.release();
+    ctx->pgo_scratch.release();
     for (hipEvent_t& e : ctx->lc_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);
@@ -982,6 +983,11 @@ int plslam_ctx_set_option(plslam_ctx* ctx, const char* key, int value)
         ctx->post_workgroups = value;
         return PLSLAM_OK;
     }
+    if (!strcmp(key, "pgo_solver")) {          // measurement tools only: 1 = the pose graph on the dense L D L^T
+        PLSLAM_REQUIRE(value == 0 || value == 1, PLSLAM_EINVAL);
+        ctx->pgo_solver = value;
+        return PLSLAM_OK;
+    }
     set_last_error("unknown option '%s'", key);
     return PLSLAM_EINVAL;
 }
@@ -1008,6 +1014,7 @@ int plslam_ctx_get_option(plslam_ctx* ctx, const char* key, int* value)
     if (!strcmp(key, "split_target")) { *value = ctx->split_target; return PLSLAM_OK; }
     if (!strcmp(key, "split_min_tiles")) { *value = ctx->split_min_tiles; return PLSLAM_OK; }
     if (!strcmp(key, "graph")) { *value = ctx->graph; return PLSLAM_OK; }
+    if (!strcmp(key, "pgo_solver")) { *value = ctx->pgo_solver; return PLSLAM_OK; }
     set_last_error("unknown option '%s'", key);
     return PLSLAM_EINVAL;
 }

@@ -144,6 +144,8 @@ struct plslam_ctx {
     struct plslam_match_plan* lc_plan = nullptr;    // the loop-closure check's two match problems (loop_closure.hip)
     plslam::DevBuf lc_in, lc_out, lc_tab;           // ... its keyframe image, its outputs, its match tables
     hipEvent_t lc_ev[2] = {nullptr, nullptr};       // ... its fences with a caller's stream (the _dev form)
+    int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
+    plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (pgo.hip)
 };
 
 namespace plslam {

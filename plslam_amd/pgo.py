@@ -1,0 +1,113 @@
+"""Seeded generator for the loop-closure correction (plslam_pgo_*, plslam_lc_correct_map): a map whose stored poses drifted.
+
+The true keyframes run around a circle of `period` keyframes and carry on into a second lap, so that keyframe k >= period is
+back where keyframe k - period was.  The stored poses are the true relative motions composed with small errors (accumulated
+odometry drift).  full_graph counts landmarks shared inside a window of consecutive keyframes, so that the nearest neighbours
+pass min_lm_cov_graph = 75 and farther ones do not.  Each loop closure (a, b) with b = a + period carries the true relative
+pose plus noise, as x with expmap_se3(x) = T_a^-1 T_b: the measurement of the loop edge (src/mapHandler.cpp:4276-4287).
+Landmarks are anchored to keyframe slots (map_points_kf_idx / map_lines_kf_idx) as CSR lists, each with a dir_list CSR."""
+from __future__ import annotations
+
+import numpy as np
+
+from .synth import se3_exp
+
+
+def _logmap(T):
+    R = T[:3, :3]
+    c = min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))
+    s = np.sqrt(1.0 - c * c)
+    th = np.arccos(c)
+    w, V = np.zeros(3), np.eye(3)
+    if th > 1e-6:
+        w = th * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (2.0 * s)
+        k = w / th
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        V = np.eye(3) + K * (1.0 - c) / th + K @ K * (th - s) / th
+    return np.concatenate([np.linalg.solve(V, T[:3, 3]), w])
+
+
+def _inv(T):
+    o = np.eye(4)
+    o[:3, :3] = T[:3, :3].T
+    o[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return o
+
+
+def pose_graph(n_kf=120, n_loops=1, seed=3, period=None, drift=0.003, lc_noise=0.0005, null_slots=(), n_after=3,
+               window=4, step=0.3, extra_lc=(), optimized=()):
+    """-> dict(n_map_kf, kf_valid (n,) uint8, T_kf_w (n, 4, 4) stored, x_kf_w (n, 6) = logmap_se3(T_kf_w), T_true, full_graph
+    (n, n) int32, lc_idx (n_lc, 3) int32, lc_pose (n_lc, 6)).
+
+    The loop closures close at n_loops keyframes of the second lap, the last n_after keyframes before the end (those after it
+    are the 'later keyframes' of :4358).  extra_lc: more (a, b) entries appended as they are; optimized: indices of LC entries
+    whose (2) column is 0 (already optimised; they still make edges)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    period = period or (max(8, int(round(n_kf * 0.8))) | 1)     # odd: no keyframe at a rotation of exactly pi
+    assert n_kf > period + n_after
+    R = period * step / (2 * np.pi)
+    T_true = np.zeros((n_kf, 4, 4))
+    for k in range(n_kf):
+        th = 2 * np.pi * k / period
+        T = se3_exp(np.array([0.0, 0.0, 0.0, 0.0, th, 0.0]))
+        T[:3, 3] = [R * (1 - np.cos(th)), 0.02 * np.sin(3 * th), R * np.sin(th)]
+        T_true[k] = T
+    T_kf_w = np.zeros_like(T_true)
+    T_kf_w[0] = T_true[0]
+    for k in range(1, n_kf):
+        rel = _inv(T_true[k - 1]) @ T_true[k]
+        T_kf_w[k] = T_kf_w[k - 1] @ rel @ se3_exp(drift * rng.standard_normal(6))
+    x_kf_w = np.stack([_logmap(T) for T in T_kf_w])
+    valid = np.ones(n_kf, np.uint8)
+    for k in null_slots:
+        valid[k] = 0
+    fg = np.zeros((n_kf, n_kf), np.int32)
+    for i in range(n_kf):
+        for j in range(i + 1, min(n_kf, i + window + 1)):
+            c = int(200 - 40 * (j - i) + rng.integers(-12, 13))
+            fg[i, j] = fg[j, i] = max(c, 0)
+    fg[valid == 0, :] = 0
+    fg[:, valid == 0] = 0
+    last = n_kf - 1 - n_after
+    bs = set()
+    for b in np.linspace(max(period, last - 12 * (n_loops - 1)), last, n_loops).round().astype(int):
+        while b > period and not (valid[b] and valid[b - period]):       # a loop closes between two non-NULL keyframes
+            b -= 1
+        bs.add(int(b))
+    bs = sorted(bs)
+    pairs = [(b - period, b) for b in bs] + [tuple(p) for p in extra_lc]
+    lc_idx = np.array([[a, b, 1] for a, b in pairs], np.int32).reshape(-1, 3)
+    for k in optimized:
+        lc_idx[k, 2] = 0
+    lc_pose = np.stack([_logmap(_inv(T_true[a]) @ T_true[b] @ se3_exp(lc_noise * rng.standard_normal(6))) for a, b in pairs])
+    return dict(n_map_kf=n_kf, kf_valid=valid, T_kf_w=T_kf_w, x_kf_w=x_kf_w, T_true=T_true, full_graph=fg, lc_idx=lc_idx,
+                lc_pose=lc_pose)
+
+
+def anchored_landmarks(n_kf, n_lm, n_dir=4, seed=5, line=False, null_frac=0.02, n_double=8, kf_valid=None, vary_dirs=True):
+    """Landmarks anchored to keyframe slots -> dict(anchor_ptr (n_kf + 1,), anchor_idx, valid (n_lm,) uint8, X (n_lm, 3 or 6),
+    med_dir (n_lm, 3), dir_ptr (n_lm + 1,), dirs (m, 3)).  Each landmark is anchored at one slot (no NULL slot); n_double of
+    them are listed under a second, later slot too (as after removeRedundantKFs); null_frac of them are NULL.  Each has 0 ..
+    n_dir dir_list entries (exactly n_dir with vary_dirs=False)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    ok = np.flatnonzero(np.ones(n_kf, bool) if kf_valid is None else np.asarray(kf_valid).astype(bool))
+    home = np.sort(rng.choice(ok, n_lm))
+    lists = [[] for _ in range(n_kf)]
+    for j, k in enumerate(home):
+        lists[k].append(j)
+    for j in rng.choice(n_lm, min(n_double, n_lm), replace=False):
+        later = ok[ok > home[j]]
+        if later.size:
+            lists[int(rng.choice(later))].append(int(j))
+    ptr = np.zeros(n_kf + 1, np.int32)
+    ptr[1:] = np.cumsum([len(x) for x in lists])
+    idx = np.array([j for x in lists for j in x], np.int32)
+    valid = (rng.random(n_lm) >= null_frac).astype(np.uint8)
+    X = rng.uniform(-20.0, 20.0, (n_lm, 6 if line else 3))
+    med = rng.standard_normal((n_lm, 3))
+    med /= np.linalg.norm(med, axis=1, keepdims=True)
+    nd = rng.integers(0, n_dir + 1, n_lm) if vary_dirs else np.full(n_lm, n_dir)
+    dptr = np.zeros(n_lm + 1, np.int32)
+    dptr[1:] = np.cumsum(nd)
+    dirs = rng.standard_normal((int(dptr[-1]), 3))
+    return dict(anchor_ptr=ptr, anchor_idx=idx, valid=valid, X=X, med_dir=med, dir_ptr=dptr, dirs=dirs)

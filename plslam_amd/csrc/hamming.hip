@@ -543,9 +543,6 @@ __device__ __forceinline__ int ratio_pick(uint32_t k0, uint32_t k1, float nnr)
     return d0 < d1n ? (int)(k0 & KEY_IDX_MASK) : -1;
 }
 
-#ifndef PLSLAM_NT_FINALIZE
-#define PLSLAM_NT_FINALIZE 1
-#endif
 // One row of a problem: ratio test on its scan result, the mutual check against the candidate column's pair kb = fetch_kb(m)
 // (K1h / K1i plans: completed lazily, see below), the table entry, the count and the stereo gate.  EVERY lane of the workgroup
 // calls it (DPP row rotations inside); the workgroup's 256 lanes are 256 consecutive rows starting at a multiple of 16.
@@ -576,8 +573,7 @@ __device__ __forceinline__ void finalize_row(const ProblemDesc& p, const int i1,
             k = make_uint2(pre->x, pre->y);
         } else {
             // (read once: non-temporal, like the table written below -- they must not push the scan's rows out of L2)
-            const gvec2_t kv = PLSLAM_NT_FINALIZE ? __builtin_nontemporal_load(g_(reinterpret_cast<const gvec2_t*>(p.keys12)) + i1)
-                                                  : g_(reinterpret_cast<const gvec2_t*>(p.keys12))[i1];
+            const gvec2_t kv = __builtin_nontemporal_load(g_(reinterpret_cast<const gvec2_t*>(p.keys12)) + i1);
             k = make_uint2(kv.x, kv.y);
         }
         m = ratio_pick(k.x, k.y, p.nnr);
@@ -650,8 +646,7 @@ __device__ __forceinline__ void finalize_row(const ProblemDesc& p, const int i1,
     }
     if (check && !ok) { m = -1; cleared = true; }
     if (i1 < p.n1) {
-        if (PLSLAM_NT_FINALIZE) __builtin_nontemporal_store(m, g_(p.matches_12) + i1);
-        else g_(p.matches_12)[i1] = m;
+        __builtin_nontemporal_store(m, g_(p.matches_12) + i1);
         // the gather's wire table (plslam_match_plan_set_wire16): the same entry as int16 (m < n2 <= 32768)
         if (p.matches_16) g_(p.matches_16)[i1] = (int16_t)m;
     }
@@ -856,10 +851,7 @@ int launch_merge_partials(const SymDesc* d_sym, const BlockDesc* d_blocks, int n
     return PLSLAM_OK;
 }
 
-#ifndef PLSLAM_POST_FUSED_THREADS
-#define PLSLAM_POST_FUSED_THREADS 256
-#endif
-constexpr int POST_FUSED_THREADS = PLSLAM_POST_FUSED_THREADS;
+constexpr int POST_FUSED_THREADS = 256;
 int launch_post_fused(const ProblemDesc* d_probs, int nprob, const plslam_stereo_gate_problem* d_gates, size_t lds_bytes,
                       hipStream_t s)
 {

@@ -34,12 +34,6 @@
 
 #include <type_traits>
 
-// build-time experiments for tools/scan_time.py (results are WRONG with any of them on):
-//   1 = no workgroup barrier, 2 = no epilogue, 3 = no MFMA
-#ifndef PLSLAM_MF_EXPERIMENT
-#define PLSLAM_MF_EXPERIMENT 0
-#endif
-
 namespace plslam {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -136,15 +130,8 @@ __device__ __forceinline__ int xcd_remap_(int orig, int nwg) { return (orig & 7)
 // which is why the common case has its own instantiation; capi.hip picks per plan).
 // DIRECTED = true: only keys12 (row direction) is produced -- non-mutual problems and plain knnMatch(k=2):
 // no column keys, no column partials, 5 VALU ops per 2 distances.
-// experiment: -DPLSLAM_MF_SINGLE_SET=1 -> one accumulator set, no M(t)/E(t-1) overlap inside a wave, 4 waves per SIMD
-#ifndef PLSLAM_MF_SINGLE_SET
-#define PLSLAM_MF_SINGLE_SET 0
-#endif
 template <bool MULTI, bool DIRECTED>
-#ifndef PLSLAM_MF_WAVES
-#define PLSLAM_MF_WAVES 3
-#endif
-__global__ void __launch_bounds__(256, PLSLAM_MF_SINGLE_SET ? 4 : PLSLAM_MF_WAVES)      // 3 waves per SIMD: <= 168 unified VGPRs
+__global__ void __launch_bounds__(256, 3)     // 3 waves per SIMD: <= 168 unified VGPRs
 k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ blocks,
                 int32_t* __restrict__ zero, int nzero)
 {
@@ -313,7 +300,7 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
                     auto masked_tag) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         const uint32_t raw2 = t + 2 < WT1 ? load_raw(t + 2) : 0u;
-        if (PLSLAM_MF_EXPERIMENT != 1) __syncthreads();   // tile t expanded; colbuf of tile t-2 complete
+        __syncthreads();   // tile t expanded; colbuf of tile t-2 complete
         if (t - WT0 > 1 && w == (t & 3)) flush_columns(t - 2);      // the waves take turns
         const uint8_t* bt = btile + (t & 1) * MF_TILE_BYTES + c * MF_ROW_STRIDE + 16 * g;
         const bool col_ok = (t - 1) * MF_TILE_N + c < n2;
@@ -327,9 +314,7 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
         {                                                                                          \
             const i32x8 a8 = {afrag[MT][KS].x, afrag[MT][KS].y, afrag[MT][KS].z, afrag[MT][KS].w, 0, 0, 0, 0}; \
             const i32x8 b8 = {bcur.x, bcur.y, bcur.z, bcur.w, 0, 0, 0, 0};                         \
-            if (PLSLAM_MF_EXPERIMENT != 3)                                                         \
-                ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
-            else ACC[KS] = __builtin_bit_cast(float, bcur.x);                                      \
+            ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
         }
 #define PLSLAM_MF_KSTEP(KS, CIN0, CIN1)                                                            \
         {                                                                                          \
@@ -337,11 +322,11 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
             if ((KS) < MF_KSTEPS - 1) bf = *reinterpret_cast<const i32x4*>(bt + 32 * ((KS) + 1));   \
             PLSLAM_MF_MMA(m0, 0, KS, CIN0)                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                     \
-            if (with_prev && PLSLAM_MF_EXPERIMENT != 2) { PLSLAM_MF_EPI_ROW(4 * (KS)) PLSLAM_MF_EPI_ROW(4 * (KS) + 1) } \
+            if (with_prev) { PLSLAM_MF_EPI_ROW(4 * (KS)) PLSLAM_MF_EPI_ROW(4 * (KS) + 1) }         \
             __builtin_amdgcn_sched_barrier(0);                                                     \
             PLSLAM_MF_MMA(m1, 1, KS, CIN1)                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                     \
-            if (with_prev && PLSLAM_MF_EXPERIMENT != 2) { PLSLAM_MF_EPI_ROW(4 * (KS) + 2) PLSLAM_MF_EPI_ROW(4 * (KS) + 3) } \
+            if (with_prev) { PLSLAM_MF_EPI_ROW(4 * (KS) + 2) PLSLAM_MF_EPI_ROW(4 * (KS) + 3) }     \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }
         PLSLAM_MF_KSTEP(0, cinit, cinit)
@@ -350,23 +335,13 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
 #undef PLSLAM_MF_MMA
         expand_store(raw1, (t + 1) & 1);           // past the last tile: a harmless rewrite of the idle buffer
         raw1 = raw2;
-        if (PLSLAM_MF_EXPERIMENT == 2) asm volatile("" ::"v"(m0), "v"(m1));
-        if (with_prev && PLSLAM_MF_EXPERIMENT != 2) finish_columns(t - 1, cb0, cb1);
+        if (with_prev) finish_columns(t - 1, cb0, cb1);
     };
     // One window: S(WT0) | S(WT0+1)+E(WT0) | S(WT0+2)+E(WT0+1) | ... | E(WT1-1).  Two accumulator sets
     // alternate (unrolled by two: no accumulator is ever copied).  Only the last tile of the scan can lack
     // columns.
     auto pipeline = [&](auto steady_tag) __attribute__((always_inline)) {
         const bool last_partial = WT1 == ntiles && (n2 % MF_TILE_N) != 0;
-#if PLSLAM_MF_SINGLE_SET
-        f32x16 A0, A1;
-        for (int t = WT0; t < WT1; ++t) {
-            step(t, A0, A1, A0, A1, false, steady_tag);
-            __syncthreads();                       // the flush of tile t-2 (same colbuf parity as tile t) is done
-            if (t == WT1 - 1 && last_partial) epilogue(t, A0, A1, std::true_type{}); else epilogue(t, A0, A1, steady_tag);
-        }
-        return;
-#else
         f32x16 A0, A1, B0, B1;
         step(WT0, A0, A1, A0, A1, false, steady_tag);
         int t = WT0 + 1;
@@ -393,7 +368,6 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
             __syncthreads();
             if (last_partial) epilogue(t - 1, A0, A1, std::true_type{}); else epilogue(t - 1, A0, A1, steady_tag);
         }
-#endif
     };
     // Row results of a window.  Every lane holds, per accumulator register, the best two 16-bit keys
     // (d, tile + LOC) of ITS column class for two rows.  Transpose through LDS so that one lane owns one row:

@@ -35,14 +35,6 @@
 
 #include <type_traits>
 
-// build-time experiments (tools/build_exp.py; results are WRONG with any of them on), a bit mask:
-//   1 no workgroup barrier   2 no row minima   4 no MFMA   16 no second-best fix-up   64 no group push
-//   128 no expansion of the b tile (no global load, no LDS write)   256 no operand reads from LDS   1024 no finish_rows
-#ifndef PLSLAM_MD_EXPERIMENT
-#define PLSLAM_MD_EXPERIMENT 0
-#endif
-#define PLSLAM_MD_X(bit) ((PLSLAM_MD_EXPERIMENT & (bit)) != 0)
-
 namespace plslam {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -225,7 +217,6 @@ k_scan_dir_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
     // a group is over: its minima (two rows per packed key: M-tile 0 low, M-tile 1 high) get the group number and go into the
     // parked sorted pairs; the minima restart
     auto push_groups = [&](int t) __attribute__((always_inline)) {
-        if (PLSLAM_MD_X(64)) return;
         const uint32_t gtag = (uint32_t)(((t - wt0) >> 4) << 4) * 0x00010001u;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -251,17 +242,16 @@ k_scan_dir_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
     asm volatile("" : "+v"(seed));
     auto tile_step = [&](int t, bool with_prev, auto masked_tag) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_tag)::value;      // the last tile of a scan: lanes without a column
-        if (!PLSLAM_MD_X(1)) __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
+        __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
         const uint8_t* bt = btile + (t & 1) * MD_TILE_BYTES + c * MD_ROW_STRIDE + 16 * g;
         i32x4 bfr[MD_KSTEPS];
 #pragma unroll
         for (int ks = 0; ks < MD_KSTEPS; ++ks)
-            bfr[ks] = PLSLAM_MD_X(256) ? i32x4{(int)FP4_ONE + t, (int)FP4_ONE, (int)FP4_ONE + ks, (int)FP4_ONE}
-                                       : *reinterpret_cast<const i32x4*>(bt + 32 * ks);
-        if (!PLSLAM_MD_X(128)) expand_store(raw1, (t + 1) & 1);   // past the last tile: a harmless rewrite of the idle buffer
+            bfr[ks] = *reinterpret_cast<const i32x4*>(bt + 32 * ks);
+        expand_store(raw1, (t + 1) & 1);   // past the last tile: a harmless rewrite of the idle buffer
         raw1 = raw2;
         raw2 = raw3;
-        if (!PLSLAM_MD_X(128)) raw3 = load_raw(t + 4);
+        raw3 = load_raw(t + 4);
         const f32x16 cseed = __builtin_bit_cast(f32x16, seed);
         // lanes whose column does not exist (last tile only): their keys become "none"
         const uint32_t colmask = MASKED ? (md_row_of(t, c, n2) < n2 ? 0u : 0xFFFFu) : 0u;
@@ -269,15 +259,13 @@ k_scan_dir_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
         {                                                                                          \
             const i32x8 a8 = {afrag[MT][KS].x, afrag[MT][KS].y, afrag[MT][KS].z, afrag[MT][KS].w, 0, 0, 0, 0}; \
             const i32x8 b8 = {bfr[KS].x, bfr[KS].y, bfr[KS].z, bfr[KS].w, 0, 0, 0, 0};             \
-            if (!PLSLAM_MD_X(4))                                                                   \
-                ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
-            else { const f32x16 cin_ = CIN; ACC = cin_; ACC[KS] = __builtin_bit_cast(float, bfr[KS].x ^ a8[0]); } \
+            ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
             asm volatile("" : "+v"(ACC));    /* pins the MFMA here (no instruction) */              \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }
 #define PLSLAM_MD_MIN4(ACC, BASE, R0, ON)                                                          \
         {                                                                                          \
-            if ((ON) && !PLSLAM_MD_X(2)) {                                                         \
+            if (ON) {                                                                              \
                 const u32x16 ab_ = __builtin_bit_cast(u32x16, ACC);                                \
                 gm[(BASE) + (R0)]     = min_lo16(gm[(BASE) + (R0)],     ab_[(R0)]     | colmask_prev_or_cur); \
                 gm[(BASE) + (R0) + 1] = min_lo16(gm[(BASE) + (R0) + 1], ab_[(R0) + 1] | colmask_prev_or_cur); \
@@ -381,7 +369,7 @@ k_scan_dir_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
         if (row < n1) {
             const gu2_t out = (gu2_t) reinterpret_cast<u32x2_t*>(sd.keys12) + row;
             uint32_t r0 = widen(k0), r1 = widen(k1);
-            if (k0 != 0xFFFFFFFFu && !PLSLAM_MD_X(16)) {
+            if (k0 != 0xFFFFFFFFu) {
                 // the other members of the winner's (group, class): consecutive rows in a full group, 32 apart in the ragged one
                 uint32_t t0, cls0;
                 tile_cls(k0, t0, cls0);
@@ -440,7 +428,7 @@ k_scan_dir_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
             drain(wt1 - 1, std::false_type{});
         }
         __syncthreads();                           // every wave is past its last operand read of the b tile
-        if (!PLSLAM_MD_X(1024)) finish_rows();
+        finish_rows();
         if (wt1 == ntiles) break;
         __syncthreads();                           // smem becomes the b tile (+ parking area) again
         wt0 = wt1;

@@ -33,15 +33,6 @@
 
 #include <type_traits>
 
-// build-time experiments for tools/scan_time.py / tools/build_exp.py (results are WRONG with any of them on), a bit mask:
-//   1 no workgroup barrier   2 no bookkeeping rows   4 no MFMA   8 no column store   16 no second-best fix-up
-//   32 no finish_columns     64 no group push        128 no expansion of the b tile (no global load, no LDS write)
-//   256 no operand reads from LDS                    512 no pack
-#ifndef PLSLAM_MG_EXPERIMENT
-#define PLSLAM_MG_EXPERIMENT 0
-#endif
-#define PLSLAM_MG_X(bit) ((PLSLAM_MG_EXPERIMENT & (bit)) != 0)
-
 namespace plslam {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -66,17 +57,11 @@ constexpr int MF_KSTEPS = 4;                  // 256 bits = 4 x K 64
 constexpr int MF_ROW_STRIDE = 144;            // bytes per expanded b row in LDS (128 + 16: 4-bank skew)
 constexpr int MF_TILE_BYTES = MF_TILE_N * MF_ROW_STRIDE;
 // Streaming accesses (the column partials: written once by the scan, read once by the merge) carry the non-temporal hint, so
-// that they do not evict the b rows the scan re-reads from L2 -- of this scan or, in the split stepping, of the next one
-#ifndef PLSLAM_NT_STREAMS
-#define PLSLAM_NT_STREAMS 1
-#endif
-#ifndef PLSLAM_MG_GROUP
-#define PLSLAM_MG_GROUP 16
-#endif
+// that they do not evict the b rows the scan re-reads from L2 -- of this scan or, in the split stepping, of the next one.
 // tiles per row-direction group (a window of 64 tiles = 4 groups of 16).  A larger group halves the parked-pair pushes
 // (64 VALU + 16 LDS reads + 16 LDS writes each; measured 8 % of the scan at 8 tiles per group) and costs
 // MF_GROUP - 1 recomputed distances per row and window.
-constexpr int MF_GROUP = PLSLAM_MG_GROUP;
+constexpr int MF_GROUP = 16;
 constexpr int MF_CGROUP = 8;                  // tiles whose column results are staged in LDS and stored together (256 columns)
 // fp4 (e2m1) codes: +1.0 = 0x2, -1.0 = 0xA.  b side: bit 0 -> +1, bit 1 -> -1 = s(b); the a side is the b code
 // XOR 0x8 per nibble (= -s(a)) and carries the block scale 2^6 (E8M0 133), the b side 2^0 (E8M0 127).
@@ -283,13 +268,10 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     // the 8 tiles that end with tile `tl` are over: their column results go to the partial table (256 columns: 16 bytes
     // per lane)
     auto store_columns = [&](int tl) __attribute__((always_inline)) {
-        if (!DIRECTED && wave_has_rows && !PLSLAM_MG_X(8)) {
+        if (!DIRECTED && wave_has_rows) {
             const int j0 = (tl & ~(MF_CGROUP - 1)) * MF_TILE_N + 4 * lane;      // WT0 is a multiple of 8
             const i32x4 v = *reinterpret_cast<const i32x4*>(cstage + 4 * lane);
-            if (j0 < n2p) {
-                if (PLSLAM_NT_STREAMS) __builtin_nontemporal_store(v, reinterpret_cast<PLSLAM_GLOBAL i32x4*>(part + j0));
-                else *reinterpret_cast<PLSLAM_GLOBAL i32x4*>(part + j0) = v;
-            }
+            if (j0 < n2p) __builtin_nontemporal_store(v, reinterpret_cast<PLSLAM_GLOBAL i32x4*>(part + j0));
             // tiles of a partial last group that never ran leave "none" in the padding columns (never read; keeps the
             // partial table a pure function of the inputs, which tools/determinism_check.py compares word for word)
             *reinterpret_cast<i32x4*>(cstage + 4 * lane) = i32x4{-1, -1, -1, -1};
@@ -312,7 +294,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     // the same offset, so all comparisons here are unaffected and the merge step takes it off (a "none" half 0xFFFF
     // stays above KEY16_MAX after the subtraction).
     auto finish_columns = [&](int t, uint32_t cb0, uint32_t cb1) __attribute__((always_inline)) {
-        if (DIRECTED || PLSLAM_MG_X(32)) { asm volatile("" ::"v"(cb0), "v"(cb1)); return; }
+        if (DIRECTED) { asm volatile("" ::"v"(cb0), "v"(cb1)); return; }
         // The tag of a column key is LOC (bits 0,1,3,4 of the row within the wave) [+ tile]; OR-ing in bit 2 (= g) and
         // bit 5 (= M-tile, the high halves) makes it the full row within the wave [+ tile: LOC + tile < 128 and the
         // OR-ed bits are clear in LOC but NOT in LOC + tile, so they are ADDED: no carry leaves the 7-bit tag because
@@ -341,7 +323,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     uint32_t kc[16];
     auto tile_step = [&](int t, bool with_prev, auto masked_tag) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_tag)::value;
-        if (!PLSLAM_MG_X(1)) __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
+        __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
         const uint8_t* bt = btile + (t & 1) * MF_TILE_BYTES + c * MF_ROW_STRIDE + 16 * g;
         const bool col_ok = (t - 1) * MF_TILE_N + c < n2;
         uint32_t cb0 = 0xFFFFFFFFu, cb1 = 0xFFFFFFFFu;
@@ -351,15 +333,14 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         i32x4 bfr[MF_KSTEPS];
 #pragma unroll
         for (int ks = 0; ks < MF_KSTEPS; ++ks)
-            bfr[ks] = PLSLAM_MG_X(256) ? i32x4{(int)FP4_ONE + t, (int)FP4_ONE, (int)FP4_ONE + ks, (int)FP4_ONE}
-                                       : *reinterpret_cast<const i32x4*>(bt + 32 * ks);
-        if (!PLSLAM_MG_X(128)) expand_store(raw1, (t + 1) & 1);   // past the last tile: a harmless rewrite of the idle buffer
+            bfr[ks] = *reinterpret_cast<const i32x4*>(bt + 32 * ks);
+        expand_store(raw1, (t + 1) & 1);   // past the last tile: a harmless rewrite of the idle buffer
         // raw-row prefetch, three tiles deep: the request for tile t+4 goes out now, its dword is expanded in step t+3.
         // Always issued (load_raw clamps the row), so the number of loads in flight is the same on every path and the
         // waits are exact counts.
         raw1 = raw2;
         raw2 = raw3;
-        if (!PLSLAM_MG_X(128)) raw3 = load_raw(t + 4);
+        raw3 = load_raw(t + 4);
         // accumulator start: 2^23 + 16384 + LOC(reg) + tile within the window: the sum is 2^23 + 128 d + LOC + tile,
         // every partial sum an integer below 2^24, so fp32 accumulation is exact and the float's low 16 bits ARE
         // the key (d << 7 | LOC + tile).  Wave-uniform integers (scalar adds); built from integers through a scalar
@@ -375,9 +356,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         {                                                                                          \
             const i32x8 a8 = {afrag[MT][KS].x, afrag[MT][KS].y, afrag[MT][KS].z, afrag[MT][KS].w, 0, 0, 0, 0}; \
             const i32x8 b8 = {bfr[KS].x, bfr[KS].y, bfr[KS].z, bfr[KS].w, 0, 0, 0, 0};             \
-            if (!PLSLAM_MG_X(4))                                                                   \
-                ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
-            else { const f32x16 cin_ = CIN; ACC = cin_; ACC[KS] = __builtin_bit_cast(float, bfr[KS].x ^ a8[0]); } \
+            ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
             /* an EMPTY asm (no instruction): pins the MFMA here -- without a use in this block the optimizer sinks all */ \
             /* eight MFMAs of a tile down to the pack, i.e. behind the bookkeeping they are meant to overlap with */ \
             asm volatile("" : "+v"(ACC));                                                          \
@@ -385,7 +364,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         }
 #define PLSLAM_MG_EPI2(R)                                                                          \
         {                                                                                          \
-            if (with_prev && !PLSLAM_MG_X(2)) { PLSLAM_MG_EPI_ROW(R) PLSLAM_MG_EPI_ROW((R) + 1) }  \
+            if (with_prev) { PLSLAM_MG_EPI_ROW(R) PLSLAM_MG_EPI_ROW((R) + 1) }                     \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }
         // program order, fenced: [2 rows] MFMA [2 rows] MFMA ... : single MFMAs, evenly spaced, each followed by VALU work
@@ -405,15 +384,14 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
             finish_columns(t - 1, cb0, cb1);
             // wave-uniform: tile t-1 closed a block of 8 tiles / a row group
             if (((t - 1 - WT0) & (MF_CGROUP - 1)) == MF_CGROUP - 1) store_columns(t - 1);
-            if (((t - 1 - WT0) & (MF_GROUP - 1)) == MF_GROUP - 1 && !PLSLAM_MG_X(64)) push_groups();
+            if (((t - 1 - WT0) & (MF_GROUP - 1)) == MF_GROUP - 1) push_groups();
         }
         // P(t): the key pairs of tile t; the accumulators are dead from here on
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float f0 = m0[r], f1 = m1[r];
-            if (!PLSLAM_MG_X(512)) kc[r] = pack_acc(f0, f1, pack_sel);
+            kc[r] = pack_acc(f0, f1, pack_sel);
         }
-        if (PLSLAM_MG_X(512)) { asm volatile("" ::"v"(m0), "v"(m1)); kc[0] = __builtin_bit_cast(uint32_t, (float)m0[0]); }
     };
     // E(t) on its own (the last tile of a window has no following M step to hide under)
     auto epilogue = [&](int t, auto masked_tag) __attribute__((always_inline)) {
@@ -477,7 +455,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         if (row < n1) {
             const gu2_t out = (gu2_t) reinterpret_cast<u32x2_t*>(sd.keys12) + row;
             uint32_t r0 = widen(k0), r1 = widen(k1);
-            if ((k0 >> 16) <= KEY16_MAX && !PLSLAM_MG_X(16)) {
+            if ((k0 >> 16) <= KEY16_MAX) {
                 // the other members of the winner's group: tiles g0 .. g0 + 7 of the window, same class
                 const uint32_t cls0 = k0 & 0xFFFFu;
                 const uint32_t tw = ((k0 >> 16) & 127u) - loc;              // winner's tile within the window
@@ -628,8 +606,7 @@ k_merge_partials16(const SymDesc* __restrict__ syms, const BlockDesc* __restrict
         uint32_t s0 = 0xFFFFFFFFu;
 #pragma unroll 8
         for (int wb = part_id; wb < nwb; wb += PARTS) {
-            const uint32_t e = (PLSLAM_NT_STREAMS ? __builtin_nontemporal_load(&part[(size_t)wb * n2p + j])
-                                                  : part[(size_t)wb * n2p + j]) - tw2;    // both halves >= tw: no borrow between them
+            const uint32_t e = __builtin_nontemporal_load(&part[(size_t)wb * n2p + j]) - tw2;    // both halves >= tw: no borrow between them
             const uint32_t k = wide(e & 0xFFFFu, (uint32_t)wb);
             s0 = k < b0 ? e : s0;
             b1 = umin_(b1, umax_(b0, k));

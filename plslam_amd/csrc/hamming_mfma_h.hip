@@ -39,15 +39,6 @@
 
 #include <type_traits>
 
-// build-time experiments (tools/build_exp.py; results are WRONG with any of them on), a bit mask:
-//   1 no workgroup barrier   2 no bookkeeping rows   4 no MFMA   8 no column store   16 no second-best fix-up
-//   32 no finish_columns     64 no group push        128 no expansion of the b tile   256 no operand reads from LDS
-//   512 no pack              1024 no finish_rows
-#ifndef PLSLAM_MH_EXPERIMENT
-#define PLSLAM_MH_EXPERIMENT 0
-#endif
-#define PLSLAM_MH_X(bit) ((PLSLAM_MH_EXPERIMENT & (bit)) != 0)
-
 namespace plslam {
 
 // (typedefs, constants and device helpers: mfma_h_common.hpp)
@@ -217,7 +208,7 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     const uint64_t part_s = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(part_u >> 32)) << 32) |
                             (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)part_u);
     auto combine_columns = [&](int kb) __attribute__((always_inline)) {
-        if (DIRECTED || PLSLAM_MH_X(8)) return;
+        if (DIRECTED) return;
         // (the lane number from mbcnt, not from threadIdx: two instructions here instead of a value kept -- and spilled --
         // across the tile loop, whose reload would wait on vmcnt(0), i.e. on the raw-row prefetch; asm volatile: the
         // builtin form is loop-invariant, gets hoisted -- and spilled all the same)
@@ -244,25 +235,21 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         const uint32_t e0 = lo[0] & 0xFFFFu, e1 = hi[0] & 0xFFFFu, u0 = lo[0] >> 16, u1 = hi[0] >> 16;
         uint32_t k0 = e0 + (e0 & 0xFF80u), k1 = e1 + (e1 & 0xFF80u);
         merge2(k0, k1, u0 + (u0 & 0xFF80u) + 128u, u1 + (u1 & 0xFF80u) + 128u);
-        if (PLSLAM_MH_X(32)) k0 = p[0];
         const uint32_t slot4 = (uint32_t)(256 * kb + 64 * w) * 4u;                             // (scalar) n2p is a multiple of 256
         if (!wide_part) {
             const uint32_t e = (k0 << 9) | (k1 >> 8);
             PLSLAM_GLOBAL uint32_t* dst = (PLSLAM_GLOBAL uint32_t*)((PLSLAM_GLOBAL char*)(uintptr_t)(part_s + slot4) + 4u * l_);
-            if (PLSLAM_NT_STREAMS) __builtin_nontemporal_store(e, dst);
-            else *dst = e;
+            __builtin_nontemporal_store(e, dst);
         } else {
             const u32x2_t e = {k0, k1};
             PLSLAM_GLOBAL u32x2_t* dst = (PLSLAM_GLOBAL u32x2_t*)((PLSLAM_GLOBAL char*)(uintptr_t)(part_s + 2u * slot4) + 8u * l_);
-            if (PLSLAM_NT_STREAMS) __builtin_nontemporal_store(e, dst);
-            else *dst = e;
+            __builtin_nontemporal_store(e, dst);
         }
         // (slots of tiles of a last, partial block that never ran hold older values: never read, and a function of the
         // inputs like everything else in the table)
     };
     // a row group is over: its minima get the group number and go into the parked sorted pairs; the minima restart
     auto push_groups = [&](int t) __attribute__((always_inline)) {
-        if (PLSLAM_MH_X(64)) return;
         // the tag's wave bits become the group number (an XOR: "none" stays above every key, whatever its low bits)
         const uint32_t gtag = (uint32_t)(((((t - wt0) >> 4) ^ w) & 3) << 5) * 0x00010001u;
 #pragma unroll
@@ -276,7 +263,7 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     };
     // column minima of a finished tile: parked as they are (the seeds made the tags), combined in combine_columns
     auto finish_columns = [&](int t, uint32_t cm) __attribute__((always_inline)) {
-        if (DIRECTED || PLSLAM_MH_X(32)) { asm volatile("" ::"v"(cm)); return; }
+        if (DIRECTED) { asm volatile("" ::"v"(cm)); return; }
         cstage[(t & (MH_CGROUP - 1)) * 256 + lane] = cm;
     };
 
@@ -301,21 +288,20 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
     auto tile_step = [&](int t, auto u_tag, bool with_prev, auto masked_tag) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         constexpr int U = decltype(u_tag)::value;                      // t & 3
-        if (!PLSLAM_MH_X(1)) __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
+        __syncthreads();  // tile t expanded; every wave is past its reads of the other buffer
         const uint8_t* bt = btile + (U & 1) * MH_TILE_BYTES + c * MH_ROW_STRIDE + 16 * g;
         uint32_t cm = 0xFFFFFFFFu, cm1 = 0xFFFFFFFFu;
         // operand reads: K-steps 0 and 1 now, 2 and 3 behind the MFMAs of steps 0 and 1 (their registers): 8 live registers, not 16
         auto read_b = [&](int ks) __attribute__((always_inline)) -> i32x4 {
-            return PLSLAM_MH_X(256) ? i32x4{(int)FP4_ONE + t, (int)FP4_ONE, (int)FP4_ONE + ks, (int)FP4_ONE}
-                                    : *reinterpret_cast<const i32x4*>(bt + 32 * ks);
+            (void)t;   // (captured, not needed: without the capture the compiler orders the scalar code of this kernel differently)
+            return *reinterpret_cast<const i32x4*>(bt + 32 * ks);
         };
         i32x4 bfr[MH_KSTEPS];
         bfr[0] = read_b(0);
         bfr[1] = read_b(1);
         // the next tile's raw dword (requested three steps ago) leaves the ring now, with the operand reads: its LDS latency is
         // long over when the expansion behind the MFMAs needs it
-        uint32_t raw_next = 0u;
-        if (!PLSLAM_MH_X(128)) raw_next = take_raw(ring_slot);
+        const uint32_t raw_next = take_raw(ring_slot);
         // ragged group: lanes whose class has run out of columns take the penalty from this tile on (at most two tiles of a
         // scan change anything: the group's first -- classes without any column -- and the one where the cut class ends)
         if (t >= nfull && ((t & 15) == 0 || (t & 15) == lim_part)) {
@@ -330,15 +316,13 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         {                                                                                          \
             const i32x8 a8 = {afrag[MT][KS].x, afrag[MT][KS].y, afrag[MT][KS].z, afrag[MT][KS].w, 0, 0, 0, 0}; \
             const i32x8 b8 = {bfr[KS].x, bfr[KS].y, bfr[KS].z, bfr[KS].w, 0, 0, 0, 0};             \
-            if (!PLSLAM_MH_X(4))                                                                   \
-                ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
-            else { const f32x16 cin_ = CIN; ACC = cin_; ACC[KS] = __builtin_bit_cast(float, bfr[KS].x ^ a8[0]); } \
+            ACC = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, CIN, 4, 4, 0, scale_a, 0, scale_b); \
             asm volatile("" : "+v"(ACC));    /* pins the MFMA here (no instruction) */              \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }
 #define PLSLAM_MH_EPI2(R)                                                                          \
         {                                                                                          \
-            if (!PLSLAM_MH_X(2)) { PLSLAM_MH_EPI_ROW(R) PLSLAM_MH_EPI_ROW((R) + 1) }               \
+            { PLSLAM_MH_EPI_ROW(R) PLSLAM_MH_EPI_ROW((R) + 1) }                                    \
             __builtin_amdgcn_sched_barrier(0);                                                     \
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -357,18 +341,16 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         // behind the last MFMA, in front of the pack that needs its result: the expansion of the next tile (its buffer was
         // read for the last time before this step's barrier) and the prefetch -- independent work that covers the matrix
         // pipe's latency (measured: the 16 packs cost as much time as the 33 bookkeeping ops while they sat right behind it)
-        if (!PLSLAM_MH_X(128)) {
-            expand_store(raw_next, (U + 1) & 1, t + 1);               // past the last tile: a harmless rewrite of the idle buffer
-            load_raw_async(t + 4, ring_slot);                         // three tiles ahead of its use, into the slot just read
-            ring_slot = ring_slot == 2 ? 0 : ring_slot + 1;           // (scalar)
-        }
+        expand_store(raw_next, (U + 1) & 1, t + 1);                   // past the last tile: a harmless rewrite of the idle buffer
+        load_raw_async(t + 4, ring_slot);                             // three tiles ahead of its use, into the slot just read
+        ring_slot = ring_slot == 2 ? 0 : ring_slot + 1;               // (scalar)
         if (with_prev) {
             // block (t - 9) / 8 of column results: its last tile was parked in the step before this one, by every wave before
             // this step's barrier; tile t - 1 is about to take the block's first slot: a second barrier (workgroup-uniform
             // branch).  (The blocks of the window before were finished behind its loop.)
             if (!DIRECTED && U == 1 && ((t - 1) & (MH_CGROUP - 1)) == 0 && t - 9 >= wt0) {
                 combine_columns((t - 9) >> 3);
-                if (!PLSLAM_MH_X(1)) __syncthreads();
+                __syncthreads();
             }
             finish_columns(t - 1, pk_min16(cm, cm1));
             // wave-uniform: tile t-1 closed a row group
@@ -378,9 +360,8 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float f0 = m0[r], f1 = m1[r];
-            if (!PLSLAM_MH_X(512)) kc[r] = pack_acc(f0, f1);
+            kc[r] = pack_acc(f0, f1);
         }
-        if (PLSLAM_MH_X(512)) { asm volatile("" ::"v"(m0), "v"(m1)); kc[0] = __builtin_bit_cast(uint32_t, (float)m0[0]); }
     };
     // E(t) on its own (the last tile of a window has no following M step to hide under)
     auto epilogue = [&](int t, auto masked_tag) __attribute__((always_inline)) {
@@ -484,7 +465,7 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
                 }
             };
             uint32_t r0 = KEY_NONE, r1 = KEY_NONE;
-            if ((k0 >> 16) <= KEY16_MAX && !PLSLAM_MH_X(16)) {
+            if ((k0 >> 16) <= KEY16_MAX) {
                 uint32_t jb, cnt, in2;
                 group_of(k0, jb, cnt);
                 rescan(jb, cnt, r0, in2);
@@ -503,8 +484,6 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
                 } else {
                     r1 = in2;
                 }
-            } else if (PLSLAM_MH_X(16)) {
-                r0 = k0; r1 = k1;
             }
             if (wt0 > 0) {                                  // later windows: merge with the windows before
                 const u32x2_t prev = *out;
@@ -528,7 +507,7 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         __syncthreads();                           // every wave is past its last operand read of the b tile, every column minimum is parked
         // the window's last block of column results (full or partial)
         combine_columns((wt1 - 1) >> 3);
-        if (!PLSLAM_MH_X(1024)) finish_rows();
+        finish_rows();
         if (wt1 == ntiles) break;
         __syncthreads();                           // smem becomes the b tile (+ parking area) again
         wt0 = wt1;
@@ -579,13 +558,9 @@ k_merge_fix16(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ bl
         return ((k17 >> 8) << KEY_IDX_BITS) | ((k17 & 255u) + 256u * wb);
     };
     // only a block's BEST key is widened and merged per entry
-    // PLSLAM_MERGE_WB (round 5): the default form (one word per entry, a lane per slot) requests the words of up to this many
-    // row blocks together -- a 1500-row problem's six in ONE round trip instead of three
-#ifndef PLSLAM_MERGE_WB
-#define PLSLAM_MERGE_WB 8
-#endif
-    if (PARTS == 1 && !FIX && PLSLAM_MERGE_WB > 2) {
-        constexpr int WB = PLSLAM_MERGE_WB > 2 ? PLSLAM_MERGE_WB : 2;
+    // the default form (one word per entry, a lane per slot): the words of MH_MERGE_WB row blocks are requested together
+    if (PARTS == 1 && !FIX) {
+        constexpr int WB = MH_MERGE_WB;
         for (int wb0 = 0; wb0 < nwb; wb0 += WB) {
             uint32_t e[WB][SPT];
 #pragma unroll
@@ -593,8 +568,7 @@ k_merge_fix16(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ bl
                 if (wb0 + u < nwb) {                  // (uniform)
 #pragma unroll
                     for (int q = 0; q < SPT; ++q)
-                        e[u][q] = PLSLAM_NT_STREAMS ? __builtin_nontemporal_load(&part[(size_t)(wb0 + u) * n2p + slot[q]])
-                                                    : part[(size_t)(wb0 + u) * n2p + slot[q]];
+                        e[u][q] = __builtin_nontemporal_load(&part[(size_t)(wb0 + u) * n2p + slot[q]]);
                 }
             }
 #pragma unroll
@@ -618,11 +592,10 @@ k_merge_fix16(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ bl
         for (int q = 0; q < SPT; ++q) {
             if (FIX) {
                 const gu2c_t pp = (gu2c_t) part + ((size_t)wb * n2p + slot[q]);
-                const u32x2_t e = PLSLAM_NT_STREAMS ? __builtin_nontemporal_load(pp) : *pp;
+                const u32x2_t e = __builtin_nontemporal_load(pp);
                 e0[q] = e.x; e1[q] = e.y;
             } else {
-                const uint32_t e = PLSLAM_NT_STREAMS ? __builtin_nontemporal_load(&part[(size_t)wb * n2p + slot[q]])
-                                                     : part[(size_t)wb * n2p + slot[q]];
+                const uint32_t e = __builtin_nontemporal_load(&part[(size_t)wb * n2p + slot[q]]);
                 e0[q] = e >> 9; e1[q] = ((e & 511u) << 8) | 255u;     // the second entry's row is not in the word
             }
         }

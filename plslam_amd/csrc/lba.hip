@@ -17,7 +17,7 @@ k_point_rows(CamD K, double th, const double* __restrict__ T, const double* __re
              double* __restrict__ Jl, double* __restrict__ r, double* __restrict__ w, int32_t n_pose_slots)
 {
     __shared__ __attribute__((aligned(16))) double slabs[4][64 * 6];
-    __shared__ PoseCache<PLSLAM_POSE_LINES> poses;
+    __shared__ PoseCache<POSE_LINES> poses;
     const int o = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int o0 = o - lane;                                 // first observation of this wave

@@ -228,7 +228,7 @@ k_lba_rows_cross(const LbaIterArgs A)
     // 36 instructions of 64 scattered 8-byte stores each)
     __shared__ __attribute__((aligned(16))) double slabs[4][64 * 18];
     __shared__ double red[256];
-    __shared__ PoseCache<PLSLAM_POSE_LINES> poses;
+    __shared__ PoseCache<POSE_LINES> poses;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool lines = (int)blockIdx.x >= A.nbp;
     const int nobs = lines ? A.nl : A.np;
@@ -390,21 +390,13 @@ struct LbaBlockArgs {
     int32_t* nsing = nullptr;
 };
 
-#ifndef PLSLAM_CHUNK_PB
-#define PLSLAM_CHUNK_PB 32
-#endif
 __global__ void __launch_bounds__(256)
 k_lba_blocks(const LbaBlockArgs A)
 {
     __shared__ __attribute__((aligned(16))) double slab[64 * 36];
     const int b = blockIdx.x;
-#ifdef PLSLAM_BLOCKS_X            // timing experiments (tools/r6_blocks_knockouts.sh): 1 no point landmarks, 2 no line landmarks, 4 no keyframe chunk
-                                  // partials.  At C3 the launch is 16.3 us; points alone 5.1, lines alone 8.9, the chunk partials alone 13.9 --
-                                  // the launch's critical path, and not a matter of round trips (16 / 32 observations in flight: 16.3 / 16.1 us)
-    if ((PLSLAM_BLOCKS_X & 1) && b < A.nb3) return;
-    if ((PLSLAM_BLOCKS_X & 2) && b >= A.nb3 && b < A.nb3 + A.nb6) return;
-    if ((PLSLAM_BLOCKS_X & 4) && b >= A.nb3 + A.nb6) return;
-#endif
+    // (knock-out builds at C3: the launch is 16.3 us; points alone 5.1, lines alone 8.9, the chunk partials alone 13.9 -- the launch's
+    // critical path, and not a matter of round trips: 16 / 32 observations in flight gave 16.3 / 16.1 us)
     if (b < A.nb3) {                                   // (64 landmarks: the workgroup's first wave; the others leave)
         if (threadIdx.x >= 64) return;
         landmark_block<3>(b * 64, A.npt, A.pt_ptr, A.pt_ids, A.pJl, A.pr, A.pw, A.H_pt, A.g_pt, slab, A.lambda, A.Vp, A.tp, A.nsing);
@@ -422,7 +414,7 @@ k_lba_blocks(const LbaBlockArgs A)
         const int end = beg + POSE_CHUNK < A.kf_ptr[k + 1] ? beg + POSE_CHUNK : A.kf_ptr[k + 1];
         const int a = e < 36 ? e / 6 : e - 36, bb = e < 36 ? e % 6 : 0;
         double acc = 0.0;
-        constexpr int PB = PLSLAM_CHUNK_PB;   // (observations whose loads are in flight together: 32 = two round trips per 64-observation chunk; 16 was four, and this part of the launch its critical path: 13.9 us alone)
+        constexpr int PB = 32;   // (observations whose loads are in flight together: 32 = two round trips per 64-observation chunk; 16 was four, and this part of the launch its critical path: 13.9 us alone)
         for (int i0 = beg; i0 < end; i0 += PB) {
             int oo[PB];
             bool pt[PB];
@@ -448,9 +440,6 @@ k_lba_blocks(const LbaBlockArgs A)
     }
 }
 
-#ifndef PLSLAM_SCH_WAVES
-#define PLSLAM_SCH_WAVES 1                 // chunks per workgroup of the Schur partials' launch (see wave_sync)
-#endif
 // NT = 256: a lane per partial-sum slot; NT = 64 (inside the Schur partials' launch): a lane plays the four lanes e, e + 64,
 // e + 128, e + 192 of the 256-lane form and adds them as its tree's first two levels do -- the same sums in the same order
 template <int NT>
@@ -484,15 +473,7 @@ __device__ __forceinline__ void lba_finish_wg(const LbaBlockArgs& A, int k, doub
         for (int i = e + q * NT; i < A.nerr; i += 256) acc[q] += A.err_part[i];
     }
     if constexpr (Q == 4) { acc[0] += acc[2]; acc[1] += acc[3]; acc[0] += acc[1]; }      // the tree's levels 128 and 64
-    auto sync = [] {
-        if (NT == 64 && PLSLAM_SCH_WAVES != 1) {   // (one wave, inside a workgroup whose other waves are elsewhere)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        } else {
-            __syncthreads();
-        }
-    };
+    auto sync = [] { __syncthreads(); };
     red[e] = acc[0];
     sync();
     for (int s = NT / 2; s > 0; s >>= 1) {
@@ -1070,9 +1051,6 @@ extern "C" int plslam_lba_assemble(plslam_ctx* ctx, int32_t nkf, int32_t npt, in
 namespace plslam {
 
 constexpr int SCH_CHUNK = 64;
-#ifndef PLSLAM_SCHUR_X
-#define PLSLAM_SCHUR_X 0            // timing experiments only (tools/r6_schur_knockouts.sh): parts of the partials' launch left out
-#endif
 struct SchurPair { int32_t o1, o2, lm, line; };     // observation ids within their own list (points / lines), the landmark
 
 template <int DL>
@@ -1180,28 +1158,13 @@ __device__ __forceinline__ void schur_pair_block(const double* __restrict__ W1, 
 // 64 rows of NE doubles, row r at base + NE * id(r) where lane r holds id(r): fetched by the WAVE in runs (consecutive lanes read
 // consecutive words of a row: 4-8 cache lines per instruction; a lane reading its own row word by word touches 64), parked in
 // the tile, and every lane takes its own row out of it.  One wave per workgroup: the barriers are the wave's own.
-// One chunk per workgroup of one wave (PLSLAM_SCH_WAVES = 1).  Measured at C3 (tools/r6_schur_knockouts.sh): two or four chunks
+// One chunk per workgroup of one wave.  Measured at C3: two or four chunks
 // per workgroup, a wave each with its own tile and wave-level synchronisation, are SLOWER (24.0 / 24.9 us against 19.8: a
 // workgroup's LDS and registers stay taken until its slowest wave is through), and so is the wave-level form at one wave (22.3: the
 // scheduler takes the weaker barrier as leave to spread the gathers' loads over 285 registers).
-#ifndef PLSLAM_SCH_OFF64
-#define PLSLAM_SCH_OFF64 0
-#endif
-#ifndef PLSLAM_SCH_STATIC_LDS
-#define PLSLAM_SCH_STATIC_LDS (PLSLAM_SCH_WAVES == 1)   // (a tile of known size: 20.8 us against 26.8 with the same tile as dynamic LDS --
-#endif                                                  //  the register allocator sees what the workgroup's LDS allows and keeps two waves)
-#ifndef PLSLAM_SCH_FINISH_LAST
-#define PLSLAM_SCH_FINISH_LAST 0
-#endif
 __device__ __forceinline__ void wave_sync()
 {
-#if PLSLAM_SCH_WAVES == 1
     __syncthreads();
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
 }
 // (fetch: the loads, into registers -- several gathers' loads can be in flight together; park: through the tile, one at a time)
 template <int NE>
@@ -1217,12 +1180,8 @@ __device__ __forceinline__ void gather_fetch(const double* __restrict__ base, in
             const int rid = __shfl(id, r);
             // (a 32-bit byte offset from the uniform base: the load takes it beside the base in scalar registers -- a 64-bit
             // address per load was two more registers for each of the 18 loads in flight; lba_schur_prepare bounds the tables)
-#if PLSLAM_SCH_OFF64
-            const f64x2 v = *reinterpret_cast<const f64x2*>(base + (size_t)rid * NE + 2 * c2);
-#else
             const uint32_t boff = ((uint32_t)rid * NE + 2 * c2) * 8u;
             const f64x2 v = *reinterpret_cast<const f64x2*>(reinterpret_cast<const char*>(base) + boff);
-#endif
             flat[2 * j] = v.x;
             flat[2 * j + 1] = v.y;
         }
@@ -1231,12 +1190,8 @@ __device__ __forceinline__ void gather_fetch(const double* __restrict__ base, in
         for (int j = 0; j < NE; ++j) {
             const int idx = j * 64 + lane, r = idx / NE, c = idx - r * NE;
             const int rid = __shfl(id, r);
-#if PLSLAM_SCH_OFF64
-            flat[j] = base[(size_t)rid * NE + c];
-#else
             const uint32_t boff = ((uint32_t)rid * NE + c) * 8u;
             flat[j] = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff);
-#endif
         }
     }
 }
@@ -1300,9 +1255,6 @@ schur_partials_wg(double (*tile)[37], int B, int c, const SchurPair* __restrict_
     const int n = end - beg;                       // <= 0: the block has fewer chunks than the grid is wide
     if (n <= 0) return;
     SchurPair q = pairs[beg + (i < n ? i : n - 1)];           // (lanes past the chunk's end replay its last pair: their block is dropped)
-#if PLSLAM_SCHUR_X & 1
-    if (q.o1 != -12345) return;
-#endif
     // the chunk's kind (lba_schur_prepare: one kind per chunk, null pairs -- line = 2 -- behind a block's last point pairs); a null
     // pair fetches what the chunk's first pair fetches and contributes zeros
     const bool null_pair = q.line == 2;
@@ -1311,9 +1263,6 @@ schur_partials_wg(double (*tile)[37], int B, int c, const SchurPair* __restrict_
     // The wave fetches its 64 pairs' rows together (gather_*), each lane takes its own out of the tile, and the pair's 6 x 6 block
     // goes straight back into the tile (the sums are schur_pair_product's, term for term).  Registers: what a lane holds at once
     // decides how many waves a SIMD keeps (a first form with all operands and the block in registers: 256 and one wave; this one: two).
-#if PLSLAM_SCHUR_X & 16
-    if (line_chunk) return;
-#endif
     if (!line_chunk) {
         double w1[18], w2[18], v[9];
         {
@@ -1398,9 +1347,6 @@ schur_partials_wg(double (*tile)[37], int B, int c, const SchurPair* __restrict_
         }
     }
     wave_sync();
-#if PLSLAM_SCHUR_X & 8
-    if (n != -12345) return;
-#endif
     if (i < 36) {                                  // (eight LDS reads in flight, added in pair order)
         const int slot = line_chunk ? (i % 6) * 6 + i / 6 : i;
         double acc = 0.0;
@@ -1475,19 +1421,11 @@ struct SchurPartArgs {
     int32_t nblk, schur_chunks, nkf, pose_chunks, n_pt_obs;
 };
 static_assert(SCH_CHUNK == POSE_CHUNK, "one workgroup shape for both kinds of chunk");
-// (PLSLAM_SCH_WAVES chunks per workgroup, a wave and a tile each: see wave_sync; the tiles are dynamic LDS -- four of them are past
-// the 64 kB a kernel may use without asking; PLSLAM_SCH_VGPRS: a register budget for the experiments, 0 = the compiler's own)
-constexpr int SCH_WAVES = PLSLAM_SCH_WAVES;
-#ifndef PLSLAM_SCH_VGPRS
-#define PLSLAM_SCH_VGPRS 0
-#endif
-#if PLSLAM_SCH_VGPRS
-#define SCH_VGPR_ATTR __attribute__((amdgpu_num_vgpr(PLSLAM_SCH_VGPRS / 2)))
-#else
-#define SCH_VGPR_ATTR
-#endif
+// (one chunk, one wave and one tile per workgroup: see wave_sync.  The tile is static LDS: 20.8 us against 26.8 with the same tile as
+// dynamic LDS -- the register allocator sees what the workgroup's LDS allows and keeps two waves.  The kernels still index the
+// tile by the wave's number, which is 0: taking that out changes their code, so it waits for the next change to them.)
+constexpr int SCH_WAVES = 1;
 constexpr size_t SCH_TILE_DOUBLES = (size_t)SCH_CHUNK * 37;
-constexpr size_t SCH_LDS_BYTES = SCH_WAVES * SCH_TILE_DOUBLES * 8;
 __device__ __forceinline__ void schur_partials_item(double (*tile)[37], const SchurPartArgs& A, int w, int npart)
 {
     const int nS = A.nblk * A.schur_chunks;
@@ -1497,14 +1435,10 @@ __device__ __forceinline__ void schur_partials_item(double (*tile)[37], const Sc
         schur_b_partials_wg(tile, (w - nS) / A.pose_chunks, (w - nS) % A.pose_chunks, A.kf_ptr, A.kf_obs, A.n_pt_obs, A.pt_lm, A.ls_lm,
                             A.W_pt, A.W_ls, A.tp, A.tl, A.pose_chunks, A.bpart);
 }
-__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES) SCH_VGPR_ATTR
+__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES)
 k_schur_partials(SchurPartArgs A, int32_t npart)
 {
-#if PLSLAM_SCH_STATIC_LDS
     __shared__ __attribute__((aligned(16))) double sch_lds[SCH_WAVES * SCH_TILE_DOUBLES];
-#else
-    extern __shared__ __attribute__((aligned(16))) double sch_lds[];
-#endif
     const int wv = (int)threadIdx.x >> 6;
     schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, (int)blockIdx.x * SCH_WAVES + wv, npart);
 }
@@ -1513,30 +1447,17 @@ k_schur_partials(SchurPartArgs A, int32_t npart)
 // from their partials) -- the two are independent (the partials read W and the landmark inverses, K22 behind them reads H_pose /
 // g_pose), so the iteration's third launch rides in the Schur step's second.  The last stage's workgroups come FIRST (a wave each;
 // chains of round trips: at the grid's end they would be the launch's tail).
-__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES) SCH_VGPR_ATTR
+__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES)
 k_schur_partials_lba_finish(SchurPartArgs A, const LbaBlockArgs B, int32_t npart)
 {
-#if PLSLAM_SCH_STATIC_LDS
     __shared__ __attribute__((aligned(16))) double sch_lds[SCH_WAVES * SCH_TILE_DOUBLES];
-#else
-    extern __shared__ __attribute__((aligned(16))) double sch_lds[];
-#endif
     const int wv = (int)threadIdx.x >> 6;
     const int nF = B.nkf + 1;
-#if PLSLAM_SCH_FINISH_LAST
-    const int ngrid = (npart + SCH_WAVES - 1) / SCH_WAVES;
-    if ((int)blockIdx.x >= ngrid) {
-        if (wv == 0) lba_finish_wg<SCH_CHUNK>(B, (int)blockIdx.x - ngrid, sch_lds);
-        return;
-    }
-    schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, (int)blockIdx.x * SCH_WAVES + wv, npart);
-#else
     if ((int)blockIdx.x < nF) {
         if (wv == 0) lba_finish_wg<SCH_CHUNK>(B, (int)blockIdx.x, sch_lds);
         return;
     }
     schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, ((int)blockIdx.x - nF) * SCH_WAVES + wv, npart);
-#endif
 }
 
 // block B = (k1 <= k2) in row-major upper-triangle order; S is (6 nkf) x (6 nkf) row-major, b follows it
@@ -1749,12 +1670,6 @@ static int lba_schur_prepare(plslam_lba_plan* P)
                                                                               ((size_t)P->npt / (BACK_WG / 3) + (size_t)P->nls / (BACK_WG / 6) + 2) * 8 + 256)))
         return rc;
     P->schur_pin_dev = static_cast<char*>(P->schur_pin.dev);
-#if !PLSLAM_SCH_STATIC_LDS
-    // (the experiments' four tiles are past the 64 kB a kernel may use without asking)
-    PLSLAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_partials), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCH_LDS_BYTES));
-    PLSLAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_schur_partials_lba_finish), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)SCH_LDS_BYTES));
-#endif
     hipStream_t s = P->ctx->stream;
     char* d = P->schur.as<char>();
     if (!pairs.empty()) PLSLAM_HIP_CHECK(hipMemcpyAsync(d + P->oSpair, pairs.data(), pairs.size() * sizeof(SchurPair), hipMemcpyHostToDevice, s));
@@ -1817,12 +1732,10 @@ static int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bo
     A.spart = (double*)(d + P->oSpart); A.bpart = (double*)(d + P->oBpart);
     A.nblk = P->nblk; A.schur_chunks = P->schur_chunks; A.nkf = P->nkf; A.pose_chunks = P->max_chunks; A.n_pt_obs = P->np;
     const int32_t npart_wgs = P->nblk * P->schur_chunks + P->nkf * P->max_chunks;
-    const int32_t npart_grid = (npart_wgs + SCH_WAVES - 1) / SCH_WAVES;
     if (fused)
-        hipLaunchKernelGGL(k_schur_partials_lba_finish, dim3(npart_grid + P->nkf + 1), dim3(SCH_CHUNK * SCH_WAVES), PLSLAM_SCH_STATIC_LDS ? 0 : SCH_LDS_BYTES, s, A,
-                           lba_block_args(P), npart_wgs);
-    else if (npart_grid > 0)
-        hipLaunchKernelGGL(k_schur_partials, dim3(npart_grid), dim3(SCH_CHUNK * SCH_WAVES), PLSLAM_SCH_STATIC_LDS ? 0 : SCH_LDS_BYTES, s, A, npart_wgs);
+        hipLaunchKernelGGL(k_schur_partials_lba_finish, dim3(npart_wgs + P->nkf + 1), dim3(SCH_CHUNK), 0, s, A, lba_block_args(P), npart_wgs);
+    else if (npart_wgs > 0)
+        hipLaunchKernelGGL(k_schur_partials, dim3(npart_wgs), dim3(SCH_CHUNK), 0, s, A, npart_wgs);
     // S, b, err and this call's counter: written where the host reads them (the page-locked image, mapped) when it can be -- no
     // copy behind the kernel; otherwise beside the partials on the device, and lba_schur_fetch copies
     const bool in_place = P->schur_pin_dev != nullptr;

@@ -57,9 +57,7 @@ __device__ __forceinline__ void load6(const double* __restrict__ p, double (&v)[
 // many matrices the caller says the array holds (0: unknown -- nothing is copied).  A first form that cached the slots the
 // workgroup's rows NAME (no count needed) chained slot numbers -> tags -> matrices -> rows through two barriers and was no
 // faster than the global loads.  Every thread of the workgroup calls pose_cache_fill and pose12_take (one barrier).
-#ifndef PLSLAM_POSE_LINES
-#define PLSLAM_POSE_LINES 32
-#endif
+constexpr int POSE_LINES = 32;
 template <int NC>
 struct PoseCache {
     double T[NC * 16];

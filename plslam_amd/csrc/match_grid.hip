@@ -63,18 +63,7 @@ constexpr int CB = 4;                                                  // candid
 constexpr int GRID_SPLIT = 4;                                          // flat PA: at most this many lanes share a row's window columns
 constexpr uint32_t GRID_TAIL = 256;                                   // candidates left when one wave finishes the passes alone
 constexpr int PB_BATCH = 8;                                            // stored candidates per batch of a record pass
-#ifndef PLSLAM_GRID_RECORDS
-#define PLSLAM_GRID_RECORDS 1       // 0: experiment builds that list every candidate pair of a lone problem (k_grid_candidates)
-#endif
-#ifndef PLSLAM_GRID_RUNS_PER_COLUMN
-#define PLSLAM_GRID_RUNS_PER_COLUMN 4   // k_grid_records' list is bucketed by column while a column has at most this many runs on average
-#endif
-#ifndef PLSLAM_GRID_FAST
-#define PLSLAM_GRID_FAST 1          // 0: experiment builds without the shortest bookkeeping of k_grid_records' list
-#endif
-#ifndef PLSLAM_GRID_COLUMNS
-#define PLSLAM_GRID_COLUMNS 1       // 0: experiment builds without the column-bucketed path of a lone problem
-#endif
+constexpr uint32_t GRID_RUNS_PER_COLUMN = 4;                           // k_grid_records' list is bucketed by column while a column has at most this many runs on average
 constexpr uint32_t REC_SLOT = 8;                                       // k_grid_records: list words per item of the grid
 constexpr size_t GRID_LDS_MAX_BYTES = 152 * 1024;                      // dynamic LDS of the LDS instantiations
 constexpr size_t GRID_LDS_FIXED_MAX_BYTES = 144 * 1024;                // tables that MUST fit for MODE 1
@@ -340,7 +329,7 @@ __global__ __launch_bounds__(NT) void k_match_grid(const GridDesc* __restrict__ 
     // initialisation instead of three behind it.
     constexpr uint32_t COLS_HOLD = 32, COLS_EARLY = 12;
     const bool count_empty = 2147483647.0 < 2147483647.0 * g.nnr;     // PC's nnr > 1 rule
-    const bool cols_maybe = PLSLAM_GRID_COLUMNS && MODE == 2 && NT == 1024 && pre != nullptr && !count_empty;
+    const bool cols_maybe = MODE == 2 && NT == 1024 && pre != nullptr && !count_empty;
     const uint32_t col_off = 2u * (uint32_t)(n2 + n1);
     // (k_grid_records' list: the words of item tid and item tid + NT, and the first two words per lane of the records that
     // did not fit their items' -- those are listed from the END of the store downwards, so their place is known now)
@@ -438,13 +427,6 @@ __global__ __launch_bounds__(NT) void k_match_grid(const GridDesc* __restrict__ 
 #ifdef PLSLAM_GRID_TIMING
             dbg_total = total;
 #endif
-#ifdef PLSLAM_GRID_DEBUG_LIST
-            if (tid == 0 && n2 <= 4) {
-                printf("[list] n1 %d n2 %d slots %u total %u pair_cap %d items_end %u overflow %u:", n1, n2, n_slots, total, g.pair_cap, items_end_early, total_early);
-                for (uint32_t k = 0; k < total && k < 40; ++k) printf(" %08x", list_at(k));
-                printf("\n");
-            }
-#endif
             if (total > (uint32_t)g.pair_cap) {                         // (uniform) the list did not fit: report, match nothing
                 for (int32_t i = tid; i < n1; i += NT) g_matches[i] = -1;
                 if (tid == 0) {
@@ -467,7 +449,7 @@ __global__ __launch_bounds__(NT) void k_match_grid(const GridDesc* __restrict__ 
             // the first is one iff the run has any -- the counts P0 zeroed take those, and a column counted twice has two runs:
             // the tables are wiped and the bucketed bookkeeping below runs).  The returning atomics of a lane go out together.
             const uint32_t n_over = total - n_slots;                    // (total <= pair_cap here)
-            if (PLSLAM_GRID_FAST && slots_early && items_end_early <= ITEMS_EARLY * NT && n_over <= ITEMS_EARLY * NT) {
+            if (slots_early && items_end_early <= ITEMS_EARLY * NT && n_over <= ITEMS_EARLY * NT) {
                 PLSLAM_AS_LDS uint32_t* off = s_dyn + col_off;
                 bool dup = false;
                 auto fold = [&](uint32_t w, bool first, uint32_t& was_) {           // a record word: column state, row's best
@@ -525,7 +507,7 @@ __global__ __launch_bounds__(NT) void k_match_grid(const GridDesc* __restrict__ 
             // lines against a keyframe's, took 107 us this way against ~30 us of record passes)
             // (k_grid_records' list holds records only: a few per run whatever the windows)
             if (!cols_done && cols_maybe && total <= COLS_HOLD * NT &&
-                (pre_slots > 0u ? (uint64_t)items_end_early <= (uint64_t)PLSLAM_GRID_RUNS_PER_COLUMN * (uint32_t)n2 : (uint64_t)total <= 24ull * (uint32_t)n2) &&
+                (pre_slots > 0u ? (uint64_t)items_end_early <= (uint64_t)GRID_RUNS_PER_COLUMN * (uint32_t)n2 : (uint64_t)total <= 24ull * (uint32_t)n2) &&
                 (uint64_t)col_off + (uint32_t)n2 + 1u + total <= (uint64_t)lds_words) {
                 PLSLAM_AS_LDS uint32_t* off = s_dyn + col_off;              // n2 + 1: counts (zeroed by P0), then the segments' first words
                 PLSLAM_AS_LDS uint32_t* seg = off + n2 + 1;
@@ -1533,10 +1515,7 @@ int64_t grid_store_capacity_bound(int32_t n1, int32_t n_centres, const int32_t* 
 }
 
 constexpr int GRID_SPLIT_MAX = 16;         // ... with at most this many lanes per row (one per window column)
-#ifndef PLSLAM_GRID_SPLIT_MIN_ROWS
-#define PLSLAM_GRID_SPLIT_MIN_ROWS 128
-#endif
-constexpr int GRID_SPLIT_MIN_ROWS = PLSLAM_GRID_SPLIT_MIN_ROWS;   // one problem alone: from this many rows on PA runs as its own many-workgroup launch
+constexpr int GRID_SPLIT_MIN_ROWS = 128;   // one problem alone: from this many rows on PA runs as its own many-workgroup launch
 constexpr int GRID_SMALL_ROWS = 256;    // problems of at most this many rows run on 256-lane workgroups (MODE 2 only)
 
 // launch groups: 0 = tables in global scratch, 1 = tables in LDS, 2 = everything in LDS / 1024 lanes, 3 = everything in
@@ -1927,7 +1906,7 @@ int grid_launch_single(const plslam_grid_problem& q, const GridDesc* d_desc, hip
         // be the host's), or every candidate pair (k_grid_candidates)
         const int64_t n_groups = (int64_t)q.grid_cols * ((q.grid_rows + REC_G - 1) / REC_G);
         const size_t lds = grid_group_lds_bytes(2, q.n1, q.n2, ncell, q.n_items, dirs);
-        if (PLSLAM_GRID_RECORDS && h_desc && n_groups <= REC_GROUPS_MAX && q.n1 <= REC_ROWS_MAX &&
+        if (h_desc && n_groups <= REC_GROUPS_MAX && q.n1 <= REC_ROWS_MAX &&
             (int64_t)q.n_items * REC_SLOT <= (int64_t)q.pair_capacity) {
             // (n1_upper_bound: the row count is the device descriptor's, patched by the caller's kernels)
             const int32_t* n1_dev = n1_upper_bound ? &d_desc->n1 : nullptr;

@@ -28,14 +28,11 @@ constexpr int MH_TILE_BYTES = MH_TILE_N * MH_ROW_STRIDE;
 constexpr int MH_GROUP = 16;                  // tiles per group of the row direction (512 b rows)
 constexpr int MH_GROUP_ROWS = MH_GROUP * MH_TILE_N;
 constexpr int MH_WINDOW = 64;                 // tiles per window: the row keys' tag holds the group within the window (2 bits)
-#ifndef PLSLAM_MERGE_SPT
-#define PLSLAM_MERGE_SPT 4
-#endif
-constexpr int MH_MERGE_SPT = PLSLAM_MERGE_SPT;   // slots per lane of the merge kernel (PARTS == 1)
+constexpr int MH_MERGE_SPT = 4;               // slots per lane of the merge kernel (PARTS == 1)
+// (round 5) the one-word-per-entry merge requests the words of up to this many row blocks together -- a 1500-row problem's
+// six in ONE round trip instead of three
+constexpr int MH_MERGE_WB = 8;
 constexpr int MH_CGROUP = 8;                  // tiles whose column results are staged in LDS and stored together (256 slots)
-#ifndef PLSLAM_NT_STREAMS
-#define PLSLAM_NT_STREAMS 1
-#endif
 constexpr uint32_t FP4_NEG = 0x88888888u;
 constexpr uint32_t FP4_ONE = 0x22222222u;
 constexpr uint32_t FP4_FOUR = 0x66666666u;    // e2m1 code 0b0110 = 4.0

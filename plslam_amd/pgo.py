@@ -35,13 +35,15 @@ def _inv(T):
 
 
 def pose_graph(n_kf=120, n_loops=1, seed=3, period=None, drift=0.003, lc_noise=0.0005, null_slots=(), n_after=3,
-               window=4, step=0.3, extra_lc=(), optimized=()):
+               window=4, step=0.3, extra_lc=(), optimized=(), true_poses=None, cov_step=40):
     """-> dict(n_map_kf, kf_valid (n,) uint8, T_kf_w (n, 4, 4) stored, x_kf_w (n, 6) = logmap_se3(T_kf_w), T_true, full_graph
     (n, n) int32, lc_idx (n_lc, 3) int32, lc_pose (n_lc, 6)).
 
     The loop closures close at n_loops keyframes of the second lap, the last n_after keyframes before the end (those after it
     are the 'later keyframes' of :4358).  extra_lc: more (a, b) entries appended as they are; optimized: indices of LC entries
-    whose (2) column is 0 (already optimised; they still make edges)."""
+    whose (2) column is 0 (already optimised; they still make edges).  drift and lc_noise may be 6-vectors (translation, then
+    rotation).  true_poses(n_kf, period, step) -> (n_kf, 4, 4) replaces the planar circle; it must return to its start after
+    `period` keyframes.  cov_step: the shared-landmark count falls by this much per keyframe of distance, over `window`."""
     rng = np.random.Generator(np.random.PCG64(seed))
     period = period or (max(8, int(round(n_kf * 0.8))) | 1)     # odd: no keyframe at a rotation of exactly pi
     assert n_kf > period + n_after
@@ -52,6 +54,9 @@ def pose_graph(n_kf=120, n_loops=1, seed=3, period=None, drift=0.003, lc_noise=0
         T = se3_exp(np.array([0.0, 0.0, 0.0, 0.0, th, 0.0]))
         T[:3, 3] = [R * (1 - np.cos(th)), 0.02 * np.sin(3 * th), R * np.sin(th)]
         T_true[k] = T
+    if true_poses is not None:
+        T_true = np.asarray(true_poses(n_kf, period, step), np.float64).reshape(n_kf, 4, 4)
+    drift, lc_noise = np.asarray(drift, np.float64), np.asarray(lc_noise, np.float64)
     T_kf_w = np.zeros_like(T_true)
     T_kf_w[0] = T_true[0]
     for k in range(1, n_kf):
@@ -64,7 +69,7 @@ def pose_graph(n_kf=120, n_loops=1, seed=3, period=None, drift=0.003, lc_noise=0
     fg = np.zeros((n_kf, n_kf), np.int32)
     for i in range(n_kf):
         for j in range(i + 1, min(n_kf, i + window + 1)):
-            c = int(200 - 40 * (j - i) + rng.integers(-12, 13))
+            c = int(200 - cov_step * (j - i) + rng.integers(-12, 13))
             fg[i, j] = fg[j, i] = max(c, 0)
     fg[valid == 0, :] = 0
     fg[:, valid == 0] = 0

@@ -7,6 +7,7 @@ import pytest
 import plslam_amd
 from plslam_amd import capi, pgo
 
+import pgo_cases
 import pgo_ref
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,39 @@ def test_envelope_solve_reports_a_zero_pivot(ctx):
     A[:, 10] = 0.0
     _, nb, _ = capi.envelope_ldlt_solve(ctx, A, b)
     assert nb >= 1
+
+
+def _block_banded_spd(n_blocks, bw, seed):
+    """The envelope as the pose-graph plan builds it: all six rows of a block start at the first column of the block's lowest
+    neighbour, 0 .. (bw - 5) // 6 blocks back; one block reaches the full distance, so the widest row (the block's last) is
+    6 * ((bw - 5) // 6) + 5 wide."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n, wb = 6 * n_blocks, (bw - 5) // 6
+    back = rng.integers(0, wb + 1, n_blocks)
+    back[n_blocks // 2] = wb
+    A = np.zeros((n, n))
+    for B in range(n_blocks):
+        c0 = 6 * max(0, B - int(back[B]))
+        for r in range(6 * B, 6 * B + 6):
+            A[r, c0:r] = rng.standard_normal(r - c0)
+    A = A + A.T
+    A[np.diag_indices(n)] = np.abs(A).sum(1) + 1.0 + rng.random(n)
+    return A, rng.standard_normal(n), 6 * wb + 5
+
+
+# widths 107 (the last that fits the LDS window of 112), 113 (the first that does not), 149; no n is a multiple of 16
+@pytest.mark.parametrize("n_blocks,bw", [(51, 108), (67, 114), (85, 150), (43, 114)])
+def test_block_envelope_solve_agrees_with_numpy_and_the_dense_solve(ctx, n_blocks, bw):
+    A, b, want = _block_banded_spd(n_blocks, bw, seed=n_blocks + bw)
+    assert A.shape[0] % 16 != 0
+    x, nb, width = capi.envelope_ldlt_solve(ctx, A, b)
+    assert nb == 0 and width == want
+    xr = np.linalg.solve(A, b)
+    xd, nbd = capi.dense_ldlt_solve(ctx, A, b)
+    assert nbd == 0
+    for ref in (xr, xd):
+        assert np.linalg.norm(x - ref) <= 1e-12 * np.linalg.norm(ref)
+    assert np.linalg.norm(A @ x - b) <= 1e-12 * np.linalg.norm(b)
 
 
 # ---- the pose graph ------------------------------------------------------------------------------------------------------------
@@ -240,3 +274,133 @@ def test_correct_map_dev_is_bit_identical_to_the_restatement(ctx):
         assert np.array_equal(d["X"].cpu().numpy(), X)
         assert np.array_equal(d["med_dir"].cpu().numpy(), med)
         assert np.array_equal(d["dirs"].cpu().numpy(), dirs)
+
+
+# ---- the pose graph beyond the planar circle (tests/pgo_cases.py; tests/test_pgo_cpu.py checks which branches each input reaches)
+def _compare_steps(got, ref, n):
+    """scale and rho of the first n (decisive) trials.  rho = (chi - chi') / scale is a difference: its bound is what 1e-9
+    relative on chi, chi' and scale each allow."""
+    for a, b in zip(got["trace"][:n], ref["trace"][:n]):
+        assert a["scale"] == pytest.approx(b["scale"], rel=1e-9)
+        tol = 1e-9 * (abs(b["chi"]) + abs(b["chi_new"])) / abs(b["scale"]) + 1e-9 * abs(b["rho"])
+        assert abs(a["rho"] - b["rho"]) <= tol, (a, b)
+
+
+def _compare_all(got, ref, wb, x_tol=1e-9):
+    n = _compare(got, ref, wb, x_tol)
+    _compare_steps(got, ref, n)
+    assert np.abs(got["T_corr"] - wb[2]).max() <= x_tol
+    return n
+
+
+@pytest.mark.parametrize("name", list(pgo_cases.INPUTS))
+def test_optimize_matches_the_restatement_off_the_circle(ctx, name):
+    m = pgo_cases.INPUTS[name]()
+    got = _run(ctx, m)
+    P, ref, wb = _ref(m)
+    assert got["n_active"] == len(P.active) and got["n_edges"] == len(P.g["edges"])
+    # tumbling_rejections is the rejections case over again (1.5 rad of LC noise): a large residual makes Gauss-Newton converge
+    # linearly, so after the last decisive trial the state still moves by ~1e-8 over trials whose acceptance is rounding
+    n = _compare_all(got, ref, wb, x_tol=1e-6 if name == "tumbling_rejections" else 1e-9)
+    assert n >= 2
+    assert got["chi_final"] < 0.1 * got["chi_initial"]
+    if name == "tumbling_rejections":
+        assert any(not t["accepted"] for t in ref["trace"][:n])
+
+
+@pytest.mark.parametrize("max_iters", [0, 1])
+@pytest.mark.parametrize("name", ["tumbling", "near_5e-7", "near_5e-6", "near_3e-5", "near_2e-3"])
+def test_stage_probes(ctx, name, max_iters):
+    """max_iters_pgo = 0: the measurements, the initial guess and the write-back with no solve in between (chi_initial, T, x,
+    T_corr).  1: one linearisation, its solve and the vertex update (the first trial's chi', scale and rho)."""
+    m = pgo_cases.INPUTS[name]()
+    got = _run(ctx, m, max_iters)
+    _, ref, wb = _ref(m, max_iters)
+    assert got["iterations"] == max_iters and len(got["trace"]) == len(ref["trace"])
+    n = _compare_all(got, ref, wb)
+    if max_iters == 0:
+        assert got["trace"] == [] and got["chi_final"] == pytest.approx(ref["chi_initial"], rel=1e-9)
+    else:
+        assert n >= 1 and got["trace"][0]["accepted"]
+        assert got["chi_final"] == pytest.approx(ref["chi_final"], rel=1e-9)
+
+
+def test_device_chi_does_not_depend_on_the_world_frame(ctx):
+    """The device against itself: a map conjugated by a world rotation has the chi of the original (1e-9 relative, the trace
+    tolerance), and its corrected poses mapped back are the original's."""
+    m0 = pgo.pose_graph(n_kf=60, seed=6)
+    g0 = _run(ctx, m0)
+    for name in pgo_cases.FRAMES:
+        G = pgo_cases.frame(name)
+        Gi = np.linalg.inv(G)
+        g = _run(ctx, pgo_cases.conjugate(m0, G))
+        assert g["chi_initial"] == pytest.approx(g0["chi_initial"], rel=1e-9)
+        assert g["chi_final"] == pytest.approx(g0["chi_final"], rel=1e-9)
+        assert np.abs(np.stack([Gi @ T @ G for T in g["T"]]) - g0["T"]).max() <= 1e-9
+        assert np.array_equal(g["corrected"], g0["corrected"])
+
+
+def _against_the_dense_path(ctx, m, env):
+    ctx.set_option("pgo_solver", 1)
+    try:
+        den = _run(ctx, m)
+    finally:
+        ctx.set_option("pgo_solver", 0)
+    n = _decisive(env["trace"])
+    assert n >= 2
+    for a, b in zip(env["trace"][:n], den["trace"][:n]):
+        assert a["accepted"] == b["accepted"] and a["chi_new"] == pytest.approx(b["chi_new"], rel=1e-9)
+    assert np.abs(env["x"] - den["x"]).max() <= 1e-9
+
+
+@pytest.mark.parametrize("name", ["wide_band", "many_loops"])
+def test_envelope_beyond_the_lds_window_inside_optimize(ctx, name):
+    """The global-memory path of the factor and the solve on the 6-row-block envelope with + lambda I that optimize builds."""
+    m = pgo_cases.wide_band() if name == "wide_band" else pgo_cases.many_loops()
+    got = _run(ctx, m)
+    assert got["env_width"] > 112
+    _, ref, wb = _ref(m)
+    assert _compare_all(got, ref, wb) >= 2
+    _against_the_dense_path(ctx, m, got)
+
+
+def test_envelope_of_the_last_lds_window_size_inside_optimize(ctx):
+    m = pgo_cases.wide_band(window=8)
+    got = _run(ctx, m)
+    assert 100 <= got["env_width"] <= 112
+    _, ref, wb = _ref(m)
+    assert _compare_all(got, ref, wb) >= 2
+    _against_the_dense_path(ctx, m, got)
+
+
+def test_a_non_finite_pose_fails_every_factorisation(ctx):
+    """a failed factorisation takes a zero step and chi' = DBL_MAX.  With a NaN in one stored pose every
+    trial fails; rho is NaN, so each iteration makes one trial and nothing is accepted."""
+    import warnings
+    m = pgo_cases.with_nan_pose(pgo_cases.tumbling(n_kf=60, seed=35), 20)
+    got = _run(ctx, m, 3)
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        _, ref, wb = _ref(m, 3)
+    assert len(ref["trace"]) == 3 and not any(t["ok"] or t["accepted"] for t in ref["trace"])
+    assert len(got["trace"]) == got["trials"] == len(ref["trace"])
+    for a, b in zip(got["trace"], ref["trace"]):
+        assert (a["it"], a["trial"]) == (b["it"], b["trial"])
+        assert not a["ok"] and not a["accepted"] and a["chi_new"] == pgo_ref.DBL_MAX == b["chi_new"]
+        assert a["lam"] == pytest.approx(b["lam"], rel=1e-9)
+    assert got["iterations"] == ref["iterations"] and got["stop_reason"] == ref["stop"]
+    assert np.array_equal(got["corrected"], wb[3])
+
+
+def test_correct_map_with_the_corrections_of_a_tumbling_run(ctx):
+    m = pgo_cases.tumbling(n_kf=60, seed=36, n_after=4)
+    got = _run(ctx, m)
+    Rc = got["T_corr"][1:, :3, :3]
+    assert (np.abs(Rc[:, [2, 0, 1], [1, 2, 0]] - Rc[:, [1, 2, 0], [2, 0, 1]]) > 1e-6).all(1).sum() >= 50     # turns about all axes
+    pts = pgo.anchored_landmarks(60, 2000, seed=37, kf_valid=m["kf_valid"], n_double=20)
+    lns = pgo.anchored_landmarks(60, 500, seed=38, line=True, kf_valid=m["kf_valid"], n_double=10)
+    gp, gl = capi.correct_map(ctx, got["T_corr"].reshape(-1, 16), got["corrected"], pts, lns)
+    for g, lm, line in ((gp, pts, False), (gl, lns, True)):
+        X, med, dirs = _ref_map(got, lm, line)
+        assert np.array_equal(g["X"], X) and np.array_equal(g["med_dir"], med) and np.array_equal(g["dirs"], dirs)
+        assert not np.array_equal(X, lm["X"])

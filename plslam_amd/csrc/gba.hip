@@ -366,7 +366,6 @@ k_gba_stats(const double* __restrict__ part, int32_t npart, const int32_t* __res
     }
 }
 
-inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }
 
 }  // namespace
 }  // namespace plslam

@@ -11,7 +11,7 @@
 // Result order == OpenCV batchDistance(K=2): lexicographic (distance, trainIdx).  It is encoded
 // as an unsigned min over composite keys  key = (distance << 23) | trainIdx  so that every
 // merge (per lane, across lanes, across workgroups) is associative and tie-exact.
-#include "common.hpp"
+#include "mfma_h_common.hpp"
 #include "stereo_gates_dev.hpp"
 
 namespace plslam {
@@ -24,12 +24,6 @@ __device__ __forceinline__ uint32_t bcnt0(uint32_t x)
 {
     uint32_t r;
     asm("v_bcnt_u32_b32 %0, %1, 0" : "=v"(r) : "v"(x));
-    return r;
-}
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc)
-{
-    uint32_t r;  // r = popcount(x) + acc in ONE VALU op
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
     return r;
 }
 __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
@@ -47,53 +41,35 @@ __device__ __forceinline__ uint32_t make_key_s(uint32_t d, uint32_t j_uniform)
     return r;
 }
 static_assert(KEY_IDX_BITS == 23, "make_key_s hard-codes the shift");
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
-// keep the two smallest keys; invariant b0 <= b1
+// keep the two smallest keys; invariant b0 <= b1.  Not pk_push2's min / max / min on 32-bit keys: v_med3_u32 + v_min_u32
+// are two instructions where that form is three
 __device__ __forceinline__ void best2_push(uint32_t& b0, uint32_t& b1, uint32_t key)
 {
     const uint32_t nb1 = med3_u32(b0, b1, key);
-    b0 = umin(b0, key);
+    b0 = umin_(b0, key);
     b1 = nb1;
-}
-// merge two sorted pairs
-__device__ __forceinline__ void best2_merge(uint32_t& a0, uint32_t& a1, uint32_t c0, uint32_t c1)
-{
-    const uint32_t lo = umin(a0, c0);
-    const uint32_t hi = umin(umax(a0, c0), umin(a1, c1));
-    a0 = lo;
-    a1 = hi;
 }
 
 // 8 XOR + 8 BCNT: q in VGPRs, train row in SGPRs (wave-uniform)
 #define PLSLAM_DIST8(q, tp)                                                                      \
-    bcnt_acc(q[7] ^ (tp)[7],                                                                     \
-      bcnt_acc(q[6] ^ (tp)[6],                                                                   \
-        bcnt_acc(q[5] ^ (tp)[5],                                                                 \
-          bcnt_acc(q[4] ^ (tp)[4],                                                               \
-            bcnt_acc(q[3] ^ (tp)[3],                                                             \
-              bcnt_acc(q[2] ^ (tp)[2],                                                           \
-                bcnt_acc(q[1] ^ (tp)[1], bcnt0(q[0] ^ (tp)[0]))))))))
+    bcnt_acc_(q[7] ^ (tp)[7],                                                                    \
+      bcnt_acc_(q[6] ^ (tp)[6],                                                                  \
+        bcnt_acc_(q[5] ^ (tp)[5],                                                                \
+          bcnt_acc_(q[4] ^ (tp)[4],                                                              \
+            bcnt_acc_(q[3] ^ (tp)[3],                                                            \
+              bcnt_acc_(q[2] ^ (tp)[2],                                                          \
+                bcnt_acc_(q[1] ^ (tp)[1], bcnt0(q[0] ^ (tp)[0]))))))))
 
 // same with the popcount chain started from `bias` (a VGPR) instead of 0: d + bias at no extra cost
 #define PLSLAM_DIST8B(q, tp, bias)                                                               \
-    bcnt_acc(q[7] ^ (tp)[7],                                                                     \
-      bcnt_acc(q[6] ^ (tp)[6],                                                                   \
-        bcnt_acc(q[5] ^ (tp)[5],                                                                 \
-          bcnt_acc(q[4] ^ (tp)[4],                                                               \
-            bcnt_acc(q[3] ^ (tp)[3],                                                             \
-              bcnt_acc(q[2] ^ (tp)[2],                                                           \
-                bcnt_acc(q[1] ^ (tp)[1], bcnt_acc(q[0] ^ (tp)[0], bias))))))))
-
-// XCD-striped block tables: hardware places workgroup b on XCD b % 8 and dispatches in increasing
-// b; the host lays the table out as 8 rows of L = gridDim.x / 8 entries, row x = the work of XCD x in
-// dispatch order (capi.hip, `stripe`), so the blocks of one problem -- which stream the same
-// descriptor sets -- sit on one XCD's L2 at the same time.  Rows are padded with item = -1.
-__device__ __forceinline__ int xcd_remap(int orig, int nwg)
-{
-    return (orig & 7) * (nwg >> 3) + (orig >> 3);
-}
+    bcnt_acc_(q[7] ^ (tp)[7],                                                                    \
+      bcnt_acc_(q[6] ^ (tp)[6],                                                                  \
+        bcnt_acc_(q[5] ^ (tp)[5],                                                                \
+          bcnt_acc_(q[4] ^ (tp)[4],                                                              \
+            bcnt_acc_(q[3] ^ (tp)[3],                                                            \
+              bcnt_acc_(q[2] ^ (tp)[2],                                                          \
+                bcnt_acc_(q[1] ^ (tp)[1], bcnt_acc_(q[0] ^ (tp)[0], bias))))))))
 
 // ---------------------------------------------------------------------------------------------
 // K1a  lane-per-query scan.  One lane owns one query row (8 VGPRs) for the whole scan and keeps
@@ -110,7 +86,7 @@ k_scan_lane_per_query(const ScanDesc* __restrict__ scans, const BlockDesc* __res
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < nzero; i += BLOCK) g_(zero)[i] = 0;
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int wg = xcd_remap_(blockIdx.x, gridDim.x);
     const BlockDesc bd = blocks[wg];
     if (bd.item < 0) return;                       // padding entry of the XCD-striped table
     const ScanDesc sc = scans[bd.item];
@@ -223,7 +199,7 @@ k_scan_wave_per_query(const ScanDesc* __restrict__ scans, const BlockDesc* __res
         uint32_t k0 = b[k][0], k1 = b[k][1];
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1)
-            best2_merge(k0, k1, (uint32_t)__shfl_xor((int)k0, m), (uint32_t)__shfl_xor((int)k1, m));
+            merge2(k0, k1, (uint32_t)__shfl_xor((int)k0, m), (uint32_t)__shfl_xor((int)k1, m));
         if (lane == 0 && q0 + k < nq) g_(reinterpret_cast<gvec2_t*>(sc.keys))[q0 + k] = gvec2_t{k0, k1};
     }
 }
@@ -249,18 +225,6 @@ constexpr int SYM_TILE_U16 = 64 * SYM_TILE_ROW_U16;           // 9216 bytes per 
 
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // packed keys of two candidates: ((d_hi << 6) | i_hi) << 16 | ((d_lo << 6) | i_lo);  w = d_hi<<16|d_lo.
 // Rows past the end of `a` (ragged last block) carry d + 512 (see SYM_INVALID_BIAS), i.e. key16 >=
 // 0x8000: they sort after every real candidate (real keys are <= (256 << 6) | 63 = 0x403F).
@@ -291,8 +255,7 @@ __device__ __forceinline__ void sym_column_reduce(const uint16_t* __restrict__ c
         for (int u = 0; u < 4; ++u) {
             const int i_lo = 8 * v + 2 * u;
             const uint32_t key = pk_keys(w[u], (uint32_t)(((i_lo + 1) << 16) | i_lo));
-            b1 = pk_min_u16(b1, pk_max_u16(b0, key));
-            b0 = pk_min_u16(b0, key);
+            pk_push2(b0, b1, key);
         }
     }
 }
@@ -306,7 +269,7 @@ k_scan_symmetric(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < nzero; i += 256) g_(zero)[i] = 0;
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int wg = xcd_remap_(blockIdx.x, gridDim.x);
     const BlockDesc bd = blocks[wg];
     if (bd.item < 0) return;                       // padding entry of the XCD-striped table
     const SymDesc sd = syms[bd.item];
@@ -369,8 +332,8 @@ k_scan_symmetric(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__
         {
             // two sorted streams (even i in the low halves, odd i in the high halves) -> best 2
             const uint32_t e0 = c0p & 0xFFFFu, o0 = c0p >> 16, e1 = c1p & 0xFFFFu, o1 = c1p >> 16;
-            const uint32_t m0 = umin(e0, o0);
-            const uint32_t m1 = umin(umax(e0, o0), umin(e1, o1));
+            const uint32_t m0 = umin_(e0, o0);
+            const uint32_t m1 = umin_(umax_(e0, o0), umin_(e1, o1));
             if (lane < jc)
                 part[j0 + lane] = gvec2_t{key16_to_32(m0, (uint32_t)i0), key16_to_32(m1, (uint32_t)i0)};
         }
@@ -407,7 +370,7 @@ k_scan_symmetric_r4(const SymDesc* __restrict__ syms, const BlockDesc* __restric
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < nzero; i += 64) g_(zero)[i] = 0;
 
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int wg = xcd_remap_(blockIdx.x, gridDim.x);
     const BlockDesc bd = blocks[wg];
     if (bd.item < 0) return;                       // padding entry of the XCD-striped table
     const SymDesc sd = syms[bd.item];
@@ -452,17 +415,17 @@ k_scan_symmetric_r4(const SymDesc* __restrict__ syms, const BlockDesc* __restric
     {                                                                                             \
         uint32_t x[8];                                                                            \
         _Pragma("unroll") for (int k = 0; k < 8; ++k) x[k] = q0[k] ^ (T)[k];                      \
-        const uint32_t e0 = bcnt_acc(x[7], bcnt_acc(x[6], bcnt_acc(x[5], bcnt_acc(x[4],           \
-                            bcnt_acc(x[3], bcnt_acc(x[2], bcnt_acc(x[1], bcnt_acc(x[0], bias[0]))))))));  \
-        const uint32_t e1 = bcnt_acc(x[7] ^ c1[7], bcnt_acc(x[6] ^ c1[6], bcnt_acc(x[5] ^ c1[5],  \
-                            bcnt_acc(x[4] ^ c1[4], bcnt_acc(x[3] ^ c1[3], bcnt_acc(x[2] ^ c1[2],  \
-                            bcnt_acc(x[1] ^ c1[1], bcnt_acc(x[0] ^ c1[0], bias[1]))))))));        \
-        const uint32_t e2 = bcnt_acc(x[7] ^ c2[7], bcnt_acc(x[6] ^ c2[6], bcnt_acc(x[5] ^ c2[5],  \
-                            bcnt_acc(x[4] ^ c2[4], bcnt_acc(x[3] ^ c2[3], bcnt_acc(x[2] ^ c2[2],  \
-                            bcnt_acc(x[1] ^ c2[1], bcnt_acc(x[0] ^ c2[0], bias[2]))))))));        \
-        const uint32_t e3 = bcnt_acc(x[7] ^ c3[7], bcnt_acc(x[6] ^ c3[6], bcnt_acc(x[5] ^ c3[5],  \
-                            bcnt_acc(x[4] ^ c3[4], bcnt_acc(x[3] ^ c3[3], bcnt_acc(x[2] ^ c3[2],  \
-                            bcnt_acc(x[1] ^ c3[1], bcnt_acc(x[0] ^ c3[0], bias[3]))))))));        \
+        const uint32_t e0 = bcnt_acc_(x[7], bcnt_acc_(x[6], bcnt_acc_(x[5], bcnt_acc_(x[4],       \
+                            bcnt_acc_(x[3], bcnt_acc_(x[2], bcnt_acc_(x[1], bcnt_acc_(x[0], bias[0])))))))); \
+        const uint32_t e1 = bcnt_acc_(x[7] ^ c1[7], bcnt_acc_(x[6] ^ c1[6], bcnt_acc_(x[5] ^ c1[5], \
+                            bcnt_acc_(x[4] ^ c1[4], bcnt_acc_(x[3] ^ c1[3], bcnt_acc_(x[2] ^ c1[2], \
+                            bcnt_acc_(x[1] ^ c1[1], bcnt_acc_(x[0] ^ c1[0], bias[1]))))))));      \
+        const uint32_t e2 = bcnt_acc_(x[7] ^ c2[7], bcnt_acc_(x[6] ^ c2[6], bcnt_acc_(x[5] ^ c2[5], \
+                            bcnt_acc_(x[4] ^ c2[4], bcnt_acc_(x[3] ^ c2[3], bcnt_acc_(x[2] ^ c2[2], \
+                            bcnt_acc_(x[1] ^ c2[1], bcnt_acc_(x[0] ^ c2[0], bias[2]))))))));      \
+        const uint32_t e3 = bcnt_acc_(x[7] ^ c3[7], bcnt_acc_(x[6] ^ c3[6], bcnt_acc_(x[5] ^ c3[5], \
+                            bcnt_acc_(x[4] ^ c3[4], bcnt_acc_(x[3] ^ c3[3], bcnt_acc_(x[2] ^ c3[2], \
+                            bcnt_acc_(x[1] ^ c3[1], bcnt_acc_(x[0] ^ c3[0], bias[3]))))))));      \
         wr[0 * SYM4_SUBTILE_U16 + (JJ) * SYM_TILE_ROW_U16] = (uint16_t)e0;                        \
         wr[1 * SYM4_SUBTILE_U16 + (JJ) * SYM_TILE_ROW_U16] = (uint16_t)e1;                        \
         wr[2 * SYM4_SUBTILE_U16 + (JJ) * SYM_TILE_ROW_U16] = (uint16_t)e2;                        \
@@ -496,11 +459,11 @@ k_scan_symmetric_r4(const SymDesc* __restrict__ syms, const BlockDesc* __restric
         uint32_t c0p, c1p;
         sym_column_reduce(col, c0p, c1p);
         const uint32_t ev0 = c0p & 0xFFFFu, od0 = c0p >> 16, ev1 = c1p & 0xFFFFu, od1 = c1p >> 16;
-        uint32_t k0 = key16_to_32(umin(ev0, od0), col_i_base);
-        uint32_t k1 = key16_to_32(umin(umax(ev0, od0), umin(ev1, od1)), col_i_base);
+        uint32_t k0 = key16_to_32(umin_(ev0, od0), col_i_base);
+        uint32_t k1 = key16_to_32(umin_(umax_(ev0, od0), umin_(ev1, od1)), col_i_base);
         // combine the four row-blocks of a column: lanes l, l^16, l^32, l^48
-        best2_merge(k0, k1, (uint32_t)__shfl_xor((int)k0, 16), (uint32_t)__shfl_xor((int)k1, 16));
-        best2_merge(k0, k1, (uint32_t)__shfl_xor((int)k0, 32), (uint32_t)__shfl_xor((int)k1, 32));
+        merge2(k0, k1, (uint32_t)__shfl_xor((int)k0, 16), (uint32_t)__shfl_xor((int)k1, 16));
+        merge2(k0, k1, (uint32_t)__shfl_xor((int)k0, 32), (uint32_t)__shfl_xor((int)k1, 32));
         if (lane < jc) part[j0 + lane] = gvec2_t{k0, k1};
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -526,7 +489,7 @@ k_merge_partials(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__
     uint32_t b0 = KEY_NONE, b1 = KEY_NONE;
     for (int ib = 0; ib < sd.n_iblk; ++ib) {
         const gvec2_t p = part[(size_t)ib * sd.n2 + j];
-        best2_merge(b0, b1, p.x, p.y);
+        merge2(b0, b1, p.x, p.y);
     }
     g_(reinterpret_cast<gvec2_t*>(sd.keys21))[j] = gvec2_t{b0, b1};
 }
@@ -565,7 +528,7 @@ __device__ __forceinline__ void finalize_row(const ProblemDesc& p, const int i1,
             for (int s = 0; s < p.nsplit; ++s) {
                 const gvec2_t q = tmp[(size_t)s * p.n1 + i1];
                 const uint32_t off = (uint32_t)(s * p.cstep);
-                best2_merge(b0, b1, q.x == KEY_NONE ? KEY_NONE : q.x + off, q.y == KEY_NONE ? KEY_NONE : q.y + off);
+                merge2(b0, b1, q.x == KEY_NONE ? KEY_NONE : q.x + off, q.y == KEY_NONE ? KEY_NONE : q.y + off);
             }
             k = make_uint2(b0, b1);
             g_(reinterpret_cast<gvec2_t*>(p.keys12_out))[i1] = gvec2_t{k.x, k.y};          // diagnostics (plslam_match_plan_dump)
@@ -736,15 +699,15 @@ k_post_fused(const ProblemDesc* __restrict__ probs, const plslam_stereo_gate_pro
                     const uint32_t e0 = e[q] >> 9, e1 = ((e[q] & 511u) << 8) | 255u;     // (d0 << 8 | row0), the second entry's distance
                     const uint32_t k = ((e0 >> 8) << KEY_IDX_BITS) | ((e0 & 255u) + 256u * (uint32_t)wb);
                     sx[q] = k < b0[q] ? e1 : sx[q];
-                    b1[q] = umin(b1[q], umax(b0[q], k));
-                    b0[q] = umin(b0[q], k);
+                    b1[q] = umin_(b1[q], umax_(b0[q], k));
+                    b0[q] = umin_(b0[q], k);
                 }
             }
 #pragma unroll
             for (int q = 0; q < PF; ++q) {
                 if (j[q] >= p.n2) continue;                // the slot holds no column
                 if (b0[q] < (257u << KEY_IDX_BITS)) {
-                    b1[q] = umin(b1[q], ((sx[q] >> 8) << KEY_IDX_BITS) | KEY_IDX_MASK);
+                    b1[q] = umin_(b1[q], ((sx[q] >> 8) << KEY_IDX_BITS) | KEY_IDX_MASK);
                     if (b1[q] >= (257u << KEY_IDX_BITS)) b1[q] = KEY_NONE;
                 } else {
                     b0[q] = b1[q] = KEY_NONE;

@@ -30,24 +30,11 @@
 //   column direction: best-2 over the lane's 32 accumulators (the key comes out of the MFMA: tag = local
 //                   row), halves and lane ^ 32 combined in the 16-bit domain, the four waves through LDS,
 //                   one partial per 256 rows of `a`, as K1b'.  Not built in the DIRECTED instantiation.
-#include "common.hpp"
+#include "mfma_h_common.hpp"
 
 #include <type_traits>
 
 namespace plslam {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4), aligned(4)));   // descriptor rows are only 4-byte aligned
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// Pointers read from the launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction, which
-// counts on lgkmcnt as well as vmcnt: the `s_waitcnt lgkmcnt(0)` in front of every workgroup barrier then waits for
-// the raw-row PREFETCH of two tiles ahead (round 2 finding: every tile paid a memory latency).  With the address
-// space spelled out the loads are global_load (vmcnt only) and stay in flight across the barrier.
-#define PLSLAM_GLOBAL __attribute__((address_space(1)))
-typedef const PLSLAM_GLOBAL uint32_t* gcu32_t;
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef PLSLAM_GLOBAL u32x2_t* gu2_t;
 
 namespace {
 
@@ -55,64 +42,8 @@ constexpr int MF_TILE_N = 32;                 // b rows per tile
 constexpr int MF_KSTEPS = 4;                  // 256 bits = 4 x K 64
 constexpr int MF_ROW_STRIDE = 144;            // bytes per expanded b row in LDS (128 + 16: 4-bank skew)
 constexpr int MF_TILE_BYTES = MF_TILE_N * MF_ROW_STRIDE;
-// fp4 (e2m1) codes: +1.0 = 0x2, -1.0 = 0xA.  b side: bit 0 -> +1, bit 1 -> -1 = s(b); the a side is the b code
-// XOR 0x8 per nibble (= -s(a)) and carries the block scale 2^6 (E8M0 133), the b side 2^0 (E8M0 127).
-constexpr uint32_t FP4_NEG = 0x88888888u;
-constexpr int SCALE_A = 133, SCALE_B = 127;
 constexpr float ACC_MAGIC = 8388608.0f;       // 2^23: float bits = 0x4B000000 + integer part
 
-__device__ __forceinline__ uint32_t umin_(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t umax_(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ void merge2(uint32_t& a0, uint32_t& a1, uint32_t c0, uint32_t c1)
-{
-    const uint32_t lo = umin_(a0, c0);
-    const uint32_t hi = umin_(umax_(a0, c0), umin_(a1, c1));
-    a0 = lo;
-    a1 = hi;
-}
-// packed 16-bit min / max.  Inline asm on purpose: written with the vector builtins the compiler sinks
-// the row-direction pushes out of the MFMA block into a block of their own (96 VALU ops with no MFMA to
-// hide under, 6 spilled VGPRs; measured 6.10 ms vs 5.85 ms).
-__device__ __forceinline__ uint32_t pk_min16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_max16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// two sorted streams of 16-bit keys, one per half of the register
-__device__ __forceinline__ void pk_push2(uint32_t& b0, uint32_t& b1, uint32_t key)
-{
-    b1 = pk_min16(b1, pk_max16(b0, key));
-    b0 = pk_min16(b0, key);
-}
-// accumulators of the two M-tiles (2^23 + 128 d + tag, tag <= 127) side by side: hi.lo16 << 16 | lo.lo16
-__device__ __forceinline__ uint32_t pack_acc(float lo, float hi, uint32_t sel_uniform /* 0x05040100 */)
-{
-    // The BUILTIN, not inline asm: this is the one instruction that reads MFMA results directly, and on gfx950 the
-    // wait states between an MFMA and a VALU access to its destination registers are the COMPILER's job (s_nop); its
-    // hazard recognizer does not look inside asm statements.  As `asm("v_perm_b32 ...")` the first two packs of the
-    // unpipelined epilogue issued right behind the last MFMA of the set: accumulators 0 and 1 (tile rows 0, 1, 4, 5)
-    // were read -- and register 0 overwritten -- while still in flight.  Right most of the time, wrong when waves of
-    // co-resident workgroups delayed the matrix pipe: ~1 % of the intermediate keys of a loaded batch differed from
-    // run to run, 1e-6 of the table entries at a 0.9 ratio ("K1e determinism";
-    // tools/determinism_check.py is the instrument).  The v_pk_min/max asm below only ever sees pack_acc's result.
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), sel_uniform);
-}
-// 16-bit keys are (d << 7) | tag7: the A bytes are -64 s(a), so with C = 16384 + tag the accumulator
-// itself is 128 d + tag (<= (256 << 7) + 127 = 0x807F); anything above is "none"
-constexpr uint32_t KEY16_MAX = 0x807Fu;
-__device__ __forceinline__ uint32_t key16_to_key32(uint32_t k16, uint32_t tag_bias, uint32_t idx_base,
-                                                   uint32_t idx_scale)
-{
-    return k16 > KEY16_MAX ? KEY_NONE
-                           : (((k16 >> 7) << KEY_IDX_BITS) | (idx_base + ((k16 & 127u) - tag_bias) * idx_scale));
-}
 // one byte of a descriptor -> 8 fp4 codes of s(bit): bit k -> nibble k = 0x2 | (bit << 3)
 __device__ __forceinline__ uint32_t expand_byte_fp4(uint32_t byte)
 {
@@ -121,7 +52,6 @@ __device__ __forceinline__ uint32_t expand_byte_fp4(uint32_t byte)
     x = (x | (x << 3)) & 0x11111111u;                      // 1 bit per nibble (at bit 0)
     return (x << 3) | 0x22222222u;
 }
-__device__ __forceinline__ int xcd_remap_(int orig, int nwg) { return (orig & 7) * (nwg >> 3) + (orig >> 3); }
 
 }  // namespace
 
@@ -186,7 +116,6 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 16; ++r) cinit[r] = ACC_MAGIC + 16384.0f + (float)((r & 3) + 8 * (r >> 2));
     const int scale_a = SCALE_A, scale_b = SCALE_B;
-    const uint32_t pack_sel = 0x05040100u;
 
     // row-direction state: per accumulator register r, the best two 16-bit keys (d << 6 | tile) of the
     // lane's column class, M-tile 0 in the low halves and M-tile 1 in the high halves
@@ -241,7 +170,7 @@ k_scan_sym_mfma(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ 
 #define PLSLAM_MF_EPI_ROW(R)                                                                       \
     {                                                                                              \
         constexpr uint32_t LOC = ((R) & 3) + 8 * ((R) >> 2);                                       \
-        uint32_t kc = pack_acc(acc0[R], acc1[R], pack_sel);                                        \
+        uint32_t kc = pack_acc(acc0[R], acc1[R]);                                                  \
         uint32_t kr = kc + tpair;                                                                  \
         if (MASKED) {                                                                              \
             kr = col_ok ? kr : 0xFFFFFFFFu;                                                        \

@@ -31,22 +31,11 @@
 // The tag of a key is the tile number within the group (4 bits, from the accumulator seed: 16 v_add per tile in the
 // shadow of the MFMAs); the group number within the window (3 bits) is added at push time: windows of 128 tiles = 4096
 // columns (K1f: 64 tiles).
-#include "common.hpp"
+#include "mfma_h_common.hpp"
 
 #include <type_traits>
 
 namespace plslam {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4), aligned(4)));   // descriptor rows are only 4-byte aligned
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-#define PLSLAM_GLOBAL __attribute__((address_space(1)))
-typedef const PLSLAM_GLOBAL uint32_t* gcu32_t;
-typedef const PLSLAM_GLOBAL u32x4_t* gcu32x4_t;
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef PLSLAM_GLOBAL u32x2_t* gu2_t;
 
 namespace {
 
@@ -57,44 +46,7 @@ constexpr int MD_TILE_BYTES = MD_TILE_N * MD_ROW_STRIDE;
 constexpr int MD_GROUP = 16;                  // tiles per group (512 b rows)
 constexpr int MD_GROUP_ROWS = MD_GROUP * MD_TILE_N;
 constexpr int MD_WINDOW = 128;                // tiles per window: tag = group in window (3 bits) << 4 | tile in group (4 bits)
-constexpr uint32_t FP4_NEG = 0x88888888u;
-constexpr uint32_t FP4_ONE = 0x22222222u;
-constexpr int SCALE_A = 133, SCALE_B = 127;   // E8M0: 2^6 on the a side, 2^0 on the b side
-constexpr uint32_t ACC_BITS = 0x4B000000u + 16384u;   // float bits of 2^23 + 16384
-constexpr uint32_t KEY16_MAX = 0x807Fu;       // 16-bit keys are (d << 7) | tag7; anything above is "none"
 
-__device__ __forceinline__ uint32_t umin_(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t umax_(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ void merge2(uint32_t& a0, uint32_t& a1, uint32_t c0, uint32_t c1)
-{
-    const uint32_t lo = umin_(a0, c0);
-    const uint32_t hi = umin_(umax_(a0, c0), umin_(a1, c1));
-    a0 = lo;
-    a1 = hi;
-}
-__device__ __forceinline__ uint32_t pk_min16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_max16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_add16_sat(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_add_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void pk_push2(uint32_t& b0, uint32_t& b1, uint32_t key)
-{
-    b1 = pk_min16(b1, pk_max16(b0, key));
-    b0 = pk_min16(b0, key);
-}
 // the running minimum of a (row, class): low halves only (v_min_u16: the one comparison of the fast VALU class).  Inline
 // asm, because every C++ spelling ends up in the SLP vectoriser (two scalar minima -> v_perm + v_pk_min_u16 + two unpacks).
 // The accumulator operand is an MFMA destination, and the wait states between an MFMA and a VALU read of its result are
@@ -107,30 +59,6 @@ __device__ __forceinline__ uint32_t min_lo16(uint32_t running, uint32_t acc_bits
     asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(running), "v"(acc_bits));
     return r;
 }
-// 32 bits of a descriptor -> 32 fp4 codes of s(bit): dword s holds bits 4k + s, nibble k = 0x2 | bit << 3 (see K1f)
-template <bool A_SIDE>
-__device__ __forceinline__ i32x4 expand_dword_fp4(uint32_t x)
-{
-    uint32_t x1, x2, x3;
-    asm("v_add_u32 %0, %1, %1" : "=v"(x1) : "v"(x));
-    asm("v_add_u32 %0, %1, %1" : "=v"(x2) : "v"(x1));
-    asm("v_add_u32 %0, %1, %1" : "=v"(x3) : "v"(x2));
-    constexpr uint32_t base = A_SIDE ? (FP4_ONE ^ FP4_NEG) : FP4_ONE;       // a side: sign nibble-bit flipped
-    constexpr unsigned TT = A_SIDE ? 0x6Au : 0xEAu;                         // (a & b) ^ c  |  (a & b) | c
-    i32x4 v;
-    v.x = (int)__builtin_amdgcn_bitop3_b32(x3, FP4_NEG, base, TT);
-    v.y = (int)__builtin_amdgcn_bitop3_b32(x2, FP4_NEG, base, TT);
-    v.z = (int)__builtin_amdgcn_bitop3_b32(x1, FP4_NEG, base, TT);
-    v.w = (int)__builtin_amdgcn_bitop3_b32(x, FP4_NEG, base, TT);
-    return v;
-}
-__device__ __forceinline__ uint32_t bcnt_acc_(uint32_t x, uint32_t acc)
-{
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ int xcd_remap_(int orig, int nwg) { return (orig & 7) * (nwg >> 3) + (orig >> 3); }
 
 }  // namespace
 

@@ -29,26 +29,11 @@
 //
 // The column direction is unchanged (exact best-2 per tile): a column's candidates are complete within the
 // tile, so a deferred second best would have to be recomputed per tile and row block, which costs what it saves.
-#include "common.hpp"
+#include "mfma_h_common.hpp"
 
 #include <type_traits>
 
 namespace plslam {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4), aligned(4)));   // descriptor rows are only 4-byte aligned
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// Pointers read from the launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction, which
-// counts on lgkmcnt as well as vmcnt: the `s_waitcnt lgkmcnt(0)` in front of every workgroup barrier then waits for
-// the raw-row PREFETCH of two tiles ahead, i.e. every tile pays a full memory latency.  With the address space spelled
-// out the loads are global_load (vmcnt only) and stay in flight across the barrier.
-#define PLSLAM_GLOBAL __attribute__((address_space(1)))
-typedef const PLSLAM_GLOBAL uint32_t* gcu32_t;
-typedef const PLSLAM_GLOBAL u32x4_t* gcu32x4_t;
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef PLSLAM_GLOBAL u32x2_t* gu2_t;
-typedef PLSLAM_GLOBAL uint32_t* gu32_t;
 
 namespace {
 
@@ -63,89 +48,6 @@ constexpr int MF_TILE_BYTES = MF_TILE_N * MF_ROW_STRIDE;
 // MF_GROUP - 1 recomputed distances per row and window.
 constexpr int MF_GROUP = 16;
 constexpr int MF_CGROUP = 8;                  // tiles whose column results are staged in LDS and stored together (256 columns)
-// fp4 (e2m1) codes: +1.0 = 0x2, -1.0 = 0xA.  b side: bit 0 -> +1, bit 1 -> -1 = s(b); the a side is the b code
-// XOR 0x8 per nibble (= -s(a)) and carries the block scale 2^6 (E8M0 133), the b side 2^0 (E8M0 127).
-constexpr uint32_t FP4_NEG = 0x88888888u;
-constexpr uint32_t FP4_ONE = 0x22222222u;
-constexpr int SCALE_A = 133, SCALE_B = 127;
-constexpr uint32_t ACC_BITS = 0x4B000000u + 16384u;   // float bits of 2^23 + 16384 (+ small integers: + the integer)
-
-__device__ __forceinline__ uint32_t umin_(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t umax_(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ void merge2(uint32_t& a0, uint32_t& a1, uint32_t c0, uint32_t c1)
-{
-    const uint32_t lo = umin_(a0, c0);
-    const uint32_t hi = umin_(umax_(a0, c0), umin_(a1, c1));
-    a0 = lo;
-    a1 = hi;
-}
-// packed 16-bit min / max (inline asm: see hamming_mfma.hip -- the vector builtins get sunk out of the MFMA block)
-__device__ __forceinline__ uint32_t pk_min16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_max16(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_add16_sat(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("v_pk_add_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void pk_push2(uint32_t& b0, uint32_t& b1, uint32_t key)
-{
-    b1 = pk_min16(b1, pk_max16(b0, key));
-    b0 = pk_min16(b0, key);
-}
-// accumulators of the two M-tiles (2^23 + 128 d + tag, tag <= 127) side by side: hi.lo16 << 16 | lo.lo16.
-// The BUILTIN, never inline asm: this is the one instruction that reads MFMA results, and the wait states between an
-// MFMA and a VALU access to its destination are the compiler's job ("K1e determinism").
-__device__ __forceinline__ uint32_t pack_acc(float lo, float hi, uint32_t sel_uniform /* 0x05040100 */)
-{
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), sel_uniform);
-}
-// 16-bit keys are (d << 7) | tag7 (<= (256 << 7) + 127 = 0x807F); anything above is "none"
-constexpr uint32_t KEY16_MAX = 0x807Fu;
-__device__ __forceinline__ uint32_t key16_to_key32(uint32_t k16, uint32_t tag_bias, uint32_t idx_base,
-                                                   uint32_t idx_scale)
-{
-    return k16 > KEY16_MAX ? KEY_NONE
-                           : (((k16 >> 7) << KEY_IDX_BITS) | (idx_base + ((k16 & 127u) - tag_bias) * idx_scale));
-}
-// 32 bits of a descriptor -> 32 fp4 codes of s(bit): dword s holds bits 4k + s, nibble k = 0x2 | bit << 3
-// 7 VALU ops of the fast class (measured ~2.5 cycles per wave instruction against ~4.2 for shifts and v_and_or): three adds
-// for x << 1, 2, 3 and four v_bitop3 (a & b) | c.  Written with asm / the builtin because the compiler turns x + x back
-// into a shift and (x & m) | c into v_and + v_or.
-template <bool A_SIDE>
-__device__ __forceinline__ i32x4 expand_dword_fp4(uint32_t x)
-{
-    uint32_t x1, x2, x3;
-    asm("v_add_u32 %0, %1, %1" : "=v"(x1) : "v"(x));
-    asm("v_add_u32 %0, %1, %1" : "=v"(x2) : "v"(x1));
-    asm("v_add_u32 %0, %1, %1" : "=v"(x3) : "v"(x2));
-    constexpr uint32_t base = A_SIDE ? (FP4_ONE ^ FP4_NEG) : FP4_ONE;       // a side: sign nibble-bit flipped
-    constexpr unsigned TT = A_SIDE ? 0x6Au : 0xEAu;                         // (a & b) ^ c  |  (a & b) | c
-    i32x4 v;
-    v.x = (int)__builtin_amdgcn_bitop3_b32(x3, FP4_NEG, base, TT);
-    v.y = (int)__builtin_amdgcn_bitop3_b32(x2, FP4_NEG, base, TT);
-    v.z = (int)__builtin_amdgcn_bitop3_b32(x1, FP4_NEG, base, TT);
-    v.w = (int)__builtin_amdgcn_bitop3_b32(x, FP4_NEG, base, TT);
-    return v;
-}
-__device__ __forceinline__ uint32_t bcnt_acc_(uint32_t x, uint32_t acc)
-{
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ int xcd_remap_(int orig, int nwg) { return (orig & 7) * (nwg >> 3) + (orig >> 3); }
-
 }  // namespace
 
 // MULTI = false: every problem of the launch has n2 <= 2048 (one window of 64 tiles; the window bounds are
@@ -208,7 +110,6 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         for (int ks = 0; ks < MF_KSTEPS; ++ks) afrag[mt][ks] = expand_dword_fp4<true>(p[2 * ks]);
     }
     const int scale_a = SCALE_A, scale_b = SCALE_B;
-    const uint32_t pack_sel = 0x05040100u;
 
     // row-direction state per accumulator register r (M-tile 0 in the low halves, M-tile 1 in the high halves):
     //   gm[r]    running minimum of the 16-bit keys (d << 7 | tile + LOC) of the current group of MF_GROUP tiles
@@ -390,7 +291,7 @@ k_scan_sym_mfma_g(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float f0 = m0[r], f1 = m1[r];
-            kc[r] = pack_acc(f0, f1, pack_sel);
+            kc[r] = pack_acc(f0, f1);
         }
     };
     // E(t) on its own (the last tile of a window has no following M step to hide under)

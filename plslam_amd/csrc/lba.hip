@@ -87,14 +87,6 @@ k_line_rows(CamD K, double th, int compat, const double* __restrict__ T,
 
 struct Pose12 { double m[12]; };  // rows 0..2 of the row-major 4x4
 
-__device__ __forceinline__ void xform44(const Pose12& T, const double* X, double o[3])
-{
-    const double x = X[0], y = X[1], z = X[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        o[i] = (T.m[4 * i] * x + T.m[4 * i + 1] * y + T.m[4 * i + 2] * z) + T.m[4 * i + 3];
-}
-
 // The gates as the LAST kernel of a one-synchronisation driver call (map2kf.hip): the workgroup that finishes last copies the call's
 // counters (device words, some of them this kernel's own atomic counts) into the page-locked block the host reads -- a launch less
 // at the end of a call that is bound by its launches.  Every wave WAITS for its count atomic (a returning one) before the
@@ -137,7 +129,7 @@ k_point_gate(CamD K, Pose12 Twf, const double* __restrict__ Xw, const int32_t* _
         const int i2 = m12[i];
         if (i2 >= 0) {
             double Pf[3], u, v;
-            xform44(Twf, Xw + 3 * (size_t)i, Pf);
+            xform(Twf.m, Xw + 3 * (size_t)i, Pf);
             project(K, Pf, u, v);
             const double ex = u - pl[2 * (size_t)i2], ey = v - pl[2 * (size_t)i2 + 1];
             ok = sqrt(ex * ex + ey * ey) < th;
@@ -162,9 +154,9 @@ k_line_gate(CamD K, Pose12 Twf, const double* __restrict__ Lw, const int32_t* __
         const int i2 = m12[i];
         if (i2 >= 0) {
             double sP[3], eP[3], su, sv, eu, ev;
-            xform44(Twf, Lw + 6 * (size_t)i, sP);
+            xform(Twf.m, Lw + 6 * (size_t)i, sP);
             project(K, sP, su, sv);
-            xform44(Twf, Lw + 6 * (size_t)i + 3, eP);
+            xform(Twf.m, Lw + 6 * (size_t)i + 3, eP);
             project(K, eP, eu, ev);
             const double lx = le[3 * (size_t)i2], ly = le[3 * (size_t)i2 + 1], lz = le[3 * (size_t)i2 + 2];
             const double e0 = lx * su + ly * sv + lz;
@@ -194,12 +186,12 @@ k_visible(CamD K, Pose12 Twf, const double* __restrict__ X, int32_t n, int lines
     const bool c = cand == nullptr || cand[i] != 0;      // (cand: the caller's candidate flags live on the device -- folded in)
     double P[3];
     if (!lines) {
-        xform44(Twf, X + 3 * (size_t)i, P);
+        xform(Twf.m, X + 3 * (size_t)i, P);
         vis[i] = (uint8_t)(c && inside(K, P));
     } else {
         double E[3];
-        xform44(Twf, X + 6 * (size_t)i, P);
-        xform44(Twf, X + 6 * (size_t)i + 3, E);
+        xform(Twf.m, X + 6 * (size_t)i, P);
+        xform(Twf.m, X + 6 * (size_t)i + 3, E);
         vis[i] = (uint8_t)(c && inside(K, P) && inside(K, E));
     }
 }
@@ -299,7 +291,7 @@ k_project_cells(CamD K, Pose12 Twf, const double* __restrict__ X, int32_t n, int
     auto cvtt = [](double v) -> int32_t { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN; };
     for (int e = 0; e < nc; ++e) {
         double P[3], u, v;
-        xform44(Twf, X + (size_t)i * 3 * nc + 3 * e, P);
+        xform(Twf.m, X + (size_t)i * 3 * nc + 3 * e, P);
         project(K, P, u, v);
         c[2 * e] = cvtt(u * inv_w);
         c[2 * e + 1] = cvtt(v * inv_h);
@@ -380,11 +372,11 @@ k_visible_compact(CamD K, Pose12 Twf, const double* __restrict__ X, const uint8_
         const uint8_t c = cand[i];
         double P[3], E[3];
         if (!lines) {
-            xform44(Twf, X + 3 * (size_t)i, P);
+            xform(Twf.m, X + 3 * (size_t)i, P);
             v = c != 0 && inside(K, P) != 0;
         } else {
-            xform44(Twf, X + 6 * (size_t)i, P);
-            xform44(Twf, X + 6 * (size_t)i + 3, E);
+            xform(Twf.m, X + 6 * (size_t)i, P);
+            xform(Twf.m, X + 6 * (size_t)i + 3, E);
             v = c != 0 && inside(K, P) && inside(K, E);
         }
         fill[i] = -1;
@@ -451,7 +443,7 @@ k_prepare_rows(CamD K, Pose12 Twf, const uint64_t* __restrict__ md, const double
     int32_t c[4];
     for (int e = 0; e < nc; ++e) {
         double P[3], u, v;
-        xform44(Twf, X + 3 * e, P);
+        xform(Twf.m, X + 3 * e, P);
         project(K, P, u, v);
         c[2 * e] = cvtt(u * inv_w);
         c[2 * e + 1] = cvtt(v * inv_h);

@@ -4,33 +4,20 @@
 #pragma once
 
 #include "common.hpp"
+#include "se3_dev.hpp"
 
 namespace plslam {
 
 struct CamD { double fx, fy, cx, cy; double width, height; };
 
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }  // std::max
+// not dmax_std: the comparison the other way round (a NaN in `a` gives b here, a there) -- what these rows have always computed
+__device__ __forceinline__ double dmax_gt(double a, double b) { return a > b ? a : b; }
 
 // stvo-pl PinholeStereoCamera::projection: u = cx + fx*X/Z, v = cy + fy*Y/Z
 __device__ __forceinline__ void project(const CamD& K, const double P[3], double& u, double& v)
 {
     u = K.cx + K.fx * P[0] / P[2];
     v = K.cy + K.fy * P[1] / P[2];
-}
-
-// inverse_se3 (stvo-pl): Tiw = [R^T, -R^T t] of the row-major 4x4 at T  (:1372)
-__device__ __forceinline__ void inv_pose(const double* __restrict__ T, double R[9], double t[3])
-{
-    double m[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) m[i] = T[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        R[3 * i] = m[i];
-        R[3 * i + 1] = m[4 + i];
-        R[3 * i + 2] = m[8 + i];
-        t[i] = (-m[i]) * m[3] + (-m[4 + i]) * m[7] + (-m[8 + i]) * m[11];
-    }
 }
 
 // A landmark's 3 (or 6) doubles with the fewest load instructions: a 16-byte load needs dword alignment only on this hardware,
@@ -93,14 +80,6 @@ __device__ __forceinline__ void pose12_take(PoseCache<NC>& c, const double* __re
 #pragma unroll
         for (int e = 0; e < 12; ++e) T12[e] = g_(Tg)[(size_t)slot * 16 + e];
     }
-}
-
-__device__ __forceinline__ void xform(const double R[9], const double t[3], const double* X,
-                                      double o[3])
-{
-    const double x = X[0], y = X[1], z = X[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = (R[3 * i] * x + R[3 * i + 1] * y + R[3 * i + 2] * z) + t[i];
 }
 
 // the 6-vector of :1392-1397 / :1475-1480
@@ -193,10 +172,10 @@ __device__ __forceinline__ void point_row(const CamD& K, double th, const double
     project(K, G, pu, pv);
     const double dx = ob.x - pu, dy = ob.y - pv;
     const double nrm = sqrt(dx * dx + dy * dy);
-    const double k = 1.0 / dmax(th, G[2] * G[2]);
+    const double k = 1.0 / dmax_gt(th, G[2] * G[2]);
     const double a = K.fx * dx, b = K.fy * dy;
     jac6(a, b, k, G, Jc);
-    const double den = dmax(th, nrm);
+    const double den = dmax_gt(th, nrm);
 #pragma unroll
     for (int c = 0; c < 6; ++c) out6[c] = Jc[c] / den;
 #pragma unroll
@@ -221,11 +200,11 @@ __device__ __forceinline__ void line_row(const CamD& K, double th, const double*
     const double e1 = lx * qu + ly * qv + lz;
     const double nrm = sqrt(e0 * e0 + e1 * e1);
     const double a = K.fx * e0, b = K.fy * e1;  // sic: the reference multiplies by l_err (:1469-1472)
-    const double kP = 1.0 / dmax(th, P[2] * P[2]);
-    const double kQ = 1.0 / dmax(th, Q[2] * Q[2]);
+    const double kP = 1.0 / dmax_gt(th, P[2] * P[2]);
+    const double kQ = 1.0 / dmax_gt(th, Q[2] * Q[2]);
     jac6(a, b, kP, P, JP);
     jac6(a, b, kQ, Q, JQ);
-    const double den = dmax(th, nrm);
+    const double den = dmax_gt(th, nrm);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const double vp = JP[0] * R[j] + JP[1] * R[3 + j] + JP[2] * R[6 + j];

@@ -163,6 +163,7 @@ k_ldlt_bwd(const double* __restrict__ S, int64_t ld, int32_t k, double* __restri
 
 // ---- host side of the LDL^T: the matrix S (npad x npad, row-major, lower triangle read) is factored in place and
 // S x = b solved; w, z: npad doubles of workspace (w holds b on entry and is overwritten); P: npad x 32 doubles ------------------
+inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }   // the npad of ldlt_enqueue
 int ldlt_enqueue(double* S, int64_t npad, double* P, double* w, double* z, double* x, int32_t* badp, hipStream_t s)
 {
     const int nt = (int)(npad / LT);

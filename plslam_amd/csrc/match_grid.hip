@@ -88,7 +88,8 @@ struct GridPtrs {
 };
 
 __device__ __forceinline__ void best2_fold(uint32_t& k1, uint32_t& k2, uint32_t key)
-{   // idempotent insertion into the two smallest distinct keys (k1 <= k2); value selects only -- a branchy form makes
+{   // idempotent insertion into the two smallest DISTINCT keys (k1 <= k2) -- which is why it is not merge2 / pk_push2 of
+    // mfma_h_common.hpp, where a key met twice takes both places; value selects only -- a branchy form makes
     // the compiler address k1 / k2 through private memory
     const uint32_t lo = key < k1 ? key : k1, hi = key < k1 ? k1 : key;
     k2 = key == k1 ? k2 : (hi < k2 ? hi : k2);

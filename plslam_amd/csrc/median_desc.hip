@@ -27,6 +27,8 @@ namespace {
 constexpr uint32_t IDX_BITS = 23, IDX_MASK = (1u << IDX_BITS) - 1u;
 constexpr int ROW_CACHE = 16;      // lists up to this long keep their distance row in LDS
 
+// (not mfma_h_common.hpp's hamming256 of four vector registers: the builtin, so that the compiler selects the popcount for a
+// row it reads from memory -- the asm form pins v_bcnt_u32_b32 and its operand order)
 __device__ __forceinline__ int hamming256(const uint32_t (&q)[8], const uint32_t* __restrict__ t)
 {
     int d = 0;

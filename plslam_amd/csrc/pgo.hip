@@ -63,19 +63,15 @@ __device__ __forceinline__ void iso_store(const Iso& X, double* __restrict__ p)
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[9 + a] = X.t[a];
 }
-__device__ __forceinline__ void mv3(const double R[9], const double v[3], double o[3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
-}
 __device__ __forceinline__ void iso_mul(const Iso& A, const Iso& B, Iso& C)
 {
     mat3_mul(A.R, B.R, C.R);
     double u[3];
-    mv3(A.R, B.t, u);
+    mv3(A.R, B.t, u);         // (not xform(A.R, A.t, B.t, C.t): the same sums, but the kernels' instruction streams change)
 #pragma unroll
     for (int i = 0; i < 3; ++i) C.t[i] = u[i] + A.t[i];
 }
+// (not inv_pose: that one negates the factors, this one the finished sum, as g2o's Isometry3::inverse does)
 __device__ __forceinline__ void iso_inv(const Iso& A, Iso& C)
 {
 #pragma unroll
@@ -670,12 +666,6 @@ k_lc_fill(const int32_t* __restrict__ aidx, const int32_t* __restrict__ eslot, i
     const int j = aidx[a];
     list[ptr[j] + atomic_add_global(cur + j, 1)] = a;
 }
-__device__ __forceinline__ void rt3(const double* __restrict__ C, double* p)
-{
-    const double p0 = p[0], p1 = p[1], p2 = p[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = ((C[4 * i] * p0 + C[4 * i + 1] * p1) + C[4 * i + 2] * p2) + C[4 * i + 3];
-}
 // K53: a lane per landmark: its anchor entries in CSR order (slot order), each applying that slot's T_corr
 template <int DL>
 __global__ void __launch_bounds__(256)
@@ -706,19 +696,19 @@ k_lc_apply(const int32_t* __restrict__ ptr, int32_t* __restrict__ list, const in
         for (int h = 0; h < DL / 3; ++h) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) p[q] = X[(size_t)DL * j + 3 * h + q];
-            rt3(c, p);
+            xform(c, p, p);
 #pragma unroll
             for (int q = 0; q < 3; ++q) X[(size_t)DL * j + 3 * h + q] = p[q];
         }
 #pragma unroll
         for (int q = 0; q < 3; ++q) p[q] = med[3 * (size_t)j + q];
-        rt3(c, p);
+        xform(c, p, p);
 #pragma unroll
         for (int q = 0; q < 3; ++q) med[3 * (size_t)j + q] = p[q];
         for (int d = d0; d < d1; ++d) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) p[q] = dirs[3 * (size_t)d + q];
-            rt3(c, p);
+            xform(c, p, p);
 #pragma unroll
             for (int q = 0; q < 3; ++q) dirs[3 * (size_t)d + q] = p[q];
         }
@@ -769,7 +759,6 @@ int env_solve_enqueue(const EnvDev& E, const double* H, double lambda, const dou
     return PLSLAM_OK;
 }
 
-inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }
 
 }  // namespace
 }  // namespace plslam

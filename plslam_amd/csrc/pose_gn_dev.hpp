@@ -6,19 +6,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "se3_dev.hpp"
+
 namespace plslam {
 
 constexpr int GN_TERMS = 21 + 6 + 1;       // upper triangle of H, g, e
 
 struct GnCam { double fx, fy, cx, cy; };
-
-__device__ __forceinline__ double dmaxd(double a, double b) { return a < b ? b : a; }   // std::max
-
-__device__ __forceinline__ void xform(const double* T, const double* X, double o[3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = (T[4 * i] * X[0] + T[4 * i + 1] * X[1] + T[4 * i + 2] * X[2]) + T[4 * i + 3];
-}
 
 __device__ __forceinline__ void jac6(double fgz2, double a, double b, double gx, double gy, double gz, double J[6])
 {
@@ -58,9 +52,9 @@ __device__ __forceinline__ void gn_point_row(const GnCam& K, double th, const do
 {
     double G[3], J[6], dx, dy;
     const double r = gn_point_residual(K, Tm, X, ox, oy, G, dx, dy);
-    const double fgz2 = K.fx / dmaxd(th, G[2] * G[2]);
+    const double fgz2 = K.fx / dmax_std(th, G[2] * G[2]);
     jac6(fgz2, dx, dy, G[0], G[1], G[2], J);
-    const double den = dmaxd(th, r);
+    const double den = dmax_std(th, r);
 #pragma unroll
     for (int k = 0; k < 6; ++k) J[k] = J[k] / den;
     accumulate(acc, J, r, 1.0 / (1.0 + r * r));
@@ -84,9 +78,9 @@ __device__ __forceinline__ void gn_line_row(const GnCam& K, double th, const dou
 {
     double S[3], E[3], Js[6], Je[6], J[6], ds, de;
     const double r = gn_line_residual(K, Tm, SE, l, S, E, ds, de);
-    jac6(K.fx / dmaxd(th, S[2] * S[2]), l[0], l[1], S[0], S[1], S[2], Js);
-    jac6(K.fx / dmaxd(th, E[2] * E[2]), l[0], l[1], E[0], E[1], E[2], Je);
-    const double den = dmaxd(th, r);
+    jac6(K.fx / dmax_std(th, S[2] * S[2]), l[0], l[1], S[0], S[1], S[2], Js);
+    jac6(K.fx / dmax_std(th, E[2] * E[2]), l[0], l[1], E[0], E[1], E[2], Je);
+    const double den = dmax_std(th, r);
 #pragma unroll
     for (int k = 0; k < 6; ++k) J[k] = (Js[k] * ds + Je[k] * de) / den;
     accumulate(acc, J, r, 1.0 / (1.0 + r * r));

@@ -1,10 +1,38 @@
-// se3_dev.hpp -- stvo-pl's SE(3) maps (expmap_se3 / logmap_se3 / inverse_se3, auxiliar.cpp) restated in fp64 for the device,
-// their theta < 1e-6 branches included.  Shared by K25 (loop_closure.hip) and the pose update of the global BA (gba.hip).
+// se3_dev.hpp -- the one copy of the small fp64 device math: std::max / std::min as the reference orders the comparison, the
+// rigid transform of a point, 3x3 products, the inverse of a pose, and stvo-pl's SE(3) maps (expmap_se3 / logmap_se3 /
+// inverse_se3, auxiliar.cpp), their theta < 1e-6 branches included.  Every includer is built with -ffp-contract=off and every
+// expression keeps the reference's order of operations (sums left to right).  Used by the row kernels (pose_gn_dev.hpp,
+// lba_rows_dev.hpp, lba.hip), the stereo gates, K25 (loop_closure.hip), the global BA (gba.hip) and the pose graph (pgo.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace plslam {
+
+// std::max / std::min of libstdc++: the SECOND argument is taken only when the comparison holds, so a NaN in either place
+// and the sign of a zero come out as in the reference
+__device__ __forceinline__ double dmax_std(double a, double b) { return a < b ? b : a; }
+__device__ __forceinline__ double dmin_std(double a, double b) { return b < a ? b : a; }
+
+// o = R X + t, ((r0 x + r1 y) + r2 z) + t per row; o may be X
+__device__ __forceinline__ void xform(const double R[9], const double t[3], const double* X, double o[3])
+{
+    const double x = X[0], y = X[1], z = X[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = (R[3 * i] * x + R[3 * i + 1] * y + R[3 * i + 2] * z) + t[i];
+}
+// the same with R | t as rows 0..2 of a row-major 4x4 (12 or 16 doubles)
+__device__ __forceinline__ void xform(const double* T, const double* X, double o[3])
+{
+    const double x = X[0], y = X[1], z = X[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = (T[4 * i] * x + T[4 * i + 1] * y + T[4 * i + 2] * z) + T[4 * i + 3];
+}
+__device__ __forceinline__ void mv3(const double R[9], const double v[3], double o[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+}
 
 __device__ __forceinline__ void skew3(const double w[3], double s[9])
 {
@@ -21,6 +49,22 @@ __device__ __forceinline__ void mat3_mul(const double a[9], const double b[9], d
         for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
 }
 
+// inverse_se3 (stvo-pl): [R^T, -R^T t] of the row-major 4x4 at T (its first 12 doubles are read)
+__device__ __forceinline__ void inv_pose(const double* __restrict__ T, double R[9], double t[3])
+{
+    double m[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) m[i] = T[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        R[3 * i] = m[i];
+        R[3 * i + 1] = m[4 + i];
+        R[3 * i + 2] = m[8 + i];
+        t[i] = (-m[i]) * m[3] + (-m[4 + i]) * m[7] + (-m[8 + i]) * m[11];
+    }
+}
+// the same as a row-major 4x4, the same operations in the same order.  Written out, not a call of inv_pose plus a copy: that
+// form leaves k_pgo_meas and k_pgo_writeback with another instruction stream
 __device__ __forceinline__ void inverse_se3(const double T[16], double o[16])
 {
 #pragma unroll

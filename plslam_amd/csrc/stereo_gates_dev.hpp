@@ -3,6 +3,7 @@
 // applies them to a row's match the moment it is decided (plans with a gate stage: no second pass over the tables).
 #pragma once
 #include "common.hpp"
+#include "se3_dev.hpp"
 
 namespace plslam {
 
@@ -25,24 +26,21 @@ __device__ __forceinline__ int32_t point_gate_one(int32_t i2, float2 a, const PL
     return i2;
 }
 
-__device__ __forceinline__ double dmin2(double a, double b) { return b < a ? b : a; }   // std::min
-__device__ __forceinline__ double dmax2(double a, double b) { return a < b ? b : a; }   // std::max
-
 // StereoFrame::lineSegmentOverlapStereo
 __device__ __forceinline__ double overlap_stereo(double spl_obs, double epl_obs, double spl_proj, double epl_proj,
                                                  double line_horiz_th)
 {
     double overlap = 1.f;
     if (fabs(epl_obs - spl_obs) > line_horiz_th) {
-        const double sln = dmin2(spl_obs, epl_obs), eln = dmax2(spl_obs, epl_obs);
-        const double spn = dmin2(spl_proj, epl_proj), epn = dmax2(spl_proj, epl_proj);
+        const double sln = dmin_std(spl_obs, epl_obs), eln = dmax_std(spl_obs, epl_obs);
+        const double spn = dmin_std(spl_proj, epl_proj), epn = dmax_std(spl_proj, epl_proj);
         const double length = eln - spn;
         if ((epn < sln) || (spn > eln))
             overlap = 0.f;
         else if ((epn > eln) && (spn < sln))
             overlap = eln - sln;
         else
-            overlap = dmin2(eln, epn) - dmax2(sln, spn);
+            overlap = dmin_std(eln, epn) - dmax_std(sln, spn);
         if (length > 0.01f)
             overlap = overlap / length;
         else
@@ -72,7 +70,7 @@ __device__ __forceinline__ int32_t line_gate_one(int32_t i2, float4 L, const PLS
     ep_r[0] = ex;
     ep_r[1] = ep_l[1];
     double disp_s = sp_l[0] - sp_r[0], disp_e = ep_l[0] - ep_r[0];
-    if (dmin2(disp_s, disp_e) / dmax2(disp_s, disp_e) < ls_min_disp_ratio) {
+    if (dmin_std(disp_s, disp_e) / dmax_std(disp_s, disp_e) < ls_min_disp_ratio) {
         disp_s = -1.0;
         disp_e = -1.0;
     }

@@ -75,18 +75,36 @@ def test_key_orders_like_distance_then_index():
     assert max(k[0] for k in keys) <= 0x807F
 
 
+def _source_with_headers(fname, seen=None):
+    """The text of a file of plslam_amd/csrc with every project header it includes (#include "...", each one once) in the
+    place of its include line: what the compiler sees of the project's own text.  The helpers the scans share (pack_acc, the
+    packed-key asm) live in mfma_h_common.hpp."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plslam_amd", "csrc")
+    seen = set() if seen is None else seen
+    seen.add(fname)
+
+    def include(m):
+        h = m.group(1)
+        if h in seen or not os.path.exists(os.path.join(csrc, h)):
+            return ""
+        return _source_with_headers(h, seen)
+    return re.sub(r'^#include "([^"]+)"[^\n]*$', include, open(os.path.join(csrc, fname)).read(), flags=re.M)
+
+
 @pytest.mark.parametrize("fname", ["hamming_mfma.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip"])
 def test_no_inline_asm_reads_mfma_results(fname):
     """Guard for the K1e determinism bug: the wait states between a v_mfma and a VALU access to
     its destination registers are inserted by the compiler, which does not look inside asm statements.  pack_acc -- the
     one consumer of accumulator registers -- must therefore stay a builtin, and no asm statement may take an accumulator
     element as an operand."""
-    import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plslam_amd", "csrc",
-                            fname)).read()
+    src = _source_with_headers(fname)
+    assert "mfma_h_common.hpp -- " in src                                # the shared header is part of what is checked
     src = "\n".join(l.split("//")[0] for l in src.split("\n"))          # code only
     assert "__builtin_amdgcn_perm(" in src
+    assert re.search(r"pack_acc\(float lo, float hi\)\s*\{\s*return __builtin_amdgcn_perm\(", src)
     assert 'asm("v_perm_b32' not in src and "asm volatile(\"v_perm_b32" not in src
     for m in re.finditer(r"asm(?:\s+volatile)?\s*\(([^;]*);", src):
         body = m.group(1)
@@ -243,9 +261,9 @@ def test_k1i_inline_asm_reads_accumulators_only_in_the_bookkeeping_macro():
     every such read must sit in that macro (whose uses are separated from the chain's last MFMA by the other chain's MFMAs,
     or by the hand-counted s_nop in front of phase 1 and of the epilogue), and the final listing is checked at the compiler's
     own distance by test_final_isa_has_no_mfma_destination_hazard."""
-    import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plslam_amd", "csrc", "hamming_mfma_i.hip")).read()
+    src = _source_with_headers("hamming_mfma_i.hip")
+    assert "mfma_h_common.hpp -- " in src
     src = "\n".join(l.split("//")[0] for l in src.split("\n"))
     stmts = [m.group(1) for m in re.finditer(r"asm(?:\s+volatile)?\s*\(([^;]*);", src) if not re.match(r'\s*""', m.group(1))]
     acc = [b for b in stmts if re.search(r"\(m[01]\)", b)]

@@ -1016,6 +1016,39 @@ int plslam_relpose_robust_gn(plslam_ctx* ctx, const plslam_lc_params* params, co
                              int32_t npt, const double* sPeP, const double* le_obs, int32_t nls, plslam_lc_result* result,
                              uint8_t* pt_inlier, uint8_t* ls_inlier);
 
+/* ---- K54: the same check for B candidate pairs in one call --------------------------------------------------------------
+ * One match plan of up to 2 B problems (per pair exactly the problems of the single call; kept while the batch's problem list
+ * -- shapes and addresses -- stays the same) and ONE launch of B workgroups, each running the single call's per-problem code:
+ * results[b], pair b's rows and masks are those of plslam_loop_closure_verify[_dev](kf0[b], kf1[b]) bit for bit (clk_* apart).
+ * kf0 / kf1: B host records each; records (and device arrays) may repeat across pairs -- every pair of a top-K verification
+ * has the same kf1.  Pair b's rows of pt_corr / pt_inlier start at row sum_{b' < b} kf0[b'].n_pt, of ls_corr / ls_inlier at
+ * row sum_{b' < b} kf0[b'].n_ls.  The params are fixed at creation.  Every buffer belongs to the batch object and only grows.
+ * EINVAL / ERANGE per pair as for the single call; B < 0 or B > max_pairs: EINVAL; B == 0: OK, nothing is launched.  A failed
+ * call leaves the object usable.  Calls on one context are serialised. */
+#define PLSLAM_LC_MAX_BATCH 65536         /* max_pairs, and B of plslam_relpose_robust_gn_batched_dev; larger -> PLSLAM_ERANGE */
+typedef struct plslam_lc_batch plslam_lc_batch;
+int plslam_lc_batch_create(plslam_ctx* ctx, const plslam_lc_params* params, int32_t max_pairs, plslam_lc_batch** out);
+void plslam_lc_batch_destroy(plslam_lc_batch* batch);
+/* Device pointers throughout (the keyframe arrays, results -- B records --, and the four outputs, which must not be NULL
+ * where some kf0 has rows of the kind); the records are host structs.  Enqueued behind `stream` (NULL = the context's
+ * stream), no synchronisation. */
+int plslam_lc_batch_verify_dev(plslam_lc_batch* batch, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B,
+                               plslam_lc_result* results, int32_t* pt_corr, uint8_t* pt_inlier, int32_t* ls_corr,
+                               uint8_t* ls_inlier, void* stream);
+/* Host pointers: one upload image (a repeated record is uploaded once), one download, one synchronisation.  Any of the four
+ * outputs may be NULL. */
+int plslam_lc_batch_verify(plslam_lc_batch* batch, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B,
+                           plslam_lc_result* results, int32_t* pt_corr, uint8_t* pt_inlier, int32_t* ls_corr, uint8_t* ls_inlier);
+/* computeRelativePoseRobustGN alone for B problems on the caller's correspondences, device pointers, enqueued behind `stream`
+ * without a synchronisation.  The arrays are concatenated: problem b owns rows [pt_off[b], pt_off[b + 1]) of P, pl_obs and
+ * pt_inlier and rows [ls_off[b], ls_off[b + 1]) of sPeP, le_obs and ls_inlier; pt_off / ls_off are B + 1 non-decreasing int32
+ * in DEVICE memory (a producer on the device can write them), each problem at most PLSLAM_LC_MAX_FEATURES rows per kind (a
+ * count outside that range is taken as 0).  A kind without rows anywhere passes NULL arrays.  results[b] is what
+ * plslam_relpose_robust_gn returns for problem b, bit for bit (clk_* apart). */
+int plslam_relpose_robust_gn_batched_dev(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
+                                         const int32_t* pt_off, const double* sPeP, const double* le_obs, const int32_t* ls_off,
+                                         int32_t B, plslam_lc_result* results, uint8_t* pt_inlier, uint8_t* ls_inlier, void* stream);
+
 /* ---- K26-K39: global bundle adjustment (MapHandler::globalBundleAdjustment + levMarquardtOptimizationGBA,
  * src/mapHandler.cpp:1995-2099, :2101-2703) ---------------------------------------------------------------------------
  * The rows and blocks of every pass are the LBA plan's: the first pass reads the stored T_kf_w of every keyframe (:2136,

@@ -56,6 +56,8 @@ ABI_SYMBOLS = (
     "plslam_bow_db_create", "plslam_bow_db_destroy", "plslam_bow_db_insert", "plslam_bow_db_insert_dev", "plslam_bow_db_size",
     "plslam_bow_db_score",
     "plslam_loop_closure_verify", "plslam_loop_closure_verify_dev", "plslam_relpose_robust_gn",
+    "plslam_lc_batch_create", "plslam_lc_batch_destroy", "plslam_lc_batch_verify", "plslam_lc_batch_verify_dev",
+    "plslam_relpose_robust_gn_batched_dev",
     "plslam_gba_plan_create", "plslam_gba_optimize", "plslam_gba_plan_destroy", "plslam_dense_ldlt_solve",
     "plslam_pgo_plan_create", "plslam_pgo_optimize", "plslam_pgo_plan_destroy", "plslam_lc_correct_map",
     "plslam_lc_correct_map_dev", "plslam_envelope_ldlt_solve",
@@ -65,6 +67,7 @@ BOW_L1_NORM = 0
 BOW_MAX_SET = 16384      # include/plslam_hip.h: PLSLAM_BOW_MAX_SET
 LC_MAX_FEATURES = 16384  # include/plslam_hip.h: PLSLAM_LC_MAX_FEATURES
 LC_MAX_ITERS = 10000     # include/plslam_hip.h: PLSLAM_LC_MAX_ITERS
+LC_MAX_BATCH = 65536     # include/plslam_hip.h: PLSLAM_LC_MAX_BATCH
 GBA_MAX_KEYFRAMES = 4096  # include/plslam_hip.h: PLSLAM_GBA_MAX_KEYFRAMES
 GBA_STOP_MAX_ITERS, GBA_STOP_ERR, GBA_STOP_DX = 0, 1, 2
 
@@ -407,6 +410,12 @@ def load() -> C.CDLL:
     L.plslam_loop_closure_verify_dev.argtypes = [vp, C.POINTER(LcParams), C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), vp,
                                                  vp, vp, vp, vp, vp]
     L.plslam_relpose_robust_gn.argtypes = [vp, C.POINTER(LcParams), vp, vp, i32, vp, vp, i32, C.POINTER(LcResult), vp, vp]
+    L.plslam_lc_batch_create.argtypes = [vp, C.POINTER(LcParams), i32, C.POINTER(vp)]
+    L.plslam_lc_batch_destroy.argtypes = [vp]
+    L.plslam_lc_batch_destroy.restype = None
+    L.plslam_lc_batch_verify.argtypes = [vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), i32, C.POINTER(LcResult), vp, vp, vp, vp]
+    L.plslam_lc_batch_verify_dev.argtypes = [vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), i32, vp, vp, vp, vp, vp, vp]
+    L.plslam_relpose_robust_gn_batched_dev.argtypes = [vp, C.POINTER(LcParams), vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.plslam_gba_plan_create.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(vp)]
     L.plslam_gba_optimize.argtypes = [vp, f64, f64, i32] + [vp] * 8 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)]
     L.plslam_gba_plan_destroy.argtypes = [vp]
@@ -644,6 +653,15 @@ class Context:
         _check(self._L.plslam_relpose_robust_gn(self._h, C.byref(params), _p(P), _p(po), P.shape[0], _p(S), _p(lo), S.shape[0],
                                                 C.byref(res), _p(pi), _p(li)), "plslam_relpose_robust_gn")
         return res.as_dict(), pi.astype(bool), li.astype(bool)
+
+    def relpose_robust_gn_batched_dev(self, params, P_ptr, pl_ptr, pt_off_ptr, sPeP_ptr, le_ptr, ls_off_ptr, B, results_ptr,
+                                      pt_inlier_ptr, ls_inlier_ptr, stream=None):
+        """computeRelativePoseRobustGN for B problems over concatenated device arrays (K54); pt_off / ls_off: B + 1 int32
+        offsets in device memory; results_ptr: B x sizeof(LcResult) bytes.  Enqueued behind `stream`, no synchronisation."""
+        _check(self._L.plslam_relpose_robust_gn_batched_dev(
+            self._h, C.byref(params), *(C.c_void_p(v or 0) for v in (P_ptr, pl_ptr, pt_off_ptr, sPeP_ptr, le_ptr, ls_off_ptr)),
+            int(B), C.c_void_p(results_ptr or 0), C.c_void_p(pt_inlier_ptr or 0), C.c_void_p(ls_inlier_ptr or 0),
+            C.c_void_p(stream or 0)), "plslam_relpose_robust_gn_batched_dev")
 
     def stereo_point_gate(self, m12, kp_l, kp_r, max_dist_epip, min_disp):
         """StereoFrame::matchStereoPoints gates -> (stereo_12, disp, n_stereo)."""
@@ -1528,6 +1546,77 @@ def envelope_ldlt_solve(ctx: Context, A, b):
     _check(ctx._L.plslam_envelope_ldlt_solve(ctx.handle, n, _p(A), _p(bb), _p(x), C.byref(nb), C.byref(bw)),
            "plslam_envelope_ldlt_solve")
     return x, int(nb.value), int(bw.value)
+
+
+class LcBatch:
+    """plslam_lc_batch: isLoopClosure for up to max_pairs candidate pairs per call (K54), with `params` fixed."""
+
+    def __init__(self, ctx: Context, params: LcParams, max_pairs: int):
+        self._L = ctx._L
+        self._ctx = ctx
+        self.params = params
+        self.max_pairs = int(max_pairs)
+        self._h = None
+        h = C.c_void_p()
+        _check(self._L.plslam_lc_batch_create(ctx.handle, C.byref(params), self.max_pairs, C.byref(h)), "plslam_lc_batch_create")
+        self._h = h
+
+    def verify(self, pairs):
+        """pairs: a sequence of (kf0, kf1) keyframe dicts (Context.loop_closure_verify's).  A dict that appears several
+        times is packed and uploaded once.  -> one (result dict, pt_corr, pt_inlier, ls_corr, ls_inlier) per pair."""
+        B = len(pairs)
+        packed = {}
+
+        def rec(kf):
+            if id(kf) not in packed:
+                a = Context._lc_kf_arrays(kf)
+                packed[id(kf)] = (Context._lc_kf_record(a), a)
+            return packed[id(kf)][0]
+
+        r0 = (LcKeyframe * max(B, 1))(*(rec(p[0]) for p in pairs))
+        r1 = (LcKeyframe * max(B, 1))(*(rec(p[1]) for p in pairs))
+        rp = np.concatenate([[0], np.cumsum([r0[b].n_pt for b in range(B)])]).astype(np.int64)
+        rl = np.concatenate([[0], np.cumsum([r0[b].n_ls for b in range(B)])]).astype(np.int64)
+        pc, pi = np.zeros((int(rp[-1]), 4), np.int32), np.zeros(int(rp[-1]), np.uint8)
+        lc, li = np.zeros((int(rl[-1]), 4), np.int32), np.zeros(int(rl[-1]), np.uint8)
+        res = (LcResult * max(B, 1))()
+        _check(self._L.plslam_lc_batch_verify(self._h, r0, r1, B, res, _p(pc), _p(pi), _p(lc), _p(li)), "plslam_lc_batch_verify")
+        out = []
+        for b in range(B):
+            d = res[b].as_dict()
+            n, m = d["common_pt"], d["common_ls"]
+            out.append((d, pc[rp[b]:rp[b] + n], pi[rp[b]:rp[b] + n].astype(bool), lc[rl[b]:rl[b] + m],
+                        li[rl[b]:rl[b] + m].astype(bool)))
+        return out
+
+    def verify_dev(self, kf0_dev, kf1_dev, results_ptr, pt_corr_ptr, pt_inlier_ptr, ls_corr_ptr, ls_inlier_ptr, stream=None):
+        """Device-pointer form.  kf0_dev / kf1_dev: B dicts of device addresses each (Context.loop_closure_verify_dev's);
+        results_ptr: B x sizeof(LcResult) bytes; pair b's rows start at row sum(n_pt of kf0_dev[:b]) (n_ls for lines).
+        Enqueued behind `stream` (None = the context's stream), no synchronisation."""
+        B = len(kf0_dev)
+        if len(kf1_dev) != B:
+            raise ValueError("kf0_dev and kf1_dev differ in length")
+
+        def recs(ks):
+            return (LcKeyframe * max(B, 1))(*(
+                LcKeyframe(*(C.c_void_p(k.get(n) or 0) for n in ("pdesc", "P", "pl", "pt_idx")), int(k["n_pt"]), int(k["n_ls"]),
+                           *(C.c_void_p(k.get(n) or 0) for n in ("ldesc", "sPeP", "le", "ls_idx"))) for k in ks))
+
+        _check(self._L.plslam_lc_batch_verify_dev(self._h, recs(kf0_dev), recs(kf1_dev), B, C.c_void_p(results_ptr or 0),
+                                                  C.c_void_p(pt_corr_ptr or 0), C.c_void_p(pt_inlier_ptr or 0),
+                                                  C.c_void_p(ls_corr_ptr or 0), C.c_void_p(ls_inlier_ptr or 0),
+                                                  C.c_void_p(stream or 0)), "plslam_lc_batch_verify_dev")
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._ctx.handle:
+            self._L.plslam_lc_batch_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PgoPlan:

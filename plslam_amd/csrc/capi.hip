@@ -788,6 +788,22 @@ int match_problems_lc(plslam_ctx* ctx, const plslam_match_problem* probs, int32_
     const int r = plan_build(ctx, probs, nprob, ctx->lc_plan);
     return r ? r : plan_run(ctx->lc_plan, ctx->stream, ctx->stream);
 }
+
+int match_plan_rebuild(plslam_ctx* ctx, plslam_match_plan** slot, const plslam_match_problem* probs, int32_t nprob)
+{
+    if (!*slot) *slot = new (std::nothrow) plslam_match_plan();
+    PLSLAM_REQUIRE(*slot != nullptr, PLSLAM_ENOMEM);
+    return plan_build(ctx, probs, nprob, *slot);
+}
+
+int match_plan_enqueue(plslam_match_plan* plan, hipStream_t s) { return plan_run(plan, s, s); }
+
+void match_plan_release(plslam_match_plan* plan)
+{
+    if (!plan) return;
+    plan->free_all();
+    delete plan;
+}
 }  // namespace plslam
 
 // ---------------------------------------------------------------------------------------------
@@ -865,7 +881,7 @@ void plslam_ctx_destroy(plslam_ctx* ctx)
         ctx->lc_plan->free_all();
         delete ctx->lc_plan;
     }
-    ctx->lc_in.release(); ctx->lc_out.release(); ctx->lc_tab.release();
+    ctx->lc_in.release(); ctx->lc_out.release(); ctx->lc_tab.release(); ctx->lc_args.release();
     ctx->pgo_scratch.release();
     for (hipEvent_t& e : ctx->lc_ev)
         if (e) (void)hipEventDestroy(e);

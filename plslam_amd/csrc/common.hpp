@@ -142,7 +142,9 @@ struct plslam_ctx {
     struct plslam_match_plan* host_plan = nullptr;  // reused by the host-pointer match entry points
     struct plslam_match_plan* lc_plan = nullptr;    // the loop-closure check's two match problems (loop_closure.hip)
     plslam::DevBuf lc_in, lc_out, lc_tab;           // ... its keyframe image, its outputs, its match tables
-    hipEvent_t lc_ev[2] = {nullptr, nullptr};       // ... its fences with a caller's stream (the _dev form)
+    hipEvent_t lc_ev[2] = {nullptr, nullptr};       // ... its fences with a caller's stream (the _dev forms)
+    plslam::DevBuf lc_args;                         // plslam_relpose_robust_gn_batched_dev: K54's argument table
+    std::vector<char> lc_args_h;                    // ... and its host image (pageable: staged by the copy call itself)
     int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
     plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (pgo.hip)
 };
@@ -152,6 +154,11 @@ namespace plslam {
 // the loop-closure check's match problems (device pointers) as one plan on the context's stream: ctx->lc_plan, whose
 // buffers only grow and whose tables are staged in pageable memory (capi.hip)
 int match_problems_lc(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob);
+// a plan kept by its owner across calls (plslam_lc_batch): (re)built for `probs` (DEVICE pointers) into *slot, its tables
+// uploaded on the context's stream without a synchronisation; run on `s`; freed with its buffers
+int match_plan_rebuild(plslam_ctx* ctx, struct plslam_match_plan** slot, const plslam_match_problem* probs, int32_t nprob);
+int match_plan_enqueue(struct plslam_match_plan* plan, hipStream_t s);
+void match_plan_release(struct plslam_match_plan* plan);
 
 // Pointers read from launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction (it counts on
 // lgkmcnt as well as vmcnt, and cannot take a scalar base).  Kernels spell the address space out at the point of use:

@@ -14,8 +14,15 @@
 //      translation / rotation tests on logmap_se3(T_inc), and pose_inc on success.
 // Every correspondence is read from global memory (L2) on every pass: nothing is staged in LDS, so the counts are bounded
 // only by PLSLAM_LC_MAX_FEATURES.  No atomics on doubles; the result does not depend on scheduling.
+//
+// K54 -- the same check for B candidates in one launch: workgroup b copies record b of a device-resident LcArgs table
+// into LDS and runs lc_problem(), the text K25 runs on its one record.  Nothing is shared between workgroups, so a
+// record's result is the single call's bit for bit wherever it sits in the table.  The match tables of the whole batch come
+// from ONE match plan (plslam_lc_batch, below), which is rebuilt only when its problem list changes.
 #include <cfloat>
 #include <cstring>
+#include <new>
+#include <vector>
 
 #include "common.hpp"
 #include "pose_gn_dev.hpp"
@@ -338,7 +345,8 @@ __device__ __forceinline__ double cov_max_eig(const double Hm[36])
     return m;
 }
 
-// correspondences of one kind in i1 order -> rows (idx0[i1], i1, idx1[i2], i2), inlier flags 1; returns their count
+// correspondences of one kind in i1 order -> rows (idx0[i1], i1, idx1[i2], i2), inlier flags 1; returns their count.
+// corr may be null where correspondence k is (k, k) (the batched GN on the caller's correspondences keeps no rows)
 __device__ __forceinline__ int32_t gather_kind(LcShared& s, const int32_t* m12, int identity, int32_t n0, int32_t n1,
                                                const int32_t* idx0, const int32_t* idx1, int32_t* corr, uint8_t* inl)
 {
@@ -359,16 +367,29 @@ __device__ __forceinline__ int32_t gather_kind(LcShared& s, const int32_t* m12, 
         const int32_t chunk = s.wsum[0] + s.wsum[1] + s.wsum[2] + s.wsum[3];
         if (f) {
             const int32_t k = off + below;
-            g_(corr)[4 * (size_t)k] = idx0 ? g_(idx0)[i1] : -1;
-            g_(corr)[4 * (size_t)k + 1] = i1;
-            g_(corr)[4 * (size_t)k + 2] = idx1 ? g_(idx1)[i2] : -1;
-            g_(corr)[4 * (size_t)k + 3] = i2;
+            if (corr) {
+                g_(corr)[4 * (size_t)k] = idx0 ? g_(idx0)[i1] : -1;
+                g_(corr)[4 * (size_t)k + 1] = i1;
+                g_(corr)[4 * (size_t)k + 2] = idx1 ? g_(idx1)[i2] : -1;
+                g_(corr)[4 * (size_t)k + 3] = i2;
+            }
             g_(inl)[k] = 1;
         }
         total += chunk;
         __syncthreads();
     }
     return total;
+}
+
+// rows (i1, i2) of correspondence k
+__device__ __forceinline__ void corr_rows(const int32_t* corr, int32_t k, int32_t& i1, int32_t& i2)
+{
+    if (corr) {
+        i1 = g_(corr)[4 * (size_t)k + 1];
+        i2 = g_(corr)[4 * (size_t)k + 3];
+    } else {
+        i1 = i2 = k;
+    }
 }
 
 __device__ __forceinline__ void load_T(const LcShared& s, double Tm[12])
@@ -390,14 +411,16 @@ __device__ __forceinline__ void assemble(LcShared& s, const LcArgs& a, int32_t n
     int np = 0, nl = 0;
     for (int32_t k = tid; k < ncp; k += LC_THREADS) {
         if (!g_(a.pt_inl)[k]) continue;
-        const int32_t i1 = g_(a.pt_corr)[4 * (size_t)k + 1], i2 = g_(a.pt_corr)[4 * (size_t)k + 3];
+        int32_t i1, i2;
+        corr_rows(a.pt_corr, k, i1, i2);
         const double X[3] = {g_(a.P)[3 * (size_t)i1], g_(a.P)[3 * (size_t)i1 + 1], g_(a.P)[3 * (size_t)i1 + 2]};
         gn_point_row(a.K, a.th, Tm, X, g_(a.pl)[2 * (size_t)i2], g_(a.pl)[2 * (size_t)i2 + 1], ap);
         ++np;
     }
     for (int32_t k = tid; k < ncl; k += LC_THREADS) {
         if (!g_(a.ls_inl)[k]) continue;
-        const int32_t i1 = g_(a.ls_corr)[4 * (size_t)k + 1], i2 = g_(a.ls_corr)[4 * (size_t)k + 3];
+        int32_t i1, i2;
+        corr_rows(a.ls_corr, k, i1, i2);
         double SE[6], l[3];
 #pragma unroll
         for (int q = 0; q < 6; ++q) SE[q] = g_(a.sPeP)[6 * (size_t)i1 + q];
@@ -489,7 +512,8 @@ __device__ __forceinline__ void outlier_pass(LcShared& s, const LcArgs& a, int32
     load_T(s, Tm);
     for (int32_t k = tid; k < ncp; k += LC_THREADS) {
         if (!g_(a.pt_inl)[k]) continue;
-        const int32_t i1 = g_(a.pt_corr)[4 * (size_t)k + 1], i2 = g_(a.pt_corr)[4 * (size_t)k + 3];
+        int32_t i1, i2;
+        corr_rows(a.pt_corr, k, i1, i2);
         const double X[3] = {g_(a.P)[3 * (size_t)i1], g_(a.P)[3 * (size_t)i1 + 1], g_(a.P)[3 * (size_t)i1 + 2]};
         double G[3], dx, dy;
         if (gn_point_residual(a.K, Tm, X, g_(a.pl)[2 * (size_t)i2], g_(a.pl)[2 * (size_t)i2 + 1], G, dx, dy) > chi)
@@ -497,7 +521,8 @@ __device__ __forceinline__ void outlier_pass(LcShared& s, const LcArgs& a, int32
     }
     for (int32_t k = tid; k < ncl; k += LC_THREADS) {
         if (!g_(a.ls_inl)[k]) continue;
-        const int32_t i1 = g_(a.ls_corr)[4 * (size_t)k + 1], i2 = g_(a.ls_corr)[4 * (size_t)k + 3];
+        int32_t i1, i2;
+        corr_rows(a.ls_corr, k, i1, i2);
         double SE[6], l[3], S[3], E[3], ds, de;
 #pragma unroll
         for (int q = 0; q < 6; ++q) SE[q] = g_(a.sPeP)[6 * (size_t)i1 + q];
@@ -507,15 +532,12 @@ __device__ __forceinline__ void outlier_pass(LcShared& s, const LcArgs& a, int32
     }
 }
 
-__global__ void __launch_bounds__(LC_THREADS) k_loop_closure(LcArgs ka)
+// one problem, one workgroup: everything K25 and K54 compute.  a: the problem's record, already in LDS and visible to
+// every lane (the arguments are read from LDS where they are used: held in registers, their ~50 scalars stay live across the
+// whole kernel and spill beside the solve's uniform state)
+__device__ __forceinline__ void lc_problem(LcShared& s, const LcArgs& a)
 {
-    __shared__ LcShared s;
-    // the arguments are read from LDS where they are used: held as kernel arguments, their ~50 scalar registers stay live
-    // across the whole kernel and spill beside the solve's uniform state
-    __shared__ LcArgs a;
     const int tid = threadIdx.x;
-    if (tid == 0) a = ka;
-    __syncthreads();
     if (tid == 0) {
         s.clk0 = wall_clock64();
         s.clk_serial = 0;
@@ -639,6 +661,43 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_closure(LcArgs ka)
     g_(&R->clk_total)[0] = c1 - s.clk0;
 }
 
+__global__ void __launch_bounds__(LC_THREADS) k_loop_closure(LcArgs ka)
+{
+    __shared__ LcShared s;
+    __shared__ LcArgs a;
+    if (threadIdx.x == 0) a = ka;
+    __syncthreads();
+    lc_problem(s, a);
+}
+
+static_assert(sizeof(LcArgs) % 8 == 0, "K54 copies its record in 8-byte words");
+
+// K54: workgroup b runs record b.  pt_off / ls_off (both or neither; B + 1 offsets in device memory): the records are
+// identity problems over concatenated arrays -- record b's P, pl, sPeP, le and masks are the bases, and its rows are
+// [off[b], off[b + 1]) (a count outside [0, PLSLAM_LC_MAX_FEATURES] is taken as 0: the offsets are the producer's, unseen by
+// the host)
+__global__ void __launch_bounds__(LC_THREADS) k_loop_closure_batched(const LcArgs* tab, const int32_t* pt_off, const int32_t* ls_off)
+{
+    __shared__ LcShared s;
+    __shared__ LcArgs a;
+    const int tid = threadIdx.x;
+    constexpr int W = (int)(sizeof(LcArgs) / 8);
+    if (tid < W) reinterpret_cast<uint64_t*>(&a)[tid] = g_(reinterpret_cast<const uint64_t*>(tab))[(size_t)blockIdx.x * W + tid];
+    __syncthreads();
+    if (tid == 0 && pt_off) {
+        const int32_t po = g_(pt_off)[blockIdx.x], lo = g_(ls_off)[blockIdx.x];
+        int32_t np = g_(pt_off)[blockIdx.x + 1] - po, nl = g_(ls_off)[blockIdx.x + 1] - lo;
+        if (np < 0 || np > PLSLAM_LC_MAX_FEATURES || po < 0 || !a.P) np = 0;          // (a kind without arrays has no rows)
+        if (nl < 0 || nl > PLSLAM_LC_MAX_FEATURES || lo < 0 || !a.sPeP) nl = 0;
+        a.P += 3 * (size_t)po; a.pl += 2 * (size_t)po; a.pt_inl += po;
+        a.sPeP += 6 * (size_t)lo; a.le += 3 * (size_t)lo; a.ls_inl += lo;
+        a.n_pt0 = a.n_pt1 = np;
+        a.n_ls0 = a.n_ls1 = nl;
+    }
+    __syncthreads();
+    lc_problem(s, a);
+}
+
 struct LcDev {             // device pointers of one call
     const uint8_t *pd0, *pd1, *ld0, *ld1;
     LcArgs a;
@@ -713,6 +772,124 @@ int enqueue_verify(plslam_ctx* ctx, const plslam_lc_params* p, const plslam_lc_k
     a.n_pt0 = k0->n_pt; a.n_pt1 = k1->n_pt; a.n_ls0 = k0->n_ls; a.n_ls1 = k1->n_ls;
     a.identity = 0;
     hipLaunchKernelGGL(k_loop_closure, dim3(1), dim3(LC_THREADS), 0, ctx->stream, a);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    return PLSLAM_OK;
+}
+
+// the _dev forms run on the context's stream, behind what the caller's stream holds on entry and in front of what it is given
+// next (ctx->lc_ev; the caller holds ctx->mu)
+int fence_enter(plslam_ctx* ctx, hipStream_t us)
+{
+    if (!us || us == ctx->stream) return PLSLAM_OK;
+    for (hipEvent_t& e : ctx->lc_ev)
+        if (!e) PLSLAM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    PLSLAM_HIP_CHECK(hipEventRecord(ctx->lc_ev[0], us));
+    PLSLAM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->lc_ev[0], 0));
+    return PLSLAM_OK;
+}
+
+int fence_leave(plslam_ctx* ctx, hipStream_t us)
+{
+    if (!us || us == ctx->stream) return PLSLAM_OK;
+    PLSLAM_HIP_CHECK(hipEventRecord(ctx->lc_ev[1], ctx->stream));
+    PLSLAM_HIP_CHECK(hipStreamWaitEvent(us, ctx->lc_ev[1], 0));
+    return PLSLAM_OK;
+}
+
+}  // namespace
+}  // namespace plslam
+
+// B candidates per call (K54).  Every buffer only grows; the match plan is kept while its problem list stays the same.
+struct plslam_lc_batch {
+    plslam_ctx* ctx = nullptr;
+    plslam_lc_params p{};
+    int32_t max_pairs = 0;
+    plslam_match_plan* plan = nullptr;
+    std::vector<plslam_match_problem> plan_probs;   // what `plan` holds; empty: none
+    std::vector<plslam_match_problem> probs;        // this call's list
+    std::vector<plslam::LcArgs> h_args;             // K54's table (pageable: the copy call stages it before it returns)
+    std::vector<plslam_lc_keyframe> d_kf;           // the host form's device records
+    plslam::DevBuf tab, args;                       // the match tables + counters; K54's table
+    plslam::DevBuf in, out;                         // the host form's keyframe image and outputs
+    plslam::HostBuf pin_in, pin_out;
+};
+
+namespace plslam {
+namespace {
+
+int check_batch(const plslam_lc_batch* bt, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B)
+{
+    int rc;
+    PLSLAM_REQUIRE(bt != nullptr, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(B >= 0 && B <= bt->max_pairs, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(B == 0 || (kf0 && kf1), PLSLAM_EINVAL);
+    for (int32_t b = 0; b < B; ++b)
+        if ((rc = check_kf(kf0 + b)) || (rc = check_kf(kf1 + b))) return rc;
+    return PLSLAM_OK;
+}
+
+// the match problems of every pair as ONE plan (per pair what enqueue_verify sets; a kind the source would not match is
+// skipped) and K54 over the B records, on ctx->stream.  Pair b's rows start at row sum_{b' < b} kf0[b'].n_pt (n_ls).
+int enqueue_batch(plslam_lc_batch* bt, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B,
+                  plslam_lc_result* res, int32_t* pc, uint8_t* pi, int32_t* lc, uint8_t* li)
+{
+    int rc;
+    plslam_ctx* ctx = bt->ctx;
+    const plslam_lc_params* p = &bt->p;
+    size_t sp = 0, sl = 0;
+    for (int32_t b = 0; b < B; ++b) { sp += (size_t)kf0[b].n_pt; sl += (size_t)kf0[b].n_ls; }
+    Carver ct;
+    const size_t oP = ct.take(sp * 4), oL = ct.take(sl * 4), oC = ct.take((size_t)B * 8);
+    if ((rc = bt->tab.reserve(ct.off))) return rc;
+    if ((rc = bt->args.reserve((size_t)B * sizeof(LcArgs)))) return rc;
+    char* tb = bt->tab.as<char>();
+    bt->probs.clear();
+    bt->h_args.assign((size_t)B, LcArgs{});
+    size_t rp = 0, rl = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const plslam_lc_keyframe *k0 = kf0 + b, *k1 = kf1 + b;
+        const bool mp = p->has_points && k0->n_pt > 0 && k1->n_pt > 0;
+        const bool ml = p->has_lines && k0->n_ls > 0 && k1->n_ls > 0;
+        plslam_match_problem q;
+        memset(&q, 0, sizeof(q));
+        q.mutual = p->mutual ? 1 : 0;
+        if (mp) {
+            q.d1 = k0->pdesc; q.d2 = k1->pdesc; q.n1 = k0->n_pt; q.n2 = k1->n_pt; q.nnr = p->min_ratio_12_p;
+            q.matches_12 = (int32_t*)(tb + oP) + rp; q.n_matches = (int32_t*)(tb + oC) + bt->probs.size();
+            bt->probs.push_back(q);
+        }
+        if (ml) {
+            q.d1 = k0->ldesc; q.d2 = k1->ldesc; q.n1 = k0->n_ls; q.n2 = k1->n_ls; q.nnr = p->min_ratio_12_l;
+            q.matches_12 = (int32_t*)(tb + oL) + rl; q.n_matches = (int32_t*)(tb + oC) + bt->probs.size();
+            bt->probs.push_back(q);
+        }
+        LcArgs& a = bt->h_args[(size_t)b];
+        fill_args(a, p);
+        a.P = k0->P; a.pl = k1->pl; a.pt_idx0 = k0->pt_idx; a.pt_idx1 = k1->pt_idx;
+        a.sPeP = k0->sPeP; a.le = k1->le; a.ls_idx0 = k0->ls_idx; a.ls_idx1 = k1->ls_idx;
+        a.m12_p = mp ? (const int32_t*)(tb + oP) + rp : nullptr;
+        a.m12_l = ml ? (const int32_t*)(tb + oL) + rl : nullptr;
+        a.n_pt0 = k0->n_pt; a.n_pt1 = k1->n_pt; a.n_ls0 = k0->n_ls; a.n_ls1 = k1->n_ls;
+        a.identity = 0;
+        a.res = res + b;
+        a.pt_corr = pc ? pc + 4 * rp : nullptr; a.pt_inl = pi ? pi + rp : nullptr;
+        a.ls_corr = lc ? lc + 4 * rl : nullptr; a.ls_inl = li ? li + rl : nullptr;
+        rp += (size_t)k0->n_pt;
+        rl += (size_t)k0->n_ls;
+    }
+    if (!bt->probs.empty()) {
+        const bool same = bt->plan && bt->plan_probs.size() == bt->probs.size() &&
+                          memcmp(bt->plan_probs.data(), bt->probs.data(), bt->probs.size() * sizeof(plslam_match_problem)) == 0;
+        if (!same) {
+            bt->plan_probs.clear();
+            if ((rc = match_plan_rebuild(ctx, &bt->plan, bt->probs.data(), (int32_t)bt->probs.size()))) return rc;
+            bt->plan_probs = bt->probs;
+        }
+        if ((rc = match_plan_enqueue(bt->plan, ctx->stream))) return rc;
+    }
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(bt->args.p, bt->h_args.data(), (size_t)B * sizeof(LcArgs), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_loop_closure_batched, dim3((unsigned)B), dim3(LC_THREADS), 0, ctx->stream, bt->args.as<LcArgs>(),
+                       (const int32_t*)nullptr, (const int32_t*)nullptr);
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }
@@ -804,22 +981,12 @@ int plslam_loop_closure_verify_dev(plslam_ctx* ctx, const plslam_lc_params* para
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard(ctx->device);
     hipStream_t us = static_cast<hipStream_t>(stream);
-    const bool fence = us && us != ctx->stream;
-    if (fence) {
-        for (hipEvent_t& e : ctx->lc_ev)
-            if (!e) PLSLAM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        PLSLAM_HIP_CHECK(hipEventRecord(ctx->lc_ev[0], us));
-        PLSLAM_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->lc_ev[0], 0));
-    }
+    if ((rc = fence_enter(ctx, us))) return rc;
     LcArgs a{};
     a.res = result;
     a.pt_corr = pt_corr; a.pt_inl = pt_inlier; a.ls_corr = ls_corr; a.ls_inl = ls_inlier;
     if ((rc = enqueue_verify(ctx, params, kf0, kf1, a))) return rc;
-    if (fence) {
-        PLSLAM_HIP_CHECK(hipEventRecord(ctx->lc_ev[1], ctx->stream));
-        PLSLAM_HIP_CHECK(hipStreamWaitEvent(us, ctx->lc_ev[1], 0));
-    }
-    return PLSLAM_OK;
+    return fence_leave(ctx, us);
 }
 
 int plslam_relpose_robust_gn(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
@@ -871,6 +1038,185 @@ int plslam_relpose_robust_gn(plslam_ctx* ctx, const plslam_lc_params* params, co
     if (pt_inlier && np) memcpy(pt_inlier, ho + oPI, np);
     if (ls_inlier && nl) memcpy(ls_inlier, ho + oLI, nl);
     return PLSLAM_OK;
+}
+
+int plslam_lc_batch_create(plslam_ctx* ctx, const plslam_lc_params* params, int32_t max_pairs, plslam_lc_batch** out)
+{
+    using namespace plslam;
+    int rc;
+    PLSLAM_REQUIRE(ctx && out, PLSLAM_EINVAL);
+    *out = nullptr;
+    if ((rc = check_params(params))) return rc;
+    PLSLAM_REQUIRE(max_pairs >= 1, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(max_pairs <= PLSLAM_LC_MAX_BATCH, PLSLAM_ERANGE);
+    plslam_lc_batch* bt = new (std::nothrow) plslam_lc_batch();
+    PLSLAM_REQUIRE(bt != nullptr, PLSLAM_ENOMEM);
+    bt->ctx = ctx;
+    bt->p = *params;
+    bt->max_pairs = max_pairs;
+    *out = bt;
+    return PLSLAM_OK;
+}
+
+void plslam_lc_batch_destroy(plslam_lc_batch* batch)
+{
+    using namespace plslam;
+    if (!batch) return;
+    {
+        std::lock_guard<std::mutex> lk(batch->ctx->mu);
+        DeviceGuard guard(batch->ctx->device);
+        (void)hipStreamSynchronize(batch->ctx->stream);
+        match_plan_release(batch->plan);
+        batch->tab.release(); batch->args.release(); batch->in.release(); batch->out.release();
+        batch->pin_in.release(); batch->pin_out.release();
+    }
+    delete batch;
+}
+
+int plslam_lc_batch_verify_dev(plslam_lc_batch* batch, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B,
+                               plslam_lc_result* results, int32_t* pt_corr, uint8_t* pt_inlier, int32_t* ls_corr,
+                               uint8_t* ls_inlier, void* stream)
+{
+    using namespace plslam;
+    int rc;
+    if ((rc = check_batch(batch, kf0, kf1, B))) return rc;
+    if (B == 0) return PLSLAM_OK;
+    PLSLAM_REQUIRE(results != nullptr, PLSLAM_EINVAL);
+    bool any_pt = false, any_ls = false;
+    for (int32_t b = 0; b < B; ++b) { any_pt = any_pt || kf0[b].n_pt > 0; any_ls = any_ls || kf0[b].n_ls > 0; }
+    PLSLAM_REQUIRE(!any_pt || (pt_corr && pt_inlier), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(!any_ls || (ls_corr && ls_inlier), PLSLAM_EINVAL);
+    plslam_ctx* ctx = batch->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    hipStream_t us = static_cast<hipStream_t>(stream);
+    if ((rc = fence_enter(ctx, us))) return rc;
+    if ((rc = enqueue_batch(batch, kf0, kf1, B, results, pt_corr, pt_inlier, ls_corr, ls_inlier))) return rc;
+    return fence_leave(ctx, us);
+}
+
+int plslam_lc_batch_verify(plslam_lc_batch* batch, const plslam_lc_keyframe* kf0, const plslam_lc_keyframe* kf1, int32_t B,
+                           plslam_lc_result* results, int32_t* pt_corr, uint8_t* pt_inlier, int32_t* ls_corr, uint8_t* ls_inlier)
+{
+    using namespace plslam;
+    int rc;
+    if ((rc = check_batch(batch, kf0, kf1, B))) return rc;
+    if (B == 0) return PLSLAM_OK;
+    PLSLAM_REQUIRE(results != nullptr, PLSLAM_EINVAL);
+    plslam_ctx* ctx = batch->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    hipStream_t s = ctx->stream;
+    StreamSyncOnError sync_on_error(s);
+    // one page-locked image of every DISTINCT keyframe record (the top-K shape repeats kf1) -> one upload
+    const size_t n2 = 2 * (size_t)B;
+    auto rec = [&](size_t q) -> const plslam_lc_keyframe& { return q < (size_t)B ? kf0[q] : kf1[q - (size_t)B]; };
+    std::vector<size_t> first(n2);
+    std::vector<size_t> off(n2 * 8, 0);
+    Carver ci;
+    for (size_t q = 0; q < n2; ++q) {
+        first[q] = q;
+        for (size_t r = 0; r < q; ++r)
+            if (first[r] == r && rec(r).pdesc == rec(q).pdesc && memcmp(&rec(r), &rec(q), sizeof(plslam_lc_keyframe)) == 0) { first[q] = r; break; }
+        if (first[q] != q) continue;
+        const size_t np = (size_t)rec(q).n_pt, nl = (size_t)rec(q).n_ls;
+        size_t* o = &off[q * 8];
+        o[0] = ci.take(np * 32); o[1] = ci.take(np * 24); o[2] = ci.take(np * 16); o[3] = ci.take(np * 4);
+        o[4] = ci.take(nl * 32); o[5] = ci.take(nl * 48); o[6] = ci.take(nl * 24); o[7] = ci.take(nl * 4);
+    }
+    size_t sp = 0, sl = 0;
+    for (int32_t b = 0; b < B; ++b) { sp += (size_t)kf0[b].n_pt; sl += (size_t)kf0[b].n_ls; }
+    Carver co;
+    const size_t oR = co.take((size_t)B * sizeof(plslam_lc_result)), oPC = co.take(sp * 16), oPI = co.take(sp),
+                 oLC = co.take(sl * 16), oLI = co.take(sl);
+    if ((rc = batch->pin_in.reserve(ci.off + 256))) return rc;
+    if ((rc = batch->in.reserve(ci.off + 256))) return rc;
+    if ((rc = batch->pin_out.reserve(co.off))) return rc;
+    if ((rc = batch->out.reserve(co.off))) return rc;
+    char* h = batch->pin_in.as<char>();
+    char* d = batch->in.as<char>();
+    batch->d_kf.assign(n2, plslam_lc_keyframe{});
+    for (size_t q = 0; q < n2; ++q) {
+        if (first[q] != q) { batch->d_kf[q] = batch->d_kf[first[q]]; continue; }
+        const plslam_lc_keyframe& k = rec(q);
+        const size_t np = (size_t)k.n_pt, nl = (size_t)k.n_ls;
+        const size_t* o = &off[q * 8];
+        if (np) {
+            memcpy(h + o[0], k.pdesc, np * 32); memcpy(h + o[1], k.P, np * 24); memcpy(h + o[2], k.pl, np * 16);
+            if (k.pt_idx) memcpy(h + o[3], k.pt_idx, np * 4);
+        }
+        if (nl) {
+            memcpy(h + o[4], k.ldesc, nl * 32); memcpy(h + o[5], k.sPeP, nl * 48); memcpy(h + o[6], k.le, nl * 24);
+            if (k.ls_idx) memcpy(h + o[7], k.ls_idx, nl * 4);
+        }
+        plslam_lc_keyframe& D = batch->d_kf[q];
+        D.n_pt = k.n_pt; D.n_ls = k.n_ls;
+        D.pdesc = (const uint8_t*)(d + o[0]); D.P = (const double*)(d + o[1]); D.pl = (const double*)(d + o[2]);
+        D.pt_idx = k.pt_idx ? (const int32_t*)(d + o[3]) : nullptr;
+        D.ldesc = (const uint8_t*)(d + o[4]); D.sPeP = (const double*)(d + o[5]); D.le = (const double*)(d + o[6]);
+        D.ls_idx = k.ls_idx ? (const int32_t*)(d + o[7]) : nullptr;
+    }
+    if (ci.off) PLSLAM_HIP_CHECK(hipMemcpyAsync(d, h, ci.off, hipMemcpyHostToDevice, s));
+    char* od = batch->out.as<char>();
+    if ((rc = enqueue_batch(batch, batch->d_kf.data(), batch->d_kf.data() + B, B, (plslam_lc_result*)(od + oR), (int32_t*)(od + oPC),
+                            (uint8_t*)(od + oPI), (int32_t*)(od + oLC), (uint8_t*)(od + oLI))))
+        return rc;
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(batch->pin_out.p, od, co.off, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    sync_on_error.dismiss();
+    const char* ho = batch->pin_out.as<char>();
+    memcpy(results, ho + oR, (size_t)B * sizeof(plslam_lc_result));
+    size_t rp = 0, rl = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const size_t ncp = (size_t)results[b].common_pt, ncl = (size_t)results[b].common_ls;
+        if (pt_corr && ncp) memcpy(pt_corr + 4 * rp, ho + oPC + 16 * rp, ncp * 16);
+        if (pt_inlier && ncp) memcpy(pt_inlier + rp, ho + oPI + rp, ncp);
+        if (ls_corr && ncl) memcpy(ls_corr + 4 * rl, ho + oLC + 16 * rl, ncl * 16);
+        if (ls_inlier && ncl) memcpy(ls_inlier + rl, ho + oLI + rl, ncl);
+        rp += (size_t)kf0[b].n_pt;
+        rl += (size_t)kf0[b].n_ls;
+    }
+    return PLSLAM_OK;
+}
+
+int plslam_relpose_robust_gn_batched_dev(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
+                                         const int32_t* pt_off, const double* sPeP, const double* le_obs, const int32_t* ls_off,
+                                         int32_t B, plslam_lc_result* results, uint8_t* pt_inlier, uint8_t* ls_inlier, void* stream)
+{
+    using namespace plslam;
+    int rc;
+    PLSLAM_REQUIRE(ctx != nullptr, PLSLAM_EINVAL);
+    if ((rc = check_params(params))) return rc;
+    PLSLAM_REQUIRE(B >= 0, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(B <= PLSLAM_LC_MAX_BATCH, PLSLAM_ERANGE);
+    if (B == 0) return PLSLAM_OK;
+    PLSLAM_REQUIRE(results && pt_off && ls_off, PLSLAM_EINVAL);
+    // (the counts live on the device: an array that a non-empty problem needs cannot be checked here)
+    PLSLAM_REQUIRE((P != nullptr) == (pl_obs != nullptr) && (P == nullptr || pt_inlier != nullptr), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE((sPeP != nullptr) == (le_obs != nullptr) && (sPeP == nullptr || ls_inlier != nullptr), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(P || sPeP, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    hipStream_t us = static_cast<hipStream_t>(stream);
+    const size_t bytes = (size_t)B * sizeof(LcArgs);
+    if ((rc = ctx->lc_args.reserve(bytes))) return rc;
+    ctx->lc_args_h.resize(bytes);
+    LcArgs* h = reinterpret_cast<LcArgs*>(ctx->lc_args_h.data());
+    LcArgs a{};
+    fill_args(a, params);
+    a.P = P; a.pl = pl_obs; a.sPeP = sPeP; a.le = le_obs;
+    a.identity = 1;
+    a.pt_inl = pt_inlier; a.ls_inl = ls_inlier;          // no correspondence rows: row k is (k, k)
+    for (int32_t b = 0; b < B; ++b) {
+        h[b] = a;
+        h[b].res = results + b;
+    }
+    if ((rc = fence_enter(ctx, us))) return rc;
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(ctx->lc_args.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_loop_closure_batched, dim3((unsigned)B), dim3(LC_THREADS), 0, ctx->stream, ctx->lc_args.as<LcArgs>(),
+                       pt_off, ls_off);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    return fence_leave(ctx, us);
 }
 
 }  // extern "C"

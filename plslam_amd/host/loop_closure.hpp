@@ -1,5 +1,6 @@
 // loop_closure.hpp -- C++ host shim: MapHandler::isLoopClosure / computeRelativePoseRobustGN on top of the C ABI
-// (plslam_loop_closure_verify, plslam_relpose_robust_gn; K25).
+// (plslam_loop_closure_verify, plslam_relpose_robust_gn; K25), and LoopClosureBatch: the same check for several candidate
+// pairs in one call (plslam_lc_batch_verify; K54).
 //
 // Mirrors   bool MapHandler::isLoopClosure(const KeyFrame* kf0, const KeyFrame* kf1, Vector6d& pose_inc,
 //                                          vector<Vector4i>& lc_pt_idx, vector<Vector4i>& lc_ls_idx, ...)   src/mapHandler.cpp:3192
@@ -13,6 +14,7 @@
 
 #include <stdint.h>
 
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -65,6 +67,7 @@ public:
     const plslam_lc_result& last() const { return last_; }
 
 private:
+    friend class LoopClosureBatch;
     struct Packed {
         std::vector<uint8_t> pdesc, ldesc;
         std::vector<double> P, pl, sPeP, le;
@@ -129,6 +132,85 @@ private:
     plslam_ctx* ctx_;
     plslam_lc_params p_;
     plslam_lc_result last_{};
+};
+
+// isLoopClosure for several (kf0, kf1) pairs in one call -- e.g. the best K candidates of lookForLoopCandidates against
+// the current keyframe.  Pair b's outputs are what LoopClosure::isLoopClosure(*kf0[b], *kf1[b], ...) leaves, bit for bit.
+class LoopClosureBatch {
+public:
+    LoopClosureBatch(plslam_ctx* ctx, const plslam_lc_params& p, int max_pairs) : max_pairs_(max_pairs)
+    {
+        LoopClosure::check(plslam_lc_batch_create(ctx, &p, max_pairs, &h_), "plslam_lc_batch_create");
+    }
+    ~LoopClosureBatch() { plslam_lc_batch_destroy(h_); }
+    LoopClosureBatch(const LoopClosureBatch&) = delete;
+    LoopClosureBatch& operator=(const LoopClosureBatch&) = delete;
+
+    // kf0[b], kf1[b]: the reference's KeyFrame* pairs (a keyframe that appears several times is packed and uploaded once).
+    // is_lc[b]: isLoopClosure's value; pose_inc[b] written on success only (resized, earlier entries kept);
+    // lc_pt_idx[b] / lc_ls_idx[b] as :3914-3946 leave them
+    template <class Frame, class Vec6, class Idx4>
+    void isLoopClosure(const std::vector<const Frame*>& kf0, const std::vector<const Frame*>& kf1, std::vector<Vec6>& pose_inc,
+                       std::vector<std::vector<Idx4>>& lc_pt_idx, std::vector<std::vector<Idx4>>& lc_ls_idx,
+                       std::vector<bool>& is_lc)
+    {
+        if (kf0.size() != kf1.size() || kf0.size() > (size_t)max_pairs_)
+            throw std::runtime_error("LoopClosureBatch::isLoopClosure: kf0 and kf1 differ in length, or exceed max_pairs");
+        const size_t B = kf0.size();
+        std::map<const Frame*, LoopClosure::Packed> packed;
+        for (size_t q = 0; q < 2 * B; ++q) {
+            const Frame* f = q < B ? kf0[q] : kf1[q - B];
+            if (!packed.count(f)) LoopClosure::pack(*f, packed[f]);
+        }
+        std::vector<plslam_lc_keyframe> r0(B), r1(B);
+        size_t sp = 0, sl = 0;
+        for (size_t b = 0; b < B; ++b) {
+            r0[b] = packed[kf0[b]].record();
+            r1[b] = packed[kf1[b]].record();
+            sp += (size_t)r0[b].n_pt;
+            sl += (size_t)r0[b].n_ls;
+        }
+        std::vector<int32_t> pc(sp * 4), lc(sl * 4);
+        std::vector<uint8_t> pi(sp), li(sl);
+        last_.assign(B, plslam_lc_result{});
+        LoopClosure::check(plslam_lc_batch_verify(h_, r0.data(), r1.data(), (int32_t)B, last_.data(), pc.data(), pi.data(), lc.data(),
+                                                  li.data()), "plslam_lc_batch_verify");
+        pose_inc.resize(B);
+        lc_pt_idx.resize(B);
+        lc_ls_idx.resize(B);
+        is_lc.assign(B, false);
+        sp = sl = 0;
+        for (size_t b = 0; b < B; ++b) {
+            const plslam_lc_result& r = last_[b];
+            rows(pc, pi, sp, r.common_pt, r.is_lc != 0, lc_pt_idx[b]);
+            rows(lc, li, sl, r.common_ls, r.is_lc != 0, lc_ls_idx[b]);
+            if (r.is_lc)
+                for (int k = 0; k < 6; ++k) pose_inc[b](k) = r.pose_inc[k];
+            is_lc[b] = r.is_lc != 0;
+            sp += (size_t)r0[b].n_pt;
+            sl += (size_t)r0[b].n_ls;
+        }
+    }
+
+    const std::vector<plslam_lc_result>& last() const { return last_; }
+
+private:
+    template <class Idx4>
+    static void rows(const std::vector<int32_t>& c, const std::vector<uint8_t>& inl, size_t row0, int32_t n, bool only_inliers,
+                     std::vector<Idx4>& out)
+    {
+        out.clear();
+        for (size_t k = row0; k < row0 + (size_t)n; ++k) {
+            if (only_inliers && !inl[k]) continue;
+            Idx4 v;
+            for (int q = 0; q < 4; ++q) v(q) = c[k * 4 + q];
+            out.push_back(v);
+        }
+    }
+
+    plslam_lc_batch* h_ = nullptr;
+    int max_pairs_;
+    std::vector<plslam_lc_result> last_;
 };
 
 }  // namespace plslam

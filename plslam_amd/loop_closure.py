@@ -1,5 +1,5 @@
-"""Loop-closure verification (K25, MapHandler::isLoopClosure): the parameter record with the shipped configuration's values,
-and a seeded synthetic keyframe pair with known correspondences and a known relative pose."""
+"""Loop-closure verification (K25 / K54, MapHandler::isLoopClosure): the parameter record with the shipped configuration's
+values, a seeded synthetic keyframe pair with known correspondences and a known relative pose, and a seeded batch of such pairs."""
 from __future__ import annotations
 
 import numpy as np
@@ -114,6 +114,36 @@ def keyframe_pair(seed, n_pt=1500, n_ls=200, pose=(0.05, -0.03, 0.10, 0.01, -0.0
         for k, w in (("pdesc", 32), ("P", 3), ("pl", 2), ("ldesc", 32), ("sPeP", 6), ("le", 3)):
             kf[k] = np.ascontiguousarray(np.asarray(kf[k]).reshape(-1, w), dtype=np.uint8 if "desc" in k else np.float64)
     return kf0, kf1, truth
+
+
+# what keyframe_batch cycles through: the sizes of the library's three workloads, and per pair one of these changes to
+# keyframe_pair's defaults -- a plain pair, too few true rows for the inlier-ratio gate, a translation beyond lcTrs, a roll
+# beyond lcRot, a keyframe pair without lines, one without points, and two more plain pairs at other poses
+BATCH_SIZES = ((1500, 200), (800, 100), (4000, 600))
+BATCH_VARIANTS = (
+    dict(),
+    dict(keep_frac=0.2),
+    dict(pose=(1.3, -0.9, 0.8, 0.01, -0.02, 0.015)),
+    dict(pose=(0.05, -0.03, 0.10, 0.0, 0.0, 0.63)),
+    dict(n_ls=0),
+    dict(n_pt=0),
+    dict(pose=(-0.2, 0.1, 0.3, -0.03, 0.02, 0.05)),
+    dict(pose=(0.4, 0.2, -0.1, 0.02, 0.04, -0.06), keep_frac=0.5),
+)
+
+
+def keyframe_batch(seed, B, sizes=BATCH_SIZES, variants=BATCH_VARIANTS, **kw):
+    """B keyframe pairs for one batched call: pair b is keyframe_pair(1000 * seed + b, *sizes[b % len(sizes)]) with
+    variants[b % len(variants)] (and kw) over its defaults.  Deterministic in (seed, B, sizes, variants, kw); pair b does not
+    depend on B.  Returns a list of (kf0, kf1, truth)."""
+    out = []
+    for b in range(B):
+        n_pt, n_ls = sizes[b % len(sizes)]
+        a = dict(n_pt=n_pt, n_ls=n_ls)
+        a.update(kw)
+        a.update(variants[b % len(variants)])
+        out.append(keyframe_pair(1000 * int(seed) + b, **a))
+    return out
 
 
 def _ring(rng, n, r0, r1):

@@ -6,6 +6,13 @@ work (correspondences, the 6 x 6 solves, the SE(3) updates, the outlier pass, th
 line: median microseconds per call.
 
     python tools/lc_bench.py [--reps 50]
+
+--batch B: the batched check (K54) instead -- B distinct pairs of --size features in one plslam_lc_batch_verify_dev call
+against B plslam_loop_closure_verify_dev calls enqueued back to back behind one synchronisation, in the same process on the
+same device arrays; the same 2 B match problems as a match plan of their own give the plan's share of the batched call, the
+rest is K54's.  Prints one JSON record.
+
+    python tools/lc_bench.py --batch 1024 [--size 1500 200] [--reps 20]
 """
 from __future__ import annotations
 
@@ -38,10 +45,90 @@ def _median_us(fn, reps, warm=3):
     return float(np.median(ts) * 1e6)
 
 
+def bench_batch(args):
+    import torch
+    B, (n_pt, n_ls) = args.batch, args.size
+    ctx = plslam_amd.Context(0)
+    dev = torch.device("cuda:0")
+    p = LC.params()
+    keep = []
+
+    def put(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        keep.append(t)
+        return t.data_ptr() if t.numel() else 0
+
+    r0, r1 = [], []
+    for k0, k1, _ in LC.keyframe_batch(3, B, sizes=((n_pt, n_ls),), variants=(dict(),)):
+        for kf, recs in ((k0, r0), (k1, r1)):
+            recs.append(dict({k: put(kf[k]) for k in ("pdesc", "P", "pl", "pt_idx", "ldesc", "sPeP", "le", "ls_idx")},
+                             n_pt=n_pt, n_ls=n_ls))
+    rsz = ctypes.sizeof(plslam_amd.LcResult)
+    res = torch.zeros(B * rsz, dtype=torch.uint8, device=dev)
+    pc = torch.zeros((B * n_pt, 4), dtype=torch.int32, device=dev)
+    pi = torch.zeros(B * n_pt, dtype=torch.uint8, device=dev)
+    lcb = torch.zeros((B * n_ls, 4), dtype=torch.int32, device=dev)
+    li = torch.zeros(B * n_ls, dtype=torch.uint8, device=dev)
+    res1, pc1, pi1, lcb1, li1 = (torch.zeros_like(t) for t in (res, pc, pi, lcb, li))
+    stream = torch.cuda.Stream(dev)
+    batch = plslam_amd.LcBatch(ctx, p, B)
+
+    def run_batched():
+        batch.verify_dev(r0, r1, res.data_ptr(), pc.data_ptr(), pi.data_ptr(), lcb.data_ptr(), li.data_ptr(),
+                         stream=stream.cuda_stream)
+        stream.synchronize()
+
+    def run_singles():
+        for b in range(B):
+            ctx.loop_closure_verify_dev(p, r0[b], r1[b], res1.data_ptr() + b * rsz, pc1.data_ptr() + 16 * b * n_pt,
+                                        pi1.data_ptr() + b * n_pt, lcb1.data_ptr() + 16 * b * n_ls, li1.data_ptr() + b * n_ls,
+                                        stream=stream.cuda_stream)
+        stream.synchronize()
+
+    # the batch's match problems as a plan of their own (tables of its own)
+    m12 = torch.zeros(B * (n_pt + n_ls), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+    probs = []
+    for b in range(B):
+        probs.append((r0[b]["pdesc"], n_pt, r1[b]["pdesc"], n_pt, p.min_ratio_12_p, p.mutual, m12.data_ptr() + 4 * b * n_pt,
+                      cnt.data_ptr() + 8 * b))
+        probs.append((r0[b]["ldesc"], n_ls, r1[b]["ldesc"], n_ls, p.min_ratio_12_l, p.mutual,
+                      m12.data_ptr() + 4 * (B * n_pt + b * n_ls), cnt.data_ptr() + 8 * b + 4))
+    plan = plslam_amd.MatchPlan(ctx, probs)
+
+    def run_plan():
+        plan.run(stream.cuda_stream)
+        stream.synchronize()
+
+    t_b = _median_us(run_batched, args.reps)
+    t_p = _median_us(run_plan, args.reps)
+    t_s = _median_us(run_singles, max(3, args.reps // 4), warm=1)
+    same = bool(torch.equal(res.view(-1, rsz)[:, :rsz - 16], res1.view(-1, rsz)[:, :rsz - 16])) and \
+        bool(torch.equal(pi, pi1)) and bool(torch.equal(li, li1))
+    recs = [plslam_amd.LcResult.from_buffer_copy(x.tobytes()) for x in res.view(-1, rsz).cpu().numpy()]
+    r = recs[0].as_dict()
+    clk = np.array([x.clk_total for x in recs]) / 100.0            # 100 MHz wall clock
+    out = {"tool": "lc_bench", "mode": "batch", "unit": "us (median)", "reps": args.reps, "B": B, "n_pt": n_pt, "n_ls": n_ls,
+           "max_iters": p.max_iters, "max_iters_ref": p.max_iters_ref, "systems": r["iters_1"] + r["iters_2"],
+           "accepted": int(sum(x.is_lc for x in recs)),
+           "batched_us": t_b, "singles_us": t_s, "ratio": t_s / t_b, "per_pair_us": t_b / B, "match_plan_us": t_p,
+           "k54_us": t_b - t_p, "match_plan_share": t_p / t_b, "k54_share": 1.0 - t_p / t_b,
+           "workgroup_us_min_mean_max": [float(clk.min()), float(clk.mean()), float(clk.max())],
+           "workgroup_serial_us_mean": float(np.mean([x.clk_serial for x in recs]) / 100.0),
+           "batched_equals_singles": same}
+    batch.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--batch", type=int, default=0, help="B > 0: the batched check against B single device calls")
+    ap.add_argument("--size", type=int, nargs=2, default=(1500, 200), metavar=("N_PT", "N_LS"))
     args = ap.parse_args()
+    if args.batch > 0:
+        return bench_batch(args)
     import torch
     import lc_ref
     from oracle import oracle as O

@@ -438,7 +438,7 @@ int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t
         hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, G->npad, (int32_t)G->n, (int32_t)G->npad);
     hipLaunchKernelGGL(k_gba_rhs, dim3(nkf), dim3(64), 0, s, I32(G->oKpp), I32(G->oKpo), I32(G->oKlp), I32(G->oKlo), I32(G->oPlm),
                        I32(G->oLlm), B.W_pt, (const double*)D(G->oTp), B.W_ls, (const double*)D(G->oTl), B.g, D(G->oW));
-    if ((rc = ldlt_enqueue(S, G->npad, D(G->oP), D(G->oW), D(G->oZ), D(G->oDp), (int32_t*)(wk + G->oBad), s))) return rc;
+    if ((rc = ldlt_enqueue(S, G->npad, (int32_t)G->n, D(G->oP), D(G->oW), D(G->oZ), D(G->oDp), (int32_t*)(wk + G->oBad), s))) return rc;
     const int nwp = (npt + 255) / 256, nwl = (nls + 255) / 256, nwk = (nkf + 255) / 256;
     double* part = D(G->oSsPart);
     hipLaunchKernelGGL(k_gba_pose, dim3(nwk), dim3(256), 0, s, nkf, (const double*)D(G->oDp), (int32_t)apply, D(G->oX),
@@ -747,7 +747,7 @@ int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const d
     PLSLAM_HIP_CHECK(hipMemcpy2DAsync(S, (size_t)npad * 8, A, (size_t)n * 8, (size_t)n * 8, n, hipMemcpyHostToDevice, s));
     PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oW, b, (size_t)n * 8, hipMemcpyHostToDevice, s));
     if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, npad, n, (int32_t)npad);
-    if ((rc = ldlt_enqueue(S, npad, (double*)(d + oP), (double*)(d + oW), (double*)(d + oZ), (double*)(d + oX),
+    if ((rc = ldlt_enqueue(S, npad, n, (double*)(d + oP), (double*)(d + oW), (double*)(d + oZ), (double*)(d + oX),
                            (int32_t*)(d + oB), s)))
         return rc;
     hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)nullptr, 0, (const int32_t*)nullptr, 0,

@@ -1,12 +1,11 @@
 // ldlt_dense_dev.hpp -- the dense right-looking fp64 L D L^T of the global bundle adjustment (K32-K36) and its enqueue
 // function, shared by gba.hip and, as the comparison path of the loop-closure pose graph, pgo.hip.  Included INSIDE the
-// includer's anonymous namespace in plslam, after it defines LT (the tile edge, 32) and dvec4_t (4 x double ext vector); the
-// text is gba.hip's as it was, so that gba.hip's code object does not change.
+// includer's anonymous namespace in plslam, after it defines LT (the tile edge, 32) and dvec4_t (4 x double ext vector).
 #pragma once
 
 // ---- K32-K34: right-looking blocked L D L^T of the lower triangle, in place (strict lower: L, diagonal: D) --------------------
 __global__ void __launch_bounds__(256)
-k_ldlt_diag(double* __restrict__ S, int64_t ld, int32_t k, int32_t* __restrict__ badp)
+k_ldlt_diag(double* __restrict__ S, int64_t ld, int32_t k, int32_t n, int32_t* __restrict__ badp)
 {
     __shared__ double A[LT][LT + 1];
     __shared__ double col[LT];
@@ -20,7 +19,8 @@ k_ldlt_diag(double* __restrict__ S, int64_t ld, int32_t k, int32_t* __restrict__
     for (int j = 0; j < LT; ++j) {
         __syncthreads();
         const double d = A[j][j];
-        if (t == 0 && !(d != 0.0 && isfinite(d))) ++bad;
+        // the pivots of the system only: the identity padding behind a bad pivot turns non-finite with it and is not counted
+        if (t == 0 && k * LT + j < n && !(d != 0.0 && isfinite(d))) ++bad;
         if (t > j && t < LT) { const double l = A[t][j] / d; col[t] = l; A[t][j] = l; }
         __syncthreads();
         for (int e = t; e < LT * LT; e += 256) {
@@ -162,13 +162,14 @@ k_ldlt_bwd(const double* __restrict__ S, int64_t ld, int32_t k, double* __restri
 }
 
 // ---- host side of the LDL^T: the matrix S (npad x npad, row-major, lower triangle read) is factored in place and
-// S x = b solved; w, z: npad doubles of workspace (w holds b on entry and is overwritten); P: npad x 32 doubles ------------------
+// S x = b solved; w, z: npad doubles of workspace (w holds b on entry and is overwritten); P: npad x 32 doubles; n <= npad: the
+// order of the system itself, whose bad pivots badp counts per tile -------------------------------------------------------------
 inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }   // the npad of ldlt_enqueue
-int ldlt_enqueue(double* S, int64_t npad, double* P, double* w, double* z, double* x, int32_t* badp, hipStream_t s)
+int ldlt_enqueue(double* S, int64_t npad, int32_t n, double* P, double* w, double* z, double* x, int32_t* badp, hipStream_t s)
 {
     const int nt = (int)(npad / LT);
     for (int k = 0; k < nt; ++k) {
-        hipLaunchKernelGGL(k_ldlt_diag, dim3(1), dim3(256), 0, s, S, npad, k, badp);
+        hipLaunchKernelGGL(k_ldlt_diag, dim3(1), dim3(256), 0, s, S, npad, k, n, badp);
         const int T = nt - k - 1;
         if (T > 0) {
             hipLaunchKernelGGL(k_ldlt_panel, dim3(T), dim3(64), 0, s, S, npad, k, P);

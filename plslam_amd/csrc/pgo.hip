@@ -808,7 +808,7 @@ int pgo_trial_enqueue(plslam_pgo_plan* P, double lambda, const double* X, double
         PLSLAM_HIP_CHECK(hipMemsetAsync(Dd(P->oW), 0, (size_t)P->npad * 8, s));
         hipLaunchKernelGGL(k_env_to_dense, dim3((unsigned)P->npad), dim3(256), 0, s, (const double*)Dd(P->oH), E.off, E.cs, P->N,
                            P->npad, lambda, (const double*)Dd(P->oB), S, Dd(P->oW));
-        if ((rc = ldlt_enqueue(S, P->npad, Dd(P->oP), Dd(P->oW), Dd(P->oZv), Dd(P->oDx), (int32_t*)(w + P->oBadp), s))) return rc;
+        if ((rc = ldlt_enqueue(S, P->npad, (int32_t)P->N, Dd(P->oP), Dd(P->oW), Dd(P->oZv), Dd(P->oDx), (int32_t*)(w + P->oBadp), s))) return rc;
         hipLaunchKernelGGL(k_count_bad, dim3(1), dim3(64), 0, s, (const int32_t*)(w + P->oBadp), (int32_t)(P->npad / LT), nbad);
     }
     hipLaunchKernelGGL(k_pgo_update, dim3((P->nv + 255) / 256), dim3(256), 0, s, (const int32_t*)(d + P->oVcol), P->nv,

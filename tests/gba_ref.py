@@ -12,7 +12,13 @@ to the reference's text and its first pass to the reference's own loops (oracle/
     SimplicialLDLT reads the lower triangle only, so W below is always "the lower block as the pass writes it".
   * The solve is the Schur complement on the keyframe blocks and a blocked dense L D L^T of the reduced system; a landmark block
     that is not positive definite after damping (an unpivoted Gauss-Jordan meets a pivot <= 0) contributes nothing and gets a
-    zero step -- the device's documented policy, where the reference's full-system LDL^T would carry non-finite values."""
+    zero step -- the device's documented policy, where the reference's full-system LDL^T would carry non-finite values.
+
+What is checked against something that is not this file: the first pass against the reference's own loops; schur_solve (both
+pass kinds, on the arc and on the ragged / gapped / tumbling inputs of tests/gba_cases.py) against a Gaussian elimination of the
+whole damped system in long double (tests/gba_dense.py, test_gba_cpu.py); expmap_se3 / logmap_se3 against the full formulas in
+long double on both sides of their 1e-6 thresholds and at theta = 2.8.  The rows of the iteration pass and the LM schedule rest
+on the reference's text alone."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,8 +55,12 @@ def inverse_se3(T):
 
 def logmap_se3(T):
     R = T[:3, :3]
-    cosine = min(1.0, max(-1.0, (R[0, 0] + R[1, 1] + R[2, 2] - 1.0) / 2.0))
-    sine = min(1.0, max(-1.0, np.sqrt(1.0 - cosine * cosine)))
+    # the clamps as comparisons, as the device and the C oracle write them: a NaN passes through both, theta is NaN, the
+    # test below fails and w stays 0 (Python's min / max would turn the NaN into -1, theta into pi and w into NaN)
+    cosine = (R[0, 0] + R[1, 1] + R[2, 2] - 1.0) / 2.0
+    cosine = 1.0 if cosine > 1.0 else -1.0 if cosine < -1.0 else cosine
+    sine = np.sqrt(1.0 - cosine * cosine)
+    sine = 1.0 if sine > 1.0 else -1.0 if sine < -1.0 else sine
     theta = np.arccos(cosine)
     w, V = np.zeros(3), np.eye(3)
     if theta > 0.000001:
@@ -297,8 +307,8 @@ def one_step(P, first, x_kf, Xw, Lw, lam):
 
 
 def gba_lm(P, x_kf, Xw, Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15):
-    """levMarquardtOptimizationGBA -> dict(trace (one dict per solve, with the state after it), iters, stop_reason, hmax, the
-    final x_kf / T / Xw / Lw)."""
+    """levMarquardtOptimizationGBA -> dict(trace (one dict per solve, with the state after it, its reduced matrix S and its
+    pose step dp), iters, stop_reason, hmax, the final x_kf / T / Xw / Lw)."""
     x = np.array(x_kf, np.float64).reshape(-1, 6).copy()
     X = np.array(Xw, np.float64).reshape(-1, 3).copy()
     Lm = np.array(Lw, np.float64).reshape(-1, 6).copy()
@@ -315,7 +325,7 @@ def gba_lm(P, x_kf, Xw, Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15):
             Lm[:] += s["dx_ls"]
         dxn = float(np.sqrt(np.sum(s["dp"] ** 2) + np.sum(s["dx_pt"] ** 2) + np.sum(s["dx_ls"] ** 2)))
         trace.append(dict(lam=lam, err_raw=err_raw, err=err, dx_norm=dxn, n_singular=s["n_singular"], n_bad_pivots=s["n_bad"],
-                          accepted=apply, x_kf=x.copy(), Xw=X.copy(), Lw=Lm.copy(), S=s["S"]))
+                          accepted=apply, x_kf=x.copy(), Xw=X.copy(), Lw=Lm.copy(), S=s["S"], dp=dp.copy()))
         return dxn
 
     with np.errstate(divide="ignore", invalid="ignore"):

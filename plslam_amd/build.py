@@ -32,7 +32,7 @@ SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_m
 # shares the other twelve objects with the product.
 LEGACY_SOURCES = ["hamming_mfma.hip", "hamming_mfma_d.hip"]
 LEGACY_AWARE = ("capi.hip", "hamming_mfma_h.hip")
-HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp",
+HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "match_tables.hpp", "match_planner.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp",
                                             "stereo_gates_dev.hpp", "pose_gn_dev.hpp", "se3_dev.hpp", "ldlt_dense_dev.hpp")] + [os.path.join(_ROOT, "include", "plslam_hip.h")]
 # -ffp-contract=off: the fp64 row kernels must execute the reference's operation order
 # (no FMA contraction) so that thresholded masks reproduce the CPU restatement bit for bit.

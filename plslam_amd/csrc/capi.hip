@@ -8,6 +8,7 @@
 #include <new>
 
 #include "common.hpp"
+#include "match_planner.hpp"
 
 namespace plslam {
 
@@ -77,49 +78,31 @@ using namespace plslam;
 // ---------------------------------------------------------------------------------------------
 struct plslam_match_plan {
     plslam_ctx* ctx = nullptr;
-    int variant = 0, block_threads = 0;
-    int32_t nprob = 0, nscan = 0, nscan_blocks = 0, nfin_blocks = 0, ncounts = 0;
-    int32_t fin_row = 0;               // > 0: the finalize table is dealt to the XCDs problem by problem, 8 rows of this length (option post_xcd 2)
-    int32_t nsym = 0, nsym_blocks = 0, nmerge_blocks = 0, sym_rows = 1;
-    bool sym_mfma = false;             // symmetric problems run on K1e (matrix cores)
-    bool sym_mfma_multi = false;       // ... and some of them have n2 > 2048 (multi-window instantiation)
-    int mfma_form = 0;                 // ctx option "mfma_form" at plan creation (0/2 = K1f, 1 = K1e)
-    bool exact_second = false;         // K1h: exact key tables (ctx option at plan creation); else the finalize kernel completes keys21 lazily
-    bool post_fused = false;           // K1h / K1i throughput plans: merge + finalize + gates in ONE kernel, a workgroup per problem (k_post_fused)
-    size_t post_lds = 0;               // ... its dynamic LDS: 8 bytes per column of the widest problem
-    bool fused = false;                // K1f, one workgroup per problem: merge + ratio + mutual inside the scan kernel
-    int merge_parts = 1;               // K1f: lanes per column in the partial merge (tall problems: many row blocks, few columns)
-    bool col_split = false;            // K1f on a FEW LARGE problems: columns cut into ranges scanned as sub-problems
-    DevBuf rowtmp;                     // ... their per-range row results (merged by the finalize kernel)
-    bool split_post = false;           // ... and everything behind the scan in ONE kernel (k_split_post): the run is two launches
-    bool split_post_ok = false;        // (what plan_build found; a gate applied by the finalize kernel switches split_post off)
-    int32_t ndir = 0, ndir_blocks = 0; // non-mutual problems on the directed form of K1e
-    bool dir_multi = false;
-    SymDesc* d_dirs = nullptr; BlockDesc* d_dir_blocks = nullptr;
+    int32_t nprob = 0;
+    PlanChoice choice;                 // what the planner decided (match_planner.hpp): scan kernels, table family, area sizes
+    PlanTables tab;                    // the launch tables it filled; tab.probs is the host image of d_probs (the gate stage patches it)
+    bool split_post = false;           // choice.split_post, until a gate applied by the finalize kernel switches it off
     DevBuf keys, counts, partials;
+    DevBuf rowtmp;                     // column-split plans: the per-range row results (merged by the finalize kernel)
     DevBuf tables;                     // all launch tables, packed, uploaded with ONE copy
     std::vector<char> staging;         // host image of `tables` (kept alive: the copy is async)
     HostBuf staging_pin;               // ... in pinned memory when pin_tables (the context's host-path plan)
     bool pin_tables = false;
-    ScanDesc* d_scans = nullptr; SymDesc* d_syms = nullptr; ProblemDesc* d_probs = nullptr;
-    BlockDesc *d_scan_blocks = nullptr, *d_sym_blocks = nullptr, *d_merge_blocks = nullptr, *d_fin_blocks = nullptr;
+    ScanDesc* d_scans = nullptr; SymDesc *d_syms = nullptr, *d_dirs = nullptr; ProblemDesc* d_probs = nullptr;
+    BlockDesc *d_scan_blocks = nullptr, *d_sym_blocks = nullptr, *d_dir_blocks = nullptr, *d_merge_blocks = nullptr, *d_fin_blocks = nullptr;
     int32_t** d_count_dst = nullptr;
     int32_t* d_counts_zero = nullptr;  // contiguous int32 counters zeroed by the first scan kernel
-    bool scatter_counts = false;       // user n_matches pointers are not one contiguous array
     // optional last stage: the stereo gates over the L<->R tables of the batch (plslam_match_plan_add_stereo_gates)
     DevBuf gate_tables;
     std::vector<char> gate_staging;
-    std::vector<ProblemDesc> h_probs;  // host image of d_probs (the gate stage patches ProblemDesc::gate)
     bool probs_in_place = false;       // d_probs IS the page-locked image
     plslam_stereo_gate_problem* d_gates = nullptr;
     BlockDesc* d_gate_blocks = nullptr;
     int32_t ngate_blocks = 0, ngates = 0;
     int32_t* d_gate_counts = nullptr;  // contiguous counters of the gate problems (or nullptr)
-    plslam_plan_info info{};
     bool profiling = false;
     // a run on one stream, captured once and replayed as a HIP graph (latency plans: a few small kernels whose launch
     // overheads are the run; option "graph")
-    bool small = false;                // fewer waves than the chip has SIMDs (plan_build)
     hipGraphExec_t graph_exec = nullptr;
     bool graph_failed = false;
     void drop_graph() { if (graph_exec) (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; graph_failed = false; }
@@ -149,529 +132,92 @@ struct plslam_match_plan {
     }
 };
 
-// n1_dev0 (internal; the map<->keyframe driver's one-synchronisation brute-force form): the row count of problem 0 lives on
-// the device, probs[0].n1 is its upper bound.  Only as a two-launch column-split plan of ONE mutual problem (K1f + k_split_post,
-// which read the count themselves); anything else returns PLSLAM_ENOTSUP and the caller takes its two-synchronisation form.
-// the context-only half of that test (the options the two-launch column-split plan cannot honour): callers ask BEFORE they
-// stage or enqueue anything for the one-synchronisation form (map2kf.hip)
-bool plslam::ctx_takes_device_row_count(const plslam_ctx* ctx)
+// the plan-relevant options of the context, the CU count and the block-table geometry of the kernels, copied once per plan
+static PlanOptions plan_options_of(const plslam_ctx* ctx)
 {
-    return (ctx->scan_variant == PLSLAM_SCAN_AUTO || ctx->scan_variant == PLSLAM_SCAN_MFMA) &&
-           (ctx->mfma_form == 0 || ctx->mfma_form == 2) && ctx->col_split != 1 && ctx->split_post != 1 && ctx->fuse != 2;
+    PlanOptions o;
+    o.cu_count = ctx->prop.multiProcessorCount;
+    o.scan_variant = ctx->scan_variant; o.scan_block = ctx->scan_block; o.sym_rows = ctx->sym_rows; o.group_cap = ctx->group_cap;
+    o.mfma_form = ctx->mfma_form; o.col_split = ctx->col_split; o.exact_second = ctx->exact_second;
+    o.split_target = ctx->split_target; o.split_min_tiles = ctx->split_min_tiles; o.split_post = ctx->split_post;
+    o.post_xcd = ctx->post_xcd; o.post_fuse = ctx->post_fuse; o.fuse = ctx->fuse;
+    o.rows_wpq = scan_rows_per_block(PLSLAM_SCAN_WAVE_PER_QUERY, 256);
+    o.rows_lpq = scan_rows_per_block(PLSLAM_SCAN_LANE_PER_QUERY, ctx->scan_block ? ctx->scan_block : 256);
+    const int lanes[3] = {1, 4, 16};
+    for (int k = 0; k < 3; ++k) { o.merge16_cols[k] = merge_partials16_cols(lanes[k]); o.fix16_cols[k] = merge_fix16_cols(lanes[k]); }
+    for (int k = 0; k < 2; ++k) { o.sym_block_rows[k] = sym_rows_per_block(lanes[k]); o.sym_partial_rows[k] = sym_rows_per_partial(lanes[k]); }
+    return o;
 }
 
+// the context-only half of the n1_dev0 test (PlanOptions::takes_device_row_count): callers ask BEFORE they stage or enqueue
+// anything for the one-synchronisation form (map2kf.hip)
+bool plslam::ctx_takes_device_row_count(const plslam_ctx* ctx) { return plan_options_of(ctx).takes_device_row_count(); }
+
+// The device half of a plan: plan_decide, the areas it sized, plan_tables over their addresses, one upload of the packed image.
+// n1_dev0 (internal; the map<->keyframe driver's one-synchronisation brute-force form): the row count of problem 0 lives on
+// the device, probs[0].n1 is its upper bound.  A plan that cannot take it returns PLSLAM_ENOTSUP and the caller takes its
+// two-synchronisation form.
 static int plan_build(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob,
                       plslam_match_plan* P, const int32_t* n1_dev0 = nullptr)
 {
-    PLSLAM_REQUIRE(nprob >= 0, PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(nprob == 0 || probs != nullptr, PLSLAM_EINVAL);
+    PlanChoice& c = P->choice;
+    PlanTables& t = P->tab;
     P->ctx = ctx;
-    P->nprob = nprob;
-
-    // AUTO: mutual problems take the symmetric scan (one distance feeds both directions) -- on the
-    // matrix cores (K1e) -- and
-    // the others its directed form (row direction only).  A forced variant applies to every problem
-    // (SYMMETRIC = the XOR+popcount form).  Measured, scan time per launch, C2 batches of 64 / 256 / 1024 /
-    // 4096 pairs: K1e 0.12 / 0.45 / 1.69 / 6.0 ms, K1b(') 0.24 / 0.78 / 2.85 / 10.9 ms.
-    // A plan too small to put one wave on every SIMD under those (e.g. ONE StVO::match call of the
-    // SLAM loop) takes the wave-per-query scan instead: 16 queries per workgroup, train tile in LDS.
-    int64_t thr_waves = 0;   // waves the throughput kernels would launch: one per 64 rows of d1
-    for (int32_t i = 0; i < nprob; ++i) thr_waves += (probs[i].n1 + 63) / 64;
-    const int64_t simds = (int64_t)ctx->prop.multiProcessorCount * 4;
-    // A plan of a FEW LARGE problems (C3: one local map against one frame, 10 000 x 1500 + 2 000 x 200, mapHandler.cpp:532-752)
-    // has too few 256-row blocks to fill the chip, but far too much work for the latency kernel (50 us there): the
-    // matrix-core scan takes it with the COLUMNS cut into ranges, one workgroup per (row block, range).
-    int64_t sym_evals = 0;
-    for (int32_t i = 0; i < nprob; ++i)
-        if (probs[i].n1 > 0 && probs[i].n2 > 0) sym_evals += (int64_t)probs[i].n1 * probs[i].n2;
-    const bool small_plan = thr_waves < simds;
-    P->small = small_plan;
     P->drop_graph();                   // (a rebuilt plan launches other tables)
-    const bool split_auto = ctx->scan_variant == PLSLAM_SCAN_AUTO && small_plan && sym_evals >= (int64_t(6) << 20) &&
-                            ctx->mfma_form != 1;
-    const bool split_forced = ctx->col_split == 2 && ctx->mfma_form != 1 &&
-                              (ctx->scan_variant == PLSLAM_SCAN_AUTO || ctx->scan_variant == PLSLAM_SCAN_MFMA);
-    P->col_split = ctx->col_split != 1 && (split_auto || split_forced);
-    if (n1_dev0) {
-        const bool can = nprob == 1 && probs[0].mutual && !probs[0].keep_prior && probs[0].n1 > 0 && probs[0].n2 > 0 &&
-                         ctx_takes_device_row_count(ctx);
-        if (!can) return PLSLAM_ENOTSUP;
-        P->col_split = true;
+    int r = plan_decide(plan_options_of(ctx), probs, nprob, n1_dev0 != nullptr, c);
+    if (r) {
+        if (c.error) set_last_error("match_planner.hpp: requirement failed: %s", c.error);
+        return r;
     }
-    const bool use_wpq = ctx->scan_variant == PLSLAM_SCAN_WAVE_PER_QUERY ||
-                         (ctx->scan_variant == PLSLAM_SCAN_AUTO && small_plan && !P->col_split);
-    const bool allow_sym = !use_wpq &&
-                           (ctx->scan_variant == PLSLAM_SCAN_AUTO || ctx->scan_variant == PLSLAM_SCAN_SYMMETRIC ||
-                            ctx->scan_variant == PLSLAM_SCAN_MFMA);
-    // mfma_form 3: a mutual problem runs as TWO DIRECTED matrix-core scans (d1 -> d2 and d2 -> d1; what the reference's two
-    // knnMatch calls evaluate) -- no column direction, no partial table, no merge kernel
-    const bool dpair = allow_sym && ctx->mfma_form == 3 &&
-                       (ctx->scan_variant == PLSLAM_SCAN_MFMA || ctx->scan_variant == PLSLAM_SCAN_AUTO);
-    auto is_sym = [&](const plslam_match_problem& p) { return allow_sym && !dpair && p.mutual && p.n1 > 0 && p.n2 > 0; };
+    P->nprob = nprob;
+    P->split_post = c.split_post;
 
-    // sym_rows 0 = auto: 4 rows of d1 per lane (4x fewer column partials, slightly faster) once the
-    // plan has enough 256-row waves for >= 6 full rounds of the chip (17 single-wave workgroups fit a
-    // CU's LDS); below that the 4x coarser work units lose more to tail quantisation than they gain
-    // (measured: 266k vs 320k pairs/s at 512 pairs, 347k vs 344k at 2048, 364k vs 347k at 4096).
-    P->sym_mfma = allow_sym && (ctx->scan_variant == PLSLAM_SCAN_MFMA || ctx->scan_variant == PLSLAM_SCAN_AUTO);
-    P->sym_mfma_multi = false;
-    P->mfma_form = ctx->mfma_form;
-    P->exact_second = ctx->exact_second != 0;
-    P->dir_multi = false;
-    // (set per scanned (sub-)problem while the tables are built)
-    P->sym_rows = P->sym_mfma ? 4 : ctx->sym_rows;      // K1e uses the 256-row tables of K1b'
-    if (P->sym_rows == 0) {
-        int64_t waves4 = 0;
-        for (int32_t i = 0; i < nprob; ++i)
-            if (is_sym(probs[i])) waves4 += (probs[i].n1 + 255) / 256;
-        P->sym_rows = waves4 >= 6 * 17 * (int64_t)ctx->prop.multiProcessorCount ? 4 : 1;
-    }
-    const bool k1f = P->sym_mfma && P->mfma_form != 1;   // K1f: column partials per 64-row block, 16-bit keys
-    // Fused form (K1f only): one workgroup per problem walks all row blocks and finishes the problem (column merge, ratio
-    // test, mutual check, count) -- ONE kernel per plan run, no merge / finalize kernels, no keys21 round trip.  Measured
-    // at C2 / 4096 pairs per step: 4.05 ms against 3.48 + 0.52 ms unfused -- the merge's VALU work (+5 %), which the
-    // separate merge kernel hides under its HBM time, and the serial tail of every workgroup cost what the two launches
-    // cost -- so AUTO does not select it; "fuse" = 2 does (it needs many more problems than the chip has workgroup slots,
-    // 3 per CU, or the 6x coarser work units lose to tail quantisation).  Mutual problems keep their merged column keys in
-    // LDS: n2 <= PLSLAM_K1F_FUSED_MAX_N2.
-    {
-        int64_t nmf = 0;
-        bool fits = true;
-        for (int32_t i = 0; i < nprob; ++i) {
-            if (probs[i].n1 <= 0 || probs[i].n2 <= 0) continue;
-            ++nmf;
-            if (probs[i].mutual && probs[i].n2 > PLSLAM_K1F_FUSED_MAX_N2) fits = false;
-            if (probs[i].keep_prior) fits = false;          // the in-kernel finalize always writes every row
-        }
-        (void)nmf;
-        P->fused = k1f && fits && ctx->fuse == 2 && !P->col_split && !dpair;
-    }
-    const int rpp = sym_rows_per_partial(P->sym_rows);   // a-rows per column partial
-    const int rps = sym_rows_per_block(P->sym_rows);     // a-rows per workgroup of the symmetric scan
-    // column split (K1f only): ranges of `cstep` columns per problem so that the launch has about 3 workgroups per CU,
-    // at least 4 tiles (128 columns) per range
-    int64_t mf_row_blocks = 0;
-    for (int32_t i = 0; i < nprob; ++i)
-        if (probs[i].n1 > 0 && probs[i].n2 > 0) mf_row_blocks += (probs[i].n1 + 255) / 256;
-    P->col_split = P->col_split && k1f && mf_row_blocks > 0 && !dpair;
-    // AUTO form: K1h for throughput plans; a column-split plan (a few large problems, e.g. C3's one map against one frame) is
-    // latency-bound -- 4-5 tiles per workgroup -- and K1f's lighter per-workgroup prologue / row finish wins there
-    // (measured at C3: 22.4 us per run against 27.4 us)
-    if (ctx->mfma_form == 0 && P->col_split) P->mfma_form = 2;
-    auto split_of = [&](const plslam_match_problem& p, int32_t* cstep) -> int32_t {
-        *cstep = 0;
-        if (!P->col_split || p.n1 <= 0 || p.n2 <= 0) return 1;
-        // (options "split_target": workgroups per CU the split aims at, 0 = 3; "split_min_tiles": tiles per range at least, 0 = 4)
-        const int64_t target = (ctx->split_target > 0 ? ctx->split_target : 3) * (int64_t)ctx->prop.multiProcessorCount;
-        const int64_t want = (target + mf_row_blocks - 1) / mf_row_blocks;
-        const int32_t tiles = (p.n2 + 31) / 32;
-        int32_t per = (int32_t)((tiles + want - 1) / want);
-        const int32_t min_tiles = ctx->split_min_tiles > 0 ? ctx->split_min_tiles : 4;
-        if (per < min_tiles) per = min_tiles;
-        const int32_t ns = (tiles + per - 1) / per;
-        if (ns <= 1) return 1;
-        *cstep = per * 32;
-        return ns;
-    };
-    {   // partial merge: share a column among several lanes when the plan has long columns and too few of them
-        int64_t cols = 0;
-        int32_t max_nwb = 0;
-        for (int32_t i = 0; i < nprob; ++i)
-            if (is_sym(probs[i])) { cols += probs[i].n2; max_nwb = std::max(max_nwb, (probs[i].n1 + 63) / 64); }
-        const int64_t lanes = 64 * 4 * (int64_t)ctx->prop.multiProcessorCount * 4;      // ~4 waves per SIMD in flight
-        P->merge_parts = (max_nwb >= 64 && cols * 16 <= lanes) ? 16 : (max_nwb >= 32 && cols * 4 <= lanes) ? 4 : 1;
-    }
-    // K1h's column partials: one word per (256-row block, column slot) -- two with exact key tables; K1f's: one word per
-    // (64-row block, column slot); rows padded to 256 slots
-    const bool h_parts = P->sym_mfma && mfma_form_is_h(P->mfma_form) && !P->fused;
-    const int mcols = h_parts ? merge_fix16_cols(P->merge_parts) : merge_partials16_cols(P->merge_parts);
-    // column partials in units of two words
-    auto part_units = [&](int32_t n1, int32_t n2) -> int64_t {
-        if (h_parts) return (int64_t)((n1 + 255) / 256) * ((n2 + 255) / 256) * (P->exact_second ? 256 : 128);
-        return (int64_t)((n1 + 63) / 64) * ((n2 + 255) / 256) * 128;
-    };
-    int64_t rows = 0, part_rows = 0, tmp_rows = 0;
-    for (int32_t i = 0; i < nprob; ++i) {
-        const plslam_match_problem& p = probs[i];
-        PLSLAM_REQUIRE(p.n1 >= 0 && p.n2 >= 0, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(p.n1 == 0 || p.d1 != nullptr, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(p.n2 == 0 || p.d2 != nullptr, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(p.n1 == 0 || p.matches_12 != nullptr, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE((reinterpret_cast<uintptr_t>(p.d1) & 3) == 0, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE((reinterpret_cast<uintptr_t>(p.d2) & 3) == 0, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(p.n2 <= PLSLAM_MAX_TRAIN_ROWS, PLSLAM_ERANGE);
-        PLSLAM_REQUIRE(!p.mutual || p.n1 <= PLSLAM_MAX_TRAIN_ROWS, PLSLAM_ERANGE);
-        rows += p.n1 + (p.mutual ? p.n2 : 0);
-        // column partials, in units of two words: K1e one (best, second) pair per (256-row block, column); K1f one word
-        // per (64-row block, column) with the rows padded to 256 columns
-        if (is_sym(p)) {
-            int32_t cstep = 0;
-            const int32_t ns = split_of(p, &cstep);
-            if (ns > 1) {
-                for (int32_t s_ = 0; s_ < ns; ++s_)
-                    part_rows += part_units(p.n1, std::min(cstep, p.n2 - s_ * cstep));
-            } else {
-                part_rows += k1f ? part_units(p.n1, p.n2) : (int64_t)((p.n1 + rpp - 1) / rpp) * p.n2;
-            }
-        }
-        if (P->sym_mfma && p.n1 > 0 && p.n2 > 0) {
-            int32_t cstep = 0;
-            const int32_t ns = split_of(p, &cstep);
-            if (ns > 1) tmp_rows += (int64_t)ns * p.n1;
-        }
-    }
-    PLSLAM_REQUIRE(rows < (int64_t(1) << 31), PLSLAM_ERANGE);
+    if ((r = P->keys.reserve(sizeof(uint32_t) * 2 * (size_t)(c.key_rows > 0 ? c.key_rows : 1)))) return r;
+    if ((r = P->partials.reserve(sizeof(uint32_t) * 2 * (size_t)(c.part_rows > 0 ? c.part_rows : 1)))) return r;
+    if (c.tmp_rows > 0 && (r = P->rowtmp.reserve(sizeof(uint32_t) * 2 * (size_t)c.tmp_rows))) return r;
+    if (!c.counts_in_place && (r = P->counts.reserve(sizeof(int32_t) * (size_t)(nprob > 0 ? nprob : 1)))) return r;
+    P->d_counts_zero = c.counts_in_place ? probs[0].n_matches : P->counts.as<int32_t>();
+    plan_tables(c, probs, {P->keys.as<uint32_t>(), P->partials.as<uint32_t>(), P->rowtmp.as<uint32_t>(), P->d_counts_zero, n1_dev0}, t);
 
-    P->variant = use_wpq ? PLSLAM_SCAN_WAVE_PER_QUERY
-                         : (allow_sym ? PLSLAM_SCAN_SYMMETRIC : PLSLAM_SCAN_LANE_PER_QUERY);
-    P->block_threads = use_wpq ? 256 : (ctx->scan_block ? ctx->scan_block : 256);
-    const int directed_variant = use_wpq ? PLSLAM_SCAN_WAVE_PER_QUERY : PLSLAM_SCAN_LANE_PER_QUERY;
-    const int rpb = scan_rows_per_block(directed_variant, P->block_threads);
-
-    int r = P->keys.reserve(sizeof(uint32_t) * 2 * (size_t)(rows > 0 ? rows : 1));
-    if (r) return r;
-    r = P->partials.reserve(sizeof(uint32_t) * 2 * (size_t)(part_rows > 0 ? part_rows : 1));
-    if (r) return r;
-    if (tmp_rows > 0 && (r = P->rowtmp.reserve(sizeof(uint32_t) * 2 * (size_t)tmp_rows))) return r;
-    uint32_t* d_tmp = P->rowtmp.as<uint32_t>();
-    uint32_t* d_keys = P->keys.as<uint32_t>();
-    uint32_t* d_part = P->partials.as<uint32_t>();
-    // #matches counters: accumulated with atomics by the finalize kernel, zeroed by the scan
-    // kernel.  If the caller's n_matches pointers form one contiguous array, count in place.
-    bool contiguous = nprob > 0, any_user = false;
-    for (int32_t i = 0; i < nprob; ++i) {
-        any_user = any_user || probs[i].n_matches != nullptr;
-        contiguous = contiguous && probs[i].n_matches != nullptr &&
-                     probs[i].n_matches == probs[0].n_matches + i;
-    }
-    int32_t* d_counts = nullptr;
-    if (contiguous) {
-        d_counts = probs[0].n_matches;
-    } else {
-        r = P->counts.reserve(sizeof(int32_t) * (size_t)(nprob > 0 ? nprob : 1));
-        if (r) return r;
-        d_counts = P->counts.as<int32_t>();
-    }
-    P->scatter_counts = any_user && !contiguous;
-    P->d_counts_zero = d_counts;
-    P->ncounts = nprob;
-
-    // A column-split plan of mutual K1f problems runs in TWO launches: k_split_post merges the column partials and decides the
-    // matches from the column side (hamming_mfma_g.hip); rows without a match keep the -1 the scan's first column range
-    // writes.  Not with kept entries (keep_prior: a rejected row's old entry goes through the consistency loop) and not with a
-    // stereo gate behind the table (add_stereo_gates switches back to merge + finalize).  Option "split_post": 0 = auto, 1 = never.
-    {
-        bool ok = P->col_split && k1f && !h_parts && !P->fused && ctx->split_post != 1 && nprob > 0;
-        for (int32_t i = 0; ok && i < nprob; ++i)
-            ok = is_sym(probs[i]) && !probs[i].keep_prior;
-        P->split_post = P->split_post_ok = ok;
-        if (n1_dev0 && !ok) return PLSLAM_ENOTSUP;
-    }
-    std::vector<ScanDesc> scans;
-    std::vector<int32_t> scan_problem;   // scans[k] belongs to problem scan_problem[k]
-    std::vector<SymDesc> syms, dirs;
-    std::vector<ProblemDesc> pds;
-    std::vector<BlockDesc> sblocks, fblocks, yblocks, mblocks, dblocks;
-    int64_t key_row = 0, part_row = 0, tmp_row = 0, evals = 0, devals = 0, abytes = 0;
-    std::vector<int32_t*> user_counts((size_t)nprob, nullptr);
-    for (int32_t i = 0; i < nprob; ++i) {
-        const plslam_match_problem& p = probs[i];
-        ProblemDesc pd{};
-        pd.n1 = p.n1; pd.n2 = p.n2; pd.nnr = p.nnr; pd.mutual = p.mutual ? 1 : 0;
-        pd.keep_prior = p.keep_prior ? 1 : 0;
-        pd.matches_12 = p.matches_12;
-        pd.n_matches = d_counts + i;
-        user_counts[i] = p.n_matches;
-        uint32_t* k12 = d_keys + 2 * key_row;
-        key_row += p.n1;
-        uint32_t* k21 = p.mutual ? d_keys + 2 * key_row : nullptr;
-        if (p.mutual) key_row += p.n2;
-        pd.keys12 = k12;
-        pd.keys21 = k21;
-        pd.d1 = p.d1; pd.d2 = p.d2;
-        pd.gate = -1;
-        const bool mf_path = P->sym_mfma && p.n1 > 0 && p.n2 > 0;    // this problem runs on K1e / K1f
-        // (finalize blocks start at multiples of 256 rows and run all 256 lanes: the lazy completion of K1h's / K1i's column keys
-        // rotates the neighbouring rows' keys through DPP within aligned groups of 16 lanes -- hamming.hip, finalize_row)
-        static_assert(256 % 16 == 0, "a finalize block must hold whole groups of 16 rows");
-        if (!(P->fused && mf_path))
-            for (int32_t r0 = 0; r0 < p.n1; r0 += 256) fblocks.push_back({i, r0});
-        int32_t cstep = 0;
-        const int32_t nsplit = mf_path ? split_of(p, &cstep) : 1;
-        if (nsplit > 1) {
-            // one sub-problem per column range: its own row results (relative column indices, merged by the finalize
-            // kernel), its own partial area, its slice of keys21
-            pd.split_tmp = d_tmp + 2 * tmp_row; pd.keys12_out = k12; pd.nsplit = nsplit; pd.cstep = cstep;
-            pd.lazy21 = p.mutual && P->sym_mfma && mfma_form_is_h(P->mfma_form) && !P->fused && !P->exact_second;
-            std::vector<SymDesc>& dst = p.mutual ? syms : dirs;
-            std::vector<BlockDesc>& dstb = p.mutual ? yblocks : dblocks;
-            for (int32_t s_ = 0; s_ < nsplit; ++s_) {
-                const int32_t c0 = s_ * cstep, n2s = std::min(cstep, p.n2 - c0);
-                SymDesc y{};
-                y.flags = ctx->exact_second ? 1 : 0;
-                y.a = p.d1; y.b = p.d2 + (size_t)c0 * 32;
-                y.keys12 = d_tmp + 2 * (tmp_row + (int64_t)s_ * p.n1);
-                y.n1 = p.n1; y.n2 = n2s;
-                if (P->split_post) { y.mutual = i + 1; y.matches_12 = s_ == 0 ? p.matches_12 : nullptr; y.n1_dev = n1_dev0; }
-                if (p.mutual) {
-                    y.keys21 = k21 + 2 * (size_t)c0;
-                    y.part21 = d_part + 2 * part_row;
-                    y.n_iblk = (p.n1 + rpp - 1) / rpp;
-                    part_row += part_units(p.n1, n2s);
-                    // (K1h's merge walks column SLOTS, 32 per tile: the table covers n2 rounded up to a tile)
-                    for (int32_t j0 = 0; j0 < ((n2s + 31) & ~31); j0 += mcols) mblocks.push_back({(int32_t)dst.size(), j0});
-                }
-                for (int32_t r0 = 0; r0 < p.n1; r0 += 256) dstb.push_back({(int32_t)dst.size(), r0});
-                if (n2s > 2048) (p.mutual ? P->sym_mfma_multi : P->dir_multi) = true;
-                dst.push_back(y);
-            }
-            tmp_row += (int64_t)nsplit * p.n1;
-            evals += (int64_t)p.n1 * p.n2;
-            devals += (p.mutual ? 2LL : 1LL) * p.n1 * p.n2;
-            abytes += p.mutual ? 2 * 32LL * (p.n1 + p.n2) + 16LL * (p.n1 + p.n2) : 32LL * (p.n1 + p.n2) + 16LL * p.n1;
-        } else if (is_sym(p)) {
-            pd.lazy21 = P->sym_mfma && mfma_form_is_h(P->mfma_form) && !P->fused && !P->exact_second;
-            SymDesc y{};
-            y.flags = ctx->exact_second ? 1 : 0;
-            y.a = p.d1; y.b = p.d2; y.keys12 = k12; y.keys21 = k21;
-            y.part21 = d_part + 2 * part_row;
-            pd.part21 = y.part21;
-            y.n1 = p.n1; y.n2 = p.n2; y.n_iblk = (p.n1 + rpp - 1) / rpp;
-            part_row += k1f ? part_units(p.n1, p.n2) : (int64_t)y.n_iblk * p.n2;
-            if (P->split_post) { y.mutual = i + 1; y.matches_12 = p.matches_12; y.n1_dev = n1_dev0; }     // (a problem of one column range)
-            if (P->fused) {
-                y.mutual = 1; y.matches_12 = p.matches_12; y.n_matches = pd.n_matches; y.nnr = p.nnr;
-                yblocks.push_back({(int32_t)syms.size(), 0});
-            } else {
-                for (int32_t r0 = 0; r0 < p.n1; r0 += rps) yblocks.push_back({(int32_t)syms.size(), r0});
-                for (int32_t c0 = 0; c0 < (k1f ? (p.n2 + 31) & ~31 : p.n2); c0 += (k1f ? mcols : 256)) mblocks.push_back({(int32_t)syms.size(), c0});
-            }
-            if (P->sym_mfma && p.n2 > 2048) P->sym_mfma_multi = true;
-            syms.push_back(y);
-            evals += (int64_t)p.n1 * p.n2;
-            devals += 2LL * p.n1 * p.n2;
-            abytes += 2 * 32LL * (p.n1 + p.n2) + 16LL * (p.n1 + p.n2);
-        } else if (P->sym_mfma && (!p.mutual || dpair) && p.n1 > 0 && p.n2 > 0) {
-            // non-mutual problem on the matrix cores: the directed form of K1e (row direction only); mfma_form 3: also the two
-            // directions of a mutual problem
-            for (int dir = 0; dir < (p.mutual ? 2 : 1); ++dir) {
-                SymDesc y{};
-                y.flags = ctx->exact_second ? 1 : 0;
-                y.a = dir ? p.d2 : p.d1; y.b = dir ? p.d1 : p.d2; y.keys12 = dir ? k21 : k12; y.keys21 = nullptr; y.part21 = nullptr;
-                y.n1 = dir ? p.n2 : p.n1; y.n2 = dir ? p.n1 : p.n2; y.n_iblk = 0;
-                if (P->fused && !p.mutual) {
-                    y.mutual = 0; y.matches_12 = p.matches_12; y.n_matches = pd.n_matches; y.nnr = p.nnr;
-                    dblocks.push_back({(int32_t)dirs.size(), 0});
-                } else {
-                    for (int32_t r0 = 0; r0 < y.n1; r0 += 256) dblocks.push_back({(int32_t)dirs.size(), r0});
-                }
-                if (y.n2 > 2048) P->dir_multi = true;
-                dirs.push_back(y);
-                evals += (int64_t)p.n1 * p.n2;
-                devals += (int64_t)p.n1 * p.n2;
-                abytes += 32LL * (p.n1 + p.n2) + 16LL * y.n1;
-            }
-        } else {
-            if (p.n1 > 0) {
-                ScanDesc sc{p.d1, p.d2, k12, p.n1, p.n2};
-                for (int32_t r0 = 0; r0 < p.n1; r0 += rpb) sblocks.push_back({(int32_t)scans.size(), r0});
-                scans.push_back(sc);
-                scan_problem.push_back(i);
-                evals += (int64_t)p.n1 * p.n2;
-                devals += (int64_t)p.n1 * p.n2;
-                abytes += 32LL * (p.n1 + p.n2) + 16LL * p.n1;
-            }
-            if (p.mutual && p.n2 > 0 && p.n1 > 0) {
-                ScanDesc sc{p.d2, p.d1, k21, p.n2, p.n1};
-                for (int32_t r0 = 0; r0 < p.n2; r0 += rpb) sblocks.push_back({(int32_t)scans.size(), r0});
-                scans.push_back(sc);
-                scan_problem.push_back(i);
-                evals += (int64_t)p.n1 * p.n2;
-                devals += (int64_t)p.n1 * p.n2;
-                abytes += 32LL * (p.n1 + p.n2) + 16LL * p.n2;
-            }
-        }
-        pds.push_back(pd);
-    }
-    // XCD-striped, longest-first block tables.  Hardware places workgroup b on XCD b % 8 and
-    // dispatches in increasing b, and the scan kernels read table entry (b % 8) * L + b / 8, so row x
-    // of the table (L entries) is XCD x's work in dispatch order.  Blocks are dealt out in GROUPS
-    // (the blocks of one problem, at most 8: they stream the same descriptor sets, so they should
-    // share one XCD's L2 at the same time), groups in descending train-stream length so that every
-    // XCD runs its long blocks (ORB) first and the short ones (LBD) fill the drain phase.  Rows are
-    // padded to equal length with no-op entries (item = -1).
-    struct Group { int64_t cost; int32_t first, count; };
-    // (Dealing the SHORT groups -- the LBD problems of a stereo batch, seven tiles of mostly memory latency -- evenly among the
-    // long ones instead of running them together at the end measured 1-3 % SLOWER, 2.62-2.70 against 2.60-2.64 ms per
-    // 4096-pair scan: round 4, option removed.)
-    auto stripe = [](std::vector<BlockDesc>& blocks, std::vector<Group> groups) {
-        std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) { return a.cost > b.cost; });
-        std::vector<BlockDesc> rows[8];
-        size_t x = 0;
-        for (const Group& g : groups) {
-            // next XCD round-robin, but prefer the currently shortest row among the next candidates
-            size_t best = x;
-            for (size_t t = 0; t < 8; ++t) {
-                const size_t c = (x + t) & 7;
-                if (rows[c].size() < rows[best].size()) best = c;
-            }
-            for (int32_t k = 0; k < g.count; ++k) rows[best].push_back(blocks[(size_t)g.first + k]);
-            x = (best + 1) & 7;
-        }
-        size_t L = 0;
-        for (auto& r : rows) L = std::max(L, r.size());
-        std::vector<BlockDesc> out(8 * L, BlockDesc{-1, 0});
-        for (size_t c = 0; c < 8; ++c)
-            for (size_t k = 0; k < rows[c].size(); ++k) out[c * L + k] = rows[c][k];
-        blocks.swap(out);
-    };
-    // group_cap: measured on MI355X (512 / 2048 pairs per step): 1 -> 321k / 343k pairs/s with 2.55 GB of
-    // HBM reads per 2048-pair launch; 2 -> 317k / 343k; >= 3 -> 310k / 335k (many waves streaming the same
-    // rows at the same moment contend for the same cache lines) with 0.67 GB of reads.  Default 2.
-    // For the 4-rows-per-lane kernel the cap is speed-neutral (364.7k / 364.9k / 364.4k / 365.9k pairs/s at
-    // cap 1 / 2 / 3 / 6), so its groups keep a whole problem together.  0 = auto.
-    const size_t group_cap = ctx->group_cap > 0 ? (size_t)ctx->group_cap : (P->sym_rows == 4 ? 8 : 2);
-    auto groups_of = [group_cap](const std::vector<BlockDesc>& blocks, auto key_of, auto cost_of) {
-        std::vector<Group> gs;
-        for (size_t i = 0; i < blocks.size();) {
-            size_t j = i;
-            while (j < blocks.size() && j - i < group_cap && key_of(blocks[j]) == key_of(blocks[i])) ++j;
-            gs.push_back({cost_of(blocks[i]), (int32_t)i, (int32_t)(j - i)});
-            i = j;
-        }
-        return gs;
-    };
-    // (fused: one entry per problem, so a group is one workgroup and its cost the whole distance matrix)
-    if (!yblocks.empty())
-        stripe(yblocks, groups_of(yblocks, [](const BlockDesc& b) { return b.item; },
-                                  [&](const BlockDesc& b) { return (int64_t)syms[b.item].n2 * (P->fused ? syms[b.item].n1 : 1); }));
-    if (!dblocks.empty())
-        stripe(dblocks, groups_of(dblocks, [](const BlockDesc& b) { return b.item; },
-                                  [&](const BlockDesc& b) { return (int64_t)dirs[b.item].n2 * (P->fused ? dirs[b.item].n1 : 1); }));
-    if (!use_wpq && !sblocks.empty())   // the two directed scans of a mutual problem are adjacent: same group key
-        stripe(sblocks, groups_of(sblocks, [&](const BlockDesc& b) { return scan_problem[b.item]; },
-                                  [&](const BlockDesc& b) { return (int64_t)scans[b.item].nt; }));
-
-    // The stage behind the scan as ONE kernel (k_post_fused): every problem a mutual one on K1h / K1i with lazy column keys,
-    // few row blocks, columns that fit the workgroup's LDS (option "post_fuse": 0 = auto, 1 = never, 2 = whenever the plan is
-    // eligible).  AUTO does NOT select it: measured at C2 / 4096 pairs it moves 0.8 GB less per step (no merged column table
-    // written and gathered back) but takes 0.335 ms against the separate kernels' 0.276 ms, and the step 2.78 against 2.71 ms --
-    // a workgroup per problem is a chain of round trips (partials -> LDS -> rows -> gates) with 2 048 problems in flight,
-    // where the separate kernels keep 8x as many independent lanes busy; the scan leaves no free registers beside it
-    // (3 x 168 of 512 per lane), so whatever runs behind it displaces scan workgroups one for one and only its own
-    // duration counts.
-    {
-        bool ok = h_parts && !P->exact_second && !P->col_split && ctx->post_fuse != 1 && nprob > 0 && scans.empty() && dirs.empty() &&
-                  (int32_t)syms.size() == nprob;
-        int32_t max_n2 = 0;
-        for (int32_t i = 0; ok && i < nprob; ++i) {
-            ok = pds[i].lazy21 && pds[i].nsplit <= 1 && pds[i].part21 != nullptr && probs[i].n2 <= POST_FUSED_MAX_N2 &&
-                 (probs[i].n1 + 255) / 256 <= POST_FUSED_MAX_ROW_BLOCKS;
-            max_n2 = std::max(max_n2, probs[i].n2);
-        }
-        ok = ok && ctx->post_fuse == 2;
-        P->post_fused = ok;
-        P->post_lds = ok ? sizeof(uint32_t) * 2 * (size_t)((max_n2 + 63) & ~63) : 0;
-    }
-    P->nscan = (int32_t)scans.size();
-    P->nscan_blocks = (int32_t)sblocks.size();
-    // option "post_xcd" = 2: the finalize table dealt to the XCDs PROBLEM BY PROBLEM (a problem's row blocks gather its column keys
-    // through one L2, and consecutive problems sit on different XCDs, so the eight of them sweep memory together): rows of equal
-    // length, no-op entries (item = -1) behind the short ones; table entry (b % 8) * row + b / 8 is workgroup b's
-    P->fin_row = 0;
-    if (ctx->post_xcd == 2 && fblocks.size() >= 64) {
-        std::vector<BlockDesc> rows[8];
-        size_t x = 0;
-        for (size_t i = 0; i < fblocks.size();) {
-            size_t j = i;
-            while (j < fblocks.size() && fblocks[j].item == fblocks[i].item) ++j;
-            size_t best = x;
-            for (size_t t = 0; t < 8; ++t) {
-                const size_t c = (x + t) & 7;
-                if (rows[c].size() < rows[best].size()) best = c;
-            }
-            for (size_t k = i; k < j; ++k) rows[best].push_back(fblocks[k]);
-            x = (best + 1) & 7;
-            i = j;
-        }
-        size_t L = 0;
-        for (auto& r_ : rows) L = std::max(L, r_.size());
-        std::vector<BlockDesc> out(8 * L, BlockDesc{-1, 0});
-        for (size_t c = 0; c < 8; ++c)
-            for (size_t k = 0; k < rows[c].size(); ++k) out[c * L + k] = rows[c][k];
-        fblocks.swap(out);
-        P->fin_row = (int32_t)L;
-    }
-    P->nfin_blocks = (int32_t)fblocks.size();
-    P->nsym = (int32_t)syms.size();
-    P->nsym_blocks = (int32_t)yblocks.size();
-    P->ndir = (int32_t)dirs.size();
-    P->ndir_blocks = (int32_t)dblocks.size();
-    P->nmerge_blocks = (int32_t)mblocks.size();
-    P->info.distance_evals = evals;      // executed
-    P->info.directed_evals = devals;     // what two directed knnMatch calls per mutual problem evaluate
-    P->info.algorithmic_bytes = abytes;  // 32(Q+T)+16Q per DIRECTED scan, however executed
-    P->info.n_scans = P->nscan + 2 * P->nsym + P->ndir;
-    P->info.scan_blocks = P->nscan_blocks + P->nsym_blocks + P->ndir_blocks;
-    P->info.scan_variant = P->nsym ? (P->sym_mfma ? PLSLAM_SCAN_MFMA : PLSLAM_SCAN_SYMMETRIC)
-                                   : (P->ndir ? PLSLAM_SCAN_MFMA : directed_variant);
-    P->info.scan_block_threads = P->nsym ? (P->sym_rows == 4 && !P->sym_mfma ? 64 : 256)
-                                         : (P->ndir ? 256 : P->block_threads);
-
-    // pack every launch table into one host image and upload it with a single copy
-    struct Piece { const void* src; size_t bytes; size_t off; };
-    Piece pc[10] = {{scans.data(), scans.size() * sizeof(ScanDesc), 0},
-                   {syms.data(), syms.size() * sizeof(SymDesc), 0},
-                   {pds.data(), pds.size() * sizeof(ProblemDesc), 0},
-                   {sblocks.data(), sblocks.size() * sizeof(BlockDesc), 0},
-                   {yblocks.data(), yblocks.size() * sizeof(BlockDesc), 0},
-                   {mblocks.data(), mblocks.size() * sizeof(BlockDesc), 0},
-                   {fblocks.data(), fblocks.size() * sizeof(BlockDesc), 0},
-                   {user_counts.data(), P->scatter_counts ? user_counts.size() * sizeof(int32_t*) : 0, 0},
-                   {dirs.data(), dirs.size() * sizeof(SymDesc), 0},
-                   {dblocks.data(), dblocks.size() * sizeof(BlockDesc), 0}};
-    size_t total = 0;
-    for (Piece& x : pc) { x.off = total; total += (x.bytes + 255) & ~size_t(255); }
-    if (total == 0) total = 256;
+    // every launch table in one host image, uploaded with a single copy
     char* stg = nullptr;
-    if (P->pin_tables && total <= (size_t(1) << 20)) {
-        if ((r = P->staging_pin.reserve(total))) return r;
+    if (P->pin_tables && t.total <= (size_t(1) << 20)) {
+        if ((r = P->staging_pin.reserve(t.total))) return r;
         stg = P->staging_pin.as<char>();
     } else {
-        P->staging.resize(total);
+        P->staging.resize(t.total);
         stg = P->staging.data();
     }
-    for (const Piece& x : pc)
+    for (const PlanTables::Piece& x : t.piece)
         if (x.bytes) memcpy(stg + x.off, x.src, x.bytes);
     // Small plans of the host-pointer path: the kernels read their launch tables (a few hundred bytes per workgroup, once)
     // straight from the page-locked image -- one copy-engine command less in front of the first kernel.  (Those callers
     // synchronise the stream before the context builds its next plan, so the image is not rewritten under a kernel.)
     char* base = nullptr;
-    if (stg == P->staging_pin.p && total <= (size_t(1) << 14)) base = static_cast<char*>(mapped_device_pointer(stg));
-    const bool tables_in_place = base != nullptr;
-    if (!tables_in_place) {
-        if ((r = P->tables.reserve(total))) return r;
+    if (stg == P->staging_pin.p && t.total <= (size_t(1) << 14)) base = static_cast<char*>(mapped_device_pointer(stg));
+    P->probs_in_place = base != nullptr;
+    if (!base) {
+        if ((r = P->tables.reserve(t.total))) return r;
         base = P->tables.as<char>();
     }
-    P->d_scans = reinterpret_cast<ScanDesc*>(base + pc[0].off);
-    P->d_syms = reinterpret_cast<SymDesc*>(base + pc[1].off);
-    P->d_probs = reinterpret_cast<ProblemDesc*>(base + pc[2].off);
-    P->d_scan_blocks = reinterpret_cast<BlockDesc*>(base + pc[3].off);
-    P->d_sym_blocks = reinterpret_cast<BlockDesc*>(base + pc[4].off);
-    P->d_merge_blocks = reinterpret_cast<BlockDesc*>(base + pc[5].off);
-    P->d_fin_blocks = reinterpret_cast<BlockDesc*>(base + pc[6].off);
-    P->d_count_dst = reinterpret_cast<int32_t**>(base + pc[7].off);
-    P->d_dirs = reinterpret_cast<SymDesc*>(base + pc[8].off);
-    P->d_dir_blocks = reinterpret_cast<BlockDesc*>(base + pc[9].off);
-    P->h_probs = pds;
-    P->probs_in_place = tables_in_place;
+    auto at = [&](int k) { return base + t.piece[k].off; };
+    P->d_scans = reinterpret_cast<ScanDesc*>(at(PlanTables::SCANS));
+    P->d_syms = reinterpret_cast<SymDesc*>(at(PlanTables::SYMS));
+    P->d_probs = reinterpret_cast<ProblemDesc*>(at(PlanTables::PROBS));
+    P->d_scan_blocks = reinterpret_cast<BlockDesc*>(at(PlanTables::SCAN_BLOCKS));
+    P->d_sym_blocks = reinterpret_cast<BlockDesc*>(at(PlanTables::SYM_BLOCKS));
+    P->d_merge_blocks = reinterpret_cast<BlockDesc*>(at(PlanTables::MERGE_BLOCKS));
+    P->d_fin_blocks = reinterpret_cast<BlockDesc*>(at(PlanTables::FIN_BLOCKS));
+    P->d_count_dst = reinterpret_cast<int32_t**>(at(PlanTables::COUNT_DST));
+    P->d_dirs = reinterpret_cast<SymDesc*>(at(PlanTables::DIRS));
+    P->d_dir_blocks = reinterpret_cast<BlockDesc*>(at(PlanTables::DIR_BLOCKS));
     P->ngate_blocks = 0;                 // a rebuilt plan (the context's host-path plan) starts without a gate stage
     P->ngates = 0;
 
     // P->staging outlives the copy (it is a member), so no synchronisation is needed here; the
     // copy is ordered before the kernels of plan_run when they use the same stream, and the public
     // plan_create synchronises once so that any stream may be used afterwards.
-    if (!tables_in_place) PLSLAM_HIP_CHECK(hipMemcpyAsync(base, stg, total, hipMemcpyHostToDevice, ctx->stream));
+    if (!P->probs_in_place) PLSLAM_HIP_CHECK(hipMemcpyAsync(base, stg, t.total, hipMemcpyHostToDevice, ctx->stream));
     return PLSLAM_OK;
 }
 
@@ -702,35 +248,34 @@ static int plan_run(plslam_match_plan* P, hipStream_t s, hipStream_t sp)
         ev = &P->evs[P->ev_used++];
         PLSLAM_HIP_CHECK(hipEventRecord(ev->e0, s));
     }
-    // the first scan kernel that runs zeroes the #matches counters
+    const PlanChoice& c = P->choice;
+    const PlanTables& t = P->tab;
+    const int nsym_blocks = (int)t.sym_blocks.size(), ndir_blocks = (int)t.dir_blocks.size(), nscan_blocks = (int)t.scan_blocks.size();
+    const int nmerge_blocks = (int)t.merge_blocks.size();
     int r;
     bool zeroed = false;               // the first scan kernel that runs zeroes the #matches counters
-    if (P->fused) {
+    if (c.fused) {
         // fused problems STORE their counts from inside the scan kernel, so the counters cannot be zeroed by that kernel's
         // first workgroup: clear them ahead of it (only problems without rows or columns keep the zero)
-        PLSLAM_HIP_CHECK(hipMemsetAsync(P->d_counts_zero, 0, sizeof(int32_t) * (size_t)P->ncounts, s));
+        PLSLAM_HIP_CHECK(hipMemsetAsync(P->d_counts_zero, 0, sizeof(int32_t) * (size_t)P->nprob, s));
         zeroed = true;
     }
-    if (P->nsym_blocks > 0) {
-        r = P->sym_mfma ? launch_scan_mfma_form(P->mfma_form, P->d_syms, P->d_sym_blocks, P->nsym_blocks, P->d_counts_zero,
-                                                zeroed ? 0 : P->ncounts, P->sym_mfma_multi, false, s, P->fused)
-                        : launch_scan_sym(P->sym_rows, P->d_syms, P->d_sym_blocks,
-                                          P->nsym_blocks, P->d_counts_zero, P->ncounts, s);
+    if (nsym_blocks > 0) {
+        r = c.sym_mfma ? launch_scan_mfma_form(c.mfma_form, P->d_syms, P->d_sym_blocks, nsym_blocks, P->d_counts_zero,
+                                               zeroed ? 0 : P->nprob, t.sym_mfma_multi, false, s, c.fused)
+                       : launch_scan_sym(c.sym_rows, P->d_syms, P->d_sym_blocks, nsym_blocks, P->d_counts_zero, P->nprob, s);
         if (r) return r;
         zeroed = true;
     }
-    if (P->ndir_blocks > 0) {
-        r = launch_scan_mfma_form(P->mfma_form, P->d_dirs, P->d_dir_blocks, P->ndir_blocks, P->d_counts_zero,
-                                  zeroed ? 0 : P->ncounts, P->dir_multi, true, s, P->fused);
+    if (ndir_blocks > 0) {
+        r = launch_scan_mfma_form(c.mfma_form, P->d_dirs, P->d_dir_blocks, ndir_blocks, P->d_counts_zero,
+                                  zeroed ? 0 : P->nprob, t.dir_multi, true, s, c.fused);
         if (r) return r;
         zeroed = true;
     }
-    if (P->nscan_blocks > 0 || !zeroed) {
-        r = launch_scan(P->ctx, P->variant == PLSLAM_SCAN_WAVE_PER_QUERY ? PLSLAM_SCAN_WAVE_PER_QUERY
-                                                                         : PLSLAM_SCAN_LANE_PER_QUERY,
-                        P->block_threads, P->d_scans,
-                        P->d_scan_blocks, P->nscan_blocks, P->d_counts_zero,
-                        zeroed ? 0 : P->ncounts, s);
+    if (nscan_blocks > 0 || !zeroed) {
+        r = launch_scan(P->ctx, c.scan_variant, c.block_threads, P->d_scans, P->d_scan_blocks, nscan_blocks, P->d_counts_zero,
+                        zeroed ? 0 : P->nprob, s);
         if (r) return r;
     }
     if (ev) PLSLAM_HIP_CHECK(hipEventRecord(ev->e1, s));   // e0..e1 = the scan kernel(s) alone
@@ -741,29 +286,30 @@ static int plan_run(plslam_match_plan* P, hipStream_t s, hipStream_t sp)
     }
 
     if (P->split_post) {
-        r = launch_split_post(P->d_syms, P->d_merge_blocks, P->nmerge_blocks, P->merge_parts, P->d_probs, s);
+        r = launch_split_post(P->d_syms, P->d_merge_blocks, nmerge_blocks, c.merge_parts, P->d_probs, s);
         if (r) return r;
-    } else if (P->post_fused) {
+    } else if (t.post_fused) {
         if (P->ngates > 0 && P->d_gate_counts) PLSLAM_HIP_CHECK(hipMemsetAsync(P->d_gate_counts, 0, sizeof(int32_t) * (size_t)P->ngates, s));
-        r = launch_post_fused(P->d_probs, P->nprob, P->ngates > 0 ? P->d_gates : nullptr, P->post_lds, s);
+        r = launch_post_fused(P->d_probs, P->nprob, P->ngates > 0 ? P->d_gates : nullptr, t.post_lds, s);
         if (r) return r;
     } else {
-    r = P->sym_mfma && mfma_form_is_h(P->mfma_form) && !P->fused
-            ? launch_merge_fix16(P->d_syms, P->d_merge_blocks, P->nmerge_blocks, P->merge_parts, P->exact_second, s, split ? P->ctx->post_workgroups : 0)
-            : P->sym_mfma && P->mfma_form != 1 ? launch_merge_partials16(P->d_syms, P->d_merge_blocks, P->nmerge_blocks, P->merge_parts, s)
-                                               : launch_merge_partials(P->d_syms, P->d_merge_blocks, P->nmerge_blocks, s);
-    if (r) return r;
-    // the gate stage: its counters are cleared first; gates over the plan's own tables run inside the finalize kernel
-    if (P->ngates > 0 && P->d_gate_counts) PLSLAM_HIP_CHECK(hipMemsetAsync(P->d_gate_counts, 0, sizeof(int32_t) * (size_t)P->ngates, s));
-    r = launch_finalize(P->d_probs, P->d_fin_blocks, P->nfin_blocks, P->ngates > 0 ? P->d_gates : nullptr, s, split ? P->ctx->post_workgroups : 0, P->ctx->post_xcd == 1, P->fin_row);
-    if (r) return r;
+        const int grid_cap = split ? P->ctx->post_workgroups : 0;
+        r = c.h_tables()     ? launch_merge_fix16(P->d_syms, P->d_merge_blocks, nmerge_blocks, c.merge_parts, c.exact_second, s, grid_cap)
+            : c.partials16() ? launch_merge_partials16(P->d_syms, P->d_merge_blocks, nmerge_blocks, c.merge_parts, s)
+                             : launch_merge_partials(P->d_syms, P->d_merge_blocks, nmerge_blocks, s);
+        if (r) return r;
+        // the gate stage: its counters are cleared first; gates over the plan's own tables run inside the finalize kernel
+        if (P->ngates > 0 && P->d_gate_counts) PLSLAM_HIP_CHECK(hipMemsetAsync(P->d_gate_counts, 0, sizeof(int32_t) * (size_t)P->ngates, s));
+        r = launch_finalize(P->d_probs, P->d_fin_blocks, (int)t.fin_blocks.size(), P->ngates > 0 ? P->d_gates : nullptr, s, grid_cap,
+                            P->ctx->post_xcd == 1, t.fin_row);
+        if (r) return r;
     }
     if (P->ngate_blocks > 0) {
         r = launch_stereo_gates(P->d_gates, P->d_gate_blocks, P->ngate_blocks, s);
         if (r) return r;
     }
     if (ev) PLSLAM_HIP_CHECK(hipEventRecord(ev->e2, s));
-    if (P->scatter_counts && (r = launch_scatter_counts(P->d_counts_zero, P->d_count_dst, P->nprob, s))) return r;
+    if (c.scatter_counts && (r = launch_scatter_counts(P->d_counts_zero, P->d_count_dst, P->nprob, s))) return r;
     if (split) {
         PLSLAM_HIP_CHECK(hipEventRecord(P->post_done, s));
         P->post_pending = true;
@@ -889,132 +435,65 @@ void plslam_ctx_destroy(plslam_ctx* ctx)
     delete ctx;
 }
 
+// every option of plslam_ctx_set_option / plslam_ctx_get_option (meanings: plslam_hip.h): a field of the context, or a
+// process-wide variable; lo > hi: read-only
+namespace {
+int g_legacy_scans = PLSLAM_BUILD_LEGACY_SCANS;
+struct OptionDesc { const char* name; int plslam_ctx::*member; int* global; int lo, hi; };
+const OptionDesc kOptions[] = {
+    {"scan_variant", &plslam_ctx::scan_variant, nullptr, PLSLAM_SCAN_AUTO, PLSLAM_SCAN_MFMA},
+    {"scan_block", &plslam_ctx::scan_block, nullptr, 0, 1024},                // (0, 256, 512 or 1024)
+    {"sym_rows", &plslam_ctx::sym_rows, nullptr, 0, 4},                       // (0, 1 or 4)
+    {"group_cap", &plslam_ctx::group_cap, nullptr, 0, 64},
+    {"mfma_form", &plslam_ctx::mfma_form, nullptr, 0, 5},                     // (a form the build lacks: PLSLAM_ENOTSUP)
+    {"legacy_scans", nullptr, &g_legacy_scans, 0, -1},                        // a fact of the build
+    {"fuse", &plslam_ctx::fuse, nullptr, 0, 2},
+    {"post_fuse", &plslam_ctx::post_fuse, nullptr, 0, 2},
+    {"exact_second", &plslam_ctx::exact_second, nullptr, 0, 1},
+    {"col_split", &plslam_ctx::col_split, nullptr, 0, 2},
+    {"graph", &plslam_ctx::graph, nullptr, 0, 2},
+    {"grid_dense", nullptr, &plslam::g_grid_dense, 0, 1},                     // the lone small matchGrid problem on one dense workgroup
+    {"zero_copy_kb", &plslam_ctx::zero_copy_kb, nullptr, -(1 << 20), 1 << 20},
+    {"post_xcd", &plslam_ctx::post_xcd, nullptr, 0, 2},
+    {"split_post", &plslam_ctx::split_post, nullptr, 0, 1},
+    {"split_target", &plslam_ctx::split_target, nullptr, 0, 64},
+    {"split_min_tiles", &plslam_ctx::split_min_tiles, nullptr, 0, 64},
+    {"post_workgroups", &plslam_ctx::post_workgroups, nullptr, 0, INT32_MAX},
+    {"pgo_solver", &plslam_ctx::pgo_solver, nullptr, 0, 1},                   // measurement tools only: 1 = the pose graph on the dense L D L^T
+};
+const OptionDesc* find_option(const char* key, bool to_write)
+{
+    for (const OptionDesc& o : kOptions)
+        if (!strcmp(key, o.name) && (!to_write || o.lo <= o.hi)) return &o;
+    set_last_error("unknown option '%s'", key);
+    return nullptr;
+}
+}  // namespace
+
 int plslam_ctx_set_option(plslam_ctx* ctx, const char* key, int value)
 {
     PLSLAM_REQUIRE(ctx && key, PLSLAM_EINVAL);
-    if (!strcmp(key, "scan_variant")) {
-        PLSLAM_REQUIRE(value >= PLSLAM_SCAN_AUTO && value <= PLSLAM_SCAN_MFMA, PLSLAM_EINVAL);
-        ctx->scan_variant = value;
-        return PLSLAM_OK;
+    const OptionDesc* o = find_option(key, true);
+    if (!o) return PLSLAM_EINVAL;
+    PLSLAM_REQUIRE(value >= o->lo && value <= o->hi, PLSLAM_EINVAL);
+    if (o->member == &plslam_ctx::scan_block) PLSLAM_REQUIRE(value == 0 || value == 256 || value == 512 || value == 1024, PLSLAM_EINVAL);
+    if (o->member == &plslam_ctx::sym_rows) PLSLAM_REQUIRE(value == 0 || value == 1 || value == 4, PLSLAM_EINVAL);
+    if (o->member == &plslam_ctx::mfma_form && !mfma_form_built(value)) {
+        set_last_error("mfma_form 1 / 3 / 4 (K1e, K1g, K1h: earlier generations of the matrix-core scan) are not in this build: "
+                       "PLSLAM_BUILD_LEGACY_SCANS=1 python -m plslam_amd.build");
+        return PLSLAM_ENOTSUP;
     }
-    if (!strcmp(key, "scan_block")) {
-        PLSLAM_REQUIRE(value == 0 || value == 256 || value == 512 || value == 1024, PLSLAM_EINVAL);
-        ctx->scan_block = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "sym_rows")) {
-        PLSLAM_REQUIRE(value == 0 || value == 1 || value == 4, PLSLAM_EINVAL);
-        ctx->sym_rows = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "group_cap")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 64, PLSLAM_EINVAL);
-        ctx->group_cap = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "mfma_form")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 5, PLSLAM_EINVAL);
-        if (!mfma_form_built(value)) {
-            set_last_error("mfma_form 1 / 3 / 4 (K1e, K1g, K1h: earlier generations of the matrix-core scan) are not in this build: "
-                           "PLSLAM_BUILD_LEGACY_SCANS=1 python -m plslam_amd.build");
-            return PLSLAM_ENOTSUP;
-        }
-        ctx->mfma_form = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "fuse")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 2, PLSLAM_EINVAL);
-        ctx->fuse = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "post_fuse")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 2, PLSLAM_EINVAL);
-        ctx->post_fuse = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "exact_second")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 1, PLSLAM_EINVAL);
-        ctx->exact_second = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "col_split")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 2, PLSLAM_EINVAL);
-        ctx->col_split = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "graph")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 2, PLSLAM_EINVAL);
-        ctx->graph = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "grid_dense")) {               // (process-wide: the lone small matchGrid problem on one dense workgroup)
-        PLSLAM_REQUIRE(value >= 0 && value <= 1, PLSLAM_EINVAL);
-        plslam::g_grid_dense = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "zero_copy_kb")) {
-        PLSLAM_REQUIRE(value >= -(1 << 20) && value <= (1 << 20), PLSLAM_EINVAL);
-        ctx->zero_copy_kb = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "post_xcd")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 2, PLSLAM_EINVAL);
-        ctx->post_xcd = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "split_post")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 1, PLSLAM_EINVAL);
-        ctx->split_post = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "split_target")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 64, PLSLAM_EINVAL);
-        ctx->split_target = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "split_min_tiles")) {
-        PLSLAM_REQUIRE(value >= 0 && value <= 64, PLSLAM_EINVAL);
-        ctx->split_min_tiles = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "post_workgroups")) {
-        PLSLAM_REQUIRE(value >= 0, PLSLAM_EINVAL);
-        ctx->post_workgroups = value;
-        return PLSLAM_OK;
-    }
-    if (!strcmp(key, "pgo_solver")) {          // measurement tools only: 1 = the pose graph on the dense L D L^T
-        PLSLAM_REQUIRE(value == 0 || value == 1, PLSLAM_EINVAL);
-        ctx->pgo_solver = value;
-        return PLSLAM_OK;
-    }
-    set_last_error("unknown option '%s'", key);
-    return PLSLAM_EINVAL;
+    (o->member ? ctx->*(o->member) : *o->global) = value;
+    return PLSLAM_OK;
 }
 
 int plslam_ctx_get_option(plslam_ctx* ctx, const char* key, int* value)
 {
     PLSLAM_REQUIRE(ctx && key && value, PLSLAM_EINVAL);
-    if (!strcmp(key, "scan_variant")) { *value = ctx->scan_variant; return PLSLAM_OK; }
-    if (!strcmp(key, "scan_block")) { *value = ctx->scan_block; return PLSLAM_OK; }
-    if (!strcmp(key, "sym_rows")) { *value = ctx->sym_rows; return PLSLAM_OK; }
-    if (!strcmp(key, "group_cap")) { *value = ctx->group_cap; return PLSLAM_OK; }
-    if (!strcmp(key, "mfma_form")) { *value = ctx->mfma_form; return PLSLAM_OK; }
-    if (!strcmp(key, "legacy_scans")) { *value = PLSLAM_BUILD_LEGACY_SCANS; return PLSLAM_OK; }     // (read-only: a fact of the build)
-    if (!strcmp(key, "post_fuse")) { *value = ctx->post_fuse; return PLSLAM_OK; }
-    if (!strcmp(key, "fuse")) { *value = ctx->fuse; return PLSLAM_OK; }
-    if (!strcmp(key, "col_split")) { *value = ctx->col_split; return PLSLAM_OK; }
-    if (!strcmp(key, "exact_second")) { *value = ctx->exact_second; return PLSLAM_OK; }
-    if (!strcmp(key, "post_workgroups")) { *value = ctx->post_workgroups; return PLSLAM_OK; }
-    if (!strcmp(key, "post_xcd")) { *value = ctx->post_xcd; return PLSLAM_OK; }
-    if (!strcmp(key, "zero_copy_kb")) { *value = ctx->zero_copy_kb; return PLSLAM_OK; }
-    if (!strcmp(key, "grid_dense")) { *value = plslam::g_grid_dense; return PLSLAM_OK; }
-    if (!strcmp(key, "split_post")) { *value = ctx->split_post; return PLSLAM_OK; }
-    if (!strcmp(key, "split_target")) { *value = ctx->split_target; return PLSLAM_OK; }
-    if (!strcmp(key, "split_min_tiles")) { *value = ctx->split_min_tiles; return PLSLAM_OK; }
-    if (!strcmp(key, "graph")) { *value = ctx->graph; return PLSLAM_OK; }
-    if (!strcmp(key, "pgo_solver")) { *value = ctx->pgo_solver; return PLSLAM_OK; }
-    set_last_error("unknown option '%s'", key);
-    return PLSLAM_EINVAL;
+    const OptionDesc* o = find_option(key, false);
+    if (!o) return PLSLAM_EINVAL;
+    *value = o->member ? ctx->*(o->member) : *o->global;
+    return PLSLAM_OK;
 }
 
 int plslam_ctx_device_info(plslam_ctx* ctx, int32_t* cu_count, int32_t* clock_khz,
@@ -1062,7 +541,7 @@ int plslam_match_plan_add_stereo_gates(plslam_match_plan* plan, const plslam_ste
     // batch) is applied by the finalize kernel itself, row by row, the moment the entry is decided (ProblemDesc::gate);
     // any other gate -- and every gate of a fused plan, which has no finalize kernel -- keeps its own workgroups
     std::vector<BlockDesc> blocks;
-    std::vector<int32_t> gate_of(plan->h_probs.size(), -1);
+    std::vector<int32_t> gate_of(plan->tab.probs.size(), -1);
     bool any_cnt = false, all_cnt = true;
     for (int32_t i = 0; i < ngates; ++i) {
         const int rc = check_stereo_gate_problem(gates[i]);
@@ -1070,9 +549,9 @@ int plslam_match_plan_add_stereo_gates(plslam_match_plan* plan, const plslam_ste
         any_cnt = any_cnt || gates[i].n_stereo != nullptr;
         all_cnt = all_cnt && gates[i].n_stereo != nullptr && gates[i].n_stereo == gates[0].n_stereo + i;
         bool in_finalize = false;
-        if (!plan->fused && gates[i].n_l > 0)
-            for (size_t k = 0; k < plan->h_probs.size(); ++k) {
-                const ProblemDesc& pd = plan->h_probs[k];
+        if (!plan->choice.fused && gates[i].n_l > 0)
+            for (size_t k = 0; k < plan->tab.probs.size(); ++k) {
+                const ProblemDesc& pd = plan->tab.probs[k];
                 if (pd.matches_12 == gates[i].matches_12 && pd.n1 == gates[i].n_l && gate_of[k] < 0) {
                     gate_of[k] = i;
                     in_finalize = true;
@@ -1092,16 +571,16 @@ int plslam_match_plan_add_stereo_gates(plslam_match_plan* plan, const plslam_ste
     plan->ngates = 0;
     plan->d_gate_counts = nullptr;
     plan->d_gates = nullptr;
-    plan->split_post = plan->split_post_ok;
+    plan->split_post = plan->choice.split_post;
     auto upload_probs = [&]() -> int {
-        if (plan->h_probs.empty()) return PLSLAM_OK;
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(plan->d_probs, plan->h_probs.data(), plan->h_probs.size() * sizeof(ProblemDesc),
+        if (plan->tab.probs.empty()) return PLSLAM_OK;
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(plan->d_probs, plan->tab.probs.data(), plan->tab.probs.size() * sizeof(ProblemDesc),
                                         plan->probs_in_place ? hipMemcpyHostToHost : hipMemcpyHostToDevice, plan->ctx->stream));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(plan->ctx->stream));
         return PLSLAM_OK;
     };
     bool had = false;
-    for (ProblemDesc& pd : plan->h_probs) { had = had || pd.gate >= 0; pd.gate = -1; }
+    for (ProblemDesc& pd : plan->tab.probs) { had = had || pd.gate >= 0; pd.gate = -1; }
     if (had) { const int rc = upload_probs(); if (rc) return rc; }
     if (ngates == 0) return PLSLAM_OK;
     // ... then the new stage: its tables first (a failed allocation returns with the consistent "no gate stage" above) ...
@@ -1117,10 +596,10 @@ int plslam_match_plan_add_stereo_gates(plslam_match_plan* plan, const plslam_ste
     PLSLAM_HIP_CHECK(hipStreamSynchronize(plan->ctx->stream));
     // ... and, last, the gate indices of the problem table together with the counters that make a run use them: a failure of
     // the upload puts the indices back (the device table then still holds -1 everywhere or is rewritten in full next time)
-    for (size_t k = 0; k < plan->h_probs.size(); ++k) plan->h_probs[k].gate = gate_of[k];
+    for (size_t k = 0; k < plan->tab.probs.size(); ++k) plan->tab.probs[k].gate = gate_of[k];
     r = upload_probs();
     if (r) {
-        for (ProblemDesc& pd : plan->h_probs) pd.gate = -1;
+        for (ProblemDesc& pd : plan->tab.probs) pd.gate = -1;
         (void)upload_probs();
         return r;
     }
@@ -1140,14 +619,14 @@ int plslam_match_plan_set_wire16(plslam_match_plan* plan, const int32_t* table32
     DeviceGuard g(plan->ctx->device);
     // only the finalize kernel (k_finalize / k_post_fused: finalize_row) stores the mirror: a fused plan decides its entries in
     // the scan kernel, a column-split plan in k_split_post
-    if (table16 && (plan->fused || plan->col_split)) {
+    if (table16 && (plan->choice.fused || plan->choice.col_split)) {
         set_last_error("plslam_match_plan_set_wire16: this plan's tables are not written by the finalize kernel");
         return PLSLAM_ENOTSUP;
     }
-    std::vector<int16_t*> mirror(plan->h_probs.size(), nullptr);
+    std::vector<int16_t*> mirror(plan->tab.probs.size(), nullptr);
     if (table16)
-        for (size_t k = 0; k < plan->h_probs.size(); ++k) {
-            const ProblemDesc& pd = plan->h_probs[k];
+        for (size_t k = 0; k < plan->tab.probs.size(); ++k) {
+            const ProblemDesc& pd = plan->tab.probs[k];
             if (pd.n1 <= 0 || pd.matches_12 < table32 || pd.matches_12 >= table32 + n_entries) continue;
             PLSLAM_REQUIRE((size_t)(pd.matches_12 - table32) + (size_t)pd.n1 <= n_entries, PLSLAM_EINVAL);
             PLSLAM_REQUIRE(pd.n2 <= 32768, PLSLAM_EINVAL);
@@ -1161,9 +640,9 @@ int plslam_match_plan_set_wire16(plslam_match_plan* plan, const int32_t* table32
         }
     PLSLAM_HIP_CHECK(hipDeviceSynchronize());               // (as add_stereo_gates: rare, so it waits for whatever is in flight)
     if (plan->graph_exec) plan->drop_graph();
-    for (size_t k = 0; k < plan->h_probs.size(); ++k) plan->h_probs[k].matches_16 = mirror[k];
-    if (!plan->h_probs.empty()) {
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(plan->d_probs, plan->h_probs.data(), plan->h_probs.size() * sizeof(ProblemDesc),
+    for (size_t k = 0; k < plan->tab.probs.size(); ++k) plan->tab.probs[k].matches_16 = mirror[k];
+    if (!plan->tab.probs.empty()) {
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(plan->d_probs, plan->tab.probs.data(), plan->tab.probs.size() * sizeof(ProblemDesc),
                                         plan->probs_in_place ? hipMemcpyHostToHost : hipMemcpyHostToDevice, plan->ctx->stream));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(plan->ctx->stream));
     }
@@ -1179,7 +658,7 @@ int plslam_match_plan_run(plslam_match_plan* plan, void* stream)
     // launches are captured once on the caller's stream and replayed with one hipGraphLaunch.  Not while profiling (the
     // events belong to the run), not for a plan with a split run pending (its ordering event is not part of the graph).
     const int gopt = plan->ctx->graph;
-    if (gopt != 1 && (gopt == 2 || plan->small) && !plan->profiling && !plan->post_pending && !plan->graph_failed) {
+    if (gopt != 1 && (gopt == 2 || plan->choice.small) && !plan->profiling && !plan->post_pending && !plan->graph_failed) {
         if (!plan->graph_exec) {
             hipGraph_t gr = nullptr;
             if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -1208,7 +687,7 @@ int plslam_match_plan_run_split(plslam_match_plan* plan, void* scan_stream, void
     // A fused plan (option "fuse" = 2) writes matches_12 and the counts from inside its scan kernel: there is no stage behind
     // the scan whose completion could order the caller's consumers against the plan's NEXT scan, so such a plan is not
     // split -- everything goes to the scan stream, where stream order does it.
-    if (plan->fused) return plan_run(plan, s, s);
+    if (plan->choice.fused) return plan_run(plan, s, s);
     return plan_run(plan, s, post_stream ? static_cast<hipStream_t>(post_stream) : s);
 }
 
@@ -1246,7 +725,7 @@ int plslam_match_plan_elapsed(plslam_match_plan* plan, double* scan_ms, double* 
 int plslam_match_plan_info(plslam_match_plan* plan, plslam_plan_info* info)
 {
     PLSLAM_REQUIRE(plan && info, PLSLAM_EINVAL);
-    *info = plan->info;
+    *info = plan->tab.info;
     return PLSLAM_OK;
 }
 
@@ -1258,7 +737,7 @@ int plslam_match_plan_dump(plslam_match_plan* plan, void* keys_out, size_t keys_
     DeviceGuard g(plan->ctx->device);
     (void)hipDeviceSynchronize();
     if (plan->split_post) {            // the two-launch form leaves the rows' merged pairs unwritten: complete them here
-        (void)launch_split_rows_dump(plan->d_probs, plan->d_fin_blocks, plan->nfin_blocks, plan->ctx->stream);
+        (void)launch_split_rows_dump(plan->d_probs, plan->d_fin_blocks, (int)plan->tab.fin_blocks.size(), plan->ctx->stream);
         (void)hipDeviceSynchronize();
     }
     *keys_bytes = plan->keys.cap;
@@ -1281,9 +760,8 @@ void plslam_match_plan_destroy(plslam_match_plan* plan)
 int plslam_match_plan_key_state(plslam_match_plan* plan, int32_t* flags)
 {
     if (!plan || !flags) return PLSLAM_EINVAL;
-    const bool h = plan->sym_mfma && mfma_form_is_h(plan->mfma_form) && !plan->fused;
-    *flags = (h && !plan->exact_second ? PLSLAM_KEYS_ROW_SECOND_INDEX_INEXACT | PLSLAM_KEYS_COLUMN_SECOND_LAZY : 0) |
-             (plan->post_fused ? PLSLAM_KEYS_COLUMNS_NOT_IN_MEMORY : 0);
+    *flags = (plan->choice.lazy_keys() ? PLSLAM_KEYS_ROW_SECOND_INDEX_INEXACT | PLSLAM_KEYS_COLUMN_SECOND_LAZY : 0) |
+             (plan->tab.post_fused ? PLSLAM_KEYS_COLUMNS_NOT_IN_MEMORY : 0);
     return PLSLAM_OK;
 }
 
@@ -2054,12 +1532,12 @@ int plslam_match_plan_step_gather(plslam_match_plan* plan, const plslam_gather_s
         PLSLAM_HIP_CHECK(hipStreamWaitEvent(sp, plan->gather_done, 0));
         plan->gather_pending = false;
     }
-    int r = plan->fused ? plan_run(plan, ss, ss) : plan_run(plan, ss, sp);
+    int r = plan->choice.fused ? plan_run(plan, ss, ss) : plan_run(plan, ss, sp);
     if (r) return r;
-    hipStream_t last = plan->fused ? ss : sp;             // the stream the table is complete on
+    hipStream_t last = plan->choice.fused ? ss : sp;             // the stream the table is complete on
     if (sc != last) {
         // (post_done is recorded by a split run; a fused plan's table is complete on the scan stream)
-        if (plan->fused) {
+        if (plan->choice.fused) {
             if (!plan->post_done) PLSLAM_HIP_CHECK(hipEventCreateWithFlags(&plan->post_done, hipEventDisableTiming));
             PLSLAM_HIP_CHECK(hipEventRecord(plan->post_done, ss));
         }

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "match_tables.hpp"   // ScanDesc, SymDesc, ProblemDesc, BlockDesc: the launch tables (no HIP header in there)
 #include "plslam_hip.h"
 
 namespace plslam {
@@ -121,7 +122,7 @@ struct plslam_ctx {
     hipDeviceProp_t prop;
     int scan_variant = PLSLAM_SCAN_AUTO;
     int scan_block = 0;  // 0 = variant default
-    int group_cap = 0;   // blocks of one problem kept together on one XCD; 0 = auto (capi.hip, `stripe`)
+    int group_cap = 0;   // blocks of one problem kept together on one XCD; 0 = auto (match_planner.hpp, deal_to_xcds)
     int sym_rows = 0;    // rows of d1 per lane in the symmetric scan: 0 = auto, 1, 4
     int mfma_form = 0;   // matrix-core scan: 0 = auto (= 5), 1 = exact push per tile (K1e), 2 = grouped rows (K1f), 3 = directed pairs (K1g), 4 = grouped both ways (K1h), 5 = K1h with the M-tiles pipelined against each other (K1i)
     int col_split = 0;   // K1f, few large problems: 0 = auto (cut the columns into ranges when the plan cannot fill the chip), 1 = never, 2 = always
@@ -180,13 +181,6 @@ constexpr uint32_t KEY_IDX_BITS = 23;
 constexpr uint32_t KEY_IDX_MASK = (1u << KEY_IDX_BITS) - 1u;
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;
 
-struct ScanDesc {       // one directed scan: every query row against every train row
-    const uint8_t* q;   // nq x 32
-    const uint8_t* t;   // nt x 32
-    uint32_t* keys;     // nq x 2 composite keys (best, second best)
-    int32_t nq, nt;
-};
-
 // ---- K1h (hamming_mfma_h.hip): the layout of b over (tile, class): class-major inside groups of 16 tiles of 32 rows ------
 // full groups: 512 rows each; the ragged rest (n2 mod 512 rows) is one more group of S = ceil(rest / 32) tiles with S rows per
 // class.  Column slot of the partial table = 32 tile + class.
@@ -214,74 +208,18 @@ struct MhLayout {
     __host__ __device__ int slots_padded() const { return (32 * ntiles + 255) & ~255; }     // slots per row of the partial table
 };
 
-struct ProblemDesc {    // one StVO::match problem = scan12 (+ scan21 when mutual)
-    const uint32_t* keys12;
-    const uint32_t* keys21;  // nullptr when !mutual
-    int32_t* matches_12;
-    int32_t* n_matches;      // may be nullptr
-    int32_t n1, n2;
-    float nnr;
-    int32_t mutual;
-    // column-split problems (K1f, capi.hip): the row results arrive as `nsplit` tables [nsplit][n1][2] with column indices
-    // relative to ranges of `cstep` columns; the finalize kernel merges them on the fly (and stores the merged pair to
-    // keys12_out for diagnostics).  nsplit <= 1: keys12 is final.
-    const uint32_t* split_tmp;
-    uint32_t* keys12_out;
-    int32_t nsplit, cstep;
-    // plslam_match_problem.keep_prior: rows the ratio test rejects keep what matches_12 holds (stvo-pl's resize())
-    int32_t keep_prior;
-    // K1h plans: keys21[j] = (best row, best row OUTSIDE the best row's aligned group of 16 rows of d1): the exact second best
-    // is recomputed here, and only for the columns a row actually points at (15 XOR + popcount distances from d1 / d2)
-    int32_t lazy21;
-    const uint8_t* d1;
-    const uint8_t* d2;
-    // index of the stereo-gate problem that consumes this table (plslam_match_plan_add_stereo_gates), or -1: the finalize
-    // kernel applies the gate to a row's match the moment it is decided -- no second launch, no second pass over the table
-    int32_t gate, pad2;
-    // K1h / K1i plans with the fused stage behind the scan (k_post_fused): the problem's column partials -- [row block][slot]
-    // words, SymDesc::part21 -- or nullptr
-    const uint32_t* part21;
-    // plslam_match_plan_set_wire16: the int16 mirror of matches_12 (the gather's wire format), or nullptr
-    int16_t* matches_16;
-};
-
-struct BlockDesc {      // one workgroup's slice of a scan / problem
-    int32_t item;       // scan or problem index
-    int32_t row0;       // first query row of this workgroup
-};
-
 // launches (all asynchronous on `s`)
 int launch_scan(const plslam_ctx* ctx, int variant, int block_threads, const ScanDesc* d_scans,
                 const BlockDesc* d_blocks, int nblocks, int32_t* d_zero, int nzero, hipStream_t s);
 int launch_finalize(const ProblemDesc* d_probs, const BlockDesc* d_blocks, int nblocks,
                     const plslam_stereo_gate_problem* d_gates, hipStream_t s, int grid_cap = 0, bool xcd_chunks = false, int dealt_row = 0);
 // K2' (hamming.hip): merge of K1h's / K1i's column partials + finalize + gates, one workgroup per problem; lds_bytes = 8 x the
-// largest n2 of the plan
-constexpr int POST_FUSED_MAX_N2 = 4096;
-constexpr int POST_FUSED_MAX_ROW_BLOCKS = 16;
+// largest n2 of the plan (POST_FUSED_MAX_*: match_tables.hpp)
 int launch_post_fused(const ProblemDesc* d_probs, int nprob, const plslam_stereo_gate_problem* d_gates, size_t lds_bytes,
                       hipStream_t s);
 int launch_scatter_counts(const int32_t* d_src, int32_t* const* d_dst, int32_t n, hipStream_t s);
 int launch_unpack_keys(const uint32_t* d_keys, int32_t n, int32_t* d_idx, int32_t* d_dist,
                        hipStream_t s);
-// symmetric scan: one mutual problem = one (a x b) distance matrix feeding both directions
-struct SymDesc {
-    const uint8_t* a;       // n1 rows: one per lane
-    const uint8_t* b;       // n2 rows: streamed
-    uint32_t* keys12;       // n1 x 2   row results (complete)
-    uint32_t* keys21;       // n2 x 2   column results (written by the merge kernel)
-    uint32_t* part21;       // [n_iblk][n2][2] column partials per 64-row block of a
-    int32_t n1, n2;
-    int32_t n_iblk;
-    int32_t mutual;         // fused form (K1f, one workgroup per problem): ratio + mutual finalize happen in the scan kernel
-    int32_t* matches_12;    //   n1 match-table entries (nullptr: not fused)
-    int32_t* n_matches;     //   one counter, STORED (not accumulated) by the problem's workgroup; may be nullptr
-    float nnr;
-    int32_t flags;          // bit 0 (K1h): the INDEX of the second-best row key must be exact too (knnMatch output, key dumps)
-    // K1f, two-launch column-split plans only (the brute-force map<->keyframe driver in one synchronisation, map2kf.hip): the
-    // number of rows of a lives on the DEVICE (*n1_dev <= n1; n1 is the bound the tables and the launch are sized for), or nullptr
-    const int32_t* n1_dev;
-};
 // rows_per_lane: 1 (K1b: 256-thread workgroups, 64 a-rows per wave) or 4 (K1b': 64-thread
 // workgroups, 256 a-rows per wave).  sym_rows_per_block() = a-rows covered by one BlockDesc.
 int sym_rows_per_block(int rows_per_lane);
@@ -298,7 +236,6 @@ int launch_scan_sym_mfma(const SymDesc* d_sym, const BlockDesc* d_blocks, int nb
 // fused: one block-table entry per PROBLEM (row0 = 0); the workgroup walks the problem's row blocks itself, then merges the
 // column partials and applies the ratio test + mutual check (SymDesc::matches_12 / n_matches / nnr / mutual): no merge
 // kernel, no finalize kernel, no counter zeroing for these problems.  Mutual problems need n2 <= PLSLAM_K1F_FUSED_MAX_N2.
-constexpr int PLSLAM_K1F_FUSED_MAX_N2 = 4096;
 int launch_scan_sym_mfma_g(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero,
                            int nzero, bool multi_window, bool directed, bool fused, hipStream_t s);
 // parts: lanes sharing one column (1, 4 or 16); the block table has one entry per merge_partials16_cols(parts) columns
@@ -311,7 +248,6 @@ int launch_split_rows_dump(const ProblemDesc* d_probs, const BlockDesc* d_fin_bl
 // workgroups than 256-row blocks alone give; the per-range row results are merged by the finalize kernel: ProblemDesc.)
 // K1h (hamming_mfma_h.hip): K1f's contract and partial table; minimum-only bookkeeping in both directions, class-major layouts;
 // its partials need launch_merge_fix16 (merge + second-best recomputation), same block table as launch_merge_partials16
-inline bool mfma_form_is_h(int form) { return form == 0 || form == 4 || form == 5; }      // 0 = auto (= 5); K1h's tables: K1h and K1i
 int launch_scan_sym_mfma_h(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero, int nzero,
                            bool directed, hipStream_t s);
 // K1i (hamming_mfma_i.hip): K1h with the two M-tiles of a wave pipelined against each other; same tables, same merge kernel
@@ -322,13 +258,6 @@ int launch_merge_fix16(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblo
 int mh_slot_of_column(int n2, int j);
 // K1g (hamming_mfma_d.hip): the directed scan, one item per (directed scan, 256-row block of a); any n2 (windows inside)
 int launch_scan_dir_mfma(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero, int nzero, hipStream_t s);
-// PLSLAM_BUILD_LEGACY_SCANS (plslam_amd/build.py; default 0): the earlier generations of the matrix-core scan -- K1e
-// (hamming_mfma.hip, mfma_form 1), K1g (hamming_mfma_d.hip, 3) and K1h's scan kernel (hamming_mfma_h.hip, 4) -- are compiled in.
-// AUTO never picks them; without them plslam_ctx_set_option("mfma_form", 1 | 3 | 4) returns PLSLAM_ENOTSUP.
-#ifndef PLSLAM_BUILD_LEGACY_SCANS
-#define PLSLAM_BUILD_LEGACY_SCANS 0
-#endif
-inline bool mfma_form_built(int form) { return PLSLAM_BUILD_LEGACY_SCANS || form == 0 || form == 2 || form == 5; }
 inline int launch_scan_mfma_form(int form, const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero,
                                  int nzero, bool multi_window, bool directed, hipStream_t s, bool fused = false)
 {

@@ -29,11 +29,12 @@ def ratio(c, n):
         return float(np.float64(100.0 * c) / np.float64(n))
 
 
-def colpiv_qr_solve(H, g):
+def colpiv_qr_solve(H, g, log=None):
     """Eigen::ColPivHouseholderQR<MatrixXd>(H).solve(g) (ColPivHouseholderQR.h computeInPlace / _solve_impl, Eigen 3.3-3.4):
     column pivoting on the largest updated norm (first index on ties), Householder reflections as makeHouseholder builds
     them, the LAPACK norm downdate, the rank cut at (max col norm * eps)^2 / rows * (rows - k), and a column-major back
-    substitution that skips zero right-hand entries (so H = 0, g = 0 gives x = 0)."""
+    substitution that skips zero right-hand entries (so H = 0, g = 0 gives x = 0).  log: a list that receives one
+    dict(tr=the transposition list, rank=, recomputes=how often the downdate recomputed a norm) per call."""
     n = 6
     A = np.array(H, dtype=np.float64).reshape(6, 6).copy()
     nd = np.array([math.sqrt(float(np.sum(A[:, j] * A[:, j]))) for j in range(n)])
@@ -45,6 +46,7 @@ def colpiv_qr_solve(H, g):
     th_help = (maxn * EPS) * (maxn * EPS) / n
     down_th = math.sqrt(EPS)
     nz = n
+    recomputes = 0
     tr = [0] * n
     hc = np.zeros(n)
     for k in range(n):
@@ -89,12 +91,15 @@ def colpiv_qr_solve(H, g):
                 if t * (q * q) <= down_th:
                     nd[j] = math.sqrt(float(np.sum(A[k + 1:, j] * A[k + 1:, j])))
                     nu[j] = nd[j]
+                    recomputes += 1
                 else:
                     nu[j] *= math.sqrt(t)
     perm = list(range(n))
     for k in range(n):
         perm[k], perm[tr[k]] = perm[tr[k]], perm[k]
     x = np.zeros(n)
+    if log is not None:
+        log.append(dict(tr=tuple(int(b) for b in tr), rank=int(nz), recomputes=recomputes))
     if nz == 0:
         return x, nz
     c = np.array(g, dtype=np.float64).reshape(6).copy()
@@ -117,12 +122,14 @@ def colpiv_qr_solve(H, g):
     return x, nz
 
 
-def lu_inverse(H):
+def lu_inverse(H, log=None):
     """Eigen's Matrix6d::inverse() = PartialPivLU(H).inverse(): partial pivoting (first largest |a|), no division when the
-    pivot column is zero; a zero pivot gives inf / NaN entries, as in Eigen."""
+    pivot column is zero; a zero pivot gives inf / NaN entries, as in Eigen.  log: a list that receives one
+    dict(swaps=[p - k: how far below row k its pivot row lay], zero_pivot=a pivot column was zero) per call."""
     A = np.array(H, dtype=np.float64).reshape(6, 6).copy()
     n = 6
     perm = []
+    zero_pivot = False
     with np.errstate(all="ignore"):
         for k in range(n):
             p = k + int(np.argmax(np.abs(A[k:, k]))) if not np.isnan(A[k:, k]).any() else k
@@ -132,6 +139,8 @@ def lu_inverse(H):
                 if p != k:
                     A[[k, p]] = A[[p, k]]
                 A[k + 1:, k] /= A[k, k]
+            else:
+                zero_pivot = True
             A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:])
         inv = np.zeros((n, n))
         for col in range(n):
@@ -144,13 +153,15 @@ def lu_inverse(H):
             for i in range(n - 1, -1, -1):
                 b[i] = (b[i] - float(np.dot(A[i, i + 1:], b[i + 1:]))) / A[i, i]
             inv[:, col] = b
+    if log is not None:
+        log.append(dict(swaps=[int(p - k) for k, p in enumerate(perm)], zero_pivot=zero_pivot))
     return inv
 
 
-def cov_max_eig(H):
+def cov_max_eig(H, log=None):
     """DT_cov = H.inverse(); SelfAdjointEigenSolver(DT_cov).eigenvalues()(5) (:3880-3884; the solver reads the lower
     triangle).  NaN when the inverse is not finite."""
-    inv = lu_inverse(H)
+    inv = lu_inverse(H, log)
     if not np.isfinite(inv).all():
         return float("nan")
     return float(np.linalg.eigvalsh(inv, UPLO="L")[-1])
@@ -176,9 +187,10 @@ def line_residuals(cam, T, sPeP, le_obs):
     return np.sqrt(out[0] * out[0] + out[1] * out[1])
 
 
-def relpose_robust_gn(prm, cam, P, pl_obs, sPeP, le_obs, accumulate=None):
+def relpose_robust_gn(prm, cam, P, pl_obs, sPeP, le_obs, accumulate=None, log=None):
     """computeRelativePoseRobustGN (:3566-3957) on lc_points (P, pl_obs) / lc_lines (sPeP, le_obs), all inlier on entry.
-    `accumulate(T, pt_inl, ls_inl) -> (H, g, e_sum, (N_p, N_l))` defaults to the oracle's C restatement of :3595-3689."""
+    `accumulate(T, pt_inl, ls_inl) -> (H, g, e_sum, (N_p, N_l))` defaults to the oracle's C restatement of :3595-3689.
+    log: a dict whose lists "qr" and "lu" receive what colpiv_qr_solve and lu_inverse report, in call order."""
     P, pl_obs = np.asarray(P, np.float64).reshape(-1, 3), np.asarray(pl_obs, np.float64).reshape(-1, 2)
     sPeP, le_obs = np.asarray(sPeP, np.float64).reshape(-1, 6), np.asarray(le_obs, np.float64).reshape(-1, 3)
     pt_inl = np.ones(P.shape[0], np.uint8)
@@ -203,7 +215,7 @@ def relpose_robust_gn(prm, cam, P, pl_obs, sPeP, le_obs, accumulate=None):
             if abs(e - err_prev) < EPS or e < EPS:                       # :3682
                 stops[stage] = "err_change" if abs(e - err_prev) < EPS else "err_small"
                 break
-            x, _ = colpiv_qr_solve(H, g)                                 # :3686-3687
+            x, _ = colpiv_qr_solve(H, g, None if log is None else log.setdefault("qr", []))    # :3686-3687
             T = T @ O.inverse_se3(O.expmap_se3(x))                       # :3688
             trace[-1]["x"] = x
             if math.sqrt(float(np.sum(x * x))) < EPS:                    # :3691
@@ -218,7 +230,7 @@ def relpose_robust_gn(prm, cam, P, pl_obs, sPeP, le_obs, accumulate=None):
             ls_inl[np.flatnonzero(ls_inl)[rl > CHI]] = 0
     x_inc = O.logmap_se3(T)                                             # :3874
     ok_res = e < prm["lc_res"]                                           # :3879
-    eig = cov_max_eig(H)                                                 # :3881-3885
+    eig = cov_max_eig(H, None if log is None else log.setdefault("lu", []))              # :3881-3885
     ok_unc = eig < prm["lc_unc"]
     N = P.shape[0] + sPeP.shape[0]
     n_inl = int(pt_inl.sum()) + int(ls_inl.sum())
@@ -246,9 +258,9 @@ def correspondences(m12, idx0, idx1):
     return np.stack([a, i1, b, i2], axis=1).astype(np.int32).reshape(-1, 4)
 
 
-def is_loop_closure(prm, cam, kf0, kf1):
+def is_loop_closure(prm, cam, kf0, kf1, log=None):
     """isLoopClosure(kf0, kf1) (:3192-3300) -> dict (the fields of plslam_lc_result, the correspondence rows and masks, the
-    match tables, and the GN trace)"""
+    match tables, and the GN trace).  log: see relpose_robust_gn"""
     out = {}
     n_pt_0, n_pt_1 = len(kf0["P"]), len(kf1["P"])
     n_ls_0, n_ls_1 = len(kf0["sPeP"]), len(kf1["sPeP"])
@@ -283,7 +295,7 @@ def is_loop_closure(prm, cam, kf0, kf1):
     pl = np.asarray(kf1["pl"], np.float64).reshape(-1, 2)[pc[:, 3]]
     S = np.asarray(kf0["sPeP"], np.float64).reshape(-1, 6)[lc[:, 1]]
     le = np.asarray(kf1["le"], np.float64).reshape(-1, 3)[lc[:, 3]]
-    out.update(relpose_robust_gn(prm, cam, P, pl, S, le))
+    out.update(relpose_robust_gn(prm, cam, P, pl, S, le, log=log))
     out["corr_inputs"] = (P, pl, S, le)
     return out
 
@@ -293,3 +305,82 @@ def reference_outputs(r):
     if r["is_lc"]:
         return r["pt_corr"][r["pt_inlier"]], r["ls_corr"][r["ls_inlier"]]
     return r["pt_corr"], r["ls_corr"]
+
+
+# ---- the first Gauss-Newton system in long double ------------------------------------------------------------------------
+LD = np.longdouble
+
+
+def _jac6_ld(fgz2, a, b, gx, gy, gz):
+    return np.array([+fgz2 * a * gz, +fgz2 * b * gz, -fgz2 * (gx * a + gy * b),
+                     -fgz2 * (gx * gy * a + gy * gy * b + gz * gz * b), +fgz2 * (gx * gx * a + gz * gz * a + gx * gy * b),
+                     +fgz2 * (gx * gz * b - gy * gz * a)], LD)
+
+
+def first_system_ld(cam, th, P, pl, S, le, with_scale=False):
+    """H, g and e of the first iteration (:3595-3689 at T_inc = I, every row an inlier) in np.longdouble (64-bit mantissa on
+    x86-64), row by row as the source writes them: a point's err = project(P) - pl_obs, a line's err = (l . sp, l . ep), the
+    Jacobian of ||err|| with gz^2 and ||err|| clamped from below by std::max(homog_th, .), Cauchy weight 1 / (1 + ||err||^2),
+    H += J J^T w, g += J ||err|| w, e += ||err||^2 w, and e /= N_l + N_p (:3679) -- what plslam_lc_result holds in H, g, e
+    after max_iters = 1, max_iters_ref = 0.  with_scale: also (sum of |term| per entry of H, of g): the scale of the rounding
+    error of any fp64 summation order of these terms."""
+    th = LD(th)
+    fx, fy, cx, cy = LD(cam.fx), LD(cam.fy), LD(cam.cx), LD(cam.cy)
+    H, g, e = np.zeros((6, 6), LD), np.zeros(6, LD), LD(0)
+    Ha, ga = np.zeros((6, 6), LD), np.zeros(6, LD)
+    P, pl = np.asarray(P, np.float64).reshape(-1, 3).astype(LD), np.asarray(pl, np.float64).reshape(-1, 2).astype(LD)
+    S, le = np.asarray(S, np.float64).reshape(-1, 6).astype(LD), np.asarray(le, np.float64).reshape(-1, 3).astype(LD)
+
+    def clamp(x):                                   # std::max(th, x) = th < x ? x : th
+        return x if th < x else th
+
+    def fold(J, r):
+        nonlocal H, g, e, Ha, ga
+        w = LD(1) / (LD(1) + r * r)
+        H += np.outer(J, J) * w
+        g += J * r * w
+        e += r * r * w
+        Ha += np.abs(np.outer(J, J) * w)
+        ga += np.abs(J * r * w)
+
+    for X, o in zip(P, pl):
+        dx, dy = cx + fx * X[0] / X[2] - o[0], cy + fy * X[1] / X[2] - o[1]
+        r = np.sqrt(dx * dx + dy * dy)
+        fold(_jac6_ld(fx / clamp(X[2] * X[2]), dx, dy, X[0], X[1], X[2]) / clamp(r), r)
+    for Q, l in zip(S, le):
+        A, B = Q[:3], Q[3:]
+        ds = l[0] * (cx + fx * A[0] / A[2]) + l[1] * (cy + fy * A[1] / A[2]) + l[2]
+        de = l[0] * (cx + fx * B[0] / B[2]) + l[1] * (cy + fy * B[1] / B[2]) + l[2]
+        r = np.sqrt(ds * ds + de * de)
+        Js = _jac6_ld(fx / clamp(A[2] * A[2]), l[0], l[1], A[0], A[1], A[2])
+        Je = _jac6_ld(fx / clamp(B[2] * B[2]), l[0], l[1], B[0], B[1], B[2])
+        fold((Js * ds + Je * de) / clamp(r), r)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = e / LD(P.shape[0] + S.shape[0])
+    return (H, g, e, (Ha, ga)) if with_scale else (H, g, e)
+
+
+def system_distance(H, g, e, ld):
+    """How far an fp64 first system (H, g, e) lies from first_system_ld(..., with_scale=True): the largest
+    |entry - long double| / sum of |term| over the entries of H and g, and |e - long double| / e (e's terms are positive)"""
+    Hl, gl, el, (Ha, ga) = ld
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.concatenate([(np.abs(np.asarray(H, np.float64).reshape(6, 6).astype(LD) - Hl) / Ha).ravel(),
+                            np.abs(np.asarray(g, np.float64).reshape(6).astype(LD) - gl) / ga, [abs(LD(e) - el) / el]])
+    d = np.where(np.isnan(d), LD(0), d)             # 0 / 0: an entry without a term (H = 0 of a pair at rest)
+    return float(np.max(d))
+
+
+def dmax_sides(cam, th, T, P, pl_obs, sPeP, le_obs):
+    """Which argument std::max(homog_th, .) returns in the rows of one system at T: per call site the number of rows that
+    take (homog_th, the computed value) -- gz^2 of a point (:3607), gz^2 of a line's end points, ||err|| of a point (:3617),
+    ||err|| of a line"""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    G = P @ T[:3, :3].T + T[:3, 3]
+    ends = np.concatenate([sPeP[:, e:e + 3] @ T[:3, :3].T + T[:3, 3] for e in (0, 3)])
+    rp, rl = point_residuals(cam, T, P, pl_obs), line_residuals(cam, T, sPeP, le_obs)
+
+    def sides(v):
+        return int(np.sum(~(th < v))), int(np.sum(th < v))
+
+    return dict(pt_z2=sides(G[:, 2] * G[:, 2]), ls_z2=sides(ends[:, 2] * ends[:, 2]), pt_r=sides(rp), ls_r=sides(rl))

@@ -11,6 +11,7 @@ import plslam_amd
 from plslam_amd import loop_closure as LC
 
 import lc_batch_cases as CASES
+import lc_cases
 import lc_ref
 from test_gpu_loop_closure import _check
 
@@ -44,7 +45,8 @@ class Dev:
     def rec(self, kf):
         if id(kf) not in self.recs:
             self.keep.append(kf)
-            self.recs[id(kf)] = dict({k: self.put(kf[k]) for k in KF_KEYS}, n_pt=len(kf["P"]), n_ls=len(kf["sPeP"]))
+            self.recs[id(kf)] = dict({k: 0 if kf[k] is None else self.put(kf[k]) for k in KF_KEYS}, n_pt=len(kf["P"]),
+                                     n_ls=len(kf["sPeP"]))
         return self.recs[id(kf)]
 
     def outputs(self, n_res, n_pt, n_ls):
@@ -137,6 +139,34 @@ def test_placement_independence(ctx):
     again = run_batch_dev(dv, batch, [distinct[b % 32] for b in range(1024)])          # one repeat
     for b in range(1024):
         assert same(again[b], big[b]), b
+    batch.close()
+
+
+@pytest.mark.parametrize("pset", sorted(lc_cases.PARAM_SETS))
+def test_every_case_in_one_call_in_two_orders(ctx, pset):
+    """A batch has one parameter record, so every case of tests/lc_cases.py runs under each of the cases' five parameter
+    sets: one batched call over all of them, another in a seeded other order, each record bit for bit its single call.  The
+    cases that belong to the set are compared with the restatement as well."""
+    over, cam = lc_cases.PARAM_SETS[pset]
+    p = LC.params(cam, **over)
+    dv = Dev()
+    names = list(lc_cases.NAMES)
+    prs = [lc_cases.case(n)[2:] for n in names]
+    batch = plslam_amd.LcBatch(ctx, p, len(prs))
+    single = [run_single_dev(dv, ctx, p, *pr) for pr in prs]
+    got = run_batch_dev(dv, batch, prs)
+    perm = [int(i) for i in np.random.Generator(np.random.PCG64(5)).permutation(len(prs))]
+    assert perm != list(range(len(prs)))
+    other = run_batch_dev(dv, batch, [prs[i] for i in perm])
+    for b, n in enumerate(names):
+        assert same(got[b], single[b]), (pset, n)
+    for k, i in enumerate(perm):
+        assert same(other[k], single[i]), (pset, names[i], k)
+    own = [n for n in lc_cases.VALUE_COMPARED if lc_cases.param_set_of(n) == pset]
+    assert own
+    for n in own:
+        ref, prm, _ = lc_cases.reference(n)
+        _check(*got[names.index(n)], ref, prm)
     batch.close()
 
 

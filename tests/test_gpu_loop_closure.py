@@ -9,6 +9,7 @@ import plslam_amd
 from plslam_amd import loop_closure as LC, synth
 from oracle import oracle as O
 
+import lc_cases as CASES
 import lc_ref
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,9 @@ def _margins(ref, prm):
             assert abs(v - th) >= 0.01 * abs(th), f"{v} is within 1 % of its threshold {th}"
 
 
-def _check(dev, pc, pi, lc, li, ref, prm, margins=True, rank_deficient=False):
+def _check(dev, pc, pi, lc, li, ref, prm, margins=True, rank_deficient=False, nan_pattern=False):
+    """nan_pattern: the input holds a NaN -- on top of everything else, every entry of T_inc is NaN where the restatement's is
+    and within REL of it where it is finite"""
     d = dev
     for k in ("common_pt", "common_ls", "gn_ran", "is_lc"):
         assert d[k] == ref[k], (k, d[k], ref[k])
@@ -68,6 +71,11 @@ def _check(dev, pc, pi, lc, li, ref, prm, margins=True, rank_deficient=False):
         return
     if np.isfinite(ref["T_inc"]).all():
         assert _rel(d["T_inc"], ref["T_inc"]) <= REL
+    if nan_pattern:
+        got, exp = np.asarray(d["T_inc"], np.float64).reshape(4, 4), ref["T_inc"]
+        assert np.array_equal(np.isnan(got), np.isnan(exp)), (got, exp)
+        fin = ~np.isnan(exp)
+        assert np.all(np.abs(got[fin] - exp[fin]) <= REL * np.abs(exp[fin]))
     assert _rel(d["pose_inc"], ref["pose_inc"]) <= REL or not ref["is_lc"]
     if ref["is_lc"]:
         got0, got1 = (pc[pi], lc[li])
@@ -249,3 +257,80 @@ def test_argument_validation(ctx):
     k.n_pt = 3                                   # rows without arrays
     assert L.plslam_loop_closure_verify(ctx._h, p, k, k, res, None, None, None, None) == plslam_amd.capi.EINVAL
     assert L.plslam_relpose_robust_gn(ctx._h, p, None, None, 2, None, None, 0, res, None, None) == plslam_amd.capi.EINVAL
+
+
+# ---- off the one forward-facing scene: tests/lc_cases.py (tests/test_lc_cpu.py shows what each case reaches) ---------------
+def _verify_case(ctx, name, **over):
+    prm_over, cam, kf0, kf1 = CASES.case(name)
+    return ctx.loop_closure_verify(LC.params(cam, **dict(prm_over, **over)), kf0, kf1)
+
+
+@pytest.mark.parametrize("name", CASES.VALUE_COMPARED)
+def test_cases_against_the_restatement(ctx, name):
+    ref, prm, _ = CASES.reference(name)
+    dev = _verify_case(ctx, name)
+    _check(*dev, ref, prm)
+    assert dev[0]["gn_ran"] == 1
+
+
+def test_a_pair_at_rest_with_points_is_exact(ctx):
+    """still_p: every residual is exactly 0, so e == 0 and H == 0 whatever the summation order: all of it is compared exactly"""
+    ref, prm, _ = CASES.reference("still_p")
+    d, pc, pi, lc, li = _verify_case(ctx, "still_p")
+    _check(d, pc, pi, lc, li, ref, prm)
+    assert d["e"] == 0.0 and not np.asarray(d["H"]).any() and not np.asarray(d["g"]).any() and math.isnan(d["cov_eig"])
+    assert (d["iters_1"], d["iters_2"]) == (1, 1) and d["is_lc"] == 0 and d["ok_unc"] == 0 and d["ok_res"] == 1
+    assert np.array_equal(np.asarray(d["T_inc"]).reshape(4, 4), np.eye(4)) and d["t"] == 0.0 and d["r"] == 0.0
+    assert not np.asarray(d["pose_inc"]).any() and pi.all() and d["n_pt_inliers"] == 257 and d["common_ls"] == 0
+
+
+def test_a_pair_at_rest_with_lines_stops_on_a_small_error(ctx):
+    """still_pl: e (1e-27) and H are rounding noise and the eigenvalue of H^-1 (1e8) is rounding-decided: the counts, rows,
+    masks, iteration counts, flags and T_inc == I are what the data decide"""
+    ref, prm, _ = CASES.reference("still_pl")
+    d, pc, pi, lc, li = _verify_case(ctx, "still_pl")
+    for k in ("common_pt", "common_ls", "gn_ran", "is_lc", "iters_1", "iters_2", "ok_unc", "n_pt_inliers", "n_ls_inliers",
+              "inl_ratio_pt", "inl_ratio_ls"):
+        assert d[k] == ref[k], (k, d[k], ref[k])
+    assert (d["iters_1"], d["iters_2"]) == (1, 1) and d["is_lc"] == 0 and d["ok_unc"] == 0 and d["gn_ran"] == 1
+    assert np.array_equal(pc, ref["pt_corr"]) and np.array_equal(lc, ref["ls_corr"]) and pi.all() and li.all()
+    assert np.array_equal(np.asarray(d["T_inc"]).reshape(4, 4), np.eye(4))
+    assert 0.0 <= d["e"] < lc_ref.EPS
+
+
+def test_a_nan_landmark(ctx):
+    ref, prm, _ = CASES.reference("nan_landmark")
+    d, pc, pi, lc, li = _verify_case(ctx, "nan_landmark")
+    _check(d, pc, pi, lc, li, ref, prm, nan_pattern=True)
+    assert d["gn_ran"] == 1 and pi.all() and li.all() and (d["iters_1"], d["iters_2"]) == (5, 10) and d["is_lc"] == 0
+    assert math.isnan(d["e"]) and math.isnan(d["cov_eig"])
+
+
+@pytest.mark.parametrize("name", CASES.VALUE_COMPARED)
+def test_first_system_against_long_double(ctx, name):
+    """One iteration leaves the first system in the result.  The device sums the oracle's terms in a tree where the oracle sums
+    them in sequence; one order says little about the tail of another, so the device may lie ten times as far from the
+    long-double system as the oracle does on the same input (tests/test_lc_cpu.py prints that distance; DESIGN.md has both)"""
+    ld, oracle_dist = CASES.first_system(name)
+    d = _verify_case(ctx, name, max_iters=1, max_iters_ref=0)[0]
+    assert (d["iters_1"], d["iters_2"]) == (1, 0)
+    dist = lc_ref.system_distance(d["H"], d["g"], d["e"], ld)
+    print(f"first system {name}: device {dist:.2e} oracle {oracle_dist:.2e}")
+    assert dist <= 10.0 * oracle_dist, (name, dist, oracle_dist)
+
+
+@pytest.mark.parametrize("name", sorted(CASES.IDENTITY))
+def test_relpose_robust_gn_at_the_chunk_sizes(ctx, name):
+    """the identity path (correspondence k is row k, no rows kept) with one kind only, at 255 / 256 / 257 points and at
+    63 / 64 / 65 lines"""
+    P, pl, S, le = CASES.identity_problem(name)
+    ref, prm, _ = CASES.reference(name)
+    d, pi, li = ctx.relpose_robust_gn(LC.params(), P, pl, S, le)
+    _margins(ref, prm)
+    assert (d["common_pt"], d["common_ls"]) == (len(P), len(S)) and d["gn_ran"] == 1
+    assert np.array_equal(pi, ref["pt_inlier"]) and np.array_equal(li, ref["ls_inlier"])
+    for k in ("is_lc", "ok_res", "ok_unc", "ok_inl", "ok_trs", "ok_rot", "n_pt_inliers", "n_ls_inliers", "iters_1", "iters_2"):
+        assert d[k] == ref[k], (k, d[k], ref[k])
+    for k in ("e", "t", "r", "cov_eig", "ratio_inliers"):
+        assert abs(d[k] - ref[k]) <= REL * abs(ref[k]), (k, d[k], ref[k])
+    assert _rel(d["T_inc"], ref["T_inc"]) <= REL and _rel(d["pose_inc"], ref["pose_inc"]) <= REL and ref["is_lc"] == 1

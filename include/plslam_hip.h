@@ -44,7 +44,8 @@ extern "C" {
  * plslam_relpose_robust_gn with plslam_lc_params / plslam_lc_keyframe / plslam_lc_result; the global bundle adjustment
  * plslam_gba_plan_create / plslam_gba_optimize / plslam_gba_plan_destroy and plslam_dense_ldlt_solve; the loop-closure
  * correction plslam_pgo_plan_create / plslam_pgo_optimize / plslam_pgo_plan_destroy, plslam_lc_correct_map[_dev] and
- * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks.
+ * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks; the local map
+ * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1177,6 +1178,86 @@ int plslam_lc_correct_map_dev(plslam_ctx* ctx, int32_t n_map_kf, const double* T
                               const plslam_lc_landmarks* points, const plslam_lc_landmarks* lines, void* stream);
 int plslam_envelope_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots,
                                int32_t* env_width);
+
+/* ---- the local map on the device: formLocalMap, the gather of localBundleAdjustment, removeBadMapLandmarks ------------- */
+/* MapHandler::addKeyFrame runs formLocalMap() -> localBundleAdjustment() -> removeBadMapLandmarks() every keyframe
+ * (src/mapHandler.cpp:212-225); each is a host loop over the WHOLE map.  Over a CSR image of the map kept on the device they
+ * are flag scatters, stable compactions and a segmented expansion (K55-K61, KERNELS.md).
+ *
+ * plslam_map_index: DEVICE pointers, owned and kept up to date by the caller across keyframes.
+ *   keyframes  kf_valid[n_map_kf] (0 = a NULL slot of map_keyframes; the slot index is kf_idx), x_kf_w[n_map_kf x 6]
+ *   landmarks  per kind: valid[n] (0 = NULL), inlier[n], X (n x 3 point3D / n x 6 line3D), obs_ptr[n + 1] / obs_kf[n_obs] =
+ *              kf_obs_list in list order, obs_val = obs_list in plslam_lba_plan_create's layout (n_obs x 2 / n_obs x 3)
+ *   features   per kind: feat_ptr[n_map_kf + 1], feat_idx[n_feat] = stereo_pt[i]->idx / stereo_ls[i]->idx: -1 = no landmark,
+ *              PLSLAM_FEAT_NULL = the feature pointer itself is NULL
+ * plslam_local_map_cull writes valid and feat_idx; nothing else is written.  n_obs < 2^30 per kind.
+ * Every index read from the image is range-checked on the device; one out of range is treated as "no landmark" / "NULL slot". */
+#define PLSLAM_FEAT_NULL (-2)
+typedef struct plslam_map_landmarks {
+    int32_t n, n_obs;
+    uint8_t* valid;
+    const uint8_t* inlier;
+    const double* X;
+    const int32_t* obs_ptr;
+    const int32_t* obs_kf;
+    const double* obs_val;
+    int32_t n_feat;
+    const int32_t* feat_ptr;
+    int32_t* feat_idx;
+} plslam_map_landmarks;
+typedef struct plslam_map_index {
+    int32_t n_map_kf;
+    const uint8_t* kf_valid;
+    const double* x_kf_w;
+    plslam_map_landmarks points, lines;
+} plslam_map_index;
+/* What the calls leave on the device (plslam_local_map_buffers: device pointers, valid until the next form / destroy, ordered on
+ * `stream`) or bring to the host (plslam_local_map_download: the same struct with HOST pointers, NULL = skip; `stream` ignored).
+ *   form        kf_local[n_map_kf], pt_local[npt], ls_local[nls]   uint8
+ *   candidates  pt_candidate[npt], ls_candidate[nls]               uint8: d_candidate of plslam_map2kf_match_{points,lines}_dev
+ *   gather      kf_list[nkf], pt_list[npt_l], ls_list[nls_l]; pt_obs / ls_obs: n_obs x 6 int32, the Vector6i columns (lm idx, lm
+ *               local idx, obs idx, kf idx, kf local idx or -1, 1); the columns plslam_lba_plan_create takes: *_lm_loc (column 1),
+ *               *_kf_loc (column 4), *_pose_slot (column 3: n_pose_slots = n_map_kf), pt_obs_uv (n x 2), ls_l_obs (n x 3);
+ *               X_aux[6 nkf + 3 npt_l + 6 nls_l]
+ *   cull        pt_removed[npt], ls_removed[nls]                   uint8 */
+typedef struct plslam_local_map_buffers {
+    uint8_t *kf_local, *pt_local, *ls_local, *pt_candidate, *ls_candidate, *pt_removed, *ls_removed;
+    int32_t *kf_list, *pt_list, *ls_list, *pt_obs, *ls_obs;
+    int32_t *pt_lm_loc, *pt_kf_loc, *pt_pose_slot, *ls_lm_loc, *ls_kf_loc, *ls_pose_slot;
+    double *pt_obs_uv, *ls_l_obs, *X_aux;
+    void* stream;
+} plslam_local_map_buffers;
+typedef struct plslam_local_map_counts {
+    int32_t n_kf_local, n_pt_local, n_ls_local;          /* form: flags set                                                  */
+    int32_t nkf, npt, nls, n_pt_obs, n_ls_obs;           /* gather: list lengths (nkf excludes slot 0, :1231)                */
+    int32_t empty;                                       /* gather: n_pt_obs + n_ls_obs == 0, the reference's return -1 (:1327) */
+    int32_t n_pt_removed, n_ls_removed;                  /* cull                                                             */
+} plslam_local_map_counts;
+typedef struct plslam_local_map plslam_local_map;
+int plslam_local_map_create(plslam_ctx* ctx, plslam_local_map** out);
+void plslam_local_map_destroy(plslam_local_map* lm);
+/* formLocalMap() (:836-902; anchor_kf = n_map_kf - 1) and formLocalMap(kf) (:904-968; anchor_kf = kf->kf_idx).  row: HOST pointer
+ * to full_graph[n_map_kf - 1] (n_map_kf int32) -- the overload reads the LAST row too (:946), not the anchor's.  All flags are
+ * cleared; the anchor and every landmark its non-NULL features name (idx != -1 && valid) become local; every valid slot
+ * i < n_map_kf - 1 with row[i] >= min_lm_cov_graph || |n_map_kf - 1 - i| <= min_kf_local_map becomes local with its features'
+ * landmarks.  Deviations: the reference dereferences a NULL map_keyframes[i] (:885) and NULL features (:889) in that loop; here
+ * a NULL slot and a PLSLAM_FEAT_NULL feature are skipped (so is a NULL anchor slot).  counts: the three form fields are set. */
+int plslam_local_map_form(plslam_local_map* lm, const plslam_map_index* map, int32_t anchor_kf, const int32_t* row,
+                          int32_t min_lm_cov_graph, int32_t min_kf_local_map, plslam_local_map_counts* counts);
+/* candidate[i] = valid && local && kf_obs_list.back() != kf2_idx (:547, :649); an empty observation list gives 0 (the reference's
+ * back() is undefined there).  After form on the same map. */
+int plslam_local_map_candidates(plslam_local_map* lm, const plslam_map_index* map, int32_t kf2_idx);
+/* The gather of localBundleAdjustment (:1225-1321), order for order.  After form on the same map; counts: the gather fields. */
+int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts);
+/* removeBadMapLandmarks (:2705-2786): a valid landmark with observations is removed when !local && max_kf_idx - obs_kf[first] >
+ * 10 and (!inlier || n_obs < min_lm_obs).  In place on the index: valid cleared; in keyframe obs_kf[first] the FIRST feature whose
+ * feat_idx equals the landmark becomes -1 (a later duplicate stays).  Erasing from map_*_kf_idx stays with the caller, driven by
+ * the removed masks.  Deviations: a NULL first-observer keyframe or a NULL feature (:2720-2723) is skipped; an empty observation
+ * list is not culled.  After form on the same map; counts: the cull fields. */
+int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int32_t max_kf_idx, int32_t min_lm_obs,
+                          plslam_local_map_counts* counts);
+int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out);
+int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffers* host);
 
 #ifdef __cplusplus
 }

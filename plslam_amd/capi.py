@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "plslam_gba_plan_create", "plslam_gba_optimize", "plslam_gba_plan_destroy", "plslam_dense_ldlt_solve",
     "plslam_pgo_plan_create", "plslam_pgo_optimize", "plslam_pgo_plan_destroy", "plslam_lc_correct_map",
     "plslam_lc_correct_map_dev", "plslam_envelope_ldlt_solve",
+    "plslam_local_map_create", "plslam_local_map_destroy", "plslam_local_map_form", "plslam_local_map_candidates",
+    "plslam_local_map_gather", "plslam_local_map_cull", "plslam_local_map_device_buffers", "plslam_local_map_download",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -428,13 +430,24 @@ def load() -> C.CDLL:
     L.plslam_lc_correct_map.argtypes = [vp, i32, vp, vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks)]
     L.plslam_lc_correct_map_dev.argtypes = [vp, i32, vp, vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks), vp]
     L.plslam_envelope_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    # the local map (plslam_amd/local_map.py holds the structs and the wrapper): every struct goes by address
+    L.plslam_local_map_create.argtypes = [vp, C.POINTER(vp)]
+    L.plslam_local_map_destroy.argtypes = [vp]
+    L.plslam_local_map_destroy.restype = None
+    L.plslam_local_map_form.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+    L.plslam_local_map_candidates.argtypes = [vp, vp, i32]
+    L.plslam_local_map_gather.argtypes = [vp, vp, vp]
+    L.plslam_local_map_cull.argtypes = [vp, vp, i32, i32, vp]
+    L.plslam_local_map_device_buffers.argtypes = [vp, vp]
+    L.plslam_local_map_download.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("plslam_strerror", "plslam_last_error", "plslam_ctx_destroy",
                         "plslam_match_plan_destroy", "plslam_lba_plan_destroy", "plslam_grid_plan_destroy",
                         "plslam_match_pipeline_destroy", "plslam_pinned_alloc", "plslam_pinned_free",
                         "plslam_grid_pair_capacity", "plslam_grid_pair_capacity_bound", "plslam_bow_vocab_destroy",
-                        "plslam_bow_db_destroy", "plslam_gba_plan_destroy", "plslam_pgo_plan_destroy"):
+                        "plslam_bow_db_destroy", "plslam_gba_plan_destroy", "plslam_pgo_plan_destroy",
+                        "plslam_local_map_destroy"):
             f.restype = C.c_int
     _lib = L
     return L

@@ -23,16 +23,17 @@ OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 # other row of SURVEY section 8
 SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_mfma_i.hip", "lba.hip", "lba_assemble.hip",
            "map2kf.hip", "lbd.hip", "median_desc.hip", "match_grid.hip", "stereo_gates.hip", "pose_gn.hip", "lbd_float.hip", "bow.hip",
-           "loop_closure.hip", "gba.hip", "pgo.hip", "local_map.hip", "capi.hip"]
+           "loop_closure.hip", "gba.hip", "pgo.hip", "local_map.hip",
+           "context.hip", "match_plan.hip", "host_calls.hip", "match_pipeline.hip", "gather.hip"]
 # earlier generations of the matrix-core scan, reachable only through the context option "mfma_form" (1 = K1e, 3 = K1g,
 # 4 = K1h -- whose scan kernel sits behind the same macro in hamming_mfma_h.hip): cross-checks for the tests and A/B baselines
 # for the tools.  OPT-IN: build_hip(legacy=True) / PLSLAM_BUILD_LEGACY_SCANS=1 python -m plslam_amd.build -> LEGACY_OUT.
 # Without them (the product) the option values are refused with PLSLAM_ENOTSUP and the test cases that use them skip in the
-# main test process.  Only the translation units that see the macro are compiled twice (LEGACY_AWARE): the legacy library
-# shares the other twelve objects with the product.
+# main test process.  Only the translation units that see the macro are compiled twice (LEGACY_AWARE: the context,
+# which answers what the build carries, and K1h's scan kernel): the legacy library shares every other object with the product.
 LEGACY_SOURCES = ["hamming_mfma.hip", "hamming_mfma_d.hip"]
-LEGACY_AWARE = ("capi.hip", "hamming_mfma_h.hip")
-HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "match_tables.hpp", "match_planner.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp",
+LEGACY_AWARE = ("context.hip", "hamming_mfma_h.hip")
+HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "match_tables.hpp", "match_planner.hpp", "match_plan.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp",
                                             "stereo_gates_dev.hpp", "pose_gn_dev.hpp", "se3_dev.hpp", "ldlt_dense_dev.hpp", "lookback_dev.hpp")] + [os.path.join(_ROOT, "include", "plslam_hip.h")]
 # -ffp-contract=off: the fp64 row kernels must execute the reference's operation order
 # (no FMA contraction) so that thresholded masks reproduce the CPU restatement bit for bit.

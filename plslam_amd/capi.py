@@ -263,6 +263,19 @@ def _preload_shared_hip_runtime() -> None:
                 continue
 
 
+# every entry point returns an int status except these (load() gives each name of ABI_SYMBOLS its return type from here).
+# plslam_lc_batch_destroy is void in the header and is bound as int, as it has been since it was added; its value is not read.
+_RESTYPES = {
+    "plslam_strerror": C.c_char_p, "plslam_last_error": C.c_char_p,
+    "plslam_pinned_alloc": C.c_void_p, "plslam_pinned_free": None,
+    "plslam_grid_pair_capacity": C.c_int64, "plslam_grid_pair_capacity_bound": C.c_int64,
+    "plslam_ctx_destroy": None, "plslam_match_plan_destroy": None, "plslam_lba_plan_destroy": None,
+    "plslam_grid_plan_destroy": None, "plslam_match_pipeline_destroy": None, "plslam_bow_vocab_destroy": None,
+    "plslam_bow_db_destroy": None, "plslam_gba_plan_destroy": None, "plslam_pgo_plan_destroy": None,
+    "plslam_local_map_destroy": None,
+}
+
+
 def load() -> C.CDLL:
     """dlopen libplslam_hip.so and declare prototypes.  Fails loudly if it was not built."""
     global _lib
@@ -275,9 +288,7 @@ def load() -> C.CDLL:
     _preload_shared_hip_runtime()
     L = C.CDLL(LIB_PATH)
     vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
-    L.plslam_strerror.restype = C.c_char_p
     L.plslam_strerror.argtypes = [C.c_int]
-    L.plslam_last_error.restype = C.c_char_p
     L.plslam_last_error.argtypes = []
     L.plslam_abi_version.restype = C.c_int
     L.plslam_abi_version.argtypes = []
@@ -291,7 +302,6 @@ def load() -> C.CDLL:
                                                  C.c_void_p, C.c_void_p]
     L.plslam_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.plslam_ctx_destroy.argtypes = [vp]
-    L.plslam_ctx_destroy.restype = None
     L.plslam_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.plslam_ctx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
     L.plslam_ctx_device_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
@@ -310,7 +320,6 @@ def load() -> C.CDLL:
                                          C.POINTER(C.c_size_t)]
     L.plslam_match_plan_key_state.argtypes = [vp, C.POINTER(C.c_int32)]
     L.plslam_match_plan_destroy.argtypes = [vp]
-    L.plslam_match_plan_destroy.restype = None
     L.plslam_lba_point_rows.argtypes = [vp, C.POINTER(Cam), f64, vp, i32, vp, i32, vp, vp, vp, i32,
                                         vp, vp, vp, vp]
     L.plslam_lba_line_rows.argtypes = [vp, C.POINTER(Cam), f64, C.c_int, vp, i32, vp, i32, vp, vp, vp,
@@ -341,7 +350,6 @@ def load() -> C.CDLL:
     L.plslam_lba_plan_host_state.argtypes = [vp, vp]
     L.plslam_lba_plan_blocks.argtypes = [vp] * 8
     L.plslam_lba_plan_destroy.argtypes = [vp]
-    L.plslam_lba_plan_destroy.restype = None
     for f in (L.plslam_map2kf_point_gate, L.plslam_map2kf_line_gate):
         f.argtypes = [vp, C.POINTER(Cam), vp, vp, vp, i32, vp, i32, f64, vp, C.POINTER(i32)]
     for f in (L.plslam_map_point_visible, L.plslam_map_line_visible):
@@ -374,22 +382,16 @@ def load() -> C.CDLL:
     L.plslam_match_pipeline_submit.argtypes = [vp, vp, vp, vp]
     L.plslam_match_pipeline_wait.argtypes = [vp]
     L.plslam_match_pipeline_destroy.argtypes = [vp]
-    L.plslam_match_pipeline_destroy.restype = None
     L.plslam_pinned_alloc.argtypes = [C.c_size_t]
-    L.plslam_pinned_alloc.restype = vp
     L.plslam_pinned_free.argtypes = [vp]
-    L.plslam_pinned_free.restype = None
     L.plslam_match_grid.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, f64, vp, f64, C.c_int, vp,
                                     C.POINTER(i32)]
     L.plslam_grid_plan_create.argtypes = [vp, C.POINTER(GridProblem), i32, C.POINTER(vp)]
     L.plslam_grid_plan_run.argtypes = [vp, vp]
     L.plslam_grid_plan_overflows.argtypes = [vp, vp, C.POINTER(i32)]
     L.plslam_grid_plan_destroy.argtypes = [vp]
-    L.plslam_grid_plan_destroy.restype = None
     L.plslam_grid_pair_capacity.argtypes = [vp, i32, i32, vp, i32, i32, vp, C.c_int]
-    L.plslam_grid_pair_capacity.restype = C.c_int64
     L.plslam_grid_pair_capacity_bound.argtypes = [i32, i32, vp, i32, i32, vp, C.c_int]
-    L.plslam_grid_pair_capacity_bound.restype = C.c_int64
     L.plslam_gather_match_tables.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp]
     L.plslam_rccl_use.argtypes = [C.c_char_p]
     L.plslam_match_plan_step_gather.argtypes = [vp, C.POINTER(GatherStep)]
@@ -397,12 +399,10 @@ def load() -> C.CDLL:
     L.plslam_rccl_available.argtypes = []
     L.plslam_bow_vocab_create.argtypes = [vp, C.POINTER(BowVocabDesc), C.POINTER(vp)]
     L.plslam_bow_vocab_destroy.argtypes = [vp]
-    L.plslam_bow_vocab_destroy.restype = None
     L.plslam_bow_transform.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.plslam_bow_transform_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.plslam_bow_db_create.argtypes = [vp, vp, vp, i32, C.POINTER(vp)]
     L.plslam_bow_db_destroy.argtypes = [vp]
-    L.plslam_bow_db_destroy.restype = None
     L.plslam_bow_db_insert.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(BowPlStats), vp, vp]
     L.plslam_bow_db_insert_dev.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(BowPlStats), vp, vp]
     L.plslam_bow_db_size.argtypes = [vp, C.POINTER(i32)]
@@ -414,26 +414,22 @@ def load() -> C.CDLL:
     L.plslam_relpose_robust_gn.argtypes = [vp, C.POINTER(LcParams), vp, vp, i32, vp, vp, i32, C.POINTER(LcResult), vp, vp]
     L.plslam_lc_batch_create.argtypes = [vp, C.POINTER(LcParams), i32, C.POINTER(vp)]
     L.plslam_lc_batch_destroy.argtypes = [vp]
-    L.plslam_lc_batch_destroy.restype = None
     L.plslam_lc_batch_verify.argtypes = [vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), i32, C.POINTER(LcResult), vp, vp, vp, vp]
     L.plslam_lc_batch_verify_dev.argtypes = [vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), i32, vp, vp, vp, vp, vp, vp]
     L.plslam_relpose_robust_gn_batched_dev.argtypes = [vp, C.POINTER(LcParams), vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.plslam_gba_plan_create.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(vp)]
     L.plslam_gba_optimize.argtypes = [vp, f64, f64, i32] + [vp] * 8 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)]
     L.plslam_gba_plan_destroy.argtypes = [vp]
-    L.plslam_gba_plan_destroy.restype = None
     L.plslam_dense_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32)]
     L.plslam_pgo_plan_create.argtypes = [vp, C.POINTER(PgoParams), i32, vp, vp, i32, vp, C.POINTER(vp)]
     L.plslam_pgo_optimize.argtypes = [vp] + [vp] * 7 + [C.POINTER(PgoTrial), i32, C.POINTER(PgoResult)]
     L.plslam_pgo_plan_destroy.argtypes = [vp]
-    L.plslam_pgo_plan_destroy.restype = None
     L.plslam_lc_correct_map.argtypes = [vp, i32, vp, vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks)]
     L.plslam_lc_correct_map_dev.argtypes = [vp, i32, vp, vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks), vp]
     L.plslam_envelope_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     # the local map (plslam_amd/local_map.py holds the structs and the wrapper): every struct goes by address
     L.plslam_local_map_create.argtypes = [vp, C.POINTER(vp)]
     L.plslam_local_map_destroy.argtypes = [vp]
-    L.plslam_local_map_destroy.restype = None
     L.plslam_local_map_form.argtypes = [vp, vp, i32, vp, i32, i32, vp]
     L.plslam_local_map_candidates.argtypes = [vp, vp, i32]
     L.plslam_local_map_gather.argtypes = [vp, vp, vp]
@@ -441,14 +437,7 @@ def load() -> C.CDLL:
     L.plslam_local_map_device_buffers.argtypes = [vp, vp]
     L.plslam_local_map_download.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:
-        f = getattr(L, name)
-        if name not in ("plslam_strerror", "plslam_last_error", "plslam_ctx_destroy",
-                        "plslam_match_plan_destroy", "plslam_lba_plan_destroy", "plslam_grid_plan_destroy",
-                        "plslam_match_pipeline_destroy", "plslam_pinned_alloc", "plslam_pinned_free",
-                        "plslam_grid_pair_capacity", "plslam_grid_pair_capacity_bound", "plslam_bow_vocab_destroy",
-                        "plslam_bow_db_destroy", "plslam_gba_plan_destroy", "plslam_pgo_plan_destroy",
-                        "plslam_local_map_destroy"):
-            f.restype = C.c_int
+        getattr(L, name).restype = _RESTYPES.get(name, C.c_int)
     _lib = L
     return L
 

@@ -108,10 +108,21 @@ struct StreamSyncOnError {
     }
 };
 
-// carve several arrays out of one scratch buffer (256-byte aligned slices)
+// a scratch buffer that lives for one call: whatever way the call returns, the stream is drained and the buffer freed
+struct ReleaseAfterSync {
+    DevBuf& b;
+    hipStream_t s;
+    ~ReleaseAfterSync()
+    {
+        (void)hipStreamSynchronize(s);
+        b.release();
+    }
+};
+
+// carve several arrays out of one scratch buffer (slices aligned as align256 says: match_tables.hpp)
 struct Carver {
     size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
+    size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
 };
 
 }  // namespace plslam
@@ -151,15 +162,6 @@ struct plslam_ctx {
 };
 
 namespace plslam {
-
-// the loop-closure check's match problems (device pointers) as one plan on the context's stream: ctx->lc_plan, whose
-// buffers only grow and whose tables are staged in pageable memory (capi.hip)
-int match_problems_lc(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob);
-// a plan kept by its owner across calls (plslam_lc_batch): (re)built for `probs` (DEVICE pointers) into *slot, its tables
-// uploaded on the context's stream without a synchronisation; run on `s`; freed with its buffers
-int match_plan_rebuild(plslam_ctx* ctx, struct plslam_match_plan** slot, const plslam_match_problem* probs, int32_t nprob);
-int match_plan_enqueue(struct plslam_match_plan* plan, hipStream_t s);
-void match_plan_release(struct plslam_match_plan* plan);
 
 // Pointers read from launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction (it counts on
 // lgkmcnt as well as vmcnt, and cannot take a scalar base).  Kernels spell the address space out at the point of use:
@@ -258,29 +260,13 @@ int launch_merge_fix16(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblo
 int mh_slot_of_column(int n2, int j);
 // K1g (hamming_mfma_d.hip): the directed scan, one item per (directed scan, 256-row block of a); any n2 (windows inside)
 int launch_scan_dir_mfma(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero, int nzero, hipStream_t s);
-inline int launch_scan_mfma_form(int form, const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero,
-                                 int nzero, bool multi_window, bool directed, hipStream_t s, bool fused = false)
-{
-#if PLSLAM_BUILD_LEGACY_SCANS
-    if (form == 3 && directed && !fused) return launch_scan_dir_mfma(d_sym, d_blocks, nblocks, d_zero, nzero, s);
-    if (form == 4 && !fused) return launch_scan_sym_mfma_h(d_sym, d_blocks, nblocks, d_zero, nzero, directed, s);
-#endif
-    if (mfma_form_is_h(form) && !fused) return launch_scan_sym_mfma_i(d_sym, d_blocks, nblocks, d_zero, nzero, directed, s);
-#if PLSLAM_BUILD_LEGACY_SCANS
-    if (form == 1) return launch_scan_sym_mfma(d_sym, d_blocks, nblocks, d_zero, nzero, multi_window, directed, s);
-#endif
-    return launch_scan_sym_mfma_g(d_sym, d_blocks, nblocks, d_zero, nzero, multi_window, directed, fused, s);
-}
+// the matrix-core scan of `form` (context.hip: the one place that knows which generations the build carries)
+int launch_scan_mfma_form(int form, const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero,
+                          int nzero, bool multi_window, bool directed, hipStream_t s, bool fused = false);
 int launch_merge_partials(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, hipStream_t s);
 
 int scan_rows_per_block(int variant, int block_threads);
 
-// builds the plan for `probs` (DEVICE pointers) into the context's persistent host-path plan and
-// enqueues it on the context stream; no synchronisation.  Caller holds ctx->mu.  (capi.hip)
-// n1_dev0: the row count of problem 0 on the device (probs[0].n1 = its bound); PLSLAM_ENOTSUP when the plan cannot take it
-int match_problems_on_ctx_stream(plslam_ctx* ctx, const plslam_match_problem* probs, int32_t nprob, const int32_t* n1_dev0 = nullptr);
-// whether the context's options allow the n1_dev0 form at all (asked before anything is staged or enqueued for it)
-bool ctx_takes_device_row_count(const plslam_ctx* ctx);
 // dst[i] = src[idx[i]] for rows of row_bytes (a multiple of 8) bytes  (map2kf.hip)
 int launch_gather_rows(const void* src, const int32_t* idx, int32_t n, int32_t row_bytes, void* dst,
                        hipStream_t s);

@@ -739,7 +739,7 @@ int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const d
                  oR = c.take(sizeof(GbaStats));
     int rc = buf.reserve(c.off);
     if (rc) return rc;
-    struct Rel { DevBuf& b; hipStream_t s; ~Rel() { (void)hipStreamSynchronize(s); b.release(); } } rel{buf, s};
+    ReleaseAfterSync rel{buf, s};
     char* d = buf.as<char>();
     double* S = (double*)(d + oS);
     PLSLAM_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)npad * npad * 8, s));

@@ -357,7 +357,7 @@ k_scan_symmetric(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__
 // MEASURED (profiles/r1_valu_microbench.txt, "alt xor(v,v)/bcnt"): a fast op alternating with a slow
 // one issues at nearly the slow rate, so the VALU gain is small; what pays is the 4x smaller partial
 // table and merge: 364k vs 347k pairs/s at 4096 pairs/step, 347k vs 344k at 2048 -- but 266k vs 320k
-// at 512, where the 4x coarser work units lose to tail quantisation.  The plan picks (capi.hip).
+// at 512, where the 4x coarser work units lose to tail quantisation.  The plan picks (match_planner.hpp).
 // ---------------------------------------------------------------------------------------------
 constexpr int SYM4_SUBTILE_U16 = 16 * SYM_TILE_ROW_U16;      // 16 b-rows x 144 B = 2304 B per row-block
 
@@ -820,7 +820,7 @@ int launch_post_fused(const ProblemDesc* d_probs, int nprob, const plslam_stereo
 {
     if (nprob <= 0) return PLSLAM_OK;
     // (measured per 16 384-problem step at C2, exclusive: this kernel with 256 lanes per problem 0.335 ms, with 1024 lanes
-    // 0.65 ms, the separate merge + finalize kernels 0.276 ms -- see capi.hip plan_build, option "post_fuse")
+    // 0.65 ms, the separate merge + finalize kernels 0.276 ms -- see match_planner.hpp plan_decide, option "post_fuse")
     hipLaunchKernelGGL(k_post_fused<POST_FUSED_THREADS>, dim3(nprob), dim3(POST_FUSED_THREADS), lds_bytes, s, d_probs, d_gates, nprob);
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;

@@ -57,7 +57,7 @@ __device__ __forceinline__ uint32_t expand_byte_fp4(uint32_t byte)
 
 // MULTI = false: every problem of the launch has n2 <= 2048 (one window of 64 tiles; the window bounds are
 // compile-time facts).  MULTI = true: any n2 (the extra live state costs ~2 % through register pressure,
-// which is why the common case has its own instantiation; capi.hip picks per plan).
+// which is why the common case has its own instantiation; match_planner.hpp picks per plan).
 // DIRECTED = true: only keys12 (row direction) is produced -- non-mutual problems and plain knnMatch(k=2):
 // no column keys, no column partials, 5 VALU ops per 2 distances.
 template <bool MULTI, bool DIRECTED>

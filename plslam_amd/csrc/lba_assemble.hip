@@ -490,12 +490,6 @@ k_lba_finish(const LbaBlockArgs A)
     lba_finish_wg<256>(A, (int)blockIdx.x, red);
 }
 
-namespace {
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
-};
-}  // namespace
 }  // namespace plslam
 
 namespace plslam {
@@ -644,18 +638,18 @@ extern "C" int plslam_lba_plan_create(plslam_ctx* ctx, const plslam_cam* K, doub
     if (n_pt_obs) P->h_pt_kf.assign(pt_kf_loc, pt_kf_loc + n_pt_obs);
     if (n_ls_obs) P->h_ls_kf.assign(ls_kf_loc, ls_kf_loc + n_ls_obs);
     const size_t np = (size_t)n_pt_obs, nl = (size_t)n_ls_obs;
-    Carve cs;
+    Carver cs;
     P->oPlm = cs.take(np * 4); P->oPslot = cs.take(np * 4); P->oPkf = cs.take(np * 4); P->oPuv = cs.take(np * 16);
     P->oLlm = cs.take(nl * 4); P->oLslot = cs.take(nl * 4); P->oLkf = cs.take(nl * 4); P->oLobs = cs.take(nl * 24);
     P->oPtp = cs.take(c.ptp.size() * 4); P->oPti = cs.take(c.pti.size() * 4 + 4); P->oLsp = cs.take(c.lsp.size() * 4);
     P->oLsi = cs.take(c.lsi.size() * 4 + 4); P->oKfp = cs.take(c.kfp.size() * 4); P->oKfi = cs.take(c.kfi.size() * 4 + 4);
-    Carve cd;
+    Carver cd;
     P->oT = cd.take((size_t)n_pose_slots * 128 + 8); P->oX = cd.take((size_t)npt * 24 + 8); P->oL = cd.take((size_t)nls * 48 + 8);
-    Carve cr;
+    Carver cr;
     P->oPJp = cr.take(np * 48 + 8); P->oPJl = cr.take(np * 24 + 8); P->oPr = cr.take(np * 8 + 8); P->oPw = cr.take(np * 8 + 8);
     P->oLJp = cr.take(nl * 48 + 8); P->oLJl = cr.take(nl * 48 + 8); P->oLr = cr.take(nl * 8 + 8); P->oLw = cr.take(nl * 8 + 8);
     const size_t N = 6 * (size_t)nkf + 3 * (size_t)npt + 6 * (size_t)nls;
-    Carve co;
+    Carver co;
     P->oG = co.take(N * 8 + 8); P->oHp = co.take((size_t)nkf * 288 + 8); P->oHpt = co.take((size_t)npt * 72 + 8);
     P->oHls = co.take((size_t)nls * 288 + 8); P->oWp = co.take(np * 144 + 8); P->oWl = co.take(nl * 288 + 8);
     P->oErr = P->oG + N * 8;                      // err: the double right behind g (one copy brings both back)
@@ -973,7 +967,7 @@ extern "C" int plslam_lba_assemble(plslam_ctx* ctx, int32_t nkf, int32_t npt, in
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg_(ctx->device);    // every entry point runs on the context's device, whatever the calling thread's current one
     hipStream_t s = ctx->stream;
-    Carve c;
+    Carver c;
     const size_t np = (size_t)n_pt_obs, nl = (size_t)n_ls_obs;
     const size_t oPJp = c.take(np * 48), oPJl = c.take(np * 24), oPr = c.take(np * 8), oPw = c.take(np * 8),
                  oPk = c.take(np * 4), oLJp = c.take(nl * 48), oLJl = c.take(nl * 48), oLr = c.take(nl * 8),
@@ -981,7 +975,7 @@ extern "C" int plslam_lba_assemble(plslam_ctx* ctx, int32_t nkf, int32_t npt, in
                  oLsp = c.take(lsp.size() * 4), oLsi = c.take(lsi.size() * 4), oKfp = c.take(kfp.size() * 4),
                  oKfi = c.take(kfi.size() * 4 + 4);
     const size_t N = 6 * (size_t)nkf + 3 * (size_t)npt + 6 * (size_t)nls;
-    Carve co;
+    Carver co;
     const size_t oG = co.take(N * 8 + 8), oHp = co.take((size_t)nkf * 288 + 8), oHpt = co.take((size_t)npt * 72 + 8),
                  oHls = co.take((size_t)nls * 288 + 8), oWp = co.take(np * 144 + 8), oWl = co.take(nl * 288 + 8),
                  oErr = co.take(8 * (1 + ERR_BLOCKS));
@@ -1653,7 +1647,7 @@ static int lba_schur_prepare(plslam_lba_plan* P)
     for (int32_t B = 0; B < P->nblk; ++B) mc = std::max(mc, (cnt[(size_t)B + 1] - cnt[B] + SCH_CHUNK - 1) / SCH_CHUNK);
     P->schur_chunks = mc;
     const size_t n6 = 6 * (size_t)nkf;
-    Carve c;
+    Carver c;
     P->oSpair = c.take(pairs.size() * sizeof(SchurPair) + 16); P->oSblk = c.take(cnt.size() * 4);
     P->oVp = c.take((size_t)P->npt * 72 + 8); P->oVl = c.take((size_t)P->nls * 288 + 8);
     P->oTp = c.take((size_t)P->npt * 24 + 8); P->oTl = c.take((size_t)P->nls * 48 + 8);

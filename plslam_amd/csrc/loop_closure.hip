@@ -24,7 +24,7 @@
 #include <new>
 #include <vector>
 
-#include "common.hpp"
+#include "match_plan.hpp"
 #include "pose_gn_dev.hpp"
 #include "se3_dev.hpp"
 

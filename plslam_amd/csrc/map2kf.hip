@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "match_plan.hpp"
 
 namespace plslam {
 
@@ -83,11 +83,6 @@ static bool tab_in_place_enabled()
 }
 
 namespace {
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
-};
-
 // getLineCoords of stvo-pl ([RECALL]; the callers' grid fill :693-697): Bresenham cells, the last x excluded
 void line_cells(double x1, double y1, double x2, double y2, std::vector<int32_t>& xy)
 {
@@ -185,7 +180,7 @@ int grid_path(plslam_ctx* ctx, int lines, const plslam_cam* K, const double* T16
     const int32_t n_items = cs.back();
     // image (host -> device in one copy): result words | cell_start | items | directions | descriptor; behind it, device only:
     // the projected cells and the query directions
-    Carve cf;
+    Carver cf;
     const size_t oSt = cf.take(16), oCs = cf.take(cs.size() * 4), oIt = cf.take((size_t)(n_items + 1) * 4),
                  oD2 = cf.take(lines ? (size_t)nt * 16 : 0), oDesc = cf.take(sizeof(GridDesc)), oAux = cf.take(grid_aux_words(nt) * 4);
     const size_t image = cf.off;
@@ -312,7 +307,7 @@ int map2kf_fast_once(plslam_ctx* ctx, int lines, const plslam_cam* K, const doub
         return PLSLAM_OK;
     }
     // ---- one image up
-    Carve c;
+    Carver c;
     const size_t oLM = c.take(map_dev ? 0 : (size_t)n_map * lw * 8), oMD = c.take(map_dev ? 0 : (size_t)n_map * 32),
                  oCand = c.take(map_dev ? 0 : (size_t)n_map), oT = c.take((size_t)nt * 32), oTF = c.take((size_t)nt * fw * 8),
                  oTi = c.take((size_t)nt * 4), oCs = c.take(cs.size() * 4), oIt = c.take((size_t)(n_items + 1) * 4),
@@ -438,7 +433,7 @@ int map2kf_bf_once(plslam_ctx* ctx, int lines, const plslam_cam* K, const double
     const int32_t nt = (int32_t)ti.size();
     const int lw = lines ? 6 : 3, fw = lines ? 3 : 2;
     // ---- one image up: [the map, unless it is resident] | T rows | their features | ti | zeroed counters
-    Carve c;
+    Carver c;
     const size_t oLM = c.take(map_dev ? 0 : (size_t)n_map * lw * 8), oMD = c.take(map_dev ? 0 : (size_t)n_map * 32),
                  oCand = c.take(map_dev ? 0 : (size_t)n_map), oT = c.take((size_t)nt * 32), oTF = c.take((size_t)nt * fw * 8),
                  oTi = c.take((size_t)nt * 4),
@@ -544,7 +539,7 @@ int kf2kf_driver(plslam_ctx* ctx, int lines, const plslam_cam* K, const double* 
     StreamSyncOnError sg(s);
     // ONE page-locked image [X_prev | desc_prev | desc_curr] -> one upload (X only when the windowed matcher runs); the
     // match table comes back through page-locked memory the kernels write (no download on the common path)
-    Carve c;
+    Carver c;
     const size_t oQ = c.take(rows_dev ? 0 : (size_t)n_prev * 32), oT = c.take(rows_dev ? 0 : (size_t)n_curr * 32),
                  oX = c.take(fast && !rows_dev ? (size_t)n_prev * xw * 8 : 0);
     const size_t image = c.off;
@@ -686,7 +681,7 @@ int map2kf_driver(plslam_ctx* ctx, int lines, const plslam_cam* K, const double*
     hipStream_t s = ctx->stream;
     StreamSyncOnError sg(s);
     // ---- stage the map and the keyframe on the device (ONE page-locked image, one upload), project + visibility test ----
-    Carve c;
+    Carver c;
     const size_t oLM = c.take(map_dev ? 0 : (size_t)n_map * lw * 8), oMD = c.take(map_dev ? 0 : (size_t)n_map * 32),
                  oKD = c.take((size_t)n_kf * 32), oKF = c.take((size_t)n_kf * fw * 8);
     const size_t image1 = c.off;

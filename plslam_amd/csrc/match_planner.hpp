@@ -1,7 +1,7 @@
 // match_planner.hpp -- the host half of a match plan that needs no device: which scan every problem takes, how large the
 // key / partial / row-temp areas are (plan_decide), and the launch tables over given base addresses (plan_tables).
 // Standard library only: arithmetic on (options, CU count, problem shapes), so tests/cpp/test_match_planner.cpp runs it
-// without a GPU.  capi.hip (plan_build) allocates between the two calls and uploads the packed image.
+// without a GPU.  match_plan.hip (plan_build) allocates between the two calls and uploads the packed image.
 #pragma once
 
 #include <algorithm>
@@ -491,7 +491,7 @@ inline void plan_tables(const PlanChoice& c, const plslam_match_problem* probs, 
     put(PlanTables::DIRS, t.dirs, t.dirs.size());
     put(PlanTables::DIR_BLOCKS, t.dir_blocks, t.dir_blocks.size());
     t.total = 0;
-    for (PlanTables::Piece& x : t.piece) { x.off = t.total; t.total += (x.bytes + 255) & ~size_t(255); }
+    for (PlanTables::Piece& x : t.piece) { x.off = t.total; t.total += align256(x.bytes); }
     if (t.total == 0) t.total = 256;
 }
 

@@ -3,6 +3,7 @@
 // compiler.  common.hpp includes it for the kernels.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "plslam_hip.h"
@@ -70,6 +71,9 @@ struct SymDesc {
     // number of rows of a lives on the DEVICE (*n1_dev <= n1; n1 is the bound the tables and the launch are sized for), or nullptr
     const int32_t* n1_dev;
 };
+
+// every area and every packed table starts on a multiple of 256 bytes
+constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 // the kernels index these tables with fixed strides: a reordered or resized field must not slip through
 static_assert(sizeof(ScanDesc) == 32, "ScanDesc layout");

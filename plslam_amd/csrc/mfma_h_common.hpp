@@ -139,7 +139,7 @@ __device__ __forceinline__ uint32_t hamming256(u32x4_t a_lo, u32x4_t a_hi, u32x4
 }
 // XCD-striped block tables: hardware places workgroup b on XCD b % 8 and dispatches in increasing
 // b; the host lays the table out as 8 rows of L = gridDim.x / 8 entries, row x = the work of XCD x in
-// dispatch order (capi.hip, `stripe`), so the blocks of one problem -- which stream the same
+// dispatch order (match_planner.hpp, deal_to_xcds), so the blocks of one problem -- which stream the same
 // descriptor sets -- sit on one XCD's L2 at the same time.  Rows are padded with item = -1.
 __device__ __forceinline__ int xcd_remap_(int orig, int nwg) { return (orig & 7) * (nwg >> 3) + (orig >> 3); }
 

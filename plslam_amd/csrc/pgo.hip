@@ -1208,7 +1208,7 @@ int plslam_envelope_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, cons
                  oZg = c.take((size_t)n * 8), oX = c.take((size_t)n * 8), oBad = c.take(8);
     int rc = buf.reserve(c.off);
     if (rc) return rc;
-    struct Rel { DevBuf& b; hipStream_t s; ~Rel() { (void)hipStreamSynchronize(s); b.release(); } } rel{buf, s};
+    ReleaseAfterSync rel{buf, s};
     char* d = buf.as<char>();
     PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oOff, E.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
     PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oCs, E.cs.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -1348,7 +1348,7 @@ int plslam_lc_correct_map(plslam_ctx* ctx, int32_t n_map_kf, const double* T_cor
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg2_(ctx->device);
     hipStream_t s = ctx->stream;
-    struct Rel { DevBuf& b; hipStream_t s; ~Rel() { (void)hipStreamSynchronize(s); b.release(); } } rel{buf, s};
+    ReleaseAfterSync rel{buf, s};
     if (rc) return rc;
     for (int k = 0; k < 2; ++k) {
         const plslam_lc_landmarks* L = kinds[k];

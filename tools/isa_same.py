@@ -7,8 +7,12 @@ Compiles every source of the product and of the legacy build (or the sources nam
 the flags plslam_amd/build.py gives that source, splits the listing per function symbol and compares, symbol by symbol, the
 instruction stream with its .amdhsa_ block and the kernel's entry in the code-object metadata (VGPRs, AGPRs, SGPRs, LDS
 and scratch bytes, spill counts, arguments); what is outside every function (LDS and constant symbols) is compared as
-"<file scope>".  Normalised away: comments, .file / .loc / .ident lines, the numbering of local labels and the
+"<file scope>".  Each tree is compiled from its own plslam_amd/build.py (source lists and flags).  A source both trees have is
+compared file against file; then the function symbols of the whole product library, and of the whole legacy library, are
+compared by name, so a kernel that moved to another file is matched and "only in A / B" is said of the library.  The file
+scope of the sources only one tree has is compared as the set of its lines.  Normalised away: comments, .file / .loc / .ident lines, the numbering of local labels and the
 __hip_cuid_<hash> symbol (derived from the file's text); nothing else.  Needs no GPU.  Exit status 1 when anything differs."""
+import importlib.util
 import os
 import re
 import subprocess
@@ -20,16 +24,27 @@ from plslam_amd import build as B  # noqa: E402
 
 
 def tree(path):
-    """(csrc, include) of a checkout, or of a bare csrc directory (then the include directory two levels up, else ours)."""
+    """(csrc, include, build module) of a checkout, or of a bare csrc directory (then the include directory two levels up and
+    the build.py beside it, else ours)."""
     path = os.path.abspath(path)
     csrc = path if os.path.exists(os.path.join(path, "common.hpp")) else os.path.join(path, "plslam_amd", "csrc")
     inc = os.path.join(os.path.dirname(os.path.dirname(csrc)), "include")
-    return csrc, inc if os.path.isdir(inc) else os.path.join(B._ROOT, "include")
+    build, Bt = os.path.join(os.path.dirname(csrc), "build.py"), B
+    if os.path.exists(build) and not os.path.samefile(build, B.__file__):
+        spec = importlib.util.spec_from_file_location("build_of_" + re.sub(r"\W", "_", path), build)
+        Bt = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(Bt)
+    return csrc, inc if os.path.isdir(inc) else os.path.join(B._ROOT, "include"), Bt
+
+
+def jobs_of(t):
+    Bt = t[2]
+    return [(s, False) for s in Bt.SOURCES] + [(s, True) for s in Bt.LEGACY_SOURCES + list(Bt.LEGACY_AWARE)]
 
 
 def assembly(t, src, legacy):
-    csrc, inc = t
-    flags = [f.replace(B.CSRC, csrc) for f in B._flags_for(src, legacy) if not f.startswith("-I")] + ["-I" + inc]
+    csrc, inc, Bt = t
+    flags = [f.replace(Bt.CSRC, csrc) for f in Bt._flags_for(src, legacy) if not f.startswith("-I")] + ["-I" + inc]
     r = subprocess.run([B.hipcc_path()] + flags + ["-S", "--cuda-device-only", os.path.join(csrc, src), "-o", "-"],
                        capture_output=True, text=True)
     if r.returncode != 0:
@@ -64,30 +79,63 @@ def split(text):
     return parts
 
 
+def library(t, listing, legacy, shared):
+    """{symbol: [its bodies, sorted]} over the sources of one library of tree t; "<file scope>": the set of file-scope lines of
+    its sources outside `shared` (the shared ones are compared file against file), local labels without their numbers."""
+    Bt, syms, scope = t[2], {}, set()
+    for src in Bt.SOURCES + (Bt.LEGACY_SOURCES if legacy else []):
+        for sym, v in listing[(src, legacy and (src, True) in listing)].items():
+            if sym != "<file scope>":
+                syms.setdefault(sym, []).append(v)
+            elif src not in shared:
+                scope |= {re.sub(r"\.L\d+", ".L", l) for l in v["code"]}
+    return {**{k: sorted(v, key=repr) for k, v in syms.items()}, "<file scope>": sorted(scope)}
+
+
+def differences(pa, pb):
+    bad = []
+    for sym in sorted(set(pa) | set(pb)):
+        if sym not in pa or sym not in pb:
+            bad.append(f"    {sym}: only in {'B' if sym in pb else 'A'}")
+        elif pa[sym] != pb[sym]:
+            bad.append(f"    {sym}: differs" if isinstance(pa[sym], list) else
+                       f"    {sym}: {', '.join(k for k in ('code', 'metadata') if pa[sym][k] != pb[sym][k])} differs")
+    return bad
+
+
 def main():
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     a, b = tree(sys.argv[1]), tree(sys.argv[2])
-    jobs = [(s, False) for s in B.SOURCES] + [(s, True) for s in B.LEGACY_SOURCES + list(B.LEGACY_AWARE)]
+    ja, jb = jobs_of(a), jobs_of(b)
     if sys.argv[3:]:
-        jobs = [j for j in jobs if j[0] in sys.argv[3:]]
+        ja, jb = ([j for j in jobs if j[0] in sys.argv[3:]] for jobs in (ja, jb))
     with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 2))) as ex:
-        listings = list(ex.map(lambda j: (split(assembly(a, *j)), split(assembly(b, *j))), jobs))
+        la, lb = (dict(zip(jobs, ex.map(lambda j: split(assembly(t, *j)), jobs))) for t, jobs in ((a, ja), (b, jb)))
     total, differing = 0, []
-    for (src, legacy), (pa, pb) in zip(jobs, listings):
-        bad = []
-        for sym in sorted(set(pa) | set(pb)):
-            if sym not in pa or sym not in pb:
-                bad.append(f"    {sym}: only in {'B' if sym in pb else 'A'}")
-            elif pa[sym] != pb[sym]:
-                bad.append(f"    {sym}: {', '.join(k for k in ('code', 'metadata') if pa[sym][k] != pb[sym][k])} differs")
+
+    def report(title, kernels, symbols, bad):
+        print(f"{title}  {kernels:3d} kernels, {symbols:3d} symbols: " + ("identical" if not bad else f"{len(bad)} DIFFER"))
+        print("\n".join(bad), end="\n" if bad else "")
+        differing.extend((title, l) for l in bad)
+
+    for src, legacy in [j for j in jb if j in la]:
+        pa, pb = la[(src, legacy)], lb[(src, legacy)]
         kernels = sum(1 for v in pb.values() if v["metadata"])
         total += kernels
-        print(f"{src:22s} {'legacy ' if legacy else 'product'}  {kernels:3d} kernels, {len(pb) - 1:3d} symbols: "
-              + ("identical" if not bad else f"{len(bad)} DIFFER"))
-        print("\n".join(bad), end="\n" if bad else "")
-        differing += [(src, l) for l in bad]
-    print(f"{len(jobs)} compilations, {total} kernels: " + ("all identical" if not differing else f"{len(differing)} symbols differ"))
+        report(f"{src:22s} {'legacy ' if legacy else 'product'}", kernels, len(pb) - 1, differences(pa, pb))
+    for side, mine, other in (("A", la, lb), ("B", lb, la)):
+        for src, legacy in [j for j in mine if j not in other]:
+            kernels = sum(1 for v in mine[(src, legacy)].values() if v["metadata"])
+            total += kernels if side == "B" else 0
+            print(f"{src:22s} {'legacy ' if legacy else 'product'}  {kernels:3d} kernels: only in {side}, compared library-wide")
+    if not sys.argv[3:]:
+        shared = {j[0] for j in ja} & {j[0] for j in jb}
+        for legacy in (False, True):
+            ua, ub = library(a, la, legacy, shared), library(b, lb, legacy, shared)
+            kernels = sum(1 for sym, bodies in ub.items() if sym != "<file scope>" and any(v["metadata"] for v in bodies))
+            report(f"{'every source, by symbol':22s} {'legacy ' if legacy else 'product'}", kernels, len(ub) - 1, differences(ua, ub))
+    print(f"{len(ja)} + {len(jb)} compilations, {total} kernels: " + ("all identical" if not differing else f"{len(differing)} symbols differ"))
     return 1 if differing else 0
 
 

@@ -5,48 +5,7 @@ import numpy as np
 import pytest
 
 
-def _rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
-def stereo_points(seed, n_l=1500, n_r=1500, width=752, height=480):
-    """Left key points, right ones displaced by a disparity along x with sub-pixel noise in y; a match table that is
-    mostly right, sometimes wrong, sometimes empty."""
-    r = _rng(seed)
-    kp_l = np.stack([r.uniform(0, width, n_l), r.uniform(0, height, n_l)], 1).astype(np.float32)
-    src = r.permutation(max(n_l, n_r))[:n_r] % max(n_l, 1)
-    disp = r.uniform(-3, 60, n_r)
-    kp_r = (kp_l[src] - np.stack([disp, r.normal(0, 0.8, n_r)], 1)).astype(np.float32)
-    m12 = np.full(n_l, -1, np.int32)
-    m12[src] = np.arange(n_r)
-    wrong = r.random(n_l) < 0.1
-    m12[wrong] = r.integers(0, max(n_r, 1), int(wrong.sum()))
-    m12[r.random(n_l) < 0.2] = -1
-    return m12, kp_l, kp_r
-
-
-def stereo_lines(seed, n_l=200, n_r=200, width=752, height=480):
-    r = _rng(seed)
-    a = np.stack([r.uniform(0, width, n_l), r.uniform(0, height, n_l)], 1)
-    ang = r.uniform(0, np.pi, n_l)
-    ln = r.uniform(5, 150, n_l)
-    ln[r.random(n_l) < 0.05] = 0.0                                     # zero-length segments
-    ang[r.random(n_l) < 0.1] = 0.0                                     # horizontal segments (dy = 0: division by zero)
-    seg_l = np.concatenate([a, a + np.stack([np.cos(ang), np.sin(ang)], 1) * ln[:, None]], 1)
-    src = r.permutation(max(n_l, n_r))[:n_r] % max(n_l, 1)
-    d0, d1 = r.uniform(-2, 50, n_r), r.uniform(0.5, 1.5, n_r)
-    seg_r = seg_l[src].copy()
-    seg_r[:, 0] -= d0
-    seg_r[:, 2] -= d0 * d1
-    seg_r += r.normal(0, 0.7, seg_r.shape)
-    cut = r.random(n_r) < 0.3                                          # right segment only partly overlapping in y
-    seg_r[cut, 2:] = seg_r[cut, :2] + (seg_r[cut, 2:] - seg_r[cut, :2]) * r.uniform(0.1, 0.9, (int(cut.sum()), 1))
-    m12 = np.full(n_l, -1, np.int32)
-    m12[src] = np.arange(n_r)
-    wrong = r.random(n_l) < 0.1
-    m12[wrong] = r.integers(0, max(n_r, 1), int(wrong.sum()))
-    m12[r.random(n_l) < 0.15] = -1
-    return m12, seg_l.astype(np.float32), seg_r.astype(np.float32)
+from stereo_gate_cases import _rng, stereo_lines, stereo_points  # noqa: F401  (shared with the threshold cases)
 
 
 def test_point_gate_semantics(oracle):

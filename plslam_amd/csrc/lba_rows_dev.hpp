@@ -1,5 +1,5 @@
 // lba_rows_dev.hpp -- device-side arithmetic of the local-BA rows (K3 / K4), shared by the row kernels (lba.hip) and the fused
-// iteration kernels of the LBA plan (lba_assemble.hip).  fp64; every translation unit that includes this is compiled with
+// iteration kernels of the LBA plan (lba_plan.hip).  fp64; every translation unit that includes this is compiled with
 // -ffp-contract=off, and every expression keeps the reference's source order (src/mapHandler.cpp:1358-1407, :1436-1516).
 #pragma once
 

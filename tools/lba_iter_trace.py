@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """plslam_lba_plan_iterate_dev at C3 sizes, repeated, for rocprofv3 --kernel-trace (tools/kt.sh): where one LM iteration's time goes.
 argv[2] = "schur": the whole LM iteration with state and blocks resident instead (iterate_resident + Schur step + the host's
-dense solve + back-substitution with the update applied): the kernels K19-K24 of lba_assemble.hip."""
+dense solve + back-substitution with the update applied): the kernels K19-K24 of lba_schur.hip (the iteration's own F1-F3: lba_plan.hip)."""
 import os
 import sys
 import time

@@ -300,45 +300,6 @@ int check_stereo_gate_problem(const plslam_stereo_gate_problem& q);
 int launch_median_desc(const uint8_t* desc, const int32_t* off, int32_t n_lm, int32_t total,
                        int32_t* med_idx, uint8_t* med_desc, hipStream_t s);
 
-// --- StVO::matchGrid, the windowed matcher (match_grid.hip) --------------------------------------
-struct GridDesc {              // one matchGrid problem; every pointer is a device pointer
-    const uint8_t* d1;         // n1 x 32
-    const uint8_t* d2;         // n2 x 32
-    const int32_t* centres;    // n1 x n_centres x 2 window centres (x, y)
-    const int32_t* cell_start; // cols*rows + 1   GridStructure in CSR form, cell id = x*rows + y
-    const int32_t* cell_items;
-    const double* dir1;        // n1 x 2 or nullptr (points)
-    const double* dir2;        // n2 x 2 or nullptr
-    int32_t* matches_12;       // n1
-    int32_t* n_matches;        // 1 or nullptr
-    uint32_t* scratch;         // grid_scratch_words() words: [tables when they do not fit LDS |] pair list
-    int32_t* status;           // incremented when the pair list does not fit pair_cap; may be nullptr
-    double sim_th, nnr;
-    int32_t n1, n2, n_centres, cols, rows, mutual;
-    int32_t w[4];              // width.first, width.second, height.first, height.second
-    int32_t pair_cap;
-    int32_t n_items;           // entries of cell_items the caller declared (cell_start[cols*rows] must not exceed it)
-};
-extern int g_grid_dense;       // ctx option "grid_dense" (process-wide): 1 = a small lone problem runs on k_match_grid_dense
-size_t grid_fixed_words(int32_t n1, int32_t n2, int64_t ncell);   // tables kept in LDS when they fit
-bool grid_fits_lds(int32_t n1, int32_t n2, int64_t ncell);
-size_t grid_lds_bytes(int mode, int32_t n1, int32_t n2, int64_t ncell, int32_t n_items, bool dirs = false);
-int grid_mode(int32_t n1, int32_t n2, int64_t ncell, int32_t n_items, bool dirs = false);   // 2: all in LDS, 1: tables in LDS, 0: global
-size_t grid_scratch_words(int32_t n1, int32_t n2, int64_t ncell, int32_t pair_cap);
-int64_t grid_store_capacity_host(const int32_t* centres, int32_t n1, int32_t n_centres, const int32_t* cell_start,
-                                 int32_t cols, int32_t rows, const int32_t window[4], int mutual);
-// one problem with DEVICE pointers on `s` (scratch: grid_scratch_words() words; status: one zeroed int32)
-int launch_match_grid_one(const plslam_grid_problem& q, uint32_t* scratch, int32_t* status, GridDesc* d_desc_slot,
-                          GridDesc* h_desc_slot, hipStream_t s);
-// the same in two steps (the descriptor inside a larger upload of the caller): host-side check + fill, then the launch
-int grid_prepare_one(const plslam_grid_problem& q, uint32_t* scratch, int32_t* status, GridDesc* h_desc_slot);
-int grid_launch_prepared(const plslam_grid_problem& q, const GridDesc* d_desc_slot, hipStream_t s);
-// launch groups: 3 = all in LDS / 256-lane workgroups (n1 <= 256), 2 = all in LDS, 1 = tables in LDS, 0 = global
-int grid_group(int32_t n1, int32_t n2, int64_t ncell, int32_t n_items, bool dirs = false);
-size_t grid_group_lds_bytes(int group, int32_t n1, int32_t n2, int64_t ncell, int32_t n_items, bool dirs = false);
-// table order: the n[3] problems of group 3, then n[2], n[1], n[0]
-int launch_match_grid(const GridDesc* d_probs, const int32_t n[4], const size_t lds_bytes[4], hipStream_t s);
-
 // --- LBD float -> binary line descriptor (lbd.hip) ---------------------------------------------
 // lbd: n x 72 f32, codes: n x 32 u8 (both 16-byte aligned)
 int launch_lbd_binarise(const float* lbd, int32_t n, uint8_t* codes, hipStream_t s);

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "common.hpp"
+#include "match_grid.hpp"   // g_grid_dense
 #include "match_plan.hpp"   // match_plan_release: the context owns two plans
 
 namespace plslam {

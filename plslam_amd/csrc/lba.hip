@@ -7,6 +7,7 @@
 // (inlier masks) are reproducible bit for bit against the CPU restatement.
 #include "lba_rows_dev.hpp"
 #include "lookback_dev.hpp"
+#include "match_grid.hpp"   // GridDesc: k_visible_compact writes the row count into a descriptor
 
 namespace plslam {
 

@@ -11,17 +11,11 @@
 #include <cstring>
 #include <vector>
 
+#include "match_grid.hpp"
 #include "match_plan.hpp"
 
 namespace plslam {
 
-// match_grid.hip: one matchGrid problem on `s`, with its scratch (a large mutual problem gets its distances from a
-// many-workgroup launch)
-int grid_launch_single(const plslam_grid_problem& q, const GridDesc* d_desc, hipStream_t s, uint32_t* aux, bool n1_upper_bound,
-                       const GridDesc* h_desc = nullptr);   // h_desc: the host's copy (kernels of a lone problem take it by value)
-bool grid_dense_ok(int32_t n1, int32_t n2, int64_t ncell, int32_t n_items, bool dirs, int32_t n_centres);   // the one-workgroup kernel takes it
-size_t grid_aux_words(int32_t n2);            // the words the two launches share, prefilled by grid_aux_fill in the upload image
-void grid_aux_fill(void* host_image, int32_t n2);
 // lba.hip: the visibility pre-filter AND the candidate flags, both on the device
 int launch_visible_cand(const plslam_cam& K, const double* Twf16, const double* X, const uint8_t* cand, int32_t n, int lines,
                         uint8_t* vis, hipStream_t s);
@@ -38,9 +32,6 @@ int launch_visible_compact(const plslam_cam& K, const double* Twf16, const doubl
 int launch_prepare_rows(const plslam_cam& K, const double* Twf16, const void* md, const double* lm, const int32_t* idx,
                         const int32_t* n_dev, int32_t n_max, int lines, double inv_w, double inv_h, void* Q, double* QL, int32_t* cells,
                         double* dir1, hipStream_t s);
-// match_grid.hip: capacity of the windowed matcher's candidate store from the grid alone
-int64_t grid_store_capacity_bound(int32_t n1, int32_t n_centres, const int32_t* cell_start, int32_t cols, int32_t rows,
-                                  const int32_t window[4], int mutual);
 
 __global__ void __launch_bounds__(256)
 k_gather_rows(const uint64_t* __restrict__ src, const int32_t* __restrict__ idx, int32_t n, int32_t words,

@@ -8,7 +8,7 @@ the flags plslam_amd/build.py gives that source, splits the listing per function
 instruction stream with its .amdhsa_ block and the kernel's entry in the code-object metadata (VGPRs, AGPRs, SGPRs, LDS
 and scratch bytes, spill counts, arguments); what is outside every function (LDS and constant symbols) is compared as
 "<file scope>".  Each tree is compiled from its own plslam_amd/build.py (source lists and flags).  A source both trees have is
-compared file against file; then the function symbols of the whole product library, and of the whole legacy library, are
+compared file against file (unless its functions are not the same set in both: it was split or merged); then the function symbols of the whole product library, and of the whole legacy library, are
 compared by name, so a kernel that moved to another file is matched and "only in A / B" is said of the library.  The file
 scope of the sources only one tree has is compared as the set of its lines.  Normalised away: comments, .file / .loc / .ident lines, the numbering of local labels and the
 __hip_cuid_<hash> symbol (derived from the file's text); nothing else.  Needs no GPU.  Exit status 1 when anything differs."""
@@ -119,10 +119,15 @@ def main():
         print("\n".join(bad), end="\n" if bad else "")
         differing.extend((title, l) for l in bad)
 
+    # a source both trees have whose functions are not the same set was split or merged: library-wide, like a new source
+    moved = {j for j in jb if j in la and set(la[j]) != set(lb[j])}
     for src, legacy in [j for j in jb if j in la]:
         pa, pb = la[(src, legacy)], lb[(src, legacy)]
         kernels = sum(1 for v in pb.values() if v["metadata"])
         total += kernels
+        if (src, legacy) in moved:
+            print(f"{src:22s} {'legacy ' if legacy else 'product'}  {kernels:3d} kernels: other functions than in A, compared library-wide")
+            continue
         report(f"{src:22s} {'legacy ' if legacy else 'product'}", kernels, len(pb) - 1, differences(pa, pb))
     for side, mine, other in (("A", la, lb), ("B", lb, la)):
         for src, legacy in [j for j in mine if j not in other]:
@@ -130,7 +135,7 @@ def main():
             total += kernels if side == "B" else 0
             print(f"{src:22s} {'legacy ' if legacy else 'product'}  {kernels:3d} kernels: only in {side}, compared library-wide")
     if not sys.argv[3:]:
-        shared = {j[0] for j in ja} & {j[0] for j in jb}
+        shared = ({j[0] for j in ja} & {j[0] for j in jb}) - {j[0] for j in moved}
         for legacy in (False, True):
             ua, ub = library(a, la, legacy, shared), library(b, lb, legacy, shared)
             kernels = sum(1 for sym, bodies in ub.items() if sym != "<file scope>" and any(v["metadata"] for v in bodies))

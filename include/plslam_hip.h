@@ -45,7 +45,8 @@ extern "C" {
  * plslam_gba_plan_create / plslam_gba_optimize / plslam_gba_plan_destroy and plslam_dense_ldlt_solve; the loop-closure
  * correction plslam_pgo_plan_create / plslam_pgo_optimize / plslam_pgo_plan_destroy, plslam_lc_correct_map[_dev] and
  * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks; the local map
- * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts.
+ * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts; the map
+ * insertion plslam_map_insert_* with plslam_map_insert_kind / _dst / _counts / _events.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1258,6 +1259,78 @@ int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int
                           plslam_local_map_counts* counts);
 int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out);
 int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffers* host);
+
+/* ---- a keyframe's matches into the device-resident map: the four insertion loops of MapHandler::addKeyFrame ------------- */
+/* matchKF2KFPoints :280-360, matchKF2KFLines :428-527, matchMap2KFPoints :601-629 (after the gate), matchMap2KFLines :716-749
+ * (src/mapHandler.cpp), over plslam_map_index, OUT OF PLACE: `src` is read, every array of `dst` is written (K63-K67, KERNELS.md);
+ * the caller ping-pongs two images.  Slot kf2 is already present in src with its features at -1 / PLSLAM_FEAT_NULL.
+ *
+ * An EVENT is a table entry i2 >= 0 the reference acts on, in ascending i1.
+ *   kf2kf   table[n_table] = matches_12 (i1: feature of kf1, i2: feature of kf2).  feat_idx[kf1][i1] == -1: a NEW landmark, index
+ *           n + (rank among the new-landmark events), valid, inlier, X = T_kf1_w applied to P (lines: sP, eP), two observations
+ *           (kf1, obs1[i1]) then (kf2, obs2[i2]), both features receive the index, row_delta[kf1] += 1.  Otherwise lm =
+ *           feat_idx[kf1][i1]: out of range or not valid -> nothing (:333, :493); else feat_idx[kf2][i2] = lm, one observation
+ *           (kf2, obs2[i2]) appended, row_delta[obs] += 1 for every entry obs != kf2 of the landmark's list.
+ *   map2kf  table[n_table <= n] = map_to_kf as the plslam_map2kf_match_* drivers return it (i1: the landmark, i2: ORIGINAL feature
+ *           of kf2), already gated: feat_idx[kf2][i2] = i1, one observation appended, row_delta as above; the reference has no
+ *           validity check here (:615-619) and neither has this.
+ * Two events that name the same i2 both append; the later one's index stays in feat_idx.  Two events on one landmark append in
+ * event order.  Deviation: an event that names a PLSLAM_FEAT_NULL feature, or an i1 / i2 beyond the keyframe's features or the
+ * arrays given, is SKIPPED (the reference throws, :285-288, or reads out of bounds).
+ * row_delta[n_map_kf] (HOST, int32, overwritten): the increment of full_graph[kf2][.] and of full_graph[.][kf2]; full_graph
+ * stays with the caller.  Also with the caller: hasRefinement's matched_pt / matched_ls, --matches, map_*_kf_idx, desc_list /
+ * dir_list / pts_list -- driven by the event records (plslam_map_insert_events).
+ * All arithmetic fp64 without contraction: R p + t as ((r0 p0 + r1 p1) + r2 p2) + t, the norm as sqrt((x^2 + y^2) + z^2).
+ *
+ * plslam_map_insert_kind: HOST arrays of one landmark kind; a NULL struct or table = no entry of that kind (the kind's image is
+ *   still copied).  P1 / P2: n_prev / n_curr x 3 (PointFeature::P) or x 6 (LineFeature::sP, eP) of kf1 / kf2; obs1 / obs2: x 2
+ *   (pl) or x 3 (le).  map2kf reads n_curr, P2 and obs2 only.  kf2kf: n_table <= PLSLAM_MAP_INSERT_MAX_TABLE.
+ * plslam_map_insert_dst: a plslam_map_index over caller-owned DEVICE buffers (every pointer is written through; kf_valid,
+ *   x_kf_w and the two feat_ptr may be the source's own pointers, nothing else may) and their capacities in landmarks and
+ *   observations per kind (feat_idx: the source's n_feat).  The growth is bounded by the tables alone, m = entries i2 >= 0:
+ *   kf2kf needs n + m landmarks and n_obs + 2 m observations, map2kf n and n_obs + m; a smaller capacity -> PLSLAM_ERANGE before
+ *   anything is launched or written.  On success map.n_map_kf and each kind's n, n_obs, n_feat are set: &dst->map is the next
+ *   call's source.  PLSLAM_EINVAL: NULL arguments, slots out of range, kf1 == kf2, a destination array that is a source array.
+ * Every index read from the image or a table is range-checked on the device. */
+#define PLSLAM_MAP_INSERT_MAX_TABLE 65536
+typedef struct plslam_map_insert_kind {
+    const int32_t* table;
+    int32_t n_table, n_prev, n_curr;
+    const double *P1, *obs1, *P2, *obs2;
+} plslam_map_insert_kind;
+typedef struct plslam_map_insert_dst {
+    plslam_map_index map;
+    int32_t pt_cap, pt_obs_cap, ls_cap, ls_obs_cap;
+} plslam_map_insert_dst;
+typedef struct plslam_map_insert_kind_counts {
+    int32_t n_events, n_new, n_appended, n_skipped;      /* n_appended = n_events + n_new; n_skipped: entries i2 >= 0 not acted on */
+} plslam_map_insert_kind_counts;
+typedef struct plslam_map_insert_counts {
+    plslam_map_insert_kind_counts points, lines;
+} plslam_map_insert_counts;
+/* The event records of the last insert, per kind, in event order: ev n_events x 4 int32 (landmark, i1, i2, is_new); dir
+ * n_events x 6 doubles: the direction of the new landmark's FIRST observation (zeros for an existing landmark), then that of the
+ * kf2 observation -- new point: P3d.normalized() (:299), then P3d / P3d.norm() (:311); existing point: p3d.normalized() (:338);
+ * map2kf point: R normalized(P) + t (:608, :618: the translation added to a direction is the reference's); lines: the
+ * transformed midpoint, normalised (:449-450, :463-465, :496-498, :734-736).  Device pointers (valid until the next insert /
+ * destroy, ordered on `stream`) or, for download, HOST pointers (NULL = skip; `stream` ignored). */
+typedef struct plslam_map_insert_events {
+    int32_t *pt_ev, *ls_ev;
+    double *pt_dir, *ls_dir;
+    void* stream;
+} plslam_map_insert_events;
+typedef struct plslam_map_insert plslam_map_insert;
+int plslam_map_insert_create(plslam_ctx* ctx, plslam_map_insert** out);
+void plslam_map_insert_destroy(plslam_map_insert* mi);
+/* T_kf1_w / T_kf2_w: KeyFrame::T_kf_w of the two slots, 16 doubles row-major. */
+int plslam_map_insert_kf2kf(plslam_map_insert* mi, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf1_idx,
+                            int32_t kf2_idx, const double* T_kf1_w, const double* T_kf2_w, const plslam_map_insert_kind* points,
+                            const plslam_map_insert_kind* lines, int32_t* row_delta, plslam_map_insert_counts* counts);
+int plslam_map_insert_map2kf(plslam_map_insert* mi, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf2_idx,
+                             const double* T_kf2_w, const plslam_map_insert_kind* points, const plslam_map_insert_kind* lines,
+                             int32_t* row_delta, plslam_map_insert_counts* counts);
+int plslam_map_insert_device_buffers(plslam_map_insert* mi, plslam_map_insert_events* out);
+int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_events* host);
 
 #ifdef __cplusplus
 }

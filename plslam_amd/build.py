@@ -23,7 +23,7 @@ OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 # other row of SURVEY section 8
 SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_mfma_i.hip", "lba.hip", "lba_assemble_rows.hip", "lba_plan.hip", "lba_schur.hip",
            "map2kf.hip", "lbd.hip", "median_desc.hip", "match_grid.hip", "match_grid_listers.hip", "match_grid_dense.hip", "match_grid_api.hip", "stereo_gates.hip", "pose_gn.hip", "lbd_float.hip", "bow.hip",
-           "loop_closure.hip", "gba.hip", "pgo.hip", "local_map.hip",
+           "loop_closure.hip", "gba.hip", "pgo.hip", "local_map.hip", "map_insert.hip",
            "context.hip", "match_plan.hip", "host_calls.hip", "match_pipeline.hip", "gather.hip"]
 # earlier generations of the matrix-core scan, reachable only through the context option "mfma_form" (1 = K1e, 3 = K1g,
 # 4 = K1h -- whose scan kernel sits behind the same macro in hamming_mfma_h.hip): cross-checks for the tests and A/B baselines

@@ -63,6 +63,8 @@ ABI_SYMBOLS = (
     "plslam_lc_correct_map_dev", "plslam_envelope_ldlt_solve",
     "plslam_local_map_create", "plslam_local_map_destroy", "plslam_local_map_form", "plslam_local_map_candidates",
     "plslam_local_map_gather", "plslam_local_map_cull", "plslam_local_map_device_buffers", "plslam_local_map_download",
+    "plslam_map_insert_create", "plslam_map_insert_destroy", "plslam_map_insert_kf2kf", "plslam_map_insert_map2kf",
+    "plslam_map_insert_device_buffers", "plslam_map_insert_download",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -272,7 +274,7 @@ _RESTYPES = {
     "plslam_ctx_destroy": None, "plslam_match_plan_destroy": None, "plslam_lba_plan_destroy": None,
     "plslam_grid_plan_destroy": None, "plslam_match_pipeline_destroy": None, "plslam_bow_vocab_destroy": None,
     "plslam_bow_db_destroy": None, "plslam_gba_plan_destroy": None, "plslam_pgo_plan_destroy": None,
-    "plslam_local_map_destroy": None,
+    "plslam_local_map_destroy": None, "plslam_map_insert_destroy": None,
 }
 
 
@@ -436,6 +438,13 @@ def load() -> C.CDLL:
     L.plslam_local_map_cull.argtypes = [vp, vp, i32, i32, vp]
     L.plslam_local_map_device_buffers.argtypes = [vp, vp]
     L.plslam_local_map_download.argtypes = [vp, vp]
+    # the map insertion (plslam_amd/map_insert.py): structs by address, host arrays as pointers
+    L.plslam_map_insert_create.argtypes = [vp, C.POINTER(vp)]
+    L.plslam_map_insert_destroy.argtypes = [vp]
+    L.plslam_map_insert_kf2kf.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.plslam_map_insert_map2kf.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.plslam_map_insert_device_buffers.argtypes = [vp, vp]
+    L.plslam_map_insert_download.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:
         getattr(L, name).restype = _RESTYPES.get(name, C.c_int)
     _lib = L

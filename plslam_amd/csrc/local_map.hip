@@ -38,18 +38,6 @@ KindD kind_d(const plslam_map_landmarks& L, int lines)
     return KindD{L.n, L.n_obs, L.n_feat, lines ? 6 : 3, lines ? 3 : 2, L.valid, L.inlier, L.X, L.obs_ptr, L.obs_kf, L.obs_val, L.feat_ptr, L.feat_idx};
 }
 
-// the largest k in [0, n) with ptr[k] <= x (ptr ascending, ptr[0] <= x): the segment an item of a CSR list belongs to
-__device__ __forceinline__ int segment_of(const int32_t* __restrict__ ptr, int n, int32_t x)
-{
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The counters of a call's LAST kernel: every wave adds its ballots to the device words and WAITS for the atomics (returning
 // ones) before the workgroup's barrier; one lane then counts the workgroup in, and the last workgroup copies the words to the
 // page-locked block the host reads (lba.hip: gate_count_and_publish).  done: a ZERO device word.

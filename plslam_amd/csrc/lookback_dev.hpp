@@ -1,5 +1,6 @@
 // lookback_dev.hpp -- the decoupled look-back the stable compactions share (lba.hip: k_visible_compact; local_map.hip: the
-// local-map lists and the observation offsets).  One copy: a change here moves every list that is built with it.
+// local-map lists and the observation offsets; map_insert.hip: the event list and the new obs_ptr), and the bisection that finds
+// an item's segment in the offsets such a scan leaves.  One copy: a change here moves every list that is built with it.
 //
 // A launch's workgroups chain their counts through part[b], one word per workgroup, ZERO when the kernel starts: bit 30 = "my own
 // count is here", bit 31 = "the count of everything up to and including me is here", the low 30 bits the count (sums stay below
@@ -47,6 +48,18 @@ __device__ __forceinline__ uint32_t lookback_exclusive(uint32_t* __restrict__ pa
     }
     __syncthreads();
     return *s_before;
+}
+
+// the largest k in [0, n) with ptr[k] <= x (ptr ascending, ptr[0] <= x): the segment an item of a CSR list belongs to
+__device__ __forceinline__ int segment_of(const int32_t* __restrict__ ptr, int n, int32_t x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (ptr[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
 }
 
 }  // namespace plslam

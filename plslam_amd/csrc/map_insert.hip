@@ -1,0 +1,592 @@
+// map_insert.hip -- the four insertion loops of MapHandler::addKeyFrame (src/mapHandler.cpp: matchKF2KFPoints :280-360,
+// matchKF2KFLines :428-527, matchMap2KFPoints :601-629, matchMap2KFLines :716-749) over the device-resident CSR image of the map
+// (plslam_map_index), OUT OF PLACE: the source image is read, every array of the destination is written.  Per landmark kind:
+//   K63 the event list: a lane per table entry classifies it from the SOURCE image (no event reads what another one writes: the
+//       keyframe-1 features are written by their own event only, keyframe 2's are never read as landmark indices), one stable
+//       compaction with three look-back chains (events, new landmarks, (event, old observation) pairs); the event records and
+//       directions; integer atomics COUNT the appended observations per landmark and keep the smallest / largest event number
+//       per landmark / per keyframe-2 feature -- none of them decides an order
+//   K64 the new obs_ptr: a look-back scan over n + n_new landmarks; valid / inlier / X copied, the new rows computed
+//   K65 obs_kf / obs_val: a lane per OUTPUT observation, its landmark by bisection (K61); the old entry copied or the event's
+//       written -- the k-th event of a landmark is found by walking the event list from the landmark's first event, in event order
+//   K66 feat_idx (copy; the last event of a keyframe-2 feature wins; a new landmark's keyframe-1 feature) and row_delta: a lane
+//       per (event, old observation), int32 atomic adds
+//   K67 the counts and row_delta to the page-locked block the host reads
+// Every output is an integer, a flag, a verbatim copy of a double or a fixed-order fp64 expression of correctly rounded
+// operations: bit-exact against the sequential restatement (tests/map_insert_ref.py).  Every index read from the image or a
+// table is range-checked before it is used as an address.
+#include <cstring>
+
+#include "common.hpp"
+#include "lookback_dev.hpp"
+#include "se3_dev.hpp"
+
+namespace plslam {
+namespace {
+
+constexpr int MI_NT = 256;              // lanes per workgroup = items per look-back tile (plslam_amd/map_insert.py: LOOKBACK_TILE)
+constexpr int MI_NW = MI_NT / 64;
+constexpr unsigned MI_MAX_GRID = 4096;  // K66 strides over its items
+// the call counters (device words, mirrored in the page-locked block): four per kind
+enum { W_EV = 0, W_NEW, W_PAIRS, W_OBS, W_KIND = 4, W_WORDS = 8 };
+enum { MODE_KF2KF = 0, MODE_MAP2KF = 1 };
+
+struct SrcD {                           // one landmark kind of the source image
+    int32_t n, n_obs, n_feat, dl, dv;   // dl: doubles per landmark / feature position (3 / 6), dv: doubles per observation (2 / 3)
+    const uint8_t *valid, *inlier;
+    const double* X;
+    const int32_t *obs_ptr, *obs_kf;
+    const double* obs_val;
+    const int32_t *feat_ptr, *feat_idx;
+};
+struct DstD {                           // ... of the destination
+    uint8_t *valid, *inlier;
+    double* X;
+    int32_t *obs_ptr, *obs_kf;
+    double* obs_val;
+    int32_t* feat_idx;
+    int32_t cap, obs_cap;
+};
+struct CallD {                          // one kind's tables and scratch (device), carved from the handle's buffer
+    int32_t mode, lines, n_map_kf, kf1, kf2, n_tab, n_prev, n_curr, e_cap;
+    const double* T;                    // T_kf1_w, T_kf2_w: 2 x 16
+    const int32_t* tab;
+    const double *P1, *o1, *P2, *o2;
+    int32_t *i1_lm, *ev, *pair_off, *new_ev, *app_cnt, *head, *feat_win, *cnt;
+    double* ev_dir;
+};
+
+// the length of a landmark's list in the source image, 0 where obs_ptr is not a list inside obs_kf
+__device__ __forceinline__ int32_t old_len(const SrcD& S, int32_t lm)
+{
+    const int32_t b = S.obs_ptr[lm], e = S.obs_ptr[lm + 1];
+    return b >= 0 && e > b && e <= S.n_obs ? e - b : 0;
+}
+// the features of a slot: [f0, f0 + nf) inside feat_idx, empty where feat_ptr is not
+__device__ __forceinline__ void slot_features(const SrcD& S, int32_t kf, int32_t& f0, int32_t& nf)
+{
+    f0 = nf = 0;
+    if (S.n_feat <= 0) return;
+    const int32_t b = S.feat_ptr[kf], e = S.feat_ptr[kf + 1];
+    if (b >= 0 && e > b && e <= S.n_feat) { f0 = b; nf = e - b; }
+}
+// Eigen's normalized(): v / sqrt(squaredNorm) where the squared norm is positive, else v itself; (x^2 + y^2) + z^2
+__device__ __forceinline__ void normalized3(const double v[3], double o[3])
+{
+    const double z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    if (z > 0.0) {
+        const double s = sqrt(z);
+        o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
+    } else {
+        o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    }
+}
+// v / v.norm(): no guard (:311)
+__device__ __forceinline__ void over_norm3(const double v[3], double o[3])
+{
+    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
+}
+// 0.5 * (sP + eP) of a line feature (6 doubles)
+__device__ __forceinline__ void midpoint(const double* __restrict__ se, double m[3])
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) m[a] = 0.5 * (se[a] + se[3 + a]);
+}
+
+// K63: the event list.  A lane per table entry.
+__global__ void __launch_bounds__(MI_NT)
+k_mi_events(SrcD S, CallD C, uint32_t* __restrict__ part_e, uint32_t* __restrict__ part_n, uint32_t* __restrict__ part_p)
+{
+    __shared__ uint32_t s_e[MI_NW], s_n[MI_NW], s_p[MI_NW], s_before_e, s_before_n, s_before_p;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
+    const int32_t i1 = b * MI_NT + tid;
+    bool ev = false, nw = false;
+    int32_t lm = -1, i2 = -1;
+    uint32_t pairs = 0;
+    if (i1 < C.n_tab) {
+        i2 = C.tab[i1];
+        if (i2 >= 0) {
+            int32_t f0, nf;
+            slot_features(S, C.kf2, f0, nf);
+            const int32_t f2 = i2 < nf && i2 < C.n_curr ? S.feat_idx[f0 + i2] : PLSLAM_FEAT_NULL;
+            if (f2 != PLSLAM_FEAT_NULL) {
+                if (C.mode == MODE_KF2KF) {
+                    slot_features(S, C.kf1, f0, nf);
+                    const int32_t f1 = i1 < nf && i1 < C.n_prev ? S.feat_idx[f0 + i1] : PLSLAM_FEAT_NULL;
+                    if (f1 == -1) ev = nw = true;                                           // :291 / :439
+                    else if (f1 >= 0 && f1 < S.n && S.valid[f1]) { ev = true; lm = f1; }    // :333 / :493
+                } else if (i1 < S.n) {                                                      // :615 / :731: no validity check
+                    ev = true;
+                    lm = i1;
+                }
+            }
+        }
+    }
+    if (ev) pairs = nw ? 1u : (uint32_t)old_len(S, lm);       // (a new landmark's pair: full_graph[kf2][kf1]++)
+    const uint64_t me = __ballot(ev), mn = __ballot(nw);
+    uint32_t incl = pairs;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 0) { s_e[wv] = (uint32_t)__popcll(me); s_n[wv] = (uint32_t)__popcll(mn); }
+    if (lane == 63) s_p[wv] = incl;
+    __syncthreads();
+    uint32_t own_e = 0, in_e = 0, own_n = 0, in_n = 0, own_p = 0, in_p = 0;
+#pragma unroll
+    for (int w = 0; w < MI_NW; ++w) {
+        in_e += w < wv ? s_e[w] : 0u; own_e += s_e[w];
+        in_n += w < wv ? s_n[w] : 0u; own_n += s_n[w];
+        in_p += w < wv ? s_p[w] : 0u; own_p += s_p[w];
+    }
+    const uint32_t before_e = lookback_exclusive(part_e, b, own_e, &s_before_e);
+    const uint32_t before_n = lookback_exclusive(part_n, b, own_n, &s_before_n);
+    const uint32_t before_p = lookback_exclusive(part_p, b, own_p, &s_before_p);
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int32_t e = (int32_t)(before_e + in_e + (uint32_t)__popcll(me & below));
+    const int32_t r = (int32_t)(before_n + in_n + (uint32_t)__popcll(mn & below));
+    if (nw) lm = S.n + r;
+    if (C.mode == MODE_KF2KF && i1 < C.n_tab) C.i1_lm[i1] = nw && e < C.e_cap ? lm : -1;
+    if (ev && e < C.e_cap) {
+        int32_t* rec = C.ev + 4 * (size_t)e;
+        rec[0] = lm; rec[1] = i1; rec[2] = i2; rec[3] = nw ? 1 : 0;
+        C.pair_off[e] = (int32_t)(before_p + in_p + incl - pairs);
+        if (nw) C.new_ev[r] = e;
+        else {
+            atomicAdd(C.app_cnt + lm, 1);
+            atomicMin(C.head + lm, e);
+        }
+        atomicMax(C.feat_win + i2, e + 1);
+        // the observation directions
+        double d1[3] = {0.0, 0.0, 0.0}, d2[3], p[3], q[3];
+        const double *T1 = C.T, *T2 = C.T + 16;
+        if (C.lines) {
+            if (nw) {
+                double sP[3], eP[3];
+                xform(T1, C.P1 + 6 * (size_t)i1, sP);
+                xform(T1, C.P1 + 6 * (size_t)i1 + 3, eP);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) p[a] = 0.5 * (sP[a] + eP[a]);
+                normalized3(p, d1);
+            }
+            midpoint(C.P2 + 6 * (size_t)i2, p);
+            xform(T2, p, q);
+            normalized3(q, d2);
+        } else if (C.mode == MODE_MAP2KF) {
+            normalized3(C.P2 + 3 * (size_t)i2, p);                                          // :608
+            xform(T2, p, d2);                                                               // :618
+        } else {
+            if (nw) {
+                xform(T1, C.P1 + 3 * (size_t)i1, p);
+                normalized3(p, d1);                                                         // :299
+            }
+            xform(T2, C.P2 + 3 * (size_t)i2, q);
+            if (nw) over_norm3(q, d2);                                                      // :311
+            else normalized3(q, d2);                                                        // :338
+        }
+        double* d = C.ev_dir + 6 * (size_t)e;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { d[a] = d1[a]; d[3 + a] = d2[a]; }
+    }
+    if (b == (int)gridDim.x - 1 && tid == 0) {
+        const int32_t n_ev = (int32_t)(before_e + own_e);
+        C.cnt[W_EV] = n_ev < C.e_cap ? n_ev : C.e_cap;
+        C.cnt[W_NEW] = (int32_t)(before_n + own_n) < C.e_cap ? (int32_t)(before_n + own_n) : C.e_cap;
+        C.cnt[W_PAIRS] = (int32_t)(before_p + own_p);
+    }
+}
+
+// K64: obs_ptr of the destination (an exclusive look-back scan of the new list lengths over n + n_new landmarks) and the
+// landmark rows: valid / inlier / X copied; a new landmark is valid, an inlier and X = T_kf1_w P (:297, :445-448).
+__global__ void __launch_bounds__(MI_NT)
+k_mi_ptr(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
+{
+    __shared__ uint32_t s_o[MI_NW], s_before;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
+    const int32_t i = b * MI_NT + tid;
+    int32_t n_new = C.cnt[W_NEW];
+    if (n_new > D.cap - S.n) n_new = D.cap - S.n;
+    const int32_t n2 = S.n + (n_new > 0 ? n_new : 0);
+    uint32_t c = 0;
+    if (i < S.n) c = (uint32_t)(old_len(S, i) + C.app_cnt[i]);
+    else if (i < n2) c = 2u;
+    uint32_t incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_o[wv] = incl;
+    __syncthreads();
+    uint32_t own = 0, in = 0;
+#pragma unroll
+    for (int w = 0; w < MI_NW; ++w) {
+        in += w < wv ? s_o[w] : 0u;
+        own += s_o[w];
+    }
+    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
+    if (i < n2) {
+        D.obs_ptr[i] = (int32_t)(before + in + incl - c);
+        if (i < S.n) {
+            D.valid[i] = S.valid[i];
+            D.inlier[i] = S.inlier[i];
+            for (int w = 0; w < S.dl; ++w) D.X[(size_t)S.dl * i + w] = S.X[(size_t)S.dl * i + w];
+        } else {
+            const int32_t i1 = C.ev[4 * (size_t)C.new_ev[i - S.n] + 1];
+            D.valid[i] = 1;
+            D.inlier[i] = 1;
+            xform(C.T, C.P1 + (size_t)S.dl * i1, D.X + (size_t)S.dl * i);
+            if (C.lines) xform(C.T, C.P1 + 6 * (size_t)i1 + 3, D.X + 6 * (size_t)i + 3);
+        }
+    }
+    if (b == (int)gridDim.x - 1 && tid == 0) {
+        D.obs_ptr[n2] = (int32_t)(before + own);
+        C.cnt[W_OBS] = (int32_t)(before + own);
+    }
+}
+
+// K65: obs_kf / obs_val of the destination: a lane per OUTPUT observation.  Its landmark by bisection of the new obs_ptr (empty
+// lists share an offset with their successor: the last one at or below the lane owns it); inside the landmark's list the old
+// entries come first, verbatim, then the events' in event order: the k-th event that names the landmark, counted from the
+// landmark's first event (the atomics of K63 gave the count and the first event; the ORDER is the event list's).
+__global__ void __launch_bounds__(MI_NT)
+k_mi_obs(SrcD S, DstD D, CallD C)
+{
+    const int64_t t = (int64_t)blockIdx.x * MI_NT + threadIdx.x;
+    const int32_t total = C.cnt[W_OBS], n_ev = C.cnt[W_EV];
+    int32_t n_new = C.cnt[W_NEW];
+    if (n_new > D.cap - S.n) n_new = D.cap - S.n;
+    const int32_t n2 = S.n + (n_new > 0 ? n_new : 0);
+    if (t >= total || t >= D.obs_cap || n2 <= 0) return;
+    const int32_t j = (int32_t)t;
+    const int32_t lm = segment_of(D.obs_ptr, n2, j), o = j - D.obs_ptr[lm];
+    int32_t kf = -1;
+    const double* val = nullptr;
+    if (lm < S.n) {
+        const int32_t ol = old_len(S, lm);
+        if (o < ol) {
+            const size_t src = (size_t)S.obs_ptr[lm] + o;
+            kf = S.obs_kf[src];
+            val = S.obs_val + (size_t)S.dv * src;
+        } else {
+            int32_t k = o - ol, e = C.head[lm];
+            for (; e >= 0 && e < n_ev; ++e)
+                if (C.ev[4 * (size_t)e] == lm && k-- == 0) break;
+            if (e >= 0 && e < n_ev) {
+                kf = C.kf2;
+                val = C.o2 + (size_t)S.dv * C.ev[4 * (size_t)e + 2];
+            }
+        }
+    } else {
+        const int32_t* rec = C.ev + 4 * (size_t)C.new_ev[lm - S.n];
+        kf = o == 0 ? C.kf1 : C.kf2;
+        val = o == 0 ? C.o1 + (size_t)S.dv * rec[1] : C.o2 + (size_t)S.dv * rec[2];
+    }
+    D.obs_kf[j] = kf;
+    for (int w = 0; w < S.dv; ++w) D.obs_val[(size_t)S.dv * j + w] = val ? val[w] : 0.0;
+}
+
+// K66: feat_idx of the destination and row_delta; the kernel strides over n_feat features, then the (event, old observation)
+// pairs.  A feature of keyframe 2 takes the landmark of the LAST event that names it (K63's atomic max of the event number);
+// a feature of keyframe 1 whose event made a landmark takes that landmark (its only writer); every other feature is copied.
+// A pair adds 1 to row_delta[the observing keyframe] unless that is keyframe 2 (:345, :508, :622, :742) -- int32 adds, exact in
+// any order; a new landmark's single pair is keyframe 1 (:320-321).
+__global__ void __launch_bounds__(MI_NT)
+k_mi_feat_rows(SrcD S, DstD D, CallD C, int32_t* __restrict__ row_delta)
+{
+    const int32_t n_ev = C.cnt[W_EV];
+    const int64_t n_items = (int64_t)S.n_feat + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * MI_NT;
+    int32_t f1_0, nf1, f2_0, nf2;
+    slot_features(S, C.kf2, f2_0, nf2);
+    slot_features(S, C.kf1, f1_0, nf1);
+    for (int64_t t = (int64_t)blockIdx.x * MI_NT + threadIdx.x; t < n_items; t += stride) {
+        if (t < S.n_feat) {
+            const int32_t f = (int32_t)t;
+            int32_t v = S.feat_idx[f];
+            if (f >= f2_0 && f - f2_0 < nf2 && f - f2_0 < C.n_curr) {
+                const int32_t w = C.feat_win[f - f2_0];
+                if (w > 0 && w <= n_ev) v = C.ev[4 * (size_t)(w - 1)];
+            } else if (C.mode == MODE_KF2KF && f >= f1_0 && f - f1_0 < nf1 && f - f1_0 < C.n_tab) {
+                const int32_t l = C.i1_lm[f - f1_0];
+                if (l >= 0) v = l;
+            }
+            D.feat_idx[f] = v;
+        } else if (n_ev > 0) {
+            const int32_t p = (int32_t)(t - S.n_feat);
+            const int32_t e = segment_of(C.pair_off, n_ev, p), o = p - C.pair_off[e];
+            const int32_t* rec = C.ev + 4 * (size_t)e;
+            int32_t kf = -1;
+            if (rec[3]) kf = o == 0 ? C.kf1 : -1;
+            else if (rec[0] >= 0 && rec[0] < S.n && o >= 0 && o < old_len(S, rec[0])) kf = S.obs_kf[(size_t)S.obs_ptr[rec[0]] + o];
+            if (kf >= 0 && kf < C.n_map_kf && kf != C.kf2) atomicAdd(row_delta + kf, 1);
+        }
+    }
+}
+
+// K67: the call's last kernel: the counters and row_delta to the page-locked block
+__global__ void __launch_bounds__(MI_NT)
+k_mi_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ row_delta, int32_t n_map_kf, int32_t* __restrict__ pinned)
+{
+    for (int32_t i = (int32_t)threadIdx.x; i < W_WORDS + n_map_kf; i += MI_NT) pinned[i] = i < W_WORDS ? cnt[i] : row_delta[i - W_WORDS];
+}
+
+bool src_kind_ok(const plslam_map_landmarks& L)
+{
+    return L.n >= 0 && L.n_obs >= 0 && L.n_obs < (1 << 30) && L.n_feat >= 0 &&
+           (L.n == 0 || (L.valid && L.inlier && L.X && L.obs_ptr)) && (L.n_obs == 0 || (L.n > 0 && L.obs_kf && L.obs_val)) &&
+           (L.n_feat == 0 || (L.feat_ptr && L.feat_idx));
+}
+bool dst_kind_ok(const plslam_map_landmarks& D, const plslam_map_landmarks& S)
+{
+    const void* d[] = {D.valid, D.inlier, D.X, D.obs_ptr, D.obs_kf, D.obs_val, D.feat_idx};
+    const void* s[] = {S.valid, S.inlier, S.X, S.obs_ptr, S.obs_kf, S.obs_val, S.feat_idx, S.feat_ptr};
+    for (const void* p : d) {
+        if (!p) return false;
+        for (const void* q : s)
+            if (p == q) return false;
+    }
+    return D.feat_ptr != nullptr;
+}
+bool kind_args_ok(const plslam_map_insert_kind* k, int mode)
+{
+    if (!k || !k->table || k->n_table == 0) return !k || k->n_table >= 0;
+    if (k->n_table < 0 || k->n_curr < 0 || (k->n_curr > 0 && (!k->P2 || !k->obs2))) return false;
+    return mode == MODE_MAP2KF || (k->n_prev >= 0 && (k->n_prev == 0 || (k->P1 && k->obs1)));
+}
+unsigned tiles(int64_t n) { return (unsigned)(n > 0 ? (n + MI_NT - 1) / MI_NT : 1); }
+
+}  // namespace
+}  // namespace plslam
+
+using namespace plslam;
+
+struct plslam_map_insert {
+    plslam_ctx* ctx = nullptr;
+    DevBuf buf;
+    HostBuf pin;                                 // W_WORDS counters + row_delta, then the staged tables
+    bool done = false;
+    plslam_map_insert_events d = {};
+    int32_t n_ev[2] = {0, 0};
+};
+
+namespace {
+
+struct KindPlan {                                // one kind of one call, host side
+    const plslam_map_insert_kind* in = nullptr;  // nullptr: no table
+    int32_t n_tab = 0, n_prev = 0, n_curr = 0, m = 0, dl = 3, dv = 2;
+    size_t o_tab, o_P1, o_o1, o_P2, o_o2;        // in the staged block
+    size_t o_i1lm, o_ev, o_dir, o_pair, o_new, o_app, o_head, o_win, o_part;
+    unsigned w_tab = 1, w_lm = 1;
+};
+
+int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf1, int32_t kf2,
+           const double* T1, const double* T2, const plslam_map_insert_kind* points, const plslam_map_insert_kind* lines,
+           int32_t* row_delta, plslam_map_insert_counts* counts)
+{
+    // ---- validate everything, then commit once ----
+    PLSLAM_REQUIRE(mi && src && dst && T2 && row_delta && counts && (mode == MODE_MAP2KF || T1), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(src->n_map_kf >= 1 && src->kf_valid && src->x_kf_w && src_kind_ok(src->points) && src_kind_ok(src->lines),
+                   PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(kf2 >= 0 && kf2 < src->n_map_kf && (mode == MODE_MAP2KF || (kf1 >= 0 && kf1 < src->n_map_kf && kf1 != kf2)),
+                   PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(dst->map.kf_valid && dst->map.x_kf_w && dst_kind_ok(dst->map.points, src->points) &&
+                       dst_kind_ok(dst->map.lines, src->lines) && kind_args_ok(points, mode) && kind_args_ok(lines, mode),
+                   PLSLAM_EINVAL);
+    const plslam_map_landmarks* S[2] = {&src->points, &src->lines};
+    const int32_t cap[2] = {dst->pt_cap, dst->ls_cap}, obs_cap[2] = {dst->pt_obs_cap, dst->ls_obs_cap};
+    KindPlan K[2];
+    K[0].in = points && points->table && points->n_table > 0 ? points : nullptr;
+    K[1].in = lines && lines->table && lines->n_table > 0 ? lines : nullptr;
+    K[1].dl = 6; K[1].dv = 3;
+    for (int k = 0; k < 2; ++k) {
+        KindPlan& P = K[k];
+        if (P.in) {
+            P.n_tab = P.in->n_table; P.n_prev = mode == MODE_KF2KF ? P.in->n_prev : 0; P.n_curr = P.in->n_curr;
+            PLSLAM_REQUIRE(mode == MODE_KF2KF || P.n_tab <= S[k]->n, PLSLAM_EINVAL);
+            PLSLAM_REQUIRE(mode == MODE_MAP2KF || P.n_tab <= PLSLAM_MAP_INSERT_MAX_TABLE, PLSLAM_ERANGE);
+            for (int32_t i = 0; i < P.n_tab; ++i) P.m += P.in->table[i] >= 0;
+        }
+        const int64_t need_lm = (int64_t)S[k]->n + (mode == MODE_KF2KF ? P.m : 0);
+        const int64_t need_obs = (int64_t)S[k]->n_obs + (mode == MODE_KF2KF ? 2 : 1) * (int64_t)P.m;
+        PLSLAM_REQUIRE(cap[k] >= need_lm && obs_cap[k] >= need_obs && need_obs < (1 << 30), PLSLAM_ERANGE);
+    }
+    const int32_t nk = src->n_map_kf;
+    // ---- the layout: [zeroed: counters, row_delta, per kind app_cnt / feat_win / part] [0x7f: head] [staged] [the rest] ----
+    Carver c;
+    const size_t o_cnt = c.take(W_WORDS * 4), o_row = c.take((size_t)nk * 4);
+    for (int k = 0; k < 2; ++k) {
+        KindPlan& P = K[k];
+        P.w_tab = tiles(P.n_tab); P.w_lm = tiles((int64_t)S[k]->n + P.m);
+        P.o_app = c.take((size_t)S[k]->n * 4 + 4); P.o_win = c.take((size_t)P.n_curr * 4 + 4);
+        P.o_part = c.take((3 * (size_t)P.w_tab + P.w_lm) * 4);
+    }
+    const size_t zero_bytes = c.off;
+    for (int k = 0; k < 2; ++k) K[k].o_head = c.take((size_t)S[k]->n * 4 + 4);
+    const size_t head_off = zero_bytes, head_bytes = c.off - zero_bytes;
+    const size_t stage_off = c.off, o_T = c.take(32 * 8);
+    for (int k = 0; k < 2; ++k) {
+        KindPlan& P = K[k];
+        P.o_tab = c.take((size_t)P.n_tab * 4 + 4);
+        P.o_P1 = c.take((size_t)P.n_prev * P.dl * 8 + 8); P.o_o1 = c.take((size_t)P.n_prev * P.dv * 8 + 8);
+        P.o_P2 = c.take((size_t)P.n_curr * P.dl * 8 + 8); P.o_o2 = c.take((size_t)P.n_curr * P.dv * 8 + 8);
+    }
+    const size_t stage_bytes = c.off - stage_off;
+    for (int k = 0; k < 2; ++k) {
+        KindPlan& P = K[k];
+        P.o_i1lm = c.take((size_t)P.n_tab * 4 + 4); P.o_ev = c.take((size_t)P.m * 16 + 16); P.o_dir = c.take((size_t)P.m * 48 + 48);
+        P.o_pair = c.take((size_t)P.m * 4 + 4); P.o_new = c.take((size_t)P.m * 4 + 4);
+    }
+    std::lock_guard<std::mutex> lk(mi->ctx->mu);
+    DeviceGuard dg_(mi->ctx->device);
+    hipStream_t s = mi->ctx->stream;
+    mi->done = false;
+    int rc = mi->buf.reserve(c.off + 256);
+    if (rc) return rc;
+    const size_t res_bytes = align256((W_WORDS + (size_t)nk) * 4);
+    if ((rc = mi->pin.reserve(res_bytes + stage_bytes))) return rc;
+    PLSLAM_REQUIRE(mi->pin.dev, PLSLAM_ENOTSUP);                 // the counters are written where the host reads them
+    char* d = mi->buf.as<char>();
+    char* h = mi->pin.as<char>();
+    char* hs = h + res_bytes - stage_off;                        // (the staged block's offsets are the device layout's)
+    memset(h + res_bytes, 0, stage_bytes);
+    if (T1) memcpy(hs + o_T, T1, 128);
+    memcpy(hs + o_T + 128, T2, 128);
+    for (int k = 0; k < 2; ++k) {
+        const KindPlan& P = K[k];
+        if (!P.in) continue;
+        memcpy(hs + P.o_tab, P.in->table, (size_t)P.n_tab * 4);
+        if (P.n_prev) {
+            memcpy(hs + P.o_P1, P.in->P1, (size_t)P.n_prev * P.dl * 8);
+            memcpy(hs + P.o_o1, P.in->obs1, (size_t)P.n_prev * P.dv * 8);
+        }
+        if (P.n_curr) {
+            memcpy(hs + P.o_P2, P.in->P2, (size_t)P.n_curr * P.dl * 8);
+            memcpy(hs + P.o_o2, P.in->obs2, (size_t)P.n_curr * P.dv * 8);
+        }
+    }
+    StreamSyncOnError guard(s);
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d, 0, zero_bytes, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d + head_off, 0x7f, head_bytes, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + stage_off, h + res_bytes, stage_bytes, hipMemcpyHostToDevice, s));
+    if (dst->map.kf_valid != src->kf_valid)
+        PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)dst->map.kf_valid, src->kf_valid, (size_t)nk, hipMemcpyDeviceToDevice, s));
+    if (dst->map.x_kf_w != src->x_kf_w)
+        PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)dst->map.x_kf_w, src->x_kf_w, (size_t)nk * 48, hipMemcpyDeviceToDevice, s));
+    plslam_map_landmarks* Dk[2] = {&dst->map.points, &dst->map.lines};
+    int32_t* cnt = (int32_t*)(d + o_cnt);
+    int32_t* row = (int32_t*)(d + o_row);
+    for (int k = 0; k < 2; ++k) {
+        const KindPlan& P = K[k];
+        const plslam_map_landmarks& A = *S[k];
+        plslam_map_landmarks& B = *Dk[k];
+        if (A.n_feat > 0 && B.feat_ptr != A.feat_ptr)
+            PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)B.feat_ptr, A.feat_ptr, ((size_t)nk + 1) * 4, hipMemcpyDeviceToDevice, s));
+        const SrcD Sd{A.n, A.n_obs, A.n_feat, P.dl, P.dv, A.valid, A.inlier, A.X, A.obs_ptr, A.obs_kf, A.obs_val, A.feat_ptr, A.feat_idx};
+        const DstD Dd{B.valid, (uint8_t*)B.inlier, (double*)B.X, (int32_t*)B.obs_ptr, (int32_t*)B.obs_kf, (double*)B.obs_val, B.feat_idx,
+                      cap[k], obs_cap[k]};
+        CallD C{};
+        C.mode = mode; C.lines = k; C.n_map_kf = nk; C.kf1 = mode == MODE_KF2KF ? kf1 : -1; C.kf2 = kf2;
+        C.n_tab = P.n_tab; C.n_prev = P.n_prev; C.n_curr = P.n_curr; C.e_cap = P.m;
+        C.T = (const double*)(d + o_T); C.tab = (const int32_t*)(d + P.o_tab);
+        C.P1 = (const double*)(d + P.o_P1); C.o1 = (const double*)(d + P.o_o1);
+        C.P2 = (const double*)(d + P.o_P2); C.o2 = (const double*)(d + P.o_o2);
+        C.i1_lm = (int32_t*)(d + P.o_i1lm); C.ev = (int32_t*)(d + P.o_ev); C.pair_off = (int32_t*)(d + P.o_pair);
+        C.new_ev = (int32_t*)(d + P.o_new); C.app_cnt = (int32_t*)(d + P.o_app); C.head = (int32_t*)(d + P.o_head);
+        C.feat_win = (int32_t*)(d + P.o_win); C.cnt = cnt + W_KIND * k; C.ev_dir = (double*)(d + P.o_dir);
+        uint32_t* part = (uint32_t*)(d + P.o_part);
+        hipLaunchKernelGGL(k_mi_events, dim3(P.w_tab), dim3(MI_NT), 0, s, Sd, C, part, part + P.w_tab, part + 2 * P.w_tab);
+        hipLaunchKernelGGL(k_mi_ptr, dim3(P.w_lm), dim3(MI_NT), 0, s, Sd, Dd, C, part + 3 * P.w_tab);
+        const int64_t n_out = (int64_t)A.n_obs + (mode == MODE_KF2KF ? 2 : 1) * (int64_t)P.m;
+        if (n_out > 0) hipLaunchKernelGGL(k_mi_obs, dim3(tiles(n_out)), dim3(MI_NT), 0, s, Sd, Dd, C);
+        const unsigned g = tiles((int64_t)A.n_feat + A.n_obs + P.m);
+        hipLaunchKernelGGL(k_mi_feat_rows, dim3(g < MI_MAX_GRID ? g : MI_MAX_GRID), dim3(MI_NT), 0, s, Sd, Dd, C, row);
+        (k ? mi->d.ls_ev : mi->d.pt_ev) = C.ev;
+        (k ? mi->d.ls_dir : mi->d.pt_dir) = C.ev_dir;
+    }
+    hipLaunchKernelGGL(k_mi_publish, dim3(1), dim3(MI_NT), 0, s, (const int32_t*)cnt, (const int32_t*)row, nk, (int32_t*)mi->pin.dev);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    const int32_t* r = mi->pin.as<int32_t>();
+    memcpy(row_delta, r + W_WORDS, (size_t)nk * 4);
+    plslam_map_insert_kind_counts* out[2] = {&counts->points, &counts->lines};
+    for (int k = 0; k < 2; ++k) {
+        const int32_t* w = r + W_KIND * k;
+        *out[k] = plslam_map_insert_kind_counts{w[W_EV], w[W_NEW], w[W_EV] + w[W_NEW], K[k].m - w[W_EV]};
+        mi->n_ev[k] = w[W_EV];
+        Dk[k]->n = S[k]->n + w[W_NEW];
+        Dk[k]->n_obs = w[W_OBS];
+        Dk[k]->n_feat = S[k]->n_feat;
+    }
+    dst->map.n_map_kf = nk;
+    mi->d.stream = (void*)s;
+    mi->done = true;
+    return PLSLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plslam_map_insert_create(plslam_ctx* ctx, plslam_map_insert** out)
+{
+    PLSLAM_REQUIRE(ctx && out, PLSLAM_EINVAL);
+    *out = new plslam_map_insert();
+    (*out)->ctx = ctx;
+    return PLSLAM_OK;
+}
+
+void plslam_map_insert_destroy(plslam_map_insert* mi)
+{
+    if (!mi) return;
+    {
+        std::lock_guard<std::mutex> lk(mi->ctx->mu);
+        DeviceGuard dg_(mi->ctx->device);
+        (void)hipStreamSynchronize(mi->ctx->stream);
+        mi->buf.release();
+        mi->pin.release();
+    }
+    delete mi;
+}
+
+int plslam_map_insert_kf2kf(plslam_map_insert* mi, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf1_idx,
+                            int32_t kf2_idx, const double* T_kf1_w, const double* T_kf2_w, const plslam_map_insert_kind* points,
+                            const plslam_map_insert_kind* lines, int32_t* row_delta, plslam_map_insert_counts* counts)
+{
+    return insert(mi, MODE_KF2KF, src, dst, kf1_idx, kf2_idx, T_kf1_w, T_kf2_w, points, lines, row_delta, counts);
+}
+
+int plslam_map_insert_map2kf(plslam_map_insert* mi, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf2_idx,
+                             const double* T_kf2_w, const plslam_map_insert_kind* points, const plslam_map_insert_kind* lines,
+                             int32_t* row_delta, plslam_map_insert_counts* counts)
+{
+    return insert(mi, MODE_MAP2KF, src, dst, -1, kf2_idx, nullptr, T_kf2_w, points, lines, row_delta, counts);
+}
+
+int plslam_map_insert_device_buffers(plslam_map_insert* mi, plslam_map_insert_events* out)
+{
+    PLSLAM_REQUIRE(mi && out && mi->done, PLSLAM_EINVAL);
+    *out = mi->d;
+    return PLSLAM_OK;
+}
+
+int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_events* host)
+{
+    PLSLAM_REQUIRE(mi && host && mi->done, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(mi->ctx->mu);
+    DeviceGuard dg_(mi->ctx->device);
+    hipStream_t s = mi->ctx->stream;
+    StreamSyncOnError guard(s);
+    struct Item { void* dst; const void* src; size_t bytes; };
+    const Item items[] = {{host->pt_ev, mi->d.pt_ev, (size_t)mi->n_ev[0] * 16}, {host->pt_dir, mi->d.pt_dir, (size_t)mi->n_ev[0] * 48},
+                          {host->ls_ev, mi->d.ls_ev, (size_t)mi->n_ev[1] * 16}, {host->ls_dir, mi->d.ls_dir, (size_t)mi->n_ev[1] * 48}};
+    for (const Item& it : items)
+        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    return PLSLAM_OK;
+}
+
+}  // extern "C"

@@ -46,7 +46,8 @@ extern "C" {
  * correction plslam_pgo_plan_create / plslam_pgo_optimize / plslam_pgo_plan_destroy, plslam_lc_correct_map[_dev] and
  * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks; the local map
  * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts; the map
- * insertion plslam_map_insert_* with plslam_map_insert_kind / _dst / _counts / _events.
+ * insertion plslam_map_insert_* with plslam_map_insert_kind / _dst / _counts / _events; the loop-closure landmark fusion
+ * plslam_lc_fuse_* with plslam_lc_fuse_kind / _counts / _buffers.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1331,6 +1332,90 @@ int plslam_map_insert_map2kf(plslam_map_insert* mi, const plslam_map_index* src,
                              int32_t* row_delta, plslam_map_insert_counts* counts);
 int plslam_map_insert_device_buffers(plslam_map_insert* mi, plslam_map_insert_events* out);
 int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_events* host);
+
+/* ---- a loop closure's landmarks fused into the device-resident map: MapHandler::loopClosureFuseLandmarks ---------------- */
+/* src/mapHandler.cpp:4412-4687 over plslam_map_index, OUT OF PLACE like plslam_map_insert_*: `src` is read, every array of `dst`
+ * is written (K68-K73, KERNELS.md); one launch sequence on the context's stream, one synchronisation, the counts through
+ * page-locked memory.  plslam_pgo_* / plslam_lc_correct_map run loopClosureOptimizationCovGraphG2O up to this point.
+ *
+ * lc_idx[n_lc x 3] (HOST, int32) = lc_idx_list: (kf_prev, kf_curr, flag); an entry whose flag is not 1 contributes nothing
+ * (:4419) and is not validated.  Marking the entries optimised (:4401-4402) stays with the caller.
+ * plslam_lc_fuse_kind (HOST): tuples[m x 4] = the rows (lm_idx0, lm_ldx0, lm_idx1, lm_ldx1) of lc_pt_idxs / lc_ls_idxs, all
+ *   entries concatenated, entry_ptr[n_lc + 1] (entry_ptr[0] = 0, m = entry_ptr[n_lc] <= PLSLAM_LC_FUSE_MAX_TUPLES); per tuple the
+ *   two features' values, gathered by the caller: P0 / P1 = P of the kf_prev / kf_curr feature (m x 3; lines sP, eP: m x 6),
+ *   obs0 / obs1 = pl (m x 2) or le (m x 3).  A NULL struct or entry_ptr = no tuple of that kind (its image is still copied).
+ * T_kf_w[n_map_kf x 16] (HOST): KeyFrame::T_kf_w of every slot, row-major -- what plslam_pgo_optimize writes as T_out.
+ *
+ * An EVENT is a tuple of a flagged entry, in entry order then tuple order; its number t is its row in `tuples`.  With (a, l0, b,
+ * l1) the tuple, kp / kc the entry's slots, "valid" a landmark's flag AS THE EARLIER EVENTS LEFT IT:
+ *   A (-1, b)   feature l0 of kp not NULL and b valid: feat_idx[kp][l0] = b; (kp, obs0) appended to b; for every entry k of b's
+ *               list after the append, full_graph[k][kc]++ and [kc][k]++ (against kf_curr, :4441; k == kc adds 2 to the
+ *               diagonal).  Direction P0 / |P0|, unguarded (:4436); lines (sP + eP) / |sP + eP|.
+ *   B (a, -1)   the mirror: feature l1 of kc, (kc, obs1) appended to a, increments against kp (:4446-4462).
+ *   C (-1, -1)  both features not NULL: a NEW landmark n + (rank among the acted C events), valid, inlier, X = T_kp P0 (lines: sP,
+ *               eP), observations (kp, obs0) then (kc, obs1), both features receive the index, full_graph[kp][kc]++ and
+ *               [kc][kp]++.  Directions (T_kp P0) / |.| then (T_kc P1) / |.|; lines: 0.5 (s + e) of the transformed ends.
+ *   D (a, b)    a valid, b valid, feature l1 of kc not NULL: with Nprev = len(a), b's whole list is appended to a in order;
+ *               full_graph[i][j]++ and [j][i]++ for every i among the first Nprev entries of a and every j of b;
+ *               feat_idx[kc][l1] = a; b becomes invalid with an empty list.  Features elsewhere that name b keep the stale index.
+ * State carries from event to event: an event on a dead landmark does nothing, a later D takes a's grown list, two events that
+ * write one feature leave the later one's index.
+ * Deviations, where the reference has undefined behaviour; each is SKIPPED and counted in n_skipped, checked in this order: an
+ * entry whose slot is NULL in kf_valid; a landmark index other than -1 outside [0, n) of the SOURCE image (a tuple cannot name a
+ * landmark this call creates); an ldx the branch reads (A: l0; B, D: l1; C: both) beyond the keyframe's features; then, the
+ * reference's own condition holding, a == b in D (it pushes onto the vector it iterates) and a D whose b has an empty list
+ * (kf_obs_list[0], :4521).  An obs_kf entry outside [0, n_map_kf) adds nothing to the graph; each such PAIR is counted too.
+ * The LEVEL of an event is 1 + the largest level among the latest earlier events that name one of its landmarks (every event
+ * names its indices in [0, n), acted or not); a level above PLSLAM_LC_FUSE_MAX_LEVEL -> PLSLAM_ERANGE with dst untouched.  So
+ * is a call whose graph increments number 2^30 (event, pair) items or more (A / B: the list's length, D: len(a) x len(b)).
+ * A run that fails after validation (PLSLAM_ENOMEM, PLSLAM_EHIP, the two refusals above) invalidates the previous run's records.
+ * With the caller stay desc_list / dir_list / pts_list (one gather by obs_src; so the pts quirk of :4626 never reaches the call),
+ * map_*_kf_idx (push ev's landmark to the anchor's list for C, erase the dead landmark from the anchor's for D) and full_graph.
+ * Arithmetic as plslam_map_insert_*: fp64 without contraction, R p + t as ((r0 p0 + r1 p1) + r2 p2) + t, the norm as
+ * sqrt((x^2 + y^2) + z^2), the division per component.
+ *
+ * dst: as for plslam_map_insert_* (which pointers may alias, capacities).  With cC tuples (-1, -1) and cAB tuples with exactly one
+ * -1 among the flagged entries the call needs n + cC landmarks and n_obs + cAB + 2 cC observations per kind; a smaller capacity ->
+ * PLSLAM_ERANGE before anything is staged, launched or written.  PLSLAM_EINVAL: NULL arguments, n_lc <= 0, a flagged entry with a
+ * slot out of range or kf_prev == kf_curr, a destination array that is a source array.
+ * graph_delta: HOST, n_map_kf^2 int32 row-major, overwritten: the increment of full_graph; NULL: it stays on the device
+ * (plslam_lc_fuse_buffers).  n_map_kf^2 < 2^28. */
+#define PLSLAM_LC_FUSE_MAX_TUPLES 65536
+#define PLSLAM_LC_FUSE_MAX_LEVEL 64
+typedef struct plslam_lc_fuse_kind {
+    const int32_t *tuples, *entry_ptr;
+    const double *P0, *obs0, *P1, *obs1;
+} plslam_lc_fuse_kind;
+typedef struct plslam_lc_fuse_kind_counts {
+    int32_t n_a, n_b, n_c, n_d;                          /* events acted on per branch                                       */
+    int32_t n_new, n_dead, n_skipped;                    /* n_new = n_c, n_dead = n_d; n_skipped: the deviations above       */
+} plslam_lc_fuse_kind_counts;
+typedef struct plslam_lc_fuse_counts {
+    plslam_lc_fuse_kind_counts points, lines;
+} plslam_lc_fuse_counts;
+/* The records of the last run, per kind.  ev: m x 6 int32, one row per tuple: the code (0 not acted, 1 A, 2 B, 3 C, 4 D); the
+ * landmark that keeps or receives the observations, or -1; the dead landmark for D, else -1; the anchor keyframe (kf_prev for C,
+ * b's first observer before the fusion for D: the key of map_*_kf_idx the caller pushes to / erases from), else -1; the position
+ * in the destination's observation arrays of the first observation the event placed, or -1; the count (1, 2 or len(b)).
+ * dir: m x 6 doubles: columns 0-2 the kf_prev observation's direction, 3-5 the kf_curr one, zeros where the event made none.
+ * obs_src[dst n_obs] int32: >= 0 the source observation now at that position; -1 - (2 t + w): tuple t made it (w = 0 kf_prev's
+ * observation, 1 kf_curr's).  graph_delta: n_map_kf^2 int32.  Device pointers (valid until the next run / destroy, ordered on
+ * `stream`) or, for download, HOST pointers (NULL = skip; `stream` ignored). */
+typedef struct plslam_lc_fuse_buffers {
+    int32_t *pt_ev, *ls_ev;
+    double *pt_dir, *ls_dir;
+    int32_t *pt_obs_src, *ls_obs_src;
+    int32_t* graph_delta;
+    void* stream;
+} plslam_lc_fuse_buffers;
+typedef struct plslam_lc_fuse plslam_lc_fuse;
+int plslam_lc_fuse_create(plslam_ctx* ctx, plslam_lc_fuse** out);
+void plslam_lc_fuse_destroy(plslam_lc_fuse* lf);
+int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t n_lc,
+                       const int32_t* lc_idx, const double* T_kf_w, const plslam_lc_fuse_kind* points,
+                       const plslam_lc_fuse_kind* lines, int32_t* graph_delta, plslam_lc_fuse_counts* counts);
+int plslam_lc_fuse_device_buffers(plslam_lc_fuse* lf, plslam_lc_fuse_buffers* out);
+int plslam_lc_fuse_download(plslam_lc_fuse* lf, const plslam_lc_fuse_buffers* host);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,8 @@ ABI_SYMBOLS = (
     "plslam_local_map_gather", "plslam_local_map_cull", "plslam_local_map_device_buffers", "plslam_local_map_download",
     "plslam_map_insert_create", "plslam_map_insert_destroy", "plslam_map_insert_kf2kf", "plslam_map_insert_map2kf",
     "plslam_map_insert_device_buffers", "plslam_map_insert_download",
+    "plslam_lc_fuse_create", "plslam_lc_fuse_destroy", "plslam_lc_fuse_run", "plslam_lc_fuse_device_buffers",
+    "plslam_lc_fuse_download",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -274,7 +276,7 @@ _RESTYPES = {
     "plslam_ctx_destroy": None, "plslam_match_plan_destroy": None, "plslam_lba_plan_destroy": None,
     "plslam_grid_plan_destroy": None, "plslam_match_pipeline_destroy": None, "plslam_bow_vocab_destroy": None,
     "plslam_bow_db_destroy": None, "plslam_gba_plan_destroy": None, "plslam_pgo_plan_destroy": None,
-    "plslam_local_map_destroy": None, "plslam_map_insert_destroy": None,
+    "plslam_local_map_destroy": None, "plslam_map_insert_destroy": None, "plslam_lc_fuse_destroy": None,
 }
 
 
@@ -445,6 +447,12 @@ def load() -> C.CDLL:
     L.plslam_map_insert_map2kf.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.plslam_map_insert_device_buffers.argtypes = [vp, vp]
     L.plslam_map_insert_download.argtypes = [vp, vp]
+    # the loop-closure fusion (plslam_amd/lc_fuse.py)
+    L.plslam_lc_fuse_create.argtypes = [vp, C.POINTER(vp)]
+    L.plslam_lc_fuse_destroy.argtypes = [vp]
+    L.plslam_lc_fuse_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.plslam_lc_fuse_device_buffers.argtypes = [vp, vp]
+    L.plslam_lc_fuse_download.argtypes = [vp, vp]
     for name in ABI_SYMBOLS:
         getattr(L, name).restype = _RESTYPES.get(name, C.c_int)
     _lib = L

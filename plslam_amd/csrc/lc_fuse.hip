@@ -1,0 +1,661 @@
+// lc_fuse.hip -- MapHandler::loopClosureFuseLandmarks (src/mapHandler.cpp:4412-4687) over the device-resident CSR image of the map
+// (plslam_map_index), OUT OF PLACE: the source image is read, every array of the destination is written.  The semantics, the
+// deviations and the level rule are in include/plslam_hip.h; the sequential definition is tests/lc_fuse_ref.py.  Per landmark kind:
+//   K68 a lane per source landmark (its list length, the state the events mutate) and per tuple: what the tuple can be from the
+//       SOURCE image alone (entry flag, NULL slots, index ranges, NULL features: none of these changes during the call), the
+//       features it would write
+//   K69 the resolve: ONE workgroup.  An event's outcome depends only on (alive, length) of the landmarks it names as the earlier
+//       events that name them left it.  Rounds: every pending event posts its number to its landmarks with an atomic min; the
+//       event that is the minimum on all of its landmarks has no pending predecessor: it becomes final, records its offset o(e)
+//       inside its target's list and its width, and updates the state.  The round an event becomes final in is its level, so the
+//       rounds are capped at PLSLAM_LC_FUSE_MAX_LEVEL and what is left pending then refuses the call through the status word every
+//       later kernel tests.  Then one pass in event order: the new landmarks' ranks, the (event, pair) offsets of K72, the last
+//       writer per feature (atomic max, as K66), the counts.  Workgroup barriers only; no loop on device state without a cap.
+//   K70 the new obs_ptr: a look-back scan of the final lengths (0 for a dead landmark, 2 for a new one) over n + n_new landmarks;
+//       valid / inlier / X copied, the new rows computed
+//   K71 the observations: a lane per SOURCE observation scatters it to its place, a lane per (tuple, side) writes what the event
+//       made and its direction (zeros where it made none).  The place of entry k of landmark x: while x was fused away by event e into a, k += o(e) and x = a -- at most
+//       MAX_LEVEL steps, since the killers along the chain have rising levels; then obs_ptr[x] + k.  So the list of any landmark at
+//       the time of any event is a contiguous range of the destination.
+//   K72 feat_idx (copy; the last acted event that names a feature wins), the anchors, and the graph: a lane per (event, pair)
+//       reads the DESTINATION obs_kf ranges, int32 atomic adds into the zeroed dense delta (exact in any order)
+//   K73 the counts and graph_delta to the page-locked block; kf_valid, x_kf_w and feat_ptr copied
+// Atomics count and select; none decides an order.  Every output is an integer, a flag, a verbatim copy of a double or a
+// fixed-order fp64 expression of correctly rounded operations.  Every index read from the image or a tuple is range-checked
+// before it is used as an address.
+#include <climits>
+#include <cstring>
+
+#include "common.hpp"
+#include "lc_fuse_plan.hpp"
+#include "lookback_dev.hpp"
+#include "se3_dev.hpp"
+
+namespace plslam {
+namespace {
+
+constexpr int LF_NT = 256;              // lanes per workgroup = items per look-back tile (plslam_amd/lc_fuse.py: LOOKBACK_TILE)
+constexpr int LF_NW = LF_NT / 64;
+constexpr int LF_RES_NT = 1024;         // the resolve's one workgroup; a lane owns the events e = lane (mod LF_RES_NT): at most 64
+constexpr unsigned LF_MAX_GRID = 4096;  // K72 / K73 stride over their items
+constexpr int LF_MAX_LEVEL = PLSLAM_LC_FUSE_MAX_LEVEL;
+static_assert(PLSLAM_LC_FUSE_MAX_TUPLES <= 64 * LF_RES_NT, "a resolve lane keeps its pending events in one 64-bit mask");
+// the call counters (device words, mirrored in the page-locked block): eight per kind, then the status word
+enum { W_A = 0, W_B, W_C, W_D, W_SKIP, W_OBS, W_PAIRS, W_KIND = 8, W_STATUS = 16, W_WORDS = 20 };
+// what a tuple can be from the source image alone
+enum { SC_OFF = 0, SC_A, SC_B, SC_C, SC_D, SC_SELF, SC_NONE };
+
+struct SrcD {                           // one landmark kind of the source image
+    int32_t n, n_obs, n_feat, dl, dv;
+    const uint8_t *valid, *inlier;
+    const double* X;
+    const int32_t *obs_ptr, *obs_kf;
+    const double* obs_val;
+    const int32_t *feat_ptr, *feat_idx;
+};
+struct DstD {                           // ... of the destination
+    uint8_t *valid, *inlier;
+    double* X;
+    int32_t *obs_ptr, *obs_kf;
+    double* obs_val;
+    int32_t* feat_idx;
+    int32_t cap, obs_cap;
+};
+struct CallD {                          // one kind's tables and scratch (device), carved from the handle's buffer
+    int32_t lines, n_map_kf, n_lc, m, c_cap;                     // c_cap: the host's bound on the new landmarks
+    const uint8_t* kf_valid;
+    const int32_t *lc, *tup, *eptr;
+    const double *T, *P0, *o0, *P1, *o1;
+    int32_t *cur_len, *killer, *head, *sc, *fw0, *fw1, *ev, *ev_off, *pair_off, *new_ev, *feat_win, *obs_src, *cnt, *status;
+    double* ev_dir;
+};
+
+__device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int32_t old_len(const SrcD& S, int32_t lm)
+{
+    const int32_t b = S.obs_ptr[lm], e = S.obs_ptr[lm + 1];
+    return b >= 0 && e > b && e <= S.n_obs ? e - b : 0;
+}
+__device__ __forceinline__ void slot_features(const SrcD& S, int32_t kf, int32_t& f0, int32_t& nf)
+{
+    f0 = nf = 0;
+    if (S.n_feat <= 0) return;
+    const int32_t b = S.feat_ptr[kf], e = S.feat_ptr[kf + 1];
+    if (b >= 0 && e > b && e <= S.n_feat) { f0 = b; nf = e - b; }
+}
+// v / v.norm(): no guard (:4436, :4474)
+__device__ __forceinline__ void over_norm3(const double v[3], double* o)
+{
+    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
+}
+// the direction of a feature in its camera frame: P / |P|, lines (sP + eP) / |sP + eP| (:4560-4561)
+__device__ __forceinline__ void cam_dir(int lines, const double* __restrict__ P, double* o)
+{
+    double v[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) v[a] = lines ? P[a] + P[3 + a] : P[a];
+    over_norm3(v, o);
+}
+// ... in the world frame: (T P) / |.|, lines the midpoint 0.5 (s + e) of the transformed ends (:4608-4611)
+__device__ __forceinline__ void world_dir(int lines, const double* __restrict__ T, const double* __restrict__ P, double* o)
+{
+    double s[3], e[3];
+    xform(T, P, s);
+    if (lines) {
+        xform(T, P + 3, e);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s[a] = 0.5 * (s[a] + e[a]);
+    }
+    over_norm3(s, o);
+}
+// the entry of tuple t: the last one whose offset is at or below t (empty entries share an offset with their successor)
+__device__ __forceinline__ int32_t entry_of(const CallD& C, int32_t t) { return segment_of(C.eptr, C.n_lc, t); }
+// the place in the destination of entry `off` of landmark x's list (K71's chain)
+__device__ __forceinline__ int64_t place(const SrcD& S, const DstD& D, const CallD& C, int32_t x, int64_t off)
+{
+    for (int it = 0; it <= LF_MAX_LEVEL && x >= 0 && x < S.n; ++it) {
+        const int32_t e = C.killer[x];
+        if (e < 0 || e >= C.m) break;
+        off += C.ev_off[e];
+        x = C.ev[6 * (size_t)e + 1];
+    }
+    return x >= 0 && x < D.cap ? (int64_t)D.obs_ptr[x] + off : -1;
+}
+
+// K68: the state and the static classification.  A lane per source landmark, then per tuple.
+__global__ void __launch_bounds__(LF_NT)
+k_lf_classify(SrcD S, CallD C)
+{
+    const int64_t i = (int64_t)blockIdx.x * LF_NT + threadIdx.x;
+    if (i < S.n) {
+        C.cur_len[i] = old_len(S, (int32_t)i);
+        return;
+    }
+    const int64_t tt = i - S.n;
+    if (tt >= C.m) return;
+    const int32_t t = (int32_t)tt, ent = entry_of(C, t);
+    const int32_t kp = C.lc[3 * ent], kc = C.lc[3 * ent + 1], flag = C.lc[3 * ent + 2];
+    const int32_t a = C.tup[4 * (size_t)t], l0 = C.tup[4 * (size_t)t + 1], b = C.tup[4 * (size_t)t + 2], l1 = C.tup[4 * (size_t)t + 3];
+    int32_t sc = SC_OFF, fw0 = -1, fw1 = -1;
+    if (flag == 1) {                                             // (the host checked this entry's slots: in range, distinct)
+        sc = SC_NONE;
+        bool skip = !C.kf_valid[kp] || !C.kf_valid[kc];
+        skip = skip || (a != -1 && (a < 0 || a >= S.n)) || (b != -1 && (b < 0 || b >= S.n));
+        if (!skip) {
+            const bool need0 = a == -1, need1 = !(a == -1 && b != -1);
+            int32_t p0, np, c0, nc;
+            slot_features(S, kp, p0, np);
+            slot_features(S, kc, c0, nc);
+            skip = (need0 && (l0 < 0 || l0 >= np)) || (need1 && (l1 < 0 || l1 >= nc));
+            if (!skip) {
+                const bool f0 = need0 && S.feat_idx[p0 + l0] != PLSLAM_FEAT_NULL, f1 = need1 && S.feat_idx[c0 + l1] != PLSLAM_FEAT_NULL;
+                if (a == -1 && b != -1) {
+                    if (f0) { sc = SC_A; fw0 = p0 + l0; }
+                } else if (a != -1 && b == -1) {
+                    if (f1) { sc = SC_B; fw1 = c0 + l1; }
+                } else if (a == -1) {
+                    if (f0 && f1) { sc = SC_C; fw0 = p0 + l0; fw1 = c0 + l1; }
+                } else if (f1) {
+                    sc = a == b ? SC_SELF : SC_D;
+                    fw1 = c0 + l1;
+                }
+            }
+        }
+        if (skip) atomicAdd(C.cnt + W_SKIP, 1);
+    }
+    C.sc[t] = sc; C.fw0[t] = fw0; C.fw1[t] = fw1;
+}
+
+// K69: the resolve.  One workgroup of LF_RES_NT lanes; lane l owns the events e = l + 1024 k, bit k of its pending mask.
+__global__ void __launch_bounds__(LF_RES_NT)
+k_lf_resolve(SrcD S, CallD C)
+{
+    __shared__ uint32_t s_c[LF_RES_NT];
+    __shared__ unsigned long long s_p[LF_RES_NT];
+    __shared__ int32_t s_cnt[W_KIND];
+    const int tid = (int)threadIdx.x;
+    const int32_t m = C.m, n = S.n;
+    if (tid < W_KIND) s_cnt[tid] = 0;
+    // the records' defaults, and which events name a landmark at all
+    unsigned long long pend = 0;
+    for (int k = 0; k < 64; ++k) {
+        const int32_t e = tid + k * LF_RES_NT;
+        if (e >= m) break;
+        const int32_t sc = C.sc[e], a = C.tup[4 * (size_t)e], b = C.tup[4 * (size_t)e + 2];
+        int32_t* rec = C.ev + 6 * (size_t)e;
+        st(rec + 0, sc == SC_C ? 3 : 0); st(rec + 1, -1); st(rec + 2, -1); st(rec + 3, -1); st(rec + 4, -1); st(rec + 5, sc == SC_C ? 2 : 0);
+        st(C.ev_off + e, 0);
+        if (sc != SC_OFF && ((a >= 0 && a < n) || (b >= 0 && b < n))) pend |= 1ull << k;
+    }
+    int left = 0;
+    for (int round = 0; round <= LF_MAX_LEVEL; ++round) {
+        left = __syncthreads_or(pend != 0);
+        if (!left || round == LF_MAX_LEVEL) break;
+        for (int k = 0; k < 64 && (pend >> k); ++k) {
+            if (!((pend >> k) & 1)) continue;
+            const int32_t e = tid + k * LF_RES_NT, a = C.tup[4 * (size_t)e], b = C.tup[4 * (size_t)e + 2];
+            if (a >= 0 && a < n) atomicMin(C.head + a, e);
+            if (b >= 0 && b < n) atomicMin(C.head + b, e);
+        }
+        __syncthreads();
+        for (int k = 0; k < 64 && (pend >> k); ++k) {
+            if (!((pend >> k) & 1)) continue;
+            const int32_t e = tid + k * LF_RES_NT, a = C.tup[4 * (size_t)e], b = C.tup[4 * (size_t)e + 2];
+            const bool na = a >= 0 && a < n, nb = b >= 0 && b < n;
+            if ((na && ld(C.head + a) != e) || (nb && ld(C.head + b) != e)) continue;
+            // no earlier event that names a or b is pending, and no other event touches them in this round
+            const int32_t sc = C.sc[e];
+            const bool va = na && S.valid[a] && ld(C.killer + a) < 0, vb = nb && S.valid[b] && ld(C.killer + b) < 0;
+            int32_t code = 0, keep = -1, dead = -1, o = 0, w = 0;
+            if (sc == SC_A && vb) { code = 1; keep = b; w = 1; }
+            else if (sc == SC_B && va) { code = 2; keep = a; w = 1; }
+            else if (sc == SC_SELF && va) atomicAdd(s_cnt + W_SKIP, 1);
+            else if (sc == SC_D && va && vb) {
+                w = ld(C.cur_len + b);
+                if (w <= 0) { w = 0; atomicAdd(s_cnt + W_SKIP, 1); }
+                else { code = 4; keep = a; dead = b; }
+            }
+            if (code) {
+                o = ld(C.cur_len + keep);
+                st(C.cur_len + keep, o + w);
+                if (code == 4) { st(C.cur_len + b, 0); st(C.killer + b, e); }
+                int32_t* rec = C.ev + 6 * (size_t)e;
+                st(rec + 0, code); st(rec + 1, keep); st(rec + 2, dead); st(rec + 5, w);
+                st(C.ev_off + e, o);
+            }
+            if (na) st(C.head + a, INT_MAX);
+            if (nb) st(C.head + b, INT_MAX);
+            pend &= ~(1ull << k);
+        }
+        __syncthreads();
+    }
+    if (left) {                                                  // an event of a level above LF_MAX_LEVEL: the call is refused
+        if (tid == 0) atomicOr(C.status, 1);
+        return;
+    }
+    // one pass in event order: lane l takes the events [l per, (l + 1) per)
+    const int32_t per = (m + LF_RES_NT - 1) / LF_RES_NT, e0 = tid * per < m ? tid * per : m, e1 = e0 + per < m ? e0 + per : m;
+    uint32_t nc = 0;
+    unsigned long long np = 0;
+    for (int32_t e = e0; e < e1; ++e) {
+        const int32_t code = ld(C.ev + 6 * (size_t)e), o = ld(C.ev_off + e), w = ld(C.ev + 6 * (size_t)e + 5);
+        nc += code == 3;
+        np += code == 1 || code == 2 ? (unsigned long long)o + 1 : code == 3 ? 1ull : code == 4 ? (unsigned long long)o * w : 0ull;
+    }
+    s_c[tid] = nc;
+    s_p[tid] = np;
+    __syncthreads();
+    for (int d = 1; d < LF_RES_NT; d <<= 1) {                    // an inclusive scan of the lanes' sums
+        const uint32_t c = tid >= d ? s_c[tid - d] : 0u;
+        const unsigned long long p = tid >= d ? s_p[tid - d] : 0ull;
+        __syncthreads();
+        s_c[tid] += c;
+        s_p[tid] += p;
+        __syncthreads();
+    }
+    const unsigned long long total = s_p[LF_RES_NT - 1];
+    if (total >= (1ull << 30) || s_c[LF_RES_NT - 1] > (uint32_t)C.c_cap) {
+        if (tid == 0) atomicOr(C.status, 1);
+        return;
+    }
+    uint32_t rank = s_c[tid] - nc;
+    unsigned long long poff = s_p[tid] - np;
+    int32_t cnt[4] = {0, 0, 0, 0};
+    for (int32_t e = e0; e < e1; ++e) {
+        int32_t* rec = C.ev + 6 * (size_t)e;
+        const int32_t code = ld(rec), o = ld(C.ev_off + e), w = ld(rec + 5);
+        C.pair_off[e] = (int32_t)poff;
+        if (!code) continue;
+        ++cnt[code - 1];
+        int32_t keep = ld(rec + 1);
+        if (code == 3) {
+            keep = n + (int32_t)rank;
+            rec[1] = keep;
+            rec[3] = C.lc[3 * entry_of(C, e)];
+            C.cur_len[keep] = 2;
+            C.new_ev[rank++] = e;
+        }
+        poff += code == 3 ? 1ull : code == 4 ? (unsigned long long)o * w : (unsigned long long)o + 1;
+        const int32_t f0 = C.fw0[e], f1 = C.fw1[e];
+        if (code != 2 && code != 4 && f0 >= 0) atomicMax(C.feat_win + f0, e + 1);
+        if (code != 1 && f1 >= 0) atomicMax(C.feat_win + f1, e + 1);
+    }
+    for (int w = 0; w < 4; ++w)
+        if (cnt[w]) atomicAdd(s_cnt + W_A + w, cnt[w]);
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 0; w < 4; ++w) C.cnt[W_A + w] = s_cnt[W_A + w];
+        atomicAdd(C.cnt + W_SKIP, s_cnt[W_SKIP]);
+        C.cnt[W_PAIRS] = (int32_t)total;
+        C.pair_off[m] = (int32_t)total;
+    }
+}
+
+// K70: obs_ptr of the destination (an exclusive look-back scan of the final lengths over n + n_new landmarks) and the landmark
+// rows: inlier / X copied, valid cleared where an event fused the landmark away; a new landmark is valid, an inlier and
+// X = T_kp P0 (:4473, :4608-4609).
+__global__ void __launch_bounds__(LF_NT)
+k_lf_layout(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
+{
+    __shared__ uint32_t s_o[LF_NW], s_before;
+    if (*C.status) return;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
+    const int32_t i = b * LF_NT + tid;
+    const int32_t n2 = S.n + C.cnt[W_C];
+    const uint32_t c = i < n2 ? (uint32_t)C.cur_len[i] : 0u;
+    uint32_t incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_o[wv] = incl;
+    __syncthreads();
+    uint32_t own = 0, in = 0;
+#pragma unroll
+    for (int w = 0; w < LF_NW; ++w) {
+        in += w < wv ? s_o[w] : 0u;
+        own += s_o[w];
+    }
+    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
+    if (i < n2) {
+        D.obs_ptr[i] = (int32_t)(before + in + incl - c);
+        if (i < S.n) {
+            D.valid[i] = S.valid[i] && C.killer[i] < 0 ? S.valid[i] : 0;
+            D.inlier[i] = S.inlier[i];
+            for (int w = 0; w < S.dl; ++w) D.X[(size_t)S.dl * i + w] = S.X[(size_t)S.dl * i + w];
+        } else {
+            const int32_t e = C.new_ev[i - S.n];
+            const double* T = C.T + 16 * (size_t)C.ev[6 * (size_t)e + 3];
+            D.valid[i] = 1;
+            D.inlier[i] = 1;
+            xform(T, C.P0 + (size_t)S.dl * e, D.X + (size_t)S.dl * i);
+            if (C.lines) xform(T, C.P0 + 6 * (size_t)e + 3, D.X + 6 * (size_t)i + 3);
+        }
+    }
+    if (b == (int)gridDim.x - 1 && tid == 0) {
+        D.obs_ptr[n2] = (int32_t)(before + own);
+        C.cnt[W_OBS] = (int32_t)(before + own);
+    }
+}
+
+// K71: obs_kf / obs_val / obs_src of the destination.  Lanes [0, n_obs): a source observation to its place; lanes n_obs + 2 t + w:
+// the observation tuple t made on side w (A: w = 0, B: w = 1, C: both), and the position of the event's first observation.
+__global__ void __launch_bounds__(LF_NT)
+k_lf_obs(SrcD S, DstD D, CallD C)
+{
+    if (*C.status) return;
+    const int64_t i = (int64_t)blockIdx.x * LF_NT + threadIdx.x;
+    const int32_t total = C.cnt[W_OBS] < D.obs_cap ? C.cnt[W_OBS] : D.obs_cap;
+    int64_t pos = -1;
+    int32_t kf = -1, tag = 0;
+    const double* val = nullptr;
+    if (i < S.n_obs) {
+        if (S.n <= 0) return;
+        const int32_t j = (int32_t)i, x = segment_of(S.obs_ptr, S.n, j), k = j - S.obs_ptr[x];
+        if (k < 0 || k >= old_len(S, x)) return;
+        pos = place(S, D, C, x, k);
+        kf = S.obs_kf[j];
+        val = S.obs_val + (size_t)S.dv * j;
+        tag = j;
+    } else {
+        const int64_t u = i - S.n_obs;
+        if (u >= 2 * (int64_t)C.m) return;
+        const int32_t t = (int32_t)(u >> 1), w = (int32_t)(u & 1);
+        int32_t* rec = C.ev + 6 * (size_t)t;
+        const int32_t code = rec[0], ent = entry_of(C, t);
+        // the direction of the observation this side made: A / B in the camera frame, C in the world frame; zeros otherwise
+        double dir[3] = {0.0, 0.0, 0.0};
+        const double* Pw = (w ? C.P1 : C.P0) + (size_t)S.dl * t;
+        if ((code == 1 && w == 0) || (code == 2 && w == 1)) cam_dir(C.lines, Pw, dir);
+        else if (code == 3) world_dir(C.lines, C.T + 16 * (size_t)C.lc[3 * ent + w], Pw, dir);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) C.ev_dir[6 * (size_t)t + 3 * w + a] = dir[a];
+        if (!code) return;
+        const int64_t first = code == 3 ? (int64_t)D.obs_ptr[rec[1]] : place(S, D, C, rec[1], C.ev_off[t]);
+        if (w == 0) rec[4] = first >= 0 && first < total ? (int32_t)first : -1;
+        if (code == 4 || (code == 1 && w == 1) || (code == 2 && w == 0)) return;
+        pos = code == 3 ? first + w : first;
+        kf = C.lc[3 * ent + w];
+        val = (w ? C.o1 : C.o0) + (size_t)S.dv * t;
+        tag = -1 - (2 * t + w);
+    }
+    if (pos < 0 || pos >= total) return;
+    D.obs_kf[pos] = kf;
+    C.obs_src[pos] = tag;
+    for (int w = 0; w < S.dv; ++w) D.obs_val[(size_t)S.dv * pos + w] = val[w];
+}
+
+// K72: feat_idx, the anchors and the graph; the kernel strides over n_feat features, m events and the (event, pair) items.
+// Pair q of event e -- A / B: entry q of the target's list at the time, [first - o, first], against the other keyframe; C: (kp,
+// kc); D: entry q / w of a's first o entries against entry q % w of the w appended ones.
+__global__ void __launch_bounds__(LF_NT)
+k_lf_feat_graph(SrcD S, DstD D, CallD C, int32_t* __restrict__ graph)
+{
+    if (*C.status) return;
+    const int32_t total = C.cnt[W_OBS] < D.obs_cap ? C.cnt[W_OBS] : D.obs_cap, nk = C.n_map_kf;
+    const int64_t n_items = (int64_t)S.n_feat + C.m + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * LF_NT;
+    for (int64_t it = (int64_t)blockIdx.x * LF_NT + threadIdx.x; it < n_items; it += stride) {
+        if (it < S.n_feat) {
+            int32_t v = S.feat_idx[it];
+            const int32_t w = C.feat_win[it];
+            if (w > 0 && w <= C.m) v = C.ev[6 * (size_t)(w - 1) + 1];
+            D.feat_idx[it] = v;
+            continue;
+        }
+        if (it < (int64_t)S.n_feat + C.m) {
+            int32_t* rec = C.ev + 6 * (size_t)(it - S.n_feat);
+            if (rec[0] == 4) rec[3] = rec[4] >= 0 && rec[4] < total ? D.obs_kf[rec[4]] : -1;
+            continue;
+        }
+        const int32_t p = (int32_t)(it - S.n_feat - C.m), e = segment_of(C.pair_off, C.m, p), q = p - C.pair_off[e];
+        const int32_t* rec = C.ev + 6 * (size_t)e;
+        const int32_t code = rec[0], first = rec[4], o = C.ev_off[e], w = rec[5], ent = entry_of(C, e);
+        const int32_t kp = C.lc[3 * ent], kc = C.lc[3 * ent + 1];
+        int32_t gi = -1, gj = -1;
+        if (code == 3) { gi = kp; gj = kc; }
+        else if (first >= o && q >= 0) {
+            const int64_t a0 = (int64_t)first - o;
+            if (code == 4 && w > 0) {
+                const int64_t pi = a0 + q / w, pj = (int64_t)first + q % w;
+                if (pi < total && pj < total) { gi = D.obs_kf[pi]; gj = D.obs_kf[pj]; }
+            } else if ((code == 1 || code == 2) && a0 + q < total) {
+                gi = D.obs_kf[a0 + q];
+                gj = code == 1 ? kc : kp;
+            }
+        }
+        if (gi >= 0 && gi < nk && gj >= 0 && gj < nk) {
+            atomicAdd(graph + (size_t)gi * nk + gj, 1);
+            atomicAdd(graph + (size_t)gj * nk + gi, 1);
+        } else atomicAdd(C.cnt + W_SKIP, 1);
+    }
+}
+
+struct KfCopy {                          // what K73 copies from the source image where the destination has its own array
+    int32_t nk;
+    const uint8_t* kf_valid; uint8_t* kf_valid_d;
+    const double* x; double* x_d;
+    const int32_t* fp[2]; int32_t* fp_d[2];
+};
+
+// K73: the call's last kernel: the counters and the graph to the page-locked block; kf_valid / x_kf_w / feat_ptr copied
+__global__ void __launch_bounds__(LF_NT)
+k_lf_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ graph, KfCopy K, int32_t* __restrict__ pinned, int32_t with_graph)
+{
+    const int64_t g = (int64_t)blockIdx.x * LF_NT + threadIdx.x, stride = (int64_t)gridDim.x * LF_NT;
+    const bool ok = cnt[W_STATUS] == 0;
+    if (g < W_WORDS) pinned[g] = cnt[g];
+    if (!ok) return;
+    if (with_graph)
+        for (int64_t i = g; i < (int64_t)K.nk * K.nk; i += stride) pinned[W_WORDS + i] = graph[i];
+    for (int64_t i = g; i < K.nk; i += stride)
+        if (K.kf_valid_d) K.kf_valid_d[i] = K.kf_valid[i];
+    for (int64_t i = g; i < 6 * (int64_t)K.nk; i += stride)
+        if (K.x_d) K.x_d[i] = K.x[i];
+    for (int k = 0; k < 2; ++k)
+        for (int64_t i = g; i <= K.nk; i += stride)
+            if (K.fp_d[k]) K.fp_d[k][i] = K.fp[k][i];
+}
+
+unsigned tiles(int64_t n) { return (unsigned)(n > 0 ? (n + LF_NT - 1) / LF_NT : 1); }
+
+}  // namespace
+}  // namespace plslam
+
+using namespace plslam;
+
+struct plslam_lc_fuse {
+    plslam_ctx* ctx = nullptr;
+    DevBuf buf;
+    HostBuf pin;                                 // W_WORDS counters, the graph where it was asked for, then the staged block
+    bool done = false;
+    plslam_lc_fuse_buffers d = {};
+    int32_t m[2] = {0, 0}, n_obs[2] = {0, 0}, nk = 0;
+};
+
+extern "C" {
+
+int plslam_lc_fuse_create(plslam_ctx* ctx, plslam_lc_fuse** out)
+{
+    PLSLAM_REQUIRE(ctx && out, PLSLAM_EINVAL);
+    *out = new plslam_lc_fuse();
+    (*out)->ctx = ctx;
+    return PLSLAM_OK;
+}
+
+void plslam_lc_fuse_destroy(plslam_lc_fuse* lf)
+{
+    if (!lf) return;
+    {
+        std::lock_guard<std::mutex> lk(lf->ctx->mu);
+        DeviceGuard dg_(lf->ctx->device);
+        (void)hipStreamSynchronize(lf->ctx->stream);
+        lf->buf.release();
+        lf->pin.release();
+    }
+    delete lf;
+}
+
+int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t n_lc,
+                       const int32_t* lc_idx, const double* T_kf_w, const plslam_lc_fuse_kind* points,
+                       const plslam_lc_fuse_kind* lines, int32_t* graph_delta, plslam_lc_fuse_counts* counts)
+{
+    // ---- validate everything (lc_fuse_plan.hpp), then commit once ----
+    PLSLAM_REQUIRE(lf && counts, PLSLAM_EINVAL);
+    LcFusePlan P;
+    int rc = lc_fuse_plan(src, dst, n_lc, lc_idx, T_kf_w, points, lines, &P);
+    if (rc) {
+        set_last_error("plslam_lc_fuse_run: refused: %s", P.why);
+        return rc;
+    }
+    const plslam_map_landmarks* S[2] = {&src->points, &src->lines};
+    plslam_map_landmarks* Dk[2] = {&dst->map.points, &dst->map.lines};
+    const int32_t cap[2] = {dst->pt_cap, dst->ls_cap}, obs_cap[2] = {dst->pt_obs_cap, dst->ls_obs_cap};
+    const int32_t nk = P.nk;
+    // ---- the layout: [zeroed: counters, graph, per kind feat_win / part] [0x7f: head] [0xff: killer] [staged] [the rest] ----
+    struct KindOff { size_t win, part, head, killer, len, sc, fw0, fw1, ev, off, pair, nev, dir, osrc; unsigned w_lm; } O[2];
+    Carver c;
+    const size_t o_cnt = c.take(W_WORDS * 4), o_graph = c.take((size_t)nk * nk * 4);
+    for (int k = 0; k < 2; ++k) {
+        O[k].w_lm = tiles(P.k[k].need_lm);
+        O[k].win = c.take((size_t)S[k]->n_feat * 4 + 4);
+        O[k].part = c.take((size_t)O[k].w_lm * 4);
+    }
+    const size_t zero_bytes = c.off;
+    for (int k = 0; k < 2; ++k) O[k].head = c.take((size_t)S[k]->n * 4 + 4);
+    const size_t head_off = zero_bytes, head_bytes = c.off - head_off;
+    for (int k = 0; k < 2; ++k) O[k].killer = c.take((size_t)S[k]->n * 4 + 4);
+    const size_t killer_off = head_off + head_bytes, killer_bytes = c.off - killer_off;
+    const size_t stage_off = c.take(P.stage_bytes);
+    for (int k = 0; k < 2; ++k) {
+        const size_t m = (size_t)P.k[k].m;
+        O[k].len = c.take((size_t)P.k[k].need_lm * 4 + 4);
+        O[k].sc = c.take(m * 4 + 4); O[k].fw0 = c.take(m * 4 + 4); O[k].fw1 = c.take(m * 4 + 4);
+        O[k].ev = c.take(m * 24 + 24); O[k].off = c.take(m * 4 + 4); O[k].pair = c.take(m * 4 + 8);
+        O[k].nev = c.take((size_t)P.k[k].cC * 4 + 4); O[k].dir = c.take(m * 48 + 48);
+        O[k].osrc = c.take((size_t)obs_cap[k] * 4 + 4);
+    }
+    std::lock_guard<std::mutex> lk(lf->ctx->mu);
+    DeviceGuard dg_(lf->ctx->device);
+    hipStream_t s = lf->ctx->stream;
+    lf->done = false;
+    if ((rc = lf->buf.reserve(c.off + 256))) return rc;
+    const size_t res_bytes = align256((W_WORDS + (graph_delta ? (size_t)nk * nk : 0)) * 4);
+    if ((rc = lf->pin.reserve(res_bytes + P.stage_bytes))) return rc;
+    PLSLAM_REQUIRE(lf->pin.dev, PLSLAM_ENOTSUP);                 // the counters are written where the host reads them
+    char* d = lf->buf.as<char>();
+    char* h = lf->pin.as<char>();
+    lc_fuse_pack(P, lc_idx, T_kf_w, h + res_bytes);
+    StreamSyncOnError guard(s);
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d, 0, zero_bytes, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d + head_off, 0x7f, head_bytes, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(d + killer_off, 0xff, killer_bytes, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + stage_off, h + res_bytes, P.stage_bytes, hipMemcpyHostToDevice, s));
+    int32_t* cnt = (int32_t*)(d + o_cnt);
+    int32_t* graph = (int32_t*)(d + o_graph);
+    const char* st_ = d + stage_off;
+    SrcD Sd[2];
+    DstD Dd[2];
+    CallD C[2];
+    for (int k = 0; k < 2; ++k) {
+        const LcFuseKindPlan& K = P.k[k];
+        const plslam_map_landmarks& A = *S[k];
+        plslam_map_landmarks& B = *Dk[k];
+        Sd[k] = SrcD{A.n, A.n_obs, A.n_feat, K.dl, K.dv, A.valid, A.inlier, A.X, A.obs_ptr, A.obs_kf, A.obs_val, A.feat_ptr, A.feat_idx};
+        Dd[k] = DstD{B.valid, (uint8_t*)B.inlier, (double*)B.X, (int32_t*)B.obs_ptr, (int32_t*)B.obs_kf, (double*)B.obs_val, B.feat_idx,
+                     cap[k], obs_cap[k]};
+        CallD& Ck = C[k];
+        Ck = CallD{};
+        Ck.lines = k; Ck.n_map_kf = nk; Ck.n_lc = n_lc; Ck.m = K.m; Ck.c_cap = K.cC;
+        Ck.kf_valid = src->kf_valid;
+        Ck.lc = (const int32_t*)(st_ + P.o_lc); Ck.tup = (const int32_t*)(st_ + K.o_tup); Ck.eptr = (const int32_t*)(st_ + K.o_eptr);
+        Ck.T = (const double*)(st_ + P.o_T);
+        Ck.P0 = (const double*)(st_ + K.o_P0); Ck.o0 = (const double*)(st_ + K.o_o0);
+        Ck.P1 = (const double*)(st_ + K.o_P1); Ck.o1 = (const double*)(st_ + K.o_o1);
+        Ck.cur_len = (int32_t*)(d + O[k].len); Ck.killer = (int32_t*)(d + O[k].killer); Ck.head = (int32_t*)(d + O[k].head);
+        Ck.sc = (int32_t*)(d + O[k].sc); Ck.fw0 = (int32_t*)(d + O[k].fw0); Ck.fw1 = (int32_t*)(d + O[k].fw1);
+        Ck.ev = (int32_t*)(d + O[k].ev); Ck.ev_off = (int32_t*)(d + O[k].off); Ck.pair_off = (int32_t*)(d + O[k].pair);
+        Ck.new_ev = (int32_t*)(d + O[k].nev); Ck.feat_win = (int32_t*)(d + O[k].win); Ck.obs_src = (int32_t*)(d + O[k].osrc);
+        Ck.cnt = cnt + W_KIND * k; Ck.status = cnt + W_STATUS; Ck.ev_dir = (double*)(d + O[k].dir);
+    }
+    // both kinds are resolved before anything of the destination is written: a refusal leaves it untouched
+    for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_classify, dim3(tiles((int64_t)S[k]->n + P.k[k].m)), dim3(LF_NT), 0, s, Sd[k], C[k]);
+    for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_resolve, dim3(1), dim3(LF_RES_NT), 0, s, Sd[k], C[k]);
+    for (int k = 0; k < 2; ++k) {
+        hipLaunchKernelGGL(k_lf_layout, dim3(O[k].w_lm), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k], (uint32_t*)(d + O[k].part));
+        hipLaunchKernelGGL(k_lf_obs, dim3(tiles((int64_t)S[k]->n_obs + 2 * (int64_t)P.k[k].m)), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k]);
+        const unsigned g = tiles((int64_t)S[k]->n_feat + S[k]->n_obs + 4 * (int64_t)P.k[k].m);
+        hipLaunchKernelGGL(k_lf_feat_graph, dim3(g < LF_MAX_GRID ? g : LF_MAX_GRID), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k], graph);
+    }
+    KfCopy kc{};
+    kc.nk = nk;
+    kc.kf_valid = src->kf_valid; kc.kf_valid_d = dst->map.kf_valid != src->kf_valid ? (uint8_t*)dst->map.kf_valid : nullptr;
+    kc.x = src->x_kf_w; kc.x_d = dst->map.x_kf_w != src->x_kf_w ? (double*)dst->map.x_kf_w : nullptr;
+    for (int k = 0; k < 2; ++k) {
+        kc.fp[k] = S[k]->feat_ptr;
+        kc.fp_d[k] = S[k]->n_feat > 0 && Dk[k]->feat_ptr != S[k]->feat_ptr ? (int32_t*)Dk[k]->feat_ptr : nullptr;
+    }
+    const unsigned gp = tiles(graph_delta ? (int64_t)nk * nk : nk + 1);
+    hipLaunchKernelGGL(k_lf_publish, dim3(gp < 256u ? gp : 256u), dim3(LF_NT), 0, s, (const int32_t*)cnt, (const int32_t*)graph, kc,
+                       (int32_t*)lf->pin.dev, graph_delta ? 1 : 0);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    const int32_t* r = lf->pin.as<int32_t>();
+    if (r[W_STATUS]) {
+        set_last_error("plslam_lc_fuse_run: refused: an event's level is above PLSLAM_LC_FUSE_MAX_LEVEL (or its pairs beyond 2^30)");
+        return PLSLAM_ERANGE;
+    }
+    if (graph_delta) memcpy(graph_delta, r + W_WORDS, (size_t)nk * nk * 4);
+    plslam_lc_fuse_kind_counts* out[2] = {&counts->points, &counts->lines};
+    for (int k = 0; k < 2; ++k) {
+        const int32_t* w = r + W_KIND * k;
+        *out[k] = plslam_lc_fuse_kind_counts{w[W_A], w[W_B], w[W_C], w[W_D], w[W_C], w[W_D], w[W_SKIP]};
+        lf->m[k] = P.k[k].m;
+        lf->n_obs[k] = w[W_OBS] < obs_cap[k] ? w[W_OBS] : obs_cap[k];
+        Dk[k]->n = S[k]->n + w[W_C];
+        Dk[k]->n_obs = lf->n_obs[k];
+        Dk[k]->n_feat = S[k]->n_feat;
+        (k ? lf->d.ls_ev : lf->d.pt_ev) = C[k].ev;
+        (k ? lf->d.ls_dir : lf->d.pt_dir) = C[k].ev_dir;
+        (k ? lf->d.ls_obs_src : lf->d.pt_obs_src) = C[k].obs_src;
+    }
+    dst->map.n_map_kf = nk;
+    lf->nk = nk;
+    lf->d.graph_delta = graph;
+    lf->d.stream = (void*)s;
+    lf->done = true;
+    return PLSLAM_OK;
+}
+
+int plslam_lc_fuse_device_buffers(plslam_lc_fuse* lf, plslam_lc_fuse_buffers* out)
+{
+    PLSLAM_REQUIRE(lf && out && lf->done, PLSLAM_EINVAL);
+    *out = lf->d;
+    return PLSLAM_OK;
+}
+
+int plslam_lc_fuse_download(plslam_lc_fuse* lf, const plslam_lc_fuse_buffers* host)
+{
+    PLSLAM_REQUIRE(lf && host && lf->done, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(lf->ctx->mu);
+    DeviceGuard dg_(lf->ctx->device);
+    hipStream_t s = lf->ctx->stream;
+    StreamSyncOnError guard(s);
+    struct Item { void* dst; const void* src; size_t bytes; };
+    const Item items[] = {{host->pt_ev, lf->d.pt_ev, (size_t)lf->m[0] * 24}, {host->pt_dir, lf->d.pt_dir, (size_t)lf->m[0] * 48},
+                          {host->ls_ev, lf->d.ls_ev, (size_t)lf->m[1] * 24}, {host->ls_dir, lf->d.ls_dir, (size_t)lf->m[1] * 48},
+                          {host->pt_obs_src, lf->d.pt_obs_src, (size_t)lf->n_obs[0] * 4},
+                          {host->ls_obs_src, lf->d.ls_obs_src, (size_t)lf->n_obs[1] * 4},
+                          {host->graph_delta, lf->d.graph_delta, (size_t)lf->nk * lf->nk * 4}};
+    for (const Item& it : items)
+        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    return PLSLAM_OK;
+}
+
+}  // extern "C"

@@ -94,6 +94,16 @@ public:
     {
         return run(true, -1, kf2_idx, nullptr, T_kf2_w, pts, lns);
     }
+    // another out-of-place call of the library over the pair (host/lc_fuse.hpp): the other image is given room for the stated
+    // landmarks and observations per kind, f(current index, destination) runs the call, and the images swap when it returns
+    template <class F> void pingpong(int32_t pt_n, int32_t pt_n_obs, int32_t ls_n, int32_t ls_n_obs, F&& f)
+    {
+        const plslam_map_index& m = img_[cur_].d.map;
+        Image& dst = img_[1 - cur_];
+        reserve(dst, m.n_map_kf, Sizes{pt_n, pt_n_obs, m.points.n_feat}, Sizes{ls_n, ls_n_obs, m.lines.n_feat});
+        f(m, dst.d);
+        cur_ = 1 - cur_;
+    }
 
 private:
     struct Sizes { int32_t n, n_obs, n_feat; };

@@ -1,0 +1,224 @@
+"""A loop closure's landmarks fused into the device-resident map (plslam_lc_fuse_*, include/plslam_hip.h):
+MapHandler::loopClosureFuseLandmarks (src/mapHandler.cpp:4412-4687) over the CSR image of plslam_amd.local_map, out of place
+between two plslam_amd.map_insert.DeviceMapImage.
+
+Three parts: the ctypes structs; LcFuse, the handle; and the SEEDED generators pack_loop_closure (explicit tuples -> the call's
+arguments) and synthetic_loop_closure (entries over a synthetic_map with a stated mix of branches)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .capi import Context, _check, _p
+from .local_map import FEAT_NULL
+from .map_insert import DeviceMapImage
+
+LOOKBACK_TILE = 256       # plslam_amd/csrc/lc_fuse.hip: LF_NT, the items one workgroup of the obs_ptr scan takes
+MAX_TUPLES = 65536        # include/plslam_hip.h: PLSLAM_LC_FUSE_MAX_TUPLES
+MAX_LEVEL = 64            # include/plslam_hip.h: PLSLAM_LC_FUSE_MAX_LEVEL
+
+_vp, _i32 = C.c_void_p, C.c_int32
+COUNTS = ("n_a", "n_b", "n_c", "n_d", "n_new", "n_dead", "n_skipped")
+
+
+class LcFuseKind(C.Structure):
+    _fields_ = [(k, _vp) for k in ("tuples", "entry_ptr", "P0", "obs0", "P1", "obs1")]
+
+
+class LcFuseKindCounts(C.Structure):
+    _fields_ = [(k, _i32) for k in COUNTS]
+
+
+class LcFuseCounts(C.Structure):
+    _fields_ = [("points", LcFuseKindCounts), ("lines", LcFuseKindCounts)]
+
+
+class LcFuseBuffers(C.Structure):
+    _fields_ = [(k, _vp) for k in ("pt_ev", "ls_ev", "pt_dir", "ls_dir", "pt_obs_src", "ls_obs_src", "graph_delta", "stream")]
+
+
+def fuse_bounds(m, lc) -> dict:
+    """the capacities a fusion of `lc` into `m` needs, from the tuples of the flagged entries alone: with cC tuples (-1, -1) and
+    cAB tuples with exactly one -1, n + cC landmarks and n_obs + cAB + 2 cC observations (a fusion moves observations)"""
+    flag = np.asarray(lc["lc_idx"]).reshape(-1, 3)[:, 2] == 1
+    out = {}
+    for kind, tag in (("points", "pt"), ("lines", "ls")):
+        K, cC, cAB = lc.get(kind), 0, 0
+        if K is not None:
+            t, ep = np.asarray(K["tuples"]).reshape(-1, 4), np.asarray(K["entry_ptr"])
+            on = np.repeat(flag, np.diff(ep))
+            a, b = (t[:, 0] == -1) & on, (t[:, 2] == -1) & on
+            cC, cAB = int((a & b).sum()), int((a ^ b).sum())
+        out[tag + "_cap"] = int(m[kind]["n"]) + cC
+        out[tag + "_obs_cap"] = int(np.asarray(m[kind]["obs_kf"]).size) + cAB + 2 * cC
+    return out
+
+
+class LcFuse:
+    """plslam_lc_fuse: the handle that owns the scratch and the records of a run."""
+
+    def __init__(self, ctx: Context):
+        self._L, self._ctx, self._h = ctx._L, ctx, None
+        h = C.c_void_p()
+        _check(self._L.plslam_lc_fuse_create(ctx.handle, C.byref(h)), "plslam_lc_fuse_create")
+        self._h = h
+        self._shape = None
+
+    def run(self, src, dst: DeviceMapImage, lc, graph: bool = True) -> dict:
+        """lc: dict(lc_idx (n_lc, 3), T_kf_w (n_map_kf, 4, 4), points / lines: dict(tuples, entry_ptr, P0, obs0, P1, obs1) or
+        None) -> dict(points / lines: the counts, graph_delta (n_map_kf, n_map_kf) or None); dst's struct then describes the
+        new image"""
+        lc_idx = np.ascontiguousarray(lc["lc_idx"], np.int32).reshape(-1, 3)
+        T = np.ascontiguousarray(lc["T_kf_w"], np.float64).reshape(-1)
+        keep, ks = [lc_idx, T], []
+        for kind in ("points", "lines"):
+            K = lc.get(kind)
+            if K is None:
+                ks.append(None)
+                continue
+            arrs = [np.ascontiguousarray(K["tuples"], np.int32), np.ascontiguousarray(K["entry_ptr"], np.int32)]
+            arrs += [np.ascontiguousarray(K[k], np.float64) for k in ("P0", "obs0", "P1", "obs1")]
+            keep.append(arrs)
+            ks.append(LcFuseKind(*[_p(a) if a.size else None for a in arrs]))
+        nk = src.n_map_kf
+        g = np.zeros((nk, nk), np.int32) if graph else None
+        c = LcFuseCounts()
+        rc = self._L.plslam_lc_fuse_run(self._h, C.addressof(src.struct), C.addressof(dst.dst), lc_idx.shape[0], _p(lc_idx), _p(T),
+                                        *[C.addressof(k) if k is not None else None for k in ks], _p(g) if graph else None,
+                                        C.addressof(c))
+        _check(rc, "plslam_lc_fuse_run")
+        dst.n_map_kf = dst.struct.n_map_kf
+        out = dict(graph_delta=g)
+        for kind, kc in (("points", c.points), ("lines", c.lines)):
+            out[kind] = {k: getattr(kc, k) for k in COUNTS}
+        m = [0 if lc.get(k) is None else int(np.asarray(lc[k]["entry_ptr"])[-1]) for k in ("points", "lines")]
+        self._shape = (m, [dst.struct.points.n_obs, dst.struct.lines.n_obs], nk)
+        return out
+
+    def device_buffers(self) -> dict:
+        b = LcFuseBuffers()
+        _check(self._L.plslam_lc_fuse_device_buffers(self._h, C.addressof(b)), "plslam_lc_fuse_device_buffers")
+        return {k: (getattr(b, k) or 0) for k, _ in LcFuseBuffers._fields_}
+
+    def download(self) -> dict:
+        """the records of the last run: dict(points / lines: dict(ev (m, 6) int32, dir (m, 6) float64, obs_src (n_obs,) int32),
+        graph_delta)"""
+        m, n_obs, nk = self._shape
+        out, b = dict(graph_delta=np.zeros((nk, nk), np.int32)), LcFuseBuffers()
+        b.graph_delta = _p(out["graph_delta"])
+        for i, (kind, tag) in enumerate((("points", "pt"), ("lines", "ls"))):
+            out[kind] = dict(ev=np.zeros((m[i], 6), np.int32), dir=np.zeros((m[i], 6), np.float64), obs_src=np.zeros(n_obs[i], np.int32))
+            for f in ("ev", "dir", "obs_src"):
+                if out[kind][f].size:
+                    setattr(b, f"{tag}_{f}", _p(out[kind][f]))
+        _check(self._L.plslam_lc_fuse_download(self._h, C.addressof(b)), "plslam_lc_fuse_download")
+        return out
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value and self._ctx.handle:
+            self._L.plslam_lc_fuse_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the seeded generators ----------------------------------------------------------------------------------------------------
+def _pose(rng):
+    q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = q, rng.uniform(-2.0, 2.0, 3)
+    return T
+
+
+def pack_loop_closure(m, lc_idx, points=None, lines=None, seed=1) -> dict:
+    """explicit tuples -> the call's arguments.  lc_idx: rows (kf_prev, kf_curr, flag); points / lines: per entry a list of
+    tuples (lm_idx0, lm_ldx0, lm_idx1, lm_ldx1), or None for no tuple of the kind.  The features' values (P0, obs0, P1, obs1) and
+    T_kf_w are drawn from the seed."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    nk = int(m["n_map_kf"])
+    lc = dict(lc_idx=np.array(lc_idx, np.int32).reshape(-1, 3), T_kf_w=np.stack([_pose(rng) for _ in range(nk)]))
+    for kind, per_entry, dl, dv in (("points", points, 3, 2), ("lines", lines, 6, 3)):
+        if per_entry is None:
+            lc[kind] = None
+            continue
+        assert len(per_entry) == lc["lc_idx"].shape[0]
+        tup = np.array([t for e in per_entry for t in e], np.int32).reshape(-1, 4)
+        ep = np.zeros(len(per_entry) + 1, np.int32)
+        ep[1:] = np.cumsum([len(e) for e in per_entry])
+        n = tup.shape[0]
+        lc[kind] = dict(tuples=tup, entry_ptr=ep, P0=rng.uniform(-3.0, 3.0, (n, dl)) + np.tile([0.0, 0.0, 8.0], dl // 3),
+                        obs0=rng.uniform(0.0, 700.0, (n, dv)), P1=rng.uniform(-3.0, 3.0, (n, dl)) + np.tile([0.0, 0.0, 8.0], dl // 3),
+                        obs1=rng.uniform(0.0, 700.0, (n, dv)))
+    return lc
+
+
+_MIX = dict(n_a=0, n_b=0, n_c=0, n_d=0, n_null_feat=0, n_invalid=0, n_lm_range=0, n_ldx_range=0, n_self=0, n_empty=0, n_shared=0)
+
+
+def synthetic_loop_closure(m, entries=((3, 30, 1),), points=None, lines=None, seed=1) -> dict:
+    """-> the call's arguments for `entries` (rows of lc_idx) over the map m.  points / lines: the mix PER ENTRY, a dict of counts of
+    tuples per branch, or a list of such dicts, one per entry (None: no tuple of the kind):
+      n_a / n_b / n_c / n_d tuples the branch acts on (their landmarks valid, with observations, distinct over the whole call; the
+      features any non-NULL ones of the two keyframes); n_null_feat of EACH branch with a NULL feature; n_invalid A, B and D
+      tuples on a NULL landmark; n_lm_range / n_ldx_range tuples with an index beyond the map / the keyframe; n_self D tuples with
+      a == b; n_empty D tuples whose b is valid without observations; n_shared A tuples on a landmark an EARLIER entry's A tuple
+      named (none in the first entry).
+    The tuples of an entry are shuffled.  The same seed gives the same arguments."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    per = {}
+    for kind, mix in (("points", points), ("lines", lines)):
+        if mix is None:
+            per[kind] = None
+            continue
+        A = m[kind]
+        n, lens = int(A["n"]), np.diff(A["obs_ptr"])
+        ok = rng.permutation(np.flatnonzero((A["valid"] == 1) & (lens > 0))).tolist()
+        bad = np.flatnonzero(A["valid"] == 0)
+        empty = np.flatnonzero((A["valid"] == 1) & (lens == 0))
+        out, a_named = [], []
+        for ei, (kp, kc, _) in enumerate(entries):
+            mx = dict(_MIX, **(mix[ei] if isinstance(mix, (list, tuple)) else mix))
+            f = {k: A["feat_idx"][A["feat_ptr"][k]:A["feat_ptr"][k + 1]] for k in (kp, kc)}
+            good = {k: np.flatnonzero(v != FEAT_NULL) for k, v in f.items()}
+            null = {k: np.flatnonzero(v == FEAT_NULL) for k, v in f.items()}
+
+            def g(k):
+                return int(rng.choice(good[k])) if good[k].size else 0
+
+            def z(k):
+                return int(rng.choice(null[k])) if null[k].size else 0
+
+            def lm():
+                return ok.pop()
+
+            t = [(-1, g(kp), lm(), g(kc)) for _ in range(mx["n_a"])]
+            named_here = [x[2] for x in t]
+            t += [(lm(), g(kp), -1, g(kc)) for _ in range(mx["n_b"])]
+            t += [(-1, g(kp), -1, g(kc)) for _ in range(mx["n_c"])]
+            t += [(lm(), g(kp), lm(), g(kc)) for _ in range(mx["n_d"])]
+            for _ in range(mx["n_null_feat"]):
+                t += [(-1, z(kp), lm(), g(kc)), (lm(), g(kp), -1, z(kc)), (-1, z(kp), -1, g(kc)), (-1, g(kp), -1, z(kc)),
+                      (lm(), g(kp), lm(), z(kc))]
+            for _ in range(mx["n_invalid"]):
+                t += [(-1, g(kp), int(rng.choice(bad)), g(kc)), (int(rng.choice(bad)), g(kp), -1, g(kc)),
+                      (lm(), g(kp), int(rng.choice(bad)), g(kc)), (int(rng.choice(bad)), g(kp), lm(), g(kc))]
+            t += [((-1, g(kp), n + 5 + i, g(kc)), (n + i, g(kp), -1, g(kc)), (-3, g(kp), lm(), g(kc)))[i % 3] for i in range(mx["n_lm_range"])]
+            t += [((-1, f[kp].size + i, lm(), g(kc)), (lm(), g(kp), -1, f[kc].size + i), (lm(), g(kp), lm(), -1 - i),
+                   (-1, g(kp), -1, f[kc].size))[i % 4] for i in range(mx["n_ldx_range"])]
+            for _ in range(mx["n_self"]):
+                x = lm()
+                t.append((x, g(kp), x, g(kc)))
+            t += [(lm(), g(kp), int(x), g(kc)) for x in rng.choice(empty, mx["n_empty"], replace=False)]
+            if a_named:
+                t += [(-1, g(kp), int(x), g(kc)) for x in rng.choice(a_named, mx["n_shared"], replace=False)]
+            a_named += named_here
+            out.append([t[i] for i in rng.permutation(len(t))])
+        per[kind] = out
+    return pack_loop_closure(m, entries, per["points"], per["lines"], seed=int(rng.integers(1 << 30)))

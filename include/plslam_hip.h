@@ -47,7 +47,8 @@ extern "C" {
  * plslam_envelope_ldlt_solve with plslam_pgo_params / plslam_pgo_trial / plslam_pgo_result / plslam_lc_landmarks; the local map
  * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts; the map
  * insertion plslam_map_insert_* with plslam_map_insert_kind / _dst / _counts / _events; the loop-closure landmark fusion
- * plslam_lc_fuse_* with plslam_lc_fuse_kind / _counts / _buffers.
+ * plslam_lc_fuse_* with plslam_lc_fuse_kind / _counts / _buffers; the device-built LBA plan plslam_lba_plan_create_dev with
+ * plslam_lba_plan_list_sizes / _lists, and plslam_local_map_apply_lba (plslam_local_map_buffers / _counts grew at the END).
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -613,6 +614,49 @@ int plslam_lba_plan_get_landmarks(plslam_lba_plan* plan, double* Xw, double* Lw)
 int plslam_lba_plan_rows(plslam_lba_plan* plan, double* pt_J_pose, double* pt_J_lm, double* pt_r, double* pt_w,
                          double* ls_J_pose, double* ls_J_lm, double* ls_r, double* ls_w);
 void plslam_lba_plan_destroy(plslam_lba_plan* plan);
+/* The same plan built ON THE DEVICE from DEVICE columns (additive within 5; K74-K83, KERNELS.md): the eight observation columns
+ * are device pointers with the layouts and meanings of plslam_lba_plan_create -- e.g. what plslam_local_map_gather leaves in
+ * plslam_local_map_buffers -- read on the context's stream.  The range checks are the host call's, made on the device: an lm_loc,
+ * kf_loc or pose_slot out of range gives PLSLAM_EINVAL and no plan, and no kernel follows a bad index; NULL and negative
+ * arguments (and observations where npt / nls / n_pose_slots is 0) are refused before anything is launched.  The lists -- per
+ * landmark, per keyframe, and on first use of the Schur step the pair lists -- are built on the device, equal entry for entry
+ * to those plslam_lba_plan_create builds on the host (plslam_lba_plan_lists shows them); the plan keeps no host copy.  Every
+ * plslam_lba_plan_* call works on the plan.  One synchronisation here, one when the Schur lists are built.
+ *   d_Xw (npt x 3) / d_Lw (nls x 6)  device pointers or NULL: copied into the plan's resident landmarks (for the gather: X_aux +
+ *                        6 nkf and X_aux + 6 nkf + 3 npt).  With both given (where the kind exists) ONE plslam_lba_plan_set_poses
+ *                        makes the state valid: plslam_lba_plan_iterate_resident / _iterate_schur run with no landmark uploaded.
+ *   first_estimate_slot  -1: the slots as given.  s >= 0 (s + nkf <= n_pose_slots): the slot of every POINT observation with
+ *                        kf_loc >= 0 becomes s + kf_loc -- the current estimate of its keyframe (:1600-1601); line observations
+ *                        and keyframes that are not optimised keep the given slot (:1680).  With the gather's *_pose_slot (the
+ *                        keyframe index): n_pose_slots = n_map_kf + nkf, first_estimate_slot = n_map_kf.
+ * PLSLAM_ERANGE: 2^30 observations, or (at the Schur lists' first use) 2^30 pairs with their padding. */
+int plslam_lba_plan_create_dev(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_pose_slots, int32_t nkf,
+                               int32_t npt, int32_t nls, const int32_t* d_pt_lm_loc, const int32_t* d_pt_pose_slot,
+                               const int32_t* d_pt_kf_loc, const double* d_pt_obs_uv, int32_t n_pt_obs,
+                               const int32_t* d_ls_lm_loc, const int32_t* d_ls_pose_slot, const int32_t* d_ls_kf_loc,
+                               const double* d_ls_l_obs, int32_t n_ls_obs, const double* d_Xw, const double* d_Lw,
+                               int32_t first_estimate_slot, plslam_lba_plan** out);
+/* The lists of a plan of either kind, device -> host: a debugging aid (what the tests compare).  plslam_lba_plan_list_sizes
+ * gives the lengths; prepare_schur != 0 builds the Schur pair lists first if no Schur call has yet (what the first
+ * plslam_lba_plan_diag_max / _schur / _iterate_schur does).  plslam_lba_plan_lists: HOST pointers, NULL = skip.
+ *   pt_ptr (npt + 1) / pt_ids (n_pt_obs), ls_ptr (nls + 1) / ls_ids (n_ls_obs), kf_ptr (nkf + 1) / kf_ids (n_kf_ids: points,
+ *   then lines as n_pt_obs + o); the observation columns as the plan stores them (after the slot rewrite);
+ *   blk_ptr (nblk + 1) and pairs (n_pairs x 4 int32: o1, o2, landmark, kind; kind 2 = a null pair of the padding): only after
+ *   the Schur lists are built, PLSLAM_EINVAL before. */
+typedef struct plslam_lba_list_sizes {
+    int32_t nkf, npt, nls, n_pt_obs, n_ls_obs, n_kf_ids, max_chunks;
+    int32_t schur_ready, nblk, n_pairs, schur_chunks;
+} plslam_lba_list_sizes;
+typedef struct plslam_lba_lists {
+    int32_t *pt_ptr, *pt_ids, *ls_ptr, *ls_ids, *kf_ptr, *kf_ids;
+    int32_t *pt_lm_loc, *pt_pose_slot, *pt_kf_loc;
+    double* pt_obs_uv;
+    int32_t *ls_lm_loc, *ls_pose_slot, *ls_kf_loc;
+    double* ls_l_obs;
+    int32_t *blk_ptr, *pairs;
+} plslam_lba_lists;
+int plslam_lba_plan_list_sizes(plslam_lba_plan* plan, int prepare_schur, plslam_lba_list_sizes* out);
+int plslam_lba_plan_lists(plslam_lba_plan* plan, const plslam_lba_lists* host);
 
 /* ---- K17: pose-only Gauss-Newton system of the loop-closure relative pose ------------------------------- */
 /* The iteration body of MapHandler::computeRelativePoseGN (src/mapHandler.cpp:3324-3424) and of
@@ -1221,19 +1265,22 @@ typedef struct plslam_map_index {
  *               local idx, obs idx, kf idx, kf local idx or -1, 1); the columns plslam_lba_plan_create takes: *_lm_loc (column 1),
  *               *_kf_loc (column 4), *_pose_slot (column 3: n_pose_slots = n_map_kf), pt_obs_uv (n x 2), ls_l_obs (n x 3);
  *               X_aux[6 nkf + 3 npt_l + 6 nls_l]
- *   cull        pt_removed[npt], ls_removed[nls]                   uint8 */
+ *   cull        pt_removed[npt], ls_removed[nls]                   uint8
+ *   apply_lba   pt_moved[npt_l], ls_moved[nls_l]                   uint8 (appended behind `stream`: the struct's prefix is unchanged) */
 typedef struct plslam_local_map_buffers {
     uint8_t *kf_local, *pt_local, *ls_local, *pt_candidate, *ls_candidate, *pt_removed, *ls_removed;
     int32_t *kf_list, *pt_list, *ls_list, *pt_obs, *ls_obs;
     int32_t *pt_lm_loc, *pt_kf_loc, *pt_pose_slot, *ls_lm_loc, *ls_kf_loc, *ls_pose_slot;
     double *pt_obs_uv, *ls_l_obs, *X_aux;
     void* stream;
+    uint8_t *pt_moved, *ls_moved;
 } plslam_local_map_buffers;
 typedef struct plslam_local_map_counts {
     int32_t n_kf_local, n_pt_local, n_ls_local;          /* form: flags set                                                  */
     int32_t nkf, npt, nls, n_pt_obs, n_ls_obs;           /* gather: list lengths (nkf excludes slot 0, :1231)                */
     int32_t empty;                                       /* gather: n_pt_obs + n_ls_obs == 0, the reference's return -1 (:1327) */
     int32_t n_pt_removed, n_ls_removed;                  /* cull                                                             */
+    int32_t n_pt_moved, n_ls_moved;                      /* apply_lba (appended)                                             */
 } plslam_local_map_counts;
 typedef struct plslam_local_map plslam_local_map;
 int plslam_local_map_create(plslam_ctx* ctx, plslam_local_map** out);
@@ -1258,6 +1305,26 @@ int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, p
  * list is not culled.  After form on the same map; counts: the cull fields. */
 int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int32_t max_kf_idx, int32_t min_lm_obs,
                           plslam_local_map_counts* counts);
+/* The write-back of localBundleAdjustment (:1828-1855) from the plan's RESIDENT landmarks into the image, after gather on the
+ * handle: for local point i, j = pt_list[i]: d = Xw[i] - X[j] per component, s2 = ((0 + d0^2) + d1^2) + d2^2 (left to right, no
+ * contraction), moved = sqrt(s2) > moved_th (the reference's literal: 0.01); a moved landmark's inlier[j] is cleared (never
+ * set); X[j] = Xw[i], a verbatim copy.  Lines the same over six components.  dst: WRITABLE device pointers into the caller's
+ * image (plslam_map_landmarks declares X and inlier const: this call is their writer); they may be the very arrays of the index
+ * the gather read -- a listed landmark occurs once in its list, so in place is safe.  pt_moved[npt_l] / ls_moved[nls_l] go into
+ * the handle's buffers, n_pt_moved / n_ls_moved into counts.  One launch on the context's stream, one synchronisation.
+ * Keyframe poses are not touched: the reference stores T_kf_w = expmap_se3(X_k) and leaves x_kf_w as it was (:1822-1826), and
+ * the image holds x_kf_w only -- nothing to write.  The removal of observations behind the write-back (:1857-1979) never runs
+ * in the reference (obs(5) is never -1) and is not here.
+ * PLSLAM_EINVAL: no gather has run on the handle; the plan's npt / nls differ from the gather's counts; the plan's state is not
+ * resident (no iterate / set_poses yet); the plan belongs to another context. */
+typedef struct plslam_local_map_lba_dst {
+    double* pt_X;
+    uint8_t* pt_inlier;
+    double* ls_X;
+    uint8_t* ls_inlier;
+} plslam_local_map_lba_dst;
+int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, const plslam_local_map_lba_dst* dst, double moved_th,
+                               plslam_local_map_counts* counts);
 int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out);
 int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffers* host);
 

@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "plslam_lba_plan_iterate_resident", "plslam_lba_plan_diag_max", "plslam_lba_plan_schur", "plslam_lba_plan_backsub",
     "plslam_lba_plan_set_poses", "plslam_lba_plan_host_state", "plslam_lba_plan_get_landmarks",
     "plslam_lba_plan_iterate_schur", "plslam_lba_plan_apply_step", "plslam_lba_point_rows_dev_n", "plslam_lba_line_rows_dev_n", "plslam_rccl_available",
-    "plslam_lba_plan_blocks",
+    "plslam_lba_plan_blocks", "plslam_lba_plan_create_dev", "plslam_lba_plan_list_sizes", "plslam_lba_plan_lists",
     "plslam_map2kf_point_gate", "plslam_map2kf_line_gate", "plslam_map_point_visible",
     "plslam_map_line_visible", "plslam_map2kf_match_points", "plslam_map2kf_match_lines",
     "plslam_map2kf_match_points_fast", "plslam_map2kf_match_lines_fast", "plslam_map2kf_match_points_dev", "plslam_map2kf_match_lines_dev",
@@ -63,6 +63,7 @@ ABI_SYMBOLS = (
     "plslam_lc_correct_map_dev", "plslam_envelope_ldlt_solve",
     "plslam_local_map_create", "plslam_local_map_destroy", "plslam_local_map_form", "plslam_local_map_candidates",
     "plslam_local_map_gather", "plslam_local_map_cull", "plslam_local_map_device_buffers", "plslam_local_map_download",
+    "plslam_local_map_apply_lba",
     "plslam_map_insert_create", "plslam_map_insert_destroy", "plslam_map_insert_kf2kf", "plslam_map_insert_map2kf",
     "plslam_map_insert_device_buffers", "plslam_map_insert_download",
     "plslam_lc_fuse_create", "plslam_lc_fuse_destroy", "plslam_lc_fuse_run", "plslam_lc_fuse_device_buffers",
@@ -354,6 +355,10 @@ def load() -> C.CDLL:
     L.plslam_lba_plan_host_state.argtypes = [vp, vp]
     L.plslam_lba_plan_blocks.argtypes = [vp] * 8
     L.plslam_lba_plan_destroy.argtypes = [vp]
+    L.plslam_lba_plan_create_dev.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32,
+                                             vp, vp, i32, C.POINTER(vp)]
+    L.plslam_lba_plan_list_sizes.argtypes = [vp, C.c_int, vp]
+    L.plslam_lba_plan_lists.argtypes = [vp, vp]
     for f in (L.plslam_map2kf_point_gate, L.plslam_map2kf_line_gate):
         f.argtypes = [vp, C.POINTER(Cam), vp, vp, vp, i32, vp, i32, f64, vp, C.POINTER(i32)]
     for f in (L.plslam_map_point_visible, L.plslam_map_line_visible):
@@ -440,6 +445,7 @@ def load() -> C.CDLL:
     L.plslam_local_map_cull.argtypes = [vp, vp, i32, i32, vp]
     L.plslam_local_map_device_buffers.argtypes = [vp, vp]
     L.plslam_local_map_download.argtypes = [vp, vp]
+    L.plslam_local_map_apply_lba.argtypes = [vp, vp, vp, f64, vp]
     # the map insertion (plslam_amd/map_insert.py): structs by address, host arrays as pointers
     L.plslam_map_insert_create.argtypes = [vp, C.POINTER(vp)]
     L.plslam_map_insert_destroy.argtypes = [vp]
@@ -1053,6 +1059,56 @@ class LbaPlan:
         self._h = h
 
     COMPAT_ITER_PASS, COMPAT_GBA = 1, 2
+    DIST_TILE = 1024        # plslam_amd/csrc/distribute_dev.hpp: the items one workgroup of the device-side list builder takes
+
+    @classmethod
+    def from_device(cls, ctx: Context, cam: Cam, homog_th, n_pose_slots, nkf, npt, nls, pt_lm, pt_slot, pt_kf_loc, pt_obs_uv,
+                    n_pt_obs, ls_lm, ls_slot, ls_kf_loc, ls_l_obs, n_ls_obs, d_Xw=0, d_Lw=0, first_estimate_slot=-1):
+        """plslam_lba_plan_create_dev: the eight observation columns and d_Xw / d_Lw are DEVICE pointers (ints, 0 = NULL), e.g.
+        the entries of LocalMap.device_buffers(); the lists are built on the device.  first_estimate_slot >= 0 rewrites the slot
+        of every point observation of an optimised keyframe to first_estimate_slot + kf_loc."""
+        self = cls.__new__(cls)
+        self._L, self._ctx = ctx._L, ctx
+        self.dims = (int(nkf), int(npt), int(nls), int(n_pt_obs), int(n_ls_obs), int(n_pose_slots))
+        h = C.c_void_p()
+        q = lambda a: C.c_void_p(int(a)) if a else None                          # noqa: E731
+        _check(self._L.plslam_lba_plan_create_dev(ctx.handle, C.byref(cam), float(homog_th), int(n_pose_slots), int(nkf), int(npt),
+                                                  int(nls), q(pt_lm), q(pt_slot), q(pt_kf_loc), q(pt_obs_uv), int(n_pt_obs),
+                                                  q(ls_lm), q(ls_slot), q(ls_kf_loc), q(ls_l_obs), int(n_ls_obs), q(d_Xw), q(d_Lw),
+                                                  int(first_estimate_slot), C.byref(h)), "plslam_lba_plan_create_dev")
+        self._h = h
+        return self
+
+    def lists(self, prepare_schur=False) -> dict:
+        """The plan's lists as host arrays (plslam_lba_plan_lists): pt_ptr / pt_ids, ls_ptr / ls_ids, kf_ptr / kf_ids, the
+        observation columns as the plan stores them, max_chunks; once the Schur lists exist (prepare_schur=True builds them):
+        blk_ptr, pairs (n, 4) and schur_chunks."""
+        class _Sizes(C.Structure):
+            _fields_ = [(k, C.c_int32) for k in ("nkf", "npt", "nls", "n_pt_obs", "n_ls_obs", "n_kf_ids", "max_chunks", "schur_ready",
+                                                 "nblk", "n_pairs", "schur_chunks")]
+        names = ("pt_ptr", "pt_ids", "ls_ptr", "ls_ids", "kf_ptr", "kf_ids", "pt_lm_loc", "pt_pose_slot", "pt_kf_loc", "pt_obs_uv",
+                 "ls_lm_loc", "ls_pose_slot", "ls_kf_loc", "ls_l_obs", "blk_ptr", "pairs")
+
+        class _Lists(C.Structure):
+            _fields_ = [(k, C.c_void_p) for k in names]
+        z = _Sizes()
+        _check(self._L.plslam_lba_plan_list_sizes(self._h, int(bool(prepare_schur)), C.addressof(z)), "plslam_lba_plan_list_sizes")
+        i32, f64 = np.int32, np.float64
+        out = dict(pt_ptr=np.zeros(z.npt + 1, i32), pt_ids=np.zeros(z.n_pt_obs, i32), ls_ptr=np.zeros(z.nls + 1, i32),
+                   ls_ids=np.zeros(z.n_ls_obs, i32), kf_ptr=np.zeros(z.nkf + 1, i32), kf_ids=np.zeros(z.n_kf_ids, i32),
+                   pt_lm_loc=np.zeros(z.n_pt_obs, i32), pt_pose_slot=np.zeros(z.n_pt_obs, i32), pt_kf_loc=np.zeros(z.n_pt_obs, i32),
+                   pt_obs_uv=np.zeros((z.n_pt_obs, 2), f64), ls_lm_loc=np.zeros(z.n_ls_obs, i32), ls_pose_slot=np.zeros(z.n_ls_obs, i32),
+                   ls_kf_loc=np.zeros(z.n_ls_obs, i32), ls_l_obs=np.zeros((z.n_ls_obs, 3), f64))
+        if z.schur_ready:
+            out.update(blk_ptr=np.zeros(z.nblk + 1, i32), pairs=np.zeros((z.n_pairs, 4), i32))
+        b = _Lists()
+        for k, a in out.items():
+            setattr(b, k, _p(a) if a.size else None)
+        _check(self._L.plslam_lba_plan_lists(self._h, C.addressof(b)), "plslam_lba_plan_lists")
+        out["max_chunks"] = int(z.max_chunks)
+        if z.schur_ready:
+            out["schur_chunks"] = int(z.schur_chunks)
+        return out
 
     def iterate_dev(self, T_kf_w, Xw, Lw, compat_flags=0, want_g=True, g_out=None):
         """One iteration with the blocks left on the device -> (err, g or None).  With the arrays of host_state() as T_kf_w /

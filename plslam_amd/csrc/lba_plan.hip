@@ -309,18 +309,19 @@ int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw,
 
 // The four buffers and the image of `dyn` are laid out HERE and nowhere else.  Called twice: before the buffers exist (null
 // bases: only the sizes are wanted) and over their addresses.
-struct LbaPlanBytes { size_t stat, dyn, rows, out; };
-static LbaPlanBytes carve_plan(plslam_lba_plan* P)
+namespace plslam {
+LbaPlanBytes lba_plan_carve(plslam_lba_plan* P)
 {
     const size_t np = (size_t)P->np, nl = (size_t)P->nl, N = P->n_unknowns();
-    const CsrLists& L = P->csr;
     ArrCarver cs{P->stat.as<char>()}, cd{P->dyn.as<char>()}, ch{P->pin_in.as<char>()}, cr{P->rows.as<char>()}, co{P->out.as<char>()};
     LbaStatView& S = P->st;
     S.pt_lm = cs.take<int32_t>(np * 4); S.pt_slot = cs.take<int32_t>(np * 4); S.pt_kf = cs.take<int32_t>(np * 4); S.uv = cs.take<double>(np * 16);
     S.ls_lm = cs.take<int32_t>(nl * 4); S.ls_slot = cs.take<int32_t>(nl * 4); S.ls_kf = cs.take<int32_t>(nl * 4); S.lobs = cs.take<double>(nl * 24);
-    S.pt_ptr = cs.take<int32_t>(L.ptp.size() * 4); S.pt_ids = cs.take<int32_t>(L.pti.size() * 4, 4);
-    S.ls_ptr = cs.take<int32_t>(L.lsp.size() * 4); S.ls_ids = cs.take<int32_t>(L.lsi.size() * 4, 4);
-    S.kf_ptr = cs.take<int32_t>(L.kfp.size() * 4); S.kf_ids = cs.take<int32_t>(L.kfi.size() * 4, 4);
+    // (every observation names a landmark: the landmark lists hold them all; the keyframe list those of optimised keyframes)
+    S.pt_ptr = cs.take<int32_t>(((size_t)P->npt + 1) * 4); S.pt_ids = cs.take<int32_t>(np * 4, 4);
+    S.ls_ptr = cs.take<int32_t>(((size_t)P->nls + 1) * 4); S.ls_ids = cs.take<int32_t>(nl * 4, 4);
+    S.kf_ptr = cs.take<int32_t>(((size_t)P->nkf + 1) * 4); S.kf_ids = cs.take<int32_t>((size_t)P->n_kfi_cap * 4, 4);
+    S.kf_ids.bytes = (size_t)P->n_kfi * 4;
     for (auto [c, X] : {std::pair{&cd, &P->x}, std::pair{&ch, &P->hx}}) {
         X->T = c->take<double>((size_t)P->n_slots * 128, 8); X->Xw = c->take<double>((size_t)P->npt * 24, 8); X->Lw = c->take<double>((size_t)P->nls * 48, 8);
     }
@@ -339,6 +340,7 @@ static LbaPlanBytes carve_plan(plslam_lba_plan* P)
     }
     return {cs.size(), cd.size(), cr.size(), co.size()};
 }
+}  // namespace plslam
 
 extern "C" int plslam_lba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_pose_slots,
                                       int32_t nkf, int32_t npt, int32_t nls, const int32_t* pt_lm_loc,
@@ -367,14 +369,15 @@ extern "C" int plslam_lba_plan_create(plslam_ctx* ctx, const plslam_cam* K, doub
     if (n_pt_obs) P->h_pt_kf.assign(pt_kf_loc, pt_kf_loc + n_pt_obs);
     if (n_ls_obs) P->h_ls_kf.assign(ls_kf_loc, ls_kf_loc + n_ls_obs);
     P->max_chunks = pose_max_chunks(c.kfp);
-    const LbaPlanBytes need = carve_plan(P);
+    P->n_kfi = P->n_kfi_cap = (int32_t)c.kfi.size();
+    const LbaPlanBytes need = lba_plan_carve(P);
     P->dyn_bytes = need.dyn;
     auto fail = [P](int rc) { P->release(); delete P; return rc; };
     int rc;
     if ((rc = P->stat.reserve(need.stat + 256)) || (rc = P->dyn.reserve(need.dyn + 256)) || (rc = P->rows.reserve(need.rows + 256)) ||
         (rc = P->out.reserve(need.out + 256)) || (rc = P->pin_in.reserve(need.dyn + 256)) || (rc = P->pin_out.reserve(P->n_unknowns() * 8 + 256)))
         return fail(rc);
-    carve_plan(P);
+    lba_plan_carve(P);
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg_(ctx->device);    // every entry point runs on the context's device, whatever the calling thread's current one
     hipStream_t s = ctx->stream;
@@ -583,12 +586,14 @@ extern "C" int plslam_lba_plan_set_poses(plslam_lba_plan* P, const double* T_kf_
     plslam_ctx* ctx = P->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg_(ctx->device);
-    PLSLAM_REQUIRE(P->state_valid, PLSLAM_EINVAL);
+    // (a device-built plan whose landmarks were copied in at creation: the poses complete its state)
+    PLSLAM_REQUIRE(P->state_valid || P->lm_resident, PLSLAM_EINVAL);
     hipStream_t s = ctx->stream;
     if (P->n_slots) {
         memcpy(P->hx.T, T_kf_w, P->hx.T.bytes);
         PLSLAM_HIP_CHECK(hipMemcpyAsync(P->x.T, P->hx.T, P->x.T.bytes, hipMemcpyHostToDevice, s));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     }
+    P->state_valid = true;
     return PLSLAM_OK;
 }

@@ -80,8 +80,18 @@ LbaBlockArgs lba_block_args(plslam_lba_plan* P);
 // (lba_schur.hip: lba_schur_enqueue(fused)), which the caller enqueues next
 int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw, const double* Lw, int compat_flags, bool upload = true,
                      double fused_lambda = -1.0);
-// (lba_schur.hip) on first use: the pair lists (lba_lists.hpp), the Schur buffers carved and the lists uploaded
+// (lba_schur.hip) on first use: the pair lists (lba_lists.hpp), the Schur buffers carved and the lists uploaded -- or, for a plan
+// whose lists were built on the device (plslam_lba_plan_create_dev), lba_schur_prepare_dev
 int lba_schur_prepare(plslam_lba_plan* P);
+// (lba_schur.hip) the Schur buffer and its page-locked block for `npairs` pairs (P->nblk, P->schur_chunks set), both counters of
+// singular landmarks cleared on the stream; nothing is synchronised
+int lba_schur_reserve(plslam_lba_plan* P, size_t npairs);
+// (lba_plan.hip) the plan's four buffers and the images of `dyn`, laid out from the plan's counts (n_kfi_cap, max_chunks): the
+// sizes; views over whichever buffers exist
+struct LbaPlanBytes { size_t stat, dyn, rows, out; };
+LbaPlanBytes lba_plan_carve(plslam_lba_plan* P);
+// (lba_plan_dev.hip) the pair lists of a device-built plan: enumerated, distributed by block and laid out on the device
+int lba_schur_prepare_dev(plslam_lba_plan* P);
 
 }  // namespace plslam
 
@@ -112,9 +122,18 @@ struct plslam_lba_plan {
     bool state_valid = false;      // T / Xw / Lw have been uploaded at least once (iterate_resident needs them)
     bool blocks_valid = false;     // an iteration has left H / g / W on the device (the Schur step consumes them)
     bool blocks_gba = false;       // ... with the pose x line cross blocks transposed (PLSLAM_LBA_COMPAT_GBA): not what the Schur step reads
+    int32_t n_kfi = 0, n_kfi_cap = 0;  // entries of the keyframe list, and the room carved for them (a device-built plan carves
+                                       // before it knows: every observation)
     // ---- the Schur step (round 5): pair lists built on first use from these host copies of the observation lists
     plslam::CsrLists csr;
     std::vector<int32_t> h_pt_kf, h_ls_kf;
+    // ---- a plan built on the device (plslam_lba_plan_create_dev): no host copy of any list
+    bool dev_lists = false;
+    bool lm_resident = false;          // Xw / Lw were copied in at creation: plslam_lba_plan_set_poses completes the state
+    plslam::DevBuf aux, aux_schur;     // the builders' scratch; aux keeps the pair counts for the Schur lists' first use
+    plslam::HostBuf pin_cnt;           // the counts the builders bring back
+    int32_t* d_pair_cnt = nullptr;     // (aux) pairs each position of the landmark lists starts: points' positions, then lines'
+    int64_t n_pairs_enum = 0;          // their sum
     plslam::DevBuf schur;
     plslam::LbaSchurView sc;
     plslam::HostBuf schur_pin;
@@ -129,6 +148,6 @@ struct plslam_lba_plan {
     void release()
     {
         stat.release(); dyn.release(); rows.release(); out.release(); pin_in.release(); pin_out.release();
-        schur.release(); schur_pin.release();
+        schur.release(); schur_pin.release(); aux.release(); aux_schur.release(); pin_cnt.release();
     }
 };

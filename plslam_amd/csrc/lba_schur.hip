@@ -558,31 +558,39 @@ static size_t carve_schur(plslam_lba_plan* P, char* base, size_t npairs)
     return c.size();
 }
 
+int lba_schur_reserve(plslam_lba_plan* P, size_t npairs)
+{
+    const size_t n6 = 6 * (size_t)P->nkf;
+    int rc;
+    if ((rc = P->schur.reserve(carve_schur(P, nullptr, npairs) + 256)) ||
+        (rc = P->schur_pin.reserve(std::max(SchurTail::bytes(n6), (3 * (size_t)P->npt + 6 * (size_t)P->nls) * 8) + n6 * 8 +
+                                   ((size_t)P->npt / (BACK_WG / 3) + (size_t)P->nls / (BACK_WG / 6) + 2) * 8 + 256)))
+        return rc;
+    carve_schur(P, P->schur.as<char>(), npairs);
+    P->simg = SchurImage(P->schur_pin.as<double>(), n6);
+    P->schur_mapped = P->schur_pin.dev != nullptr;
+    if (P->schur_mapped) P->simg_dev = SchurImage(static_cast<double*>(P->schur_pin.dev), n6);
+    PLSLAM_HIP_CHECK(hipMemsetAsync(P->sc.tail.sing, 0, 8, P->ctx->stream));      // both counters of singular landmarks
+    P->schur_parity = 0;
+    return PLSLAM_OK;
+}
+
 int lba_schur_prepare(plslam_lba_plan* P)
 {
     if (P->schur_ready) return PLSLAM_OK;
     // (the partials address the cross blocks and the landmark inverses by 32-bit byte offsets: 288 bytes per line row)
     PLSLAM_REQUIRE((size_t)P->np * 144 < (size_t(1) << 32) && (size_t)P->nl * 288 < (size_t(1) << 32) &&
                    (size_t)P->npt * 72 < (size_t(1) << 32) && (size_t)P->nls * 288 < (size_t(1) << 32), PLSLAM_EINVAL);
+    if (P->dev_lists) return lba_schur_prepare_dev(P);      // (the lists are on the device already, and no host copy exists)
     const SchurLists L = build_schur_pairs(P->csr, P->h_pt_kf, P->h_ls_kf, P->nkf);
     P->nblk = (int32_t)L.cnt.size() - 1;
     P->schur_chunks = L.schur_chunks;
-    const size_t n6 = 6 * (size_t)P->nkf;
-    int rc;
-    if ((rc = P->schur.reserve(carve_schur(P, nullptr, L.pairs.size()) + 256)) ||
-        (rc = P->schur_pin.reserve(std::max(SchurTail::bytes(n6), (3 * (size_t)P->npt + 6 * (size_t)P->nls) * 8) + n6 * 8 +
-                                   ((size_t)P->npt / (BACK_WG / 3) + (size_t)P->nls / (BACK_WG / 6) + 2) * 8 + 256)))
-        return rc;
-    carve_schur(P, P->schur.as<char>(), L.pairs.size());
-    P->simg = SchurImage(P->schur_pin.as<double>(), n6);
-    P->schur_mapped = P->schur_pin.dev != nullptr;
-    if (P->schur_mapped) P->simg_dev = SchurImage(static_cast<double*>(P->schur_pin.dev), n6);
+    int rc = lba_schur_reserve(P, L.pairs.size());
+    if (rc) return rc;
     hipStream_t s = P->ctx->stream;
     const LbaSchurView& V = P->sc;
     if (V.pairs.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(V.pairs, L.pairs.data(), V.pairs.bytes, hipMemcpyHostToDevice, s));
     PLSLAM_HIP_CHECK(hipMemcpyAsync(V.blk_ptr, L.cnt.data(), V.blk_ptr.bytes, hipMemcpyHostToDevice, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(V.tail.sing, 0, 8, s));      // both counters of singular landmarks
-    P->schur_parity = 0;
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));          // (the staging vectors die here)
     P->schur_ready = true;
     return PLSLAM_OK;

@@ -5,12 +5,14 @@
 //   the gather of localBundleAdjustment :1225-1321  K59 / K60 stable compactions + observation offsets (decoupled look-back,
 //                                                   lookback_dev.hpp), K61 a lane per output observation
 //   removeBadMapLandmarks               :2705-2786  K62
+//   the write-back of the local BA      :1828-1855  K84 from an LBA plan's resident landmarks into the image
 // Every output is an integer, a flag or a verbatim copy of a double: bit-exact against the sequential loops (tests/local_map_ref.py).
 // Each entry point: the context's lock, device and stream; one synchronisation; counts through page-locked memory written by the
 // call's last kernel.  Every index read from the image is range-checked before it is used as an address.
 #include <cstring>
 
 #include "common.hpp"
+#include "lba_plan.hpp"
 #include "lookback_dev.hpp"
 
 namespace plslam {
@@ -19,7 +21,7 @@ namespace {
 constexpr int LM_NT = 256;             // lanes per workgroup = items per look-back tile (plslam_amd/local_map.py: LOOKBACK_TILE)
 constexpr int LM_NW = LM_NT / 64;
 // the call counters (device words, mirrored in the page-locked block): plslam_local_map_counts' order, then the tickets
-enum { C_KF_LOCAL = 0, C_PT_LOCAL, C_LS_LOCAL, C_NKF, C_NPT, C_NLS, C_PT_OBS, C_LS_OBS, C_PT_REM, C_LS_REM, C_CULL_DONE, C_FORM_DONE, C_WORDS = 16 };
+enum { C_KF_LOCAL = 0, C_PT_LOCAL, C_LS_LOCAL, C_NKF, C_NPT, C_NLS, C_PT_OBS, C_LS_OBS, C_PT_REM, C_LS_REM, C_CULL_DONE, C_FORM_DONE, C_PT_MOVED, C_LS_MOVED, C_APPLY_DONE, C_WORDS = 16 };
 
 struct KindD {                          // one landmark kind of the index (device pointers) + its widths
     int32_t n, n_obs, n_feat, dl, dv;   // dl: doubles per landmark (3 / 6), dv: doubles per observation (2 / 3)
@@ -300,6 +302,44 @@ k_lm_cull(KindD P, KindD L, int32_t n_map_kf, const uint8_t* __restrict__ kf_val
     count_and_publish<2>(ok, cnt, pub);
 }
 
+// K84: the write-back of localBundleAdjustment (:1828-1855): a lane per LISTED landmark of either kind.  The operations are those
+// of LbaPlanSolver::movedLandmarks (plslam_amd/host/lba_rows.hpp): d = after - before per component, s2 summed left to right
+// from 0 (no contraction: the build's -ffp-contract=off), sqrt(s2) > th.  inlier is only ever cleared; X is copied verbatim.
+// A listed landmark occurs once in its list: no two lanes touch the same landmark, in place on the image is safe.
+struct ApplyKind { const int32_t* list; const double* Xnew; double* X; uint8_t* inlier; uint8_t* moved; int32_t n_list, n; };
+__global__ void __launch_bounds__(LM_NT)
+k_lm_apply_lba(ApplyKind P, ApplyKind L, double th, int32_t* __restrict__ cnt, Publish pub)
+{
+    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    bool ok[2] = {false, false};
+    if (t < (int64_t)P.n_list + L.n_list) {
+        const bool lines = t >= P.n_list;
+        const int32_t i = (int32_t)(lines ? t - P.n_list : t);
+        const int32_t* __restrict__ list = lines ? L.list : P.list;
+        const double* __restrict__ Xnew = lines ? L.Xnew : P.Xnew;
+        double* __restrict__ X = lines ? L.X : P.X;
+        uint8_t* __restrict__ inlier = lines ? L.inlier : P.inlier;
+        const int32_t n = lines ? L.n : P.n;
+        const int dl = lines ? 6 : 3;
+        const int32_t j = list[i];
+        bool mv = false;
+        if (j >= 0 && j < n) {                              // (the list is the gather's: in range; checked all the same)
+            double s2 = 0.0;
+            for (int a = 0; a < dl; ++a) {
+                const double v = Xnew[(size_t)dl * i + a];
+                const double d = v - X[(size_t)dl * j + a];
+                s2 += d * d;
+                X[(size_t)dl * j + a] = v;
+            }
+            mv = sqrt(s2) > th;
+            if (mv) inlier[j] = 0;
+        }
+        (lines ? L.moved : P.moved)[i] = mv ? 1 : 0;
+        ok[lines ? 1 : 0] = mv;
+    }
+    count_and_publish<2>(ok, cnt, pub);
+}
+
 bool kind_ok(const plslam_map_landmarks& L)
 {
     return L.n >= 0 && L.n_obs >= 0 && L.n_obs < (1 << 30) && L.n_feat >= 0 &&
@@ -323,7 +363,7 @@ struct plslam_local_map {
     DevBuf buf;
     HostBuf pin;                                 // C_WORDS counters, then the staged graph row
     int32_t n_map_kf = 0, npt = 0, nls = 0, n_pt_obs = 0, n_ls_obs = 0;
-    bool formed = false, gathered = false;
+    bool formed = false, gathered = false, applied = false;
     plslam_local_map_buffers d = {};
     int32_t *kf_inv = nullptr, *pt_off = nullptr, *ls_off = nullptr, *row = nullptr, *cnt = nullptr;
     uint32_t* part = nullptr;                    // five chains: kf, pt, pt observations, ls, ls observations
@@ -341,7 +381,7 @@ int lm_layout(plslam_local_map* lm, const plslam_map_index* m)
     Carver c;
     const size_t o_kfl = c.take(nk), o_ptl = c.take(np), o_lsl = c.take(nl), o_cnt = c.take(C_WORDS * 4);
     const size_t zero_bytes = c.off;
-    const size_t o_ptc = c.take(np), o_lsc = c.take(nl), o_ptr_ = c.take(np), o_lsr = c.take(nl);
+    const size_t o_ptc = c.take(np), o_lsc = c.take(nl), o_ptr_ = c.take(np), o_lsr = c.take(nl), o_ptm = c.take(np), o_lsm = c.take(nl);
     const size_t o_kfi = c.take(nk * 4), o_kfv = c.take(nk * 4), o_row = c.take(nk * 4);
     const size_t o_pti = c.take(np * 4), o_lsi = c.take(nl * 4), o_pto = c.take((np + 1) * 4), o_lso = c.take((nl + 1) * 4);
     const size_t o_p6 = c.take(op * 24), o_l6 = c.take(ol * 24);
@@ -360,6 +400,7 @@ int lm_layout(plslam_local_map* lm, const plslam_map_index* m)
     lm->cnt = (int32_t*)(d + o_cnt);
     b.pt_candidate = (uint8_t*)(d + o_ptc); b.ls_candidate = (uint8_t*)(d + o_lsc);
     b.pt_removed = (uint8_t*)(d + o_ptr_); b.ls_removed = (uint8_t*)(d + o_lsr);
+    b.pt_moved = (uint8_t*)(d + o_ptm); b.ls_moved = (uint8_t*)(d + o_lsm);
     b.kf_list = (int32_t*)(d + o_kfi); lm->kf_inv = (int32_t*)(d + o_kfv); lm->row = (int32_t*)(d + o_row);
     b.pt_list = (int32_t*)(d + o_pti); b.ls_list = (int32_t*)(d + o_lsi);
     lm->pt_off = (int32_t*)(d + o_pto); lm->ls_off = (int32_t*)(d + o_lso);
@@ -414,7 +455,7 @@ int plslam_local_map_form(plslam_local_map* lm, const plslam_map_index* map, int
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    lm->formed = lm->gathered = false;
+    lm->formed = lm->gathered = lm->applied = false;
     int rc = lm_layout(lm, map);
     if (rc) return rc;
     PLSLAM_REQUIRE(lm->pin.dev, PLSLAM_ENOTSUP);               // the counters are written where the host reads them
@@ -469,7 +510,7 @@ int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, p
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
     PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
-    lm->gathered = false;
+    lm->gathered = lm->applied = false;
     StreamSyncOnError guard(s);
     const KindD P = kind_d(map->points, 0), L = kind_d(map->lines, 1);
     const int32_t nk = map->n_map_kf;
@@ -526,6 +567,37 @@ int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int
     return PLSLAM_OK;
 }
 
+int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, const plslam_local_map_lba_dst* dst, double moved_th,
+                               plslam_local_map_counts* counts)
+{
+    PLSLAM_REQUIRE(lm && plan && dst && counts && plan->ctx == lm->ctx, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(lm->ctx->mu);
+    DeviceGuard dg_(lm->ctx->device);
+    hipStream_t s = lm->ctx->stream;
+    PLSLAM_REQUIRE(lm->formed && lm->gathered, PLSLAM_EINVAL);
+    const int32_t npt_l = lm->h_cnt[C_NPT], nls_l = lm->h_cnt[C_NLS];
+    PLSLAM_REQUIRE(plan->npt == npt_l && plan->nls == nls_l && plan->state_valid, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE((npt_l == 0 || (dst->pt_X && dst->pt_inlier)) && (nls_l == 0 || (dst->ls_X && dst->ls_inlier)), PLSLAM_EINVAL);
+    counts->n_pt_moved = counts->n_ls_moved = 0;
+    lm->h_cnt[C_PT_MOVED] = lm->h_cnt[C_LS_MOVED] = 0;
+    lm->applied = true;
+    if ((int64_t)npt_l + nls_l == 0) return PLSLAM_OK;
+    StreamSyncOnError guard(s);
+    // (the two counts and the ticket: C_PT_MOVED, C_LS_MOVED, C_APPLY_DONE are consecutive words)
+    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->cnt + C_PT_MOVED, 0, (C_APPLY_DONE - C_PT_MOVED + 1) * 4, s));
+    const ApplyKind P{lm->d.pt_list, plan->x.Xw, dst->pt_X, dst->pt_inlier, lm->d.pt_moved, npt_l, lm->npt};
+    const ApplyKind L{lm->d.ls_list, plan->x.Lw, dst->ls_X, dst->ls_inlier, lm->d.ls_moved, nls_l, lm->nls};
+    const Publish pub{lm->cnt + C_APPLY_DONE, lm->cnt + C_PT_MOVED, (int32_t*)lm->pin.dev + C_PT_MOVED, 2};
+    hipLaunchKernelGGL(k_lm_apply_lba, dim3(tiles((int64_t)npt_l + nls_l)), dim3(LM_NT), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    const int32_t* h = lm->pin.as<int32_t>();
+    counts->n_pt_moved = lm->h_cnt[C_PT_MOVED] = h[C_PT_MOVED];
+    counts->n_ls_moved = lm->h_cnt[C_LS_MOVED] = h[C_LS_MOVED];
+    return PLSLAM_OK;
+}
+
 int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out)
 {
     PLSLAM_REQUIRE(lm && out && lm->formed, PLSLAM_EINVAL);
@@ -540,6 +612,7 @@ int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffe
                        host->pt_kf_loc || host->pt_pose_slot || host->ls_lm_loc || host->ls_kf_loc || host->ls_pose_slot ||
                        host->pt_obs_uv || host->ls_l_obs || host->X_aux;
     PLSLAM_REQUIRE(!lists || lm->gathered, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE((!host->pt_moved && !host->ls_moved) || lm->applied, PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
@@ -557,7 +630,7 @@ int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffe
         {host->pt_lm_loc, d.pt_lm_loc, po * 4}, {host->pt_kf_loc, d.pt_kf_loc, po * 4}, {host->pt_pose_slot, d.pt_pose_slot, po * 4},
         {host->ls_lm_loc, d.ls_lm_loc, lo * 4}, {host->ls_kf_loc, d.ls_kf_loc, lo * 4}, {host->ls_pose_slot, d.ls_pose_slot, lo * 4},
         {host->pt_obs_uv, d.pt_obs_uv, po * 16}, {host->ls_l_obs, d.ls_l_obs, lo * 24},
-        {host->X_aux, d.X_aux, (6 * nkf + 3 * npt + 6 * nls) * 8}};
+        {host->X_aux, d.X_aux, (6 * nkf + 3 * npt + 6 * nls) * 8}, {host->pt_moved, d.pt_moved, npt}, {host->ls_moved, d.ls_moved, nls}};
     for (const Item& it : items)
         if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));

@@ -176,7 +176,29 @@ public:
                                      p.pt_obs.data(), np, llm.data(), p.ls_pose_slot.data(), lkf.data(), p.ls_obs.data(), nl, &plan_),
               "plslam_lba_plan_create");
     }
+    // The plan built on the device from DEVICE columns (plslam_lba_plan_create_dev), e.g. what plslam_local_map_gather leaves in
+    // plslam_local_map_buffers: the layouts of plslam_lba_plan_create; Xw / Lw (device, or nullptr) become the plan's resident
+    // landmarks; first_estimate_slot >= 0 gives the point observations of optimised key frames the estimate slots optimize()
+    // documents.  optimizeResident() then runs with no landmark crossing PCIe in either direction.
+    struct DeviceColumns {
+        const int32_t *pt_lm_loc = nullptr, *pt_pose_slot = nullptr, *pt_kf_loc = nullptr;
+        const double* pt_obs_uv = nullptr;
+        int32_t n_pt_obs = 0;
+        const int32_t *ls_lm_loc = nullptr, *ls_pose_slot = nullptr, *ls_kf_loc = nullptr;
+        const double* ls_l_obs = nullptr;
+        int32_t n_ls_obs = 0;
+        const double *Xw = nullptr, *Lw = nullptr;
+    };
+    LbaPlanSolver(plslam_ctx* ctx, const plslam_cam& cam, double homog_th, int32_t n_pose_slots, int32_t nkf, int32_t npt, int32_t nls,
+                  const DeviceColumns& c, int32_t first_estimate_slot)
+        : nkf_(nkf), npt_(npt), nls_(nls), nslots_(n_pose_slots)
+    {
+        check(plslam_lba_plan_create_dev(ctx, &cam, homog_th, n_pose_slots, nkf, npt, nls, c.pt_lm_loc, c.pt_pose_slot, c.pt_kf_loc,
+                                         c.pt_obs_uv, c.n_pt_obs, c.ls_lm_loc, c.ls_pose_slot, c.ls_kf_loc, c.ls_l_obs, c.n_ls_obs, c.Xw,
+                                         c.Lw, first_estimate_slot, &plan_), "plslam_lba_plan_create_dev");
+    }
     ~LbaPlanSolver() { plslam_lba_plan_destroy(plan_); }
+    plslam_lba_plan* handle() const { return plan_; }
     LbaPlanSolver(const LbaPlanSolver&) = delete;
     LbaPlanSolver& operator=(const LbaPlanSolver&) = delete;
 
@@ -299,75 +321,18 @@ public:
     void optimize(LbaProblem& p, std::vector<double>& x_kf, int32_t first_estimate_slot, const LmParams& prm, const Se3Maps& maps,
                   LmTrace* trace = nullptr)
     {
-        if (x_kf.size() != 6 * (size_t)nkf_ || first_estimate_slot < 0 || first_estimate_slot + nkf_ > nslots_)
-            throw std::runtime_error("[LbaPlanSolver::optimize] x_kf must hold 6 doubles per optimised key frame, and their estimate slots must exist");
-        const double n_obs_counted = 0.0;                             // Npt_obs + Nls_obs as the reference leaves them (see above)
-        const double n_lm = (double)(npt_ + nls_);
-        LmTrace local;
-        LmTrace& tr = trace ? *trace : local;
-        tr = LmTrace();
-        std::vector<double> dp;
-        auto set_estimates = [&]() {                                  // slot first_estimate_slot + k <- expmap(X_k)
-            for (int32_t k = 0; k < nkf_; ++k) maps.expmap(&x_kf[6 * (size_t)k], &p.poses_T_kf_w[16 * (size_t)(first_estimate_slot + k)]);
-        };
-        auto update_poses = [&]() {                                   // :1560-1566 (the matrices go up with the step)
-            double Tprev[16], Tinc[16], Tinv[16], Tcur[16];
-            for (int32_t k = 0; k < nkf_; ++k) {
-                maps.expmap(&x_kf[6 * (size_t)k], Tprev);
-                maps.expmap(&dp[6 * (size_t)k], Tinc);
-                maps.inverse(Tinc, Tinv);
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) {
-                        double a = 0.0;
-                        for (int q = 0; q < 4; ++q) a += Tprev[4 * i + q] * Tinv[4 * q + j];
-                        Tcur[4 * i + j] = a;
-                    }
-                maps.logmap(Tcur, &x_kf[6 * (size_t)k]);
-            }
-            set_estimates();
-        };
-        // ---- first pass ----
-        set_estimates();
-        double err = iterate(p, false) / n_obs_counted;
-        double lambda = prm.lambda_lba_lm * diagMax();
-        int32_t nsing = 0;
-        const size_t n6 = 6 * (size_t)nkf_;
-        S_.resize(n6 * n6); dp.resize(n6);
-        check(plslam_lba_plan_schur(plan_, lambda, S_.data(), dp.data(), &nsing), "plslam_lba_plan_schur");
-        ldlt_solve(S_, dp, (int)n6);
-        tr.n_singular += nsing;
-        update_poses();
-        check(plslam_lba_plan_apply_step(plan_, dp.data(), p.poses_T_kf_w.data(), 1, nullptr), "plslam_lba_plan_apply_step");
-        tr.err.push_back(err); tr.lambda.push_back(lambda); tr.applied.push_back(1);
-        double err_prev = err;
-        // ---- LM iterations ----
-        int iters;
-        // an iteration = two calls, two synchronisations: [H, g, err + Schur step] -> dense LDL^T here -> [back-substitution,
-        // landmark update, pose slots, sum DX^2].  (The Schur step of the build that stops at the first test is computed and unused.)
-        for (iters = 1; iters < prm.max_iters_lba; ++iters) {
-            check(plslam_lba_plan_iterate_schur(plan_, PLSLAM_LBA_COMPAT_ITER_PASS, lambda, &err, S_.data(), dp.data(), &nsing),
-                  "plslam_lba_plan_iterate_schur");     // (iterateSchur() without the solve: the first stop test comes before it)
-            err /= n_lm;
-            tr.err.push_back(err);
-            if (std::fabs(err - err_prev) < prm.min_error_change || err < prm.min_error) {
-                tr.lambda.push_back(0.0); tr.applied.push_back(-1); tr.stop = 1;
-                break;
-            }
-            const bool reject = err > err_prev;
-            ldlt_solve(S_, dp, (int)n6);
-            tr.n_singular += nsing;
-            tr.lambda.push_back(lambda); tr.applied.push_back(reject ? 0 : 1);
-            if (reject) lambda /= prm.lambda_lba_k;
-            else { lambda *= prm.lambda_lba_k; update_poses(); }
-            double s2 = 0.0, s2_lm = 0.0;
-            for (double v : dp) s2 += v * v;
-            check(plslam_lba_plan_apply_step(plan_, dp.data(), reject ? nullptr : p.poses_T_kf_w.data(), reject ? 0 : 1, &s2_lm),
-                  "plslam_lba_plan_apply_step");
-            if (std::sqrt(s2 + s2_lm) < prm.min_error_change) { tr.stop = 2; break; }      // ||DX|| over all N unknowns (:1808)
-            err_prev = err;
-        }
-        tr.iters = iters;
+        lmLoop(p.poses_T_kf_w, x_kf, first_estimate_slot, prm, maps, trace, [&]() { return iterate(p, false); });
         landmarks(p.points, p.lines);
+    }
+    // The same loop on a plan whose landmarks are ALREADY resident (the device-column constructor with Xw / Lw): the first pass is
+    // setPoses + iterateResident, and no landmark comes back at the end -- plslam_local_map_apply_lba (local_map.hpp: applyLba)
+    // writes them into the map image on the device; landmarks() fetches them where the host wants them.  T_slots: one 4 x 4 per
+    // pose slot, the stored T_kf_w in the slots the observations name; the estimate slots first_estimate_slot + k are written here.
+    void optimizeResident(std::vector<double>& x_kf, std::vector<double>& T_slots, int32_t first_estimate_slot, const LmParams& prm,
+                          const Se3Maps& maps, LmTrace* trace = nullptr)
+    {
+        if (T_slots.size() != (size_t)nslots_ * 16) throw std::runtime_error("[LbaPlanSolver::optimizeResident] one 4 x 4 per pose slot");
+        lmLoop(T_slots, x_kf, first_estimate_slot, prm, maps, trace, [&]() { setPoses(T_slots); return iterateResident(false); });
     }
     // the reference's write-back test (:1822-1846): landmark i is flagged when its estimate moved by more than `th` (0.01)
     static void movedLandmarks(const std::vector<double>& before, const std::vector<double>& after, int dim, double th, std::vector<uint8_t>& moved)
@@ -409,6 +374,81 @@ public:
     }
 
 private:
+    // optimize() / optimizeResident(): everything but where the first pass's state comes from (first_pass: the raw err of the
+    // state with the estimate slots set) and where the landmarks go at the end.  T_slots: the pose slots, estimates written here.
+    template <class FirstPass>
+    void lmLoop(std::vector<double>& T_slots, std::vector<double>& x_kf, int32_t first_estimate_slot, const LmParams& prm, const Se3Maps& maps,
+                LmTrace* trace, FirstPass&& first_pass)
+    {
+        if (x_kf.size() != 6 * (size_t)nkf_ || first_estimate_slot < 0 || first_estimate_slot + nkf_ > nslots_)
+            throw std::runtime_error("[LbaPlanSolver::optimize] x_kf must hold 6 doubles per optimised key frame, and their estimate slots must exist");
+        const double n_obs_counted = 0.0;                             // Npt_obs + Nls_obs as the reference leaves them (see above)
+        const double n_lm = (double)(npt_ + nls_);
+        LmTrace local;
+        LmTrace& tr = trace ? *trace : local;
+        tr = LmTrace();
+        std::vector<double> dp;
+        auto set_estimates = [&]() {                                  // slot first_estimate_slot + k <- expmap(X_k)
+            for (int32_t k = 0; k < nkf_; ++k) maps.expmap(&x_kf[6 * (size_t)k], &T_slots[16 * (size_t)(first_estimate_slot + k)]);
+        };
+        auto update_poses = [&]() {                                   // :1560-1566 (the matrices go up with the step)
+            double Tprev[16], Tinc[16], Tinv[16], Tcur[16];
+            for (int32_t k = 0; k < nkf_; ++k) {
+                maps.expmap(&x_kf[6 * (size_t)k], Tprev);
+                maps.expmap(&dp[6 * (size_t)k], Tinc);
+                maps.inverse(Tinc, Tinv);
+                for (int i = 0; i < 4; ++i)
+                    for (int j = 0; j < 4; ++j) {
+                        double a = 0.0;
+                        for (int q = 0; q < 4; ++q) a += Tprev[4 * i + q] * Tinv[4 * q + j];
+                        Tcur[4 * i + j] = a;
+                    }
+                maps.logmap(Tcur, &x_kf[6 * (size_t)k]);
+            }
+            set_estimates();
+        };
+        // ---- first pass ----
+        set_estimates();
+        double err = first_pass() / n_obs_counted;
+        double lambda = prm.lambda_lba_lm * diagMax();
+        int32_t nsing = 0;
+        const size_t n6 = 6 * (size_t)nkf_;
+        S_.resize(n6 * n6); dp.resize(n6);
+        check(plslam_lba_plan_schur(plan_, lambda, S_.data(), dp.data(), &nsing), "plslam_lba_plan_schur");
+        ldlt_solve(S_, dp, (int)n6);
+        tr.n_singular += nsing;
+        update_poses();
+        check(plslam_lba_plan_apply_step(plan_, dp.data(), T_slots.data(), 1, nullptr), "plslam_lba_plan_apply_step");
+        tr.err.push_back(err); tr.lambda.push_back(lambda); tr.applied.push_back(1);
+        double err_prev = err;
+        // ---- LM iterations ----
+        int iters;
+        // an iteration = two calls, two synchronisations: [H, g, err + Schur step] -> dense LDL^T here -> [back-substitution,
+        // landmark update, pose slots, sum DX^2].  (The Schur step of the build that stops at the first test is computed and unused.)
+        for (iters = 1; iters < prm.max_iters_lba; ++iters) {
+            check(plslam_lba_plan_iterate_schur(plan_, PLSLAM_LBA_COMPAT_ITER_PASS, lambda, &err, S_.data(), dp.data(), &nsing),
+                  "plslam_lba_plan_iterate_schur");     // (iterateSchur() without the solve: the first stop test comes before it)
+            err /= n_lm;
+            tr.err.push_back(err);
+            if (std::fabs(err - err_prev) < prm.min_error_change || err < prm.min_error) {
+                tr.lambda.push_back(0.0); tr.applied.push_back(-1); tr.stop = 1;
+                break;
+            }
+            const bool reject = err > err_prev;
+            ldlt_solve(S_, dp, (int)n6);
+            tr.n_singular += nsing;
+            tr.lambda.push_back(lambda); tr.applied.push_back(reject ? 0 : 1);
+            if (reject) lambda /= prm.lambda_lba_k;
+            else { lambda *= prm.lambda_lba_k; update_poses(); }
+            double s2 = 0.0, s2_lm = 0.0;
+            for (double v : dp) s2 += v * v;
+            check(plslam_lba_plan_apply_step(plan_, dp.data(), reject ? nullptr : T_slots.data(), reject ? 0 : 1, &s2_lm),
+                  "plslam_lba_plan_apply_step");
+            if (std::sqrt(s2 + s2_lm) < prm.min_error_change) { tr.stop = 2; break; }      // ||DX|| over all N unknowns (:1808)
+            err_prev = err;
+        }
+        tr.iters = iters;
+    }
     static void check(int rc, const char* fn)
     {
         if (rc != PLSLAM_OK)

@@ -153,6 +153,19 @@ public:
         apply(lns, rl, true);
         return counts_.n_pt_removed + counts_.n_ls_removed;
     }
+    // the write-back of localBundleAdjustment() (:1828-1855) from the plan's resident landmarks into the image, in place, after
+    // localBundleAdjustment() / plslam_local_map_gather on this handle: point3D / line3D <- the estimate, inlier = false where it
+    // moved by more than moved_th (the reference's literal: 0.01).  The image's X and inlier arrays are this object's own device
+    // memory, so it may write them.  Returns the number of landmarks flagged; the containers follow from the masks where the
+    // caller keeps them (plslam_local_map_download: pt_moved / ls_moved).
+    int applyLba(plslam_lba_plan* plan, double moved_th = 0.01)
+    {
+        plslam_local_map_lba_dst d{};
+        d.pt_X = const_cast<double*>(map_.points.X); d.pt_inlier = const_cast<uint8_t*>(map_.points.inlier);
+        d.ls_X = const_cast<double*>(map_.lines.X); d.ls_inlier = const_cast<uint8_t*>(map_.lines.inlier);
+        check(plslam_local_map_apply_lba(lm_, plan, &d, moved_th, &counts_), "apply_lba");
+        return counts_.n_pt_moved + counts_.n_ls_moved;
+    }
     const plslam_local_map_counts& counts() const { return counts_; }
 
 private:

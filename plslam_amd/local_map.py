@@ -32,15 +32,20 @@ _U8 = ("kf_local", "pt_local", "ls_local", "pt_candidate", "ls_candidate", "pt_r
 _I32 = ("kf_list", "pt_list", "ls_list", "pt_obs", "ls_obs", "pt_lm_loc", "pt_kf_loc", "pt_pose_slot", "ls_lm_loc", "ls_kf_loc",
         "ls_pose_slot")
 _F64 = ("pt_obs_uv", "ls_l_obs", "X_aux")
+_U8_APPLY = ("pt_moved", "ls_moved")       # behind `stream`: appended to plslam_local_map_buffers
 
 
 class LocalMapBuffers(C.Structure):
-    _fields_ = [(k, _vp) for k in _U8 + _I32 + _F64] + [("stream", _vp)]
+    _fields_ = [(k, _vp) for k in _U8 + _I32 + _F64] + [("stream", _vp)] + [(k, _vp) for k in _U8_APPLY]
+
+
+class LocalMapLbaDst(C.Structure):
+    _fields_ = [("pt_X", _vp), ("pt_inlier", _vp), ("ls_X", _vp), ("ls_inlier", _vp)]
 
 
 class LocalMapCounts(C.Structure):
     _fields_ = [(k, _i32) for k in ("n_kf_local", "n_pt_local", "n_ls_local", "nkf", "npt", "nls", "n_pt_obs", "n_ls_obs", "empty",
-                                    "n_pt_removed", "n_ls_removed")]
+                                    "n_pt_removed", "n_ls_removed", "n_pt_moved", "n_ls_moved")]
 
 
 _KIND_DTYPES = dict(valid=np.uint8, inlier=np.uint8, X=np.float64, obs_ptr=np.int32, obs_kf=np.int32, obs_val=np.float64,
@@ -119,6 +124,16 @@ class LocalMap:
                "plslam_local_map_cull")
         return dict(n_pt_removed=c.n_pt_removed, n_ls_removed=c.n_ls_removed)
 
+    def apply_lba(self, plan, index: DeviceMapIndex, moved_th: float = 0.01) -> dict:
+        """The write-back of the local BA (:1828-1855) from `plan`'s resident landmarks into `index`'s own X / inlier arrays, in
+        place: a listed landmark that moved by more than moved_th loses its inlier flag, every listed landmark takes the plan's
+        estimate.  -> dict(n_pt_moved, n_ls_moved); the masks: download("pt_moved", "ls_moved")."""
+        dst = LocalMapLbaDst(index.ptr("points.X"), index.ptr("points.inlier"), index.ptr("lines.X"), index.ptr("lines.inlier"))
+        c = LocalMapCounts()
+        _check(self._L.plslam_local_map_apply_lba(self._h, plan._h, C.addressof(dst), float(moved_th), C.addressof(c)),
+               "plslam_local_map_apply_lba")
+        return dict(n_pt_moved=c.n_pt_moved, n_ls_moved=c.n_ls_moved)
+
     def device_buffers(self) -> dict:
         b = LocalMapBuffers()
         _check(self._L.plslam_local_map_device_buffers(self._h, C.addressof(b)), "plslam_local_map_device_buffers")
@@ -135,10 +150,11 @@ class LocalMap:
             po, lo = c["n_pt_obs"], c["n_ls_obs"]
             shape.update(kf_list=(c["nkf"],), pt_list=(c["npt"],), ls_list=(c["nls"],), pt_obs=(po, 6), ls_obs=(lo, 6), pt_lm_loc=(po,),
                          pt_kf_loc=(po,), pt_pose_slot=(po,), ls_lm_loc=(lo,), ls_kf_loc=(lo,), ls_pose_slot=(lo,), pt_obs_uv=(po, 2),
-                         ls_l_obs=(lo, 3), X_aux=(6 * c["nkf"] + 3 * c["npt"] + 6 * c["nls"],))
+                         ls_l_obs=(lo, 3), X_aux=(6 * c["nkf"] + 3 * c["npt"] + 6 * c["nls"],), pt_moved=(c["npt"],),
+                         ls_moved=(c["nls"],))
         out, b = {}, LocalMapBuffers()
         for k in names:
-            dt = np.uint8 if k in _U8 else np.int32 if k in _I32 else np.float64
+            dt = np.uint8 if k in _U8 + _U8_APPLY else np.int32 if k in _I32 else np.float64
             out[k] = np.zeros(shape[k], dt)
             setattr(b, k, _p(out[k]) if out[k].size else None)
         _check(self._L.plslam_local_map_download(self._h, C.addressof(b)), "plslam_local_map_download")

@@ -163,6 +163,30 @@ struct plslam_ctx {
 
 namespace plslam {
 
+// The destroy of a handle that owns one device buffer and one page-locked block (plslam_local_map, plslam_map_insert,
+// plslam_lc_fuse): nothing of the handle's may be in flight when its buffers go.
+inline void release_handle_buffers(plslam_ctx* ctx, DevBuf& buf, HostBuf& pin)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard dg_(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    buf.release();
+    pin.release();
+}
+
+// The download of a handle's device arrays: the ones the caller gave a host pointer for (dst != nullptr) and that hold something,
+// copied on s and waited for.  The caller holds the context's lock and has selected its device.
+struct DownloadItem { void* dst; const void* src; size_t bytes; };
+template <size_t N> int download_items(const DownloadItem (&items)[N], hipStream_t s)
+{
+    StreamSyncOnError guard(s);
+    for (const DownloadItem& it : items)
+        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    return PLSLAM_OK;
+}
+
 // Pointers read from launch tables are GENERIC to the compiler, and a generic access is a FLAT instruction (it counts on
 // lgkmcnt as well as vmcnt, and cannot take a scalar base).  Kernels spell the address space out at the point of use:
 // g_(p)[i] is a global_load / global_store.  (tests/test_abi.py: no flat_* instruction in any kernel's ISA.)

@@ -8,6 +8,7 @@
 #include "lba_rows_dev.hpp"
 #include "lookback_dev.hpp"
 #include "match_grid.hpp"   // GridDesc: k_visible_compact writes the row count into a descriptor
+#include "publish_dev.hpp"
 
 namespace plslam {
 
@@ -90,31 +91,18 @@ k_line_rows(CamD K, double th, int compat, const double* __restrict__ T,
 struct Pose12 { double m[12]; };  // rows 0..2 of the row-major 4x4
 
 // The gates as the LAST kernel of a one-synchronisation driver call (map2kf.hip): the workgroup that finishes last copies the call's
-// counters (device words, some of them this kernel's own atomic counts) into the page-locked block the host reads -- a launch less
-// at the end of a call that is bound by its launches.  Every wave WAITS for its count atomic (a returning one) before the
-// workgroup's barrier, one lane then counts the workgroup in; the last one reads the counters with agent-scope loads.
-struct GatePublish { int32_t* done; const int32_t* src; int32_t* dst; int32_t n; };     // done = nullptr: nothing to publish
-__device__ __forceinline__ void gate_count_and_publish(int ok, int32_t* __restrict__ count, const GatePublish& pub)
+// counters (device words, some of them this kernel's own atomic counts) into the page-locked block the host reads (publish_dev.hpp).
+// pub.done = nullptr: nothing to publish, and no wave waits for its count; count = nullptr: nothing is counted.
+__device__ __forceinline__ void gate_count_and_publish(int ok, int32_t* __restrict__ count, const Publish& pub)
 {
     if (count) {
-        const unsigned long long b = __ballot(ok);
-        if ((threadIdx.x & 63) == 0 && b) {
-            if (pub.done) {
-                const int old = atomicAdd(count, (int)__popcll(b));
-                asm volatile("" ::"v"(old));              // (the atomic has been performed when the wave passes here)
-            } else {
-                atomicAdd(count, (int)__popcll(b));
-            }
+        if (pub.done) wave_count_and_wait(ok, count);
+        else {
+            const unsigned long long b = __ballot(ok);
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (int)__popcll(b));
         }
     }
-    if (pub.done) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int prev = atomicAdd(pub.done, 1);
-            if (prev == (int)gridDim.x - 1)
-                for (int w = 0; w < pub.n; ++w) pub.dst[w] = __hip_atomic_load(pub.src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (pub.done) publish_from_last_workgroup(pub);
 }
 
 // K5: point gate  (:601-613)
@@ -122,7 +110,7 @@ __global__ void __launch_bounds__(256)
 k_point_gate(CamD K, Pose12 Twf, const double* __restrict__ Xw, const int32_t* __restrict__ m12,
              int32_t nq, const double* __restrict__ pl, double th, uint8_t* __restrict__ mask,
              int32_t* __restrict__ count, const int32_t* __restrict__ nq_dev, const int32_t* __restrict__ idx,
-             const int32_t* __restrict__ ti, int32_t* __restrict__ map_to_kf, GatePublish pub)
+             const int32_t* __restrict__ ti, int32_t* __restrict__ map_to_kf, Publish pub)
 {
     if (nq_dev) nq = *nq_dev;                  // (the row count lives on the device: the launch covers an upper bound)
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -147,7 +135,7 @@ __global__ void __launch_bounds__(256)
 k_line_gate(CamD K, Pose12 Twf, const double* __restrict__ Lw, const int32_t* __restrict__ m12,
             int32_t nq, const double* __restrict__ le, double th, uint8_t* __restrict__ mask,
             int32_t* __restrict__ count, const int32_t* __restrict__ nq_dev, const int32_t* __restrict__ idx,
-            const int32_t* __restrict__ ti, int32_t* __restrict__ map_to_kf, GatePublish pub)
+            const int32_t* __restrict__ ti, int32_t* __restrict__ map_to_kf, Publish pub)
 {
     if (nq_dev) nq = *nq_dev;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -239,7 +227,7 @@ int launch_point_gate(const plslam_cam& K, const double* Twf16, const double* Xw
     if (nq <= 0) return PLSLAM_OK;
     hipLaunchKernelGGL(k_point_gate, dim3((nq + 255) / 256), dim3(256), 0, s, cam_d(K), pose12(Twf16),
                        Xw, m12, nq, pl, th, mask, count, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr,
-                       (int32_t*)nullptr, GatePublish{nullptr, nullptr, nullptr, 0});
+                       (int32_t*)nullptr, Publish{nullptr, nullptr, nullptr, 0});
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }
@@ -252,7 +240,7 @@ int launch_line_gate(const plslam_cam& K, const double* Twf16, const double* Lw,
     if (nq <= 0) return PLSLAM_OK;
     hipLaunchKernelGGL(k_line_gate, dim3((nq + 255) / 256), dim3(256), 0, s, cam_d(K), pose12(Twf16),
                        Lw, m12, nq, le, th, mask, count, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr,
-                       (int32_t*)nullptr, GatePublish{nullptr, nullptr, nullptr, 0});
+                       (int32_t*)nullptr, Publish{nullptr, nullptr, nullptr, 0});
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }
@@ -333,7 +321,7 @@ int launch_gate_n(int lines, const plslam_cam& K, const double* Twf16, const dou
         PLSLAM_REQUIRE(!publish_done, PLSLAM_EINVAL);
         return PLSLAM_OK;
     }
-    const GatePublish pub{publish_done, publish_src, publish_dst, publish_n};
+    const Publish pub{publish_done, publish_src, publish_dst, publish_n};
     if (lines)
         hipLaunchKernelGGL(k_line_gate, dim3((n_max + 255) / 256), dim3(256), 0, s, cam_d(K), pose12(Twf16), LM, m12, n_max, feat,
                            th, mask, count, n_dev, idx, ti, map_to_kf, pub);
@@ -362,7 +350,7 @@ k_visible_compact(CamD K, Pose12 Twf, const double* __restrict__ X, const uint8_
 {
     constexpr int NW = VC_NT / 64;
     __shared__ uint32_t s_w[NW], s_before;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
     const int32_t i = b * VC_NT + tid;
     bool v = false;
     if (i < n) {                                            // (the landmark is read whether it is a candidate or not: one round trip)
@@ -378,20 +366,11 @@ k_visible_compact(CamD K, Pose12 Twf, const double* __restrict__ X, const uint8_
         }
         fill[i] = -1;
     }
-    const uint64_t m = __ballot(v);
-    if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t own = 0, inside_wg = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        inside_wg += w < wv ? s_w[w] : 0u;
-        own += s_w[w];
-    }
-    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
-    if (v) idx[before + inside_wg + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+    const TileScan sc = lookback_rank<NW>(v, part, b, s_w, &s_before);
+    if (v) idx[sc.pos] = i;
     if (b == (int)gridDim.x - 1 && tid == 0) {
-        *n_out = (int32_t)(before + own);
-        if (desc) desc->n1 = (int32_t)(before + own);
+        *n_out = (int32_t)sc.upto;
+        if (desc) desc->n1 = (int32_t)sc.upto;
     }
 }
 

@@ -197,27 +197,12 @@ k_lbp_pair_emit(const LbpLists L, const int32_t* __restrict__ cnt, uint32_t* __r
                 int32_t* __restrict__ key, SchurPair* __restrict__ pair)
 {
     __shared__ uint32_t s_w[LBP_NT / 64], s_before;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
     const int64_t t = (int64_t)b * LBP_NT + tid;
     const bool in = t < (int64_t)L.np + L.nl;
     const uint32_t c = in ? (uint32_t)cnt[t] : 0u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    uint32_t own = 0, inside = 0;
-#pragma unroll
-    for (int w = 0; w < LBP_NT / 64; ++w) {
-        inside += w < wv ? s_w[w] : 0u;
-        own += s_w[w];
-    }
-    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
+    uint32_t pos = lookback_offset<LBP_NT / 64>(c, part, b, s_w, &s_before).pos;
     if (!in || c == 0) return;
-    uint32_t pos = before + inside + incl - c;
     const bool lines = t >= L.np;
     const int32_t i1 = (int32_t)(lines ? t - L.np : t);
     const int32_t* __restrict__ ptr = lines ? L.ls_ptr : L.pt_ptr;
@@ -246,7 +231,8 @@ k_lbp_pair_emit(const LbpLists L, const int32_t* __restrict__ cnt, uint32_t* __r
 __global__ void __launch_bounds__(LBP_NT)
 k_lbp_pair_layout(const int32_t* __restrict__ ptr2, int32_t nblk, int32_t* __restrict__ blk_ptr, int32_t* __restrict__ pinned)
 {
-    __shared__ int32_t s_w[LBP_NT / 64], s_max[LBP_NT];
+    __shared__ uint32_t s_w[LBP_NT / 64];
+    __shared__ int32_t s_max[LBP_NT];
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int32_t carry = 0, mx = 0;
     for (int32_t base = 0; base < nblk; base += LBP_NT) {
@@ -258,22 +244,13 @@ k_lbp_pair_layout(const int32_t* __restrict__ ptr2, int32_t nblk, int32_t* __res
             const int32_t ch = (room + SCH_CHUNK - 1) / SCH_CHUNK;
             mx = ch > mx ? ch : mx;
         }
-        int32_t incl = room;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(incl, o);
-            if (lane >= o) incl += u;
-        }
+        const uint32_t incl = wave_inclusive_sum((uint32_t)room);
         if (lane == 63) s_w[wv] = incl;
         __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < LBP_NT / 64; ++w) {
-            before += w < wv ? s_w[w] : 0;
-            all += s_w[w];
-        }
-        if (B < nblk) blk_ptr[B] = carry + before + incl - room;
-        carry += all;
+        uint32_t before, all;
+        waves_before_and_all<LBP_NT / 64>(s_w, wv, before, all);
+        if (B < nblk) blk_ptr[B] = carry + (int32_t)(before + incl - (uint32_t)room);
+        carry += (int32_t)all;
         __syncthreads();
     }
     s_max[tid] = mx;
@@ -499,20 +476,13 @@ extern "C" int plslam_lba_plan_lists(plslam_lba_plan* P, const plslam_lba_lists*
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard dg_(ctx->device);
     PLSLAM_REQUIRE(P->schur_ready || (!host->blk_ptr && !host->pairs), PLSLAM_EINVAL);
-    hipStream_t s = ctx->stream;
-    StreamSyncOnError guard(s);
     const LbaStatView& S = P->st;
-    struct Item { void* dst; const void* src; size_t bytes; };
-    const Item items[] = {
+    const DownloadItem items[] = {
         {host->pt_ptr, S.pt_ptr, S.pt_ptr.bytes}, {host->pt_ids, S.pt_ids, S.pt_ids.bytes}, {host->ls_ptr, S.ls_ptr, S.ls_ptr.bytes},
         {host->ls_ids, S.ls_ids, S.ls_ids.bytes}, {host->kf_ptr, S.kf_ptr, S.kf_ptr.bytes}, {host->kf_ids, S.kf_ids, S.kf_ids.bytes},
         {host->pt_lm_loc, S.pt_lm, S.pt_lm.bytes}, {host->pt_pose_slot, S.pt_slot, S.pt_slot.bytes}, {host->pt_kf_loc, S.pt_kf, S.pt_kf.bytes},
         {host->pt_obs_uv, S.uv, S.uv.bytes}, {host->ls_lm_loc, S.ls_lm, S.ls_lm.bytes}, {host->ls_pose_slot, S.ls_slot, S.ls_slot.bytes},
         {host->ls_kf_loc, S.ls_kf, S.ls_kf.bytes}, {host->ls_l_obs, S.lobs, S.lobs.bytes},
         {host->blk_ptr, P->sc.blk_ptr, P->schur_ready ? P->sc.blk_ptr.bytes : 0}, {host->pairs, P->sc.pairs, P->schur_ready ? P->sc.pairs.bytes : 0}};
-    for (const Item& it : items)
-        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    return PLSLAM_OK;
+    return download_items(items, ctx->stream);
 }

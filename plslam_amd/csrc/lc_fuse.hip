@@ -29,13 +29,12 @@
 #include "common.hpp"
 #include "lc_fuse_plan.hpp"
 #include "lookback_dev.hpp"
+#include "map_image_dev.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
 namespace {
 
-constexpr int LF_NT = 256;              // lanes per workgroup = items per look-back tile (plslam_amd/lc_fuse.py: LOOKBACK_TILE)
-constexpr int LF_NW = LF_NT / 64;
 constexpr int LF_RES_NT = 1024;         // the resolve's one workgroup; a lane owns the events e = lane (mod LF_RES_NT): at most 64
 constexpr unsigned LF_MAX_GRID = 4096;  // K72 / K73 stride over their items
 constexpr int LF_MAX_LEVEL = PLSLAM_LC_FUSE_MAX_LEVEL;
@@ -45,22 +44,6 @@ enum { W_A = 0, W_B, W_C, W_D, W_SKIP, W_OBS, W_PAIRS, W_KIND = 8, W_STATUS = 16
 // what a tuple can be from the source image alone
 enum { SC_OFF = 0, SC_A, SC_B, SC_C, SC_D, SC_SELF, SC_NONE };
 
-struct SrcD {                           // one landmark kind of the source image
-    int32_t n, n_obs, n_feat, dl, dv;
-    const uint8_t *valid, *inlier;
-    const double* X;
-    const int32_t *obs_ptr, *obs_kf;
-    const double* obs_val;
-    const int32_t *feat_ptr, *feat_idx;
-};
-struct DstD {                           // ... of the destination
-    uint8_t *valid, *inlier;
-    double* X;
-    int32_t *obs_ptr, *obs_kf;
-    double* obs_val;
-    int32_t* feat_idx;
-    int32_t cap, obs_cap;
-};
 struct CallD {                          // one kind's tables and scratch (device), carved from the handle's buffer
     int32_t lines, n_map_kf, n_lc, m, c_cap;                     // c_cap: the host's bound on the new landmarks
     const uint8_t* kf_valid;
@@ -73,24 +56,6 @@ struct CallD {                          // one kind's tables and scratch (device
 __device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ int32_t old_len(const SrcD& S, int32_t lm)
-{
-    const int32_t b = S.obs_ptr[lm], e = S.obs_ptr[lm + 1];
-    return b >= 0 && e > b && e <= S.n_obs ? e - b : 0;
-}
-__device__ __forceinline__ void slot_features(const SrcD& S, int32_t kf, int32_t& f0, int32_t& nf)
-{
-    f0 = nf = 0;
-    if (S.n_feat <= 0) return;
-    const int32_t b = S.feat_ptr[kf], e = S.feat_ptr[kf + 1];
-    if (b >= 0 && e > b && e <= S.n_feat) { f0 = b; nf = e - b; }
-}
-// v / v.norm(): no guard (:4436, :4474)
-__device__ __forceinline__ void over_norm3(const double v[3], double* o)
-{
-    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
-}
 // the direction of a feature in its camera frame: P / |P|, lines (sP + eP) / |sP + eP| (:4560-4561)
 __device__ __forceinline__ void cam_dir(int lines, const double* __restrict__ P, double* o)
 {
@@ -114,7 +79,7 @@ __device__ __forceinline__ void world_dir(int lines, const double* __restrict__ 
 // the entry of tuple t: the last one whose offset is at or below t (empty entries share an offset with their successor)
 __device__ __forceinline__ int32_t entry_of(const CallD& C, int32_t t) { return segment_of(C.eptr, C.n_lc, t); }
 // the place in the destination of entry `off` of landmark x's list (K71's chain)
-__device__ __forceinline__ int64_t place(const SrcD& S, const DstD& D, const CallD& C, int32_t x, int64_t off)
+__device__ __forceinline__ int64_t place(const MapKindSrc& S, const MapKindDst& D, const CallD& C, int32_t x, int64_t off)
 {
     for (int it = 0; it <= LF_MAX_LEVEL && x >= 0 && x < S.n; ++it) {
         const int32_t e = C.killer[x];
@@ -126,10 +91,10 @@ __device__ __forceinline__ int64_t place(const SrcD& S, const DstD& D, const Cal
 }
 
 // K68: the state and the static classification.  A lane per source landmark, then per tuple.
-__global__ void __launch_bounds__(LF_NT)
-k_lf_classify(SrcD S, CallD C)
+__global__ void __launch_bounds__(MAP_TILE)
+k_lf_classify(MapKindSrc S, CallD C)
 {
-    const int64_t i = (int64_t)blockIdx.x * LF_NT + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     if (i < S.n) {
         C.cur_len[i] = old_len(S, (int32_t)i);
         return;
@@ -171,7 +136,7 @@ k_lf_classify(SrcD S, CallD C)
 
 // K69: the resolve.  One workgroup of LF_RES_NT lanes; lane l owns the events e = l + 1024 k, bit k of its pending mask.
 __global__ void __launch_bounds__(LF_RES_NT)
-k_lf_resolve(SrcD S, CallD C)
+k_lf_resolve(MapKindSrc S, CallD C)
 {
     __shared__ uint32_t s_c[LF_RES_NT];
     __shared__ unsigned long long s_p[LF_RES_NT];
@@ -297,32 +262,18 @@ k_lf_resolve(SrcD S, CallD C)
 // K70: obs_ptr of the destination (an exclusive look-back scan of the final lengths over n + n_new landmarks) and the landmark
 // rows: inlier / X copied, valid cleared where an event fused the landmark away; a new landmark is valid, an inlier and
 // X = T_kp P0 (:4473, :4608-4609).
-__global__ void __launch_bounds__(LF_NT)
-k_lf_layout(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
+__global__ void __launch_bounds__(MAP_TILE)
+k_lf_layout(MapKindSrc S, MapKindDst D, CallD C, uint32_t* __restrict__ part)
 {
-    __shared__ uint32_t s_o[LF_NW], s_before;
+    __shared__ uint32_t s_o[MAP_NW], s_before;
     if (*C.status) return;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
-    const int32_t i = b * LF_NT + tid;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
+    const int32_t i = b * MAP_TILE + tid;
     const int32_t n2 = S.n + C.cnt[W_C];
     const uint32_t c = i < n2 ? (uint32_t)C.cur_len[i] : 0u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_o[wv] = incl;
-    __syncthreads();
-    uint32_t own = 0, in = 0;
-#pragma unroll
-    for (int w = 0; w < LF_NW; ++w) {
-        in += w < wv ? s_o[w] : 0u;
-        own += s_o[w];
-    }
-    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
+    const TileScan sc = lookback_offset<MAP_NW>(c, part, b, s_o, &s_before);
     if (i < n2) {
-        D.obs_ptr[i] = (int32_t)(before + in + incl - c);
+        D.obs_ptr[i] = (int32_t)sc.pos;
         if (i < S.n) {
             D.valid[i] = S.valid[i] && C.killer[i] < 0 ? S.valid[i] : 0;
             D.inlier[i] = S.inlier[i];
@@ -337,18 +288,18 @@ k_lf_layout(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
         }
     }
     if (b == (int)gridDim.x - 1 && tid == 0) {
-        D.obs_ptr[n2] = (int32_t)(before + own);
-        C.cnt[W_OBS] = (int32_t)(before + own);
+        D.obs_ptr[n2] = (int32_t)sc.upto;
+        C.cnt[W_OBS] = (int32_t)sc.upto;
     }
 }
 
 // K71: obs_kf / obs_val / obs_src of the destination.  Lanes [0, n_obs): a source observation to its place; lanes n_obs + 2 t + w:
 // the observation tuple t made on side w (A: w = 0, B: w = 1, C: both), and the position of the event's first observation.
-__global__ void __launch_bounds__(LF_NT)
-k_lf_obs(SrcD S, DstD D, CallD C)
+__global__ void __launch_bounds__(MAP_TILE)
+k_lf_obs(MapKindSrc S, MapKindDst D, CallD C)
 {
     if (*C.status) return;
-    const int64_t i = (int64_t)blockIdx.x * LF_NT + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     const int32_t total = C.cnt[W_OBS] < D.obs_cap ? C.cnt[W_OBS] : D.obs_cap;
     int64_t pos = -1;
     int32_t kf = -1, tag = 0;
@@ -392,13 +343,13 @@ k_lf_obs(SrcD S, DstD D, CallD C)
 // K72: feat_idx, the anchors and the graph; the kernel strides over n_feat features, m events and the (event, pair) items.
 // Pair q of event e -- A / B: entry q of the target's list at the time, [first - o, first], against the other keyframe; C: (kp,
 // kc); D: entry q / w of a's first o entries against entry q % w of the w appended ones.
-__global__ void __launch_bounds__(LF_NT)
-k_lf_feat_graph(SrcD S, DstD D, CallD C, int32_t* __restrict__ graph)
+__global__ void __launch_bounds__(MAP_TILE)
+k_lf_feat_graph(MapKindSrc S, MapKindDst D, CallD C, int32_t* __restrict__ graph)
 {
     if (*C.status) return;
     const int32_t total = C.cnt[W_OBS] < D.obs_cap ? C.cnt[W_OBS] : D.obs_cap, nk = C.n_map_kf;
-    const int64_t n_items = (int64_t)S.n_feat + C.m + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * LF_NT;
-    for (int64_t it = (int64_t)blockIdx.x * LF_NT + threadIdx.x; it < n_items; it += stride) {
+    const int64_t n_items = (int64_t)S.n_feat + C.m + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * MAP_TILE;
+    for (int64_t it = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x; it < n_items; it += stride) {
         if (it < S.n_feat) {
             int32_t v = S.feat_idx[it];
             const int32_t w = C.feat_win[it];
@@ -442,10 +393,10 @@ struct KfCopy {                          // what K73 copies from the source imag
 };
 
 // K73: the call's last kernel: the counters and the graph to the page-locked block; kf_valid / x_kf_w / feat_ptr copied
-__global__ void __launch_bounds__(LF_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_lf_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ graph, KfCopy K, int32_t* __restrict__ pinned, int32_t with_graph)
 {
-    const int64_t g = (int64_t)blockIdx.x * LF_NT + threadIdx.x, stride = (int64_t)gridDim.x * LF_NT;
+    const int64_t g = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x, stride = (int64_t)gridDim.x * MAP_TILE;
     const bool ok = cnt[W_STATUS] == 0;
     if (g < W_WORDS) pinned[g] = cnt[g];
     if (!ok) return;
@@ -459,8 +410,6 @@ k_lf_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ graph,
         for (int64_t i = g; i <= K.nk; i += stride)
             if (K.fp_d[k]) K.fp_d[k][i] = K.fp[k][i];
 }
-
-unsigned tiles(int64_t n) { return (unsigned)(n > 0 ? (n + LF_NT - 1) / LF_NT : 1); }
 
 }  // namespace
 }  // namespace plslam
@@ -489,13 +438,7 @@ int plslam_lc_fuse_create(plslam_ctx* ctx, plslam_lc_fuse** out)
 void plslam_lc_fuse_destroy(plslam_lc_fuse* lf)
 {
     if (!lf) return;
-    {
-        std::lock_guard<std::mutex> lk(lf->ctx->mu);
-        DeviceGuard dg_(lf->ctx->device);
-        (void)hipStreamSynchronize(lf->ctx->stream);
-        lf->buf.release();
-        lf->pin.release();
-    }
+    release_handle_buffers(lf->ctx, lf->buf, lf->pin);
     delete lf;
 }
 
@@ -520,7 +463,7 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
     Carver c;
     const size_t o_cnt = c.take(W_WORDS * 4), o_graph = c.take((size_t)nk * nk * 4);
     for (int k = 0; k < 2; ++k) {
-        O[k].w_lm = tiles(P.k[k].need_lm);
+        O[k].w_lm = map_tiles(P.k[k].need_lm);
         O[k].win = c.take((size_t)S[k]->n_feat * 4 + 4);
         O[k].part = c.take((size_t)O[k].w_lm * 4);
     }
@@ -557,16 +500,15 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
     int32_t* cnt = (int32_t*)(d + o_cnt);
     int32_t* graph = (int32_t*)(d + o_graph);
     const char* st_ = d + stage_off;
-    SrcD Sd[2];
-    DstD Dd[2];
+    MapKindSrc Sd[2];
+    MapKindDst Dd[2];
     CallD C[2];
     for (int k = 0; k < 2; ++k) {
         const LcFuseKindPlan& K = P.k[k];
         const plslam_map_landmarks& A = *S[k];
         plslam_map_landmarks& B = *Dk[k];
-        Sd[k] = SrcD{A.n, A.n_obs, A.n_feat, K.dl, K.dv, A.valid, A.inlier, A.X, A.obs_ptr, A.obs_kf, A.obs_val, A.feat_ptr, A.feat_idx};
-        Dd[k] = DstD{B.valid, (uint8_t*)B.inlier, (double*)B.X, (int32_t*)B.obs_ptr, (int32_t*)B.obs_kf, (double*)B.obs_val, B.feat_idx,
-                     cap[k], obs_cap[k]};
+        Sd[k] = map_kind_src(A, k);
+        Dd[k] = map_kind_dst(B, cap[k], obs_cap[k]);
         CallD& Ck = C[k];
         Ck = CallD{};
         Ck.lines = k; Ck.n_map_kf = nk; Ck.n_lc = n_lc; Ck.m = K.m; Ck.c_cap = K.cC;
@@ -582,13 +524,13 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
         Ck.cnt = cnt + W_KIND * k; Ck.status = cnt + W_STATUS; Ck.ev_dir = (double*)(d + O[k].dir);
     }
     // both kinds are resolved before anything of the destination is written: a refusal leaves it untouched
-    for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_classify, dim3(tiles((int64_t)S[k]->n + P.k[k].m)), dim3(LF_NT), 0, s, Sd[k], C[k]);
+    for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_classify, dim3(map_tiles((int64_t)S[k]->n + P.k[k].m)), dim3(MAP_TILE), 0, s, Sd[k], C[k]);
     for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_resolve, dim3(1), dim3(LF_RES_NT), 0, s, Sd[k], C[k]);
     for (int k = 0; k < 2; ++k) {
-        hipLaunchKernelGGL(k_lf_layout, dim3(O[k].w_lm), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k], (uint32_t*)(d + O[k].part));
-        hipLaunchKernelGGL(k_lf_obs, dim3(tiles((int64_t)S[k]->n_obs + 2 * (int64_t)P.k[k].m)), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k]);
-        const unsigned g = tiles((int64_t)S[k]->n_feat + S[k]->n_obs + 4 * (int64_t)P.k[k].m);
-        hipLaunchKernelGGL(k_lf_feat_graph, dim3(g < LF_MAX_GRID ? g : LF_MAX_GRID), dim3(LF_NT), 0, s, Sd[k], Dd[k], C[k], graph);
+        hipLaunchKernelGGL(k_lf_layout, dim3(O[k].w_lm), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k], (uint32_t*)(d + O[k].part));
+        hipLaunchKernelGGL(k_lf_obs, dim3(map_tiles((int64_t)S[k]->n_obs + 2 * (int64_t)P.k[k].m)), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k]);
+        const unsigned g = map_tiles((int64_t)S[k]->n_feat + S[k]->n_obs + 4 * (int64_t)P.k[k].m);
+        hipLaunchKernelGGL(k_lf_feat_graph, dim3(g < LF_MAX_GRID ? g : LF_MAX_GRID), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k], graph);
     }
     KfCopy kc{};
     kc.nk = nk;
@@ -598,8 +540,8 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
         kc.fp[k] = S[k]->feat_ptr;
         kc.fp_d[k] = S[k]->n_feat > 0 && Dk[k]->feat_ptr != S[k]->feat_ptr ? (int32_t*)Dk[k]->feat_ptr : nullptr;
     }
-    const unsigned gp = tiles(graph_delta ? (int64_t)nk * nk : nk + 1);
-    hipLaunchKernelGGL(k_lf_publish, dim3(gp < 256u ? gp : 256u), dim3(LF_NT), 0, s, (const int32_t*)cnt, (const int32_t*)graph, kc,
+    const unsigned gp = map_tiles(graph_delta ? (int64_t)nk * nk : nk + 1);
+    hipLaunchKernelGGL(k_lf_publish, dim3(gp < 256u ? gp : 256u), dim3(MAP_TILE), 0, s, (const int32_t*)cnt, (const int32_t*)graph, kc,
                        (int32_t*)lf->pin.dev, graph_delta ? 1 : 0);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -643,19 +585,12 @@ int plslam_lc_fuse_download(plslam_lc_fuse* lf, const plslam_lc_fuse_buffers* ho
     PLSLAM_REQUIRE(lf && host && lf->done, PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lf->ctx->mu);
     DeviceGuard dg_(lf->ctx->device);
-    hipStream_t s = lf->ctx->stream;
-    StreamSyncOnError guard(s);
-    struct Item { void* dst; const void* src; size_t bytes; };
-    const Item items[] = {{host->pt_ev, lf->d.pt_ev, (size_t)lf->m[0] * 24}, {host->pt_dir, lf->d.pt_dir, (size_t)lf->m[0] * 48},
-                          {host->ls_ev, lf->d.ls_ev, (size_t)lf->m[1] * 24}, {host->ls_dir, lf->d.ls_dir, (size_t)lf->m[1] * 48},
-                          {host->pt_obs_src, lf->d.pt_obs_src, (size_t)lf->n_obs[0] * 4},
-                          {host->ls_obs_src, lf->d.ls_obs_src, (size_t)lf->n_obs[1] * 4},
-                          {host->graph_delta, lf->d.graph_delta, (size_t)lf->nk * lf->nk * 4}};
-    for (const Item& it : items)
-        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    return PLSLAM_OK;
+    const DownloadItem items[] = {{host->pt_ev, lf->d.pt_ev, (size_t)lf->m[0] * 24}, {host->pt_dir, lf->d.pt_dir, (size_t)lf->m[0] * 48},
+                                  {host->ls_ev, lf->d.ls_ev, (size_t)lf->m[1] * 24}, {host->ls_dir, lf->d.ls_dir, (size_t)lf->m[1] * 48},
+                                  {host->pt_obs_src, lf->d.pt_obs_src, (size_t)lf->n_obs[0] * 4},
+                                  {host->ls_obs_src, lf->d.ls_obs_src, (size_t)lf->n_obs[1] * 4},
+                                  {host->graph_delta, lf->d.graph_delta, (size_t)lf->nk * lf->nk * 4}};
+    return download_items(items, lf->ctx->stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "map_image.hpp"
 #include "plslam_hip.h"
 
 namespace plslam {
@@ -26,24 +27,6 @@ struct LcFusePlan {
 
 inline size_t lc_fuse_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-inline bool lc_fuse_src_kind_ok(const plslam_map_landmarks& L)
-{
-    return L.n >= 0 && L.n_obs >= 0 && L.n_obs < (1 << 30) && L.n_feat >= 0 && (L.n == 0 || (L.valid && L.inlier && L.X && L.obs_ptr)) &&
-           (L.n_obs == 0 || (L.n > 0 && L.obs_kf && L.obs_val)) && (L.n_feat == 0 || (L.feat_ptr && L.feat_idx));
-}
-// every destination array is there and none of them is an array of the source (feat_ptr may be the source's)
-inline bool lc_fuse_dst_kind_ok(const plslam_map_landmarks& D, const plslam_map_landmarks& S)
-{
-    const void* d[] = {D.valid, D.inlier, D.X, D.obs_ptr, D.obs_kf, D.obs_val, D.feat_idx};
-    const void* s[] = {S.valid, S.inlier, S.X, S.obs_ptr, S.obs_kf, S.obs_val, S.feat_idx, S.feat_ptr};
-    for (const void* p : d) {
-        if (!p) return false;
-        for (const void* q : s)
-            if (p == q) return false;
-    }
-    return D.feat_ptr != nullptr;
-}
-
 // Validates everything the host can and fills the plan.  PLSLAM_OK, PLSLAM_EINVAL or PLSLAM_ERANGE (P->why says which rule).
 inline int lc_fuse_plan(const plslam_map_index* src, const plslam_map_insert_dst* dst, int32_t n_lc, const int32_t* lc_idx,
                         const double* T_kf_w, const plslam_lc_fuse_kind* points, const plslam_lc_fuse_kind* lines, LcFusePlan* P)
@@ -57,11 +40,11 @@ inline int lc_fuse_plan(const plslam_map_index* src, const plslam_map_insert_dst
     } while (0)
     LCF_REFUSE(!src || !dst || !lc_idx || !T_kf_w, PLSLAM_EINVAL, "a NULL argument");
     LCF_REFUSE(n_lc <= 0, PLSLAM_EINVAL, "n_lc <= 0");
-    LCF_REFUSE(src->n_map_kf < 1 || !src->kf_valid || !src->x_kf_w || !lc_fuse_src_kind_ok(src->points) || !lc_fuse_src_kind_ok(src->lines),
+    LCF_REFUSE(src->n_map_kf < 1 || !src->kf_valid || !src->x_kf_w || !map_src_kind_ok(src->points) || !map_src_kind_ok(src->lines),
                PLSLAM_EINVAL, "the source image is incomplete");
     LCF_REFUSE((int64_t)src->n_map_kf * src->n_map_kf >= (1 << 28), PLSLAM_ERANGE, "n_map_kf^2 beyond 2^28");
-    LCF_REFUSE(!dst->map.kf_valid || !dst->map.x_kf_w || !lc_fuse_dst_kind_ok(dst->map.points, src->points) ||
-                   !lc_fuse_dst_kind_ok(dst->map.lines, src->lines),
+    LCF_REFUSE(!dst->map.kf_valid || !dst->map.x_kf_w || !map_dst_kind_ok(dst->map.points, src->points) ||
+                   !map_dst_kind_ok(dst->map.lines, src->lines),
                PLSLAM_EINVAL, "a destination array is NULL or is a source array");
     const int32_t nk = src->n_map_kf;
     for (int32_t i = 0; i < n_lc; ++i) {

@@ -14,62 +14,31 @@
 #include "common.hpp"
 #include "lba_plan.hpp"
 #include "lookback_dev.hpp"
+#include "map_image_dev.hpp"
+#include "publish_dev.hpp"
 
 namespace plslam {
 namespace {
 
-constexpr int LM_NT = 256;             // lanes per workgroup = items per look-back tile (plslam_amd/local_map.py: LOOKBACK_TILE)
-constexpr int LM_NW = LM_NT / 64;
 // the call counters (device words, mirrored in the page-locked block): plslam_local_map_counts' order, then the tickets
 enum { C_KF_LOCAL = 0, C_PT_LOCAL, C_LS_LOCAL, C_NKF, C_NPT, C_NLS, C_PT_OBS, C_LS_OBS, C_PT_REM, C_LS_REM, C_CULL_DONE, C_FORM_DONE, C_PT_MOVED, C_LS_MOVED, C_APPLY_DONE, C_WORDS = 16 };
 
-struct KindD {                          // one landmark kind of the index (device pointers) + its widths
-    int32_t n, n_obs, n_feat, dl, dv;   // dl: doubles per landmark (3 / 6), dv: doubles per observation (2 / 3)
-    uint8_t* valid;
-    const uint8_t* inlier;
-    const double* X;
-    const int32_t* obs_ptr;
-    const int32_t* obs_kf;
-    const double* obs_val;
-    const int32_t* feat_ptr;
-    int32_t* feat_idx;
-};
-
-KindD kind_d(const plslam_map_landmarks& L, int lines)
-{
-    return KindD{L.n, L.n_obs, L.n_feat, lines ? 6 : 3, lines ? 3 : 2, L.valid, L.inlier, L.X, L.obs_ptr, L.obs_kf, L.obs_val, L.feat_ptr, L.feat_idx};
-}
-
-// The counters of a call's LAST kernel: every wave adds its ballots to the device words and WAITS for the atomics (returning
-// ones) before the workgroup's barrier; one lane then counts the workgroup in, and the last workgroup copies the words to the
-// page-locked block the host reads (lba.hip: gate_count_and_publish).  done: a ZERO device word.
-struct Publish { int32_t* done; const int32_t* src; int32_t* dst; int32_t n; };
+// The counters of a call's LAST kernel (publish_dev.hpp): NC flags per lane counted into cnt[0 .. NC), then the ticket
 template <int NC>
 __device__ __forceinline__ void count_and_publish(const bool (&ok)[NC], int32_t* __restrict__ cnt, const Publish& pub)
 {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const unsigned long long b = __ballot(ok[c]);
-        if ((threadIdx.x & 63) == 0 && b) {
-            const int old = atomicAdd(cnt + c, (int)__popcll(b));
-            asm volatile("" ::"v"(old));                    // (the atomic has been performed when the wave passes here)
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int prev = atomicAdd(pub.done, 1);
-        if (prev == (int)gridDim.x - 1)
-            for (int w = 0; w < pub.n; ++w) pub.dst[w] = __hip_atomic_load(pub.src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    for (int c = 0; c < NC; ++c) wave_count_and_wait(ok[c], cnt + c);
+    publish_from_last_workgroup(pub);
 }
 
 // K55: the keyframe flags of formLocalMap (:859 / :925 the anchor, :881-885 / :947-951 the graph loop over the LAST row); a lane per
 // slot.  A NULL slot is never local (deviation: the reference dereferences it, :885).
-__global__ void __launch_bounds__(LM_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_lm_kf_flags(int32_t n_map_kf, int32_t anchor, const uint8_t* __restrict__ kf_valid, const int32_t* __restrict__ row,
               int32_t min_cov, int32_t window, uint8_t* __restrict__ kf_local)
 {
-    const int32_t i = (int32_t)blockIdx.x * LM_NT + (int32_t)threadIdx.x;
+    const int32_t i = (int32_t)blockIdx.x * MAP_TILE + (int32_t)threadIdx.x;
     if (i >= n_map_kf) return;
     const int32_t g = n_map_kf - 1;
     const bool loc = kf_valid[i] != 0 && (i == anchor || (i < g && (row[i] >= min_cov || g - i <= window)));
@@ -78,11 +47,11 @@ k_lm_kf_flags(int32_t n_map_kf, int32_t anchor, const uint8_t* __restrict__ kf_v
 
 // K56: the landmark flags (:860-877, :887-898): a lane per feature of either kind; the features of a local keyframe set the flag
 // of the landmark they name (idx != -1 && valid; PLSLAM_FEAT_NULL = a NULL feature: skipped).  Many lanes store the same byte 1.
-__global__ void __launch_bounds__(LM_NT)
-k_lm_feat_flags(int32_t n_map_kf, const uint8_t* __restrict__ kf_local, KindD P, KindD L, uint8_t* __restrict__ pt_local,
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_feat_flags(int32_t n_map_kf, const uint8_t* __restrict__ kf_local, MapKindSrc P, MapKindSrc L, uint8_t* __restrict__ pt_local,
                 uint8_t* __restrict__ ls_local)
 {
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     if (t >= (int64_t)P.n_feat + L.n_feat) return;
     const bool lines = t >= P.n_feat;
     const int32_t f = (int32_t)(lines ? t - P.n_feat : t);
@@ -98,11 +67,11 @@ k_lm_feat_flags(int32_t n_map_kf, const uint8_t* __restrict__ kf_local, KindD P,
 }
 
 // K57: the three counts of form; a lane per flag of the three arrays
-__global__ void __launch_bounds__(LM_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_lm_count_flags(const uint8_t* __restrict__ kf_local, int32_t nkf, const uint8_t* __restrict__ pt_local, int32_t npt,
                  const uint8_t* __restrict__ ls_local, int32_t nls, int32_t* __restrict__ cnt, Publish pub)
 {
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     bool ok[3] = {false, false, false};
     if (t < nkf) ok[0] = kf_local[t] != 0;
     else if (t < (int64_t)nkf + npt) ok[1] = pt_local[t - nkf] != 0;
@@ -111,11 +80,11 @@ k_lm_count_flags(const uint8_t* __restrict__ kf_local, int32_t nkf, const uint8_
 }
 
 // K58: candidate[i] = valid && local && kf_obs_list.back() != kf2_idx (:547, :649); no observation: 0
-__global__ void __launch_bounds__(LM_NT)
-k_lm_candidates(KindD P, KindD L, const uint8_t* __restrict__ pt_local, const uint8_t* __restrict__ ls_local, int32_t kf2_idx,
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_candidates(MapKindSrc P, MapKindSrc L, const uint8_t* __restrict__ pt_local, const uint8_t* __restrict__ ls_local, int32_t kf2_idx,
                 uint8_t* __restrict__ pt_cand, uint8_t* __restrict__ ls_cand)
 {
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     if (t >= (int64_t)P.n + L.n) return;
     const bool lines = t >= P.n;
     const int32_t i = (int32_t)(lines ? t - P.n : t);
@@ -123,81 +92,61 @@ k_lm_candidates(KindD P, KindD L, const uint8_t* __restrict__ pt_local, const ui
     const uint8_t* __restrict__ local = lines ? ls_local : pt_local;
     const int32_t* __restrict__ obs_ptr = lines ? L.obs_ptr : P.obs_ptr;
     const int32_t* __restrict__ obs_kf = lines ? L.obs_kf : P.obs_kf;
-    const int32_t n_obs = lines ? L.n_obs : P.n_obs;
     uint8_t c = 0;
     if (valid[i] && local[i]) {
-        const int32_t b = obs_ptr[i], e = obs_ptr[i + 1];
-        if (e > b && e <= n_obs && b >= 0) c = obs_kf[e - 1] != kf2_idx ? 1 : 0;
+        const int32_t len = lines ? old_len(L, i) : old_len(P, i);
+        if (len > 0) c = obs_kf[obs_ptr[i] + len - 1] != kf2_idx ? 1 : 0;
     }
     (lines ? ls_cand : pt_cand)[i] = c;
 }
 
 // K59: kf_list (:1226-1239): the valid, local slots other than 0, ascending; the inverse table the observations' keyframe local
 // index comes from (kf_list has no repeats: the reference's linear search :1265-1272 finds the same position); X_aux's poses.
-__global__ void __launch_bounds__(LM_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_lm_compact_kf(int32_t n_map_kf, const uint8_t* __restrict__ kf_valid, const uint8_t* __restrict__ kf_local,
                 const double* __restrict__ x_kf_w, int32_t* __restrict__ kf_list, int32_t* __restrict__ kf_inv,
                 double* __restrict__ X_aux, int32_t* __restrict__ cnt, uint32_t* __restrict__ part)
 {
-    __shared__ uint32_t s_w[LM_NW], s_before;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
-    const int32_t i = b * LM_NT + tid;
+    __shared__ uint32_t s_w[MAP_NW], s_before;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
+    const int32_t i = b * MAP_TILE + tid;
     const bool v = i < n_map_kf && i != 0 && kf_valid[i] && kf_local[i];
-    const uint64_t m = __ballot(v);
-    if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t own = 0, inside_wg = 0;
-#pragma unroll
-    for (int w = 0; w < LM_NW; ++w) {
-        inside_wg += w < wv ? s_w[w] : 0u;
-        own += s_w[w];
-    }
-    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
-    const uint32_t pos = before + inside_wg + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    const TileScan sc = lookback_rank<MAP_NW>(v, part, b, s_w, &s_before);
+    const uint32_t pos = sc.pos;
     if (i < n_map_kf) kf_inv[i] = v ? (int32_t)pos : -1;
     if (v) {
         kf_list[pos] = i;
 #pragma unroll
         for (int c = 0; c < 6; ++c) X_aux[6 * (size_t)pos + c] = x_kf_w[6 * (size_t)i + c];
     }
-    if (b == (int)gridDim.x - 1 && tid == 0) cnt[C_NKF] = (int32_t)(before + own);
+    if (b == (int)gridDim.x - 1 && tid == 0) cnt[C_NKF] = (int32_t)sc.upto;
 }
 
 // K60: pt_list / ls_list (:1245-1249, :1277; :1286-1290, :1318): the stable compaction of the valid, local landmarks, and in the
 // same pass the offset of each listed landmark's observations in the observation list (a second chain: the exclusive sum of the
 // listed landmarks' list lengths) and X_aux's landmark block (:1251-1253, :1292-1294), which starts behind the blocks in front of
 // it: their lengths are device words of the launches before this one.
-__global__ void __launch_bounds__(LM_NT)
-k_lm_compact_lm(KindD K, int lines, const uint8_t* __restrict__ local, int32_t* __restrict__ list, int32_t* __restrict__ off,
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_compact_lm(MapKindSrc K, int lines, const uint8_t* __restrict__ local, int32_t* __restrict__ list, int32_t* __restrict__ off,
                 double* __restrict__ X_aux, int32_t* __restrict__ cnt, uint32_t* __restrict__ part_n, uint32_t* __restrict__ part_o)
 {
-    __shared__ uint32_t s_w[LM_NW], s_o[LM_NW], s_before_n, s_before_o;
+    __shared__ uint32_t s_w[MAP_NW], s_o[MAP_NW], s_before_n, s_before_o;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
-    const int32_t i = b * LM_NT + tid;
+    const int32_t i = b * MAP_TILE + tid;
     const bool v = i < K.n && K.valid[i] && local[i];
     uint32_t c = 0;                                         // the landmark's observations
-    if (v) {
-        const int32_t d = K.obs_ptr[i + 1] - K.obs_ptr[i];
+    if (v) {                                                // (NOT old_len: d clamped to n_obs, b >= 0 and e <= n_obs untested -- another
+        const int32_t d = K.obs_ptr[i + 1] - K.obs_ptr[i];  //  function on a malformed image, kept; K61 range-checks every source position)
         c = d > 0 ? (uint32_t)(d < K.n_obs ? d : K.n_obs) : 0u;
     }
     const uint64_t m = __ballot(v);
-    uint32_t incl = c;                                      // inclusive sum inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += t;
-    }
+    const uint32_t incl = wave_inclusive_sum(c);
     if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
     if (lane == 63) s_o[wv] = incl;
-    __syncthreads();
-    uint32_t own_n = 0, in_n = 0, own_o = 0, in_o = 0;
-#pragma unroll
-    for (int w = 0; w < LM_NW; ++w) {
-        in_n += w < wv ? s_w[w] : 0u;
-        own_n += s_w[w];
-        in_o += w < wv ? s_o[w] : 0u;
-        own_o += s_o[w];
-    }
+    __syncthreads();                                        // (one barrier for the two chains)
+    uint32_t own_n, in_n, own_o, in_o;
+    waves_before_and_all<MAP_NW>(s_w, wv, in_n, own_n);
+    waves_before_and_all<MAP_NW>(s_o, wv, in_o, own_o);
     const uint32_t before_n = lookback_exclusive(part_n, b, own_n, &s_before_n);
     const uint32_t before_o = lookback_exclusive(part_o, b, own_o, &s_before_o);
     if (v) {
@@ -218,12 +167,12 @@ k_lm_compact_lm(KindD K, int lines, const uint8_t* __restrict__ local, int32_t* 
 // one at or below the lane is the owner), then copies: the six Vector6i columns, the columns plslam_lba_plan_create takes and the
 // observation itself.  The call's last kernel: workgroup 0 brings the counts to the page-locked block.
 struct ExpandOut { int32_t *obs6, *lm_loc, *kf_loc, *pose_slot; double* val; const int32_t *list, *off; };
-__global__ void __launch_bounds__(LM_NT)
-k_lm_expand(KindD P, KindD L, ExpandOut op, ExpandOut ol, int32_t n_map_kf, const int32_t* __restrict__ kf_inv,
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_expand(MapKindSrc P, MapKindSrc L, ExpandOut op, ExpandOut ol, int32_t n_map_kf, const int32_t* __restrict__ kf_inv,
             const int32_t* __restrict__ cnt, int32_t* __restrict__ pinned)
 {
     if (blockIdx.x == 0 && threadIdx.x >= C_NKF && threadIdx.x <= C_LS_OBS) pinned[threadIdx.x] = cnt[threadIdx.x];
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     if (t >= (int64_t)P.n_obs + L.n_obs) return;
     const bool lines = t >= P.n_obs;
     const int32_t j = (int32_t)(lines ? t - P.n_obs : t);
@@ -259,30 +208,32 @@ k_lm_expand(KindD P, KindD L, ExpandOut op, ExpandOut ol, int32_t n_map_kf, cons
 // features of its first observer in order and clears the FIRST one that names it (:2720-2728: the `break`): the minimum
 // position, whatever the other lanes do -- they only ever rewrite entries that name OTHER landmarks.  A NULL first observer and
 // NULL features are skipped (deviation: :2720-2723 dereference them); no observation: not culled.
-__global__ void __launch_bounds__(LM_NT)
-k_lm_cull(KindD P, KindD L, int32_t n_map_kf, const uint8_t* __restrict__ kf_valid, const uint8_t* __restrict__ pt_local,
-          const uint8_t* __restrict__ ls_local, int32_t max_kf_idx, int32_t min_lm_obs, uint8_t* __restrict__ pt_removed,
-          uint8_t* __restrict__ ls_removed, int32_t* __restrict__ cnt, Publish pub)
+// (valid and feat_idx are read AND written here: through the mutable pointers only, never through the read-only view)
+struct CullKind { uint8_t* valid; int32_t* feat_idx; uint8_t* removed; };
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_cull(MapKindSrc P, MapKindSrc L, CullKind wp, CullKind wl, int32_t n_map_kf, const uint8_t* __restrict__ kf_valid,
+          const uint8_t* __restrict__ pt_local, const uint8_t* __restrict__ ls_local, int32_t max_kf_idx, int32_t min_lm_obs,
+          int32_t* __restrict__ cnt, Publish pub)
 {
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     bool ok[2] = {false, false};
     if (t < (int64_t)P.n + L.n) {
         const bool lines = t >= P.n;
         const int32_t i = (int32_t)(lines ? t - P.n : t);
-        uint8_t* __restrict__ valid = lines ? L.valid : P.valid;
+        uint8_t* __restrict__ valid = lines ? wl.valid : wp.valid;
+        int32_t* __restrict__ feat_idx = lines ? wl.feat_idx : wp.feat_idx;
         const uint8_t* __restrict__ inlier = lines ? L.inlier : P.inlier;
         const uint8_t* __restrict__ local = lines ? ls_local : pt_local;
         const int32_t* __restrict__ obs_ptr = lines ? L.obs_ptr : P.obs_ptr;
         const int32_t* __restrict__ obs_kf = lines ? L.obs_kf : P.obs_kf;
         const int32_t* __restrict__ feat_ptr = lines ? L.feat_ptr : P.feat_ptr;
-        int32_t* __restrict__ feat_idx = lines ? L.feat_idx : P.feat_idx;
-        const int32_t n_obs = lines ? L.n_obs : P.n_obs, n_feat = lines ? L.n_feat : P.n_feat;
+        const int32_t n_feat = lines ? L.n_feat : P.n_feat;
         bool rem = false;
         if (valid[i] && !local[i]) {
-            const int32_t b = obs_ptr[i], e = obs_ptr[i + 1];
-            if (b >= 0 && e > b && e <= n_obs) {
+            const int32_t b = obs_ptr[i], len = lines ? old_len(L, i) : old_len(P, i);
+            if (len > 0) {
                 const int32_t first = obs_kf[b];
-                if (max_kf_idx - first > 10 && (!inlier[i] || e - b < min_lm_obs)) {
+                if (max_kf_idx - first > 10 && (!inlier[i] || len < min_lm_obs)) {
                     rem = true;
                     valid[i] = 0;
                     if (first >= 0 && first < n_map_kf && kf_valid[first] && n_feat > 0) {
@@ -296,7 +247,7 @@ k_lm_cull(KindD P, KindD L, int32_t n_map_kf, const uint8_t* __restrict__ kf_val
                 }
             }
         }
-        (lines ? ls_removed : pt_removed)[i] = rem ? 1 : 0;
+        (lines ? wl.removed : wp.removed)[i] = rem ? 1 : 0;
         ok[lines ? 1 : 0] = rem;
     }
     count_and_publish<2>(ok, cnt, pub);
@@ -307,10 +258,10 @@ k_lm_cull(KindD P, KindD L, int32_t n_map_kf, const uint8_t* __restrict__ kf_val
 // from 0 (no contraction: the build's -ffp-contract=off), sqrt(s2) > th.  inlier is only ever cleared; X is copied verbatim.
 // A listed landmark occurs once in its list: no two lanes touch the same landmark, in place on the image is safe.
 struct ApplyKind { const int32_t* list; const double* Xnew; double* X; uint8_t* inlier; uint8_t* moved; int32_t n_list, n; };
-__global__ void __launch_bounds__(LM_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_lm_apply_lba(ApplyKind P, ApplyKind L, double th, int32_t* __restrict__ cnt, Publish pub)
 {
-    const int64_t t = (int64_t)blockIdx.x * LM_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     bool ok[2] = {false, false};
     if (t < (int64_t)P.n_list + L.n_list) {
         const bool lines = t >= P.n_list;
@@ -340,18 +291,11 @@ k_lm_apply_lba(ApplyKind P, ApplyKind L, double th, int32_t* __restrict__ cnt, P
     count_and_publish<2>(ok, cnt, pub);
 }
 
-bool kind_ok(const plslam_map_landmarks& L)
-{
-    return L.n >= 0 && L.n_obs >= 0 && L.n_obs < (1 << 30) && L.n_feat >= 0 &&
-           (L.n == 0 || (L.valid && L.inlier && L.X && L.obs_ptr)) && (L.n_obs == 0 || (L.n > 0 && L.obs_kf && L.obs_val)) &&
-           (L.n_feat == 0 || (L.feat_ptr && L.feat_idx));
-}
 bool map_ok(const plslam_map_index* m)
 {
-    return m && m->n_map_kf >= 1 && m->kf_valid && m->x_kf_w && kind_ok(m->points) && kind_ok(m->lines) &&
+    return m && m->n_map_kf >= 1 && m->kf_valid && m->x_kf_w && map_src_kind_ok(m->points) && map_src_kind_ok(m->lines) &&
            6 * (int64_t)m->n_map_kf + 3 * (int64_t)m->points.n + 6 * (int64_t)m->lines.n < (int64_t)1 << 31;
 }
-unsigned tiles(int64_t n) { return (unsigned)(n > 0 ? (n + LM_NT - 1) / LM_NT : 1); }
 
 }  // namespace
 }  // namespace plslam
@@ -389,7 +333,7 @@ int lm_layout(plslam_local_map* lm, const plslam_map_index* m)
     for (int k = 0; k < 3; ++k) o_col[k] = c.take(op * 4);
     for (int k = 3; k < 6; ++k) o_col[k] = c.take(ol * 4);
     const size_t o_puv = c.take(op * 16), o_llo = c.take(ol * 24), o_x = c.take((6 * nk + 3 * np + 6 * nl) * 8);
-    const size_t wk = tiles((int64_t)nk), wp = tiles((int64_t)np), wl = tiles((int64_t)nl);
+    const size_t wk = map_tiles((int64_t)nk), wp = map_tiles((int64_t)np), wl = map_tiles((int64_t)nl);
     const size_t part_words = wk + 2 * wp + 2 * wl, o_part = c.take(part_words * 4);
     int rc = lm->buf.reserve(c.off + 256);
     if (rc) return rc;
@@ -438,13 +382,7 @@ int plslam_local_map_create(plslam_ctx* ctx, plslam_local_map** out)
 void plslam_local_map_destroy(plslam_local_map* lm)
 {
     if (!lm) return;
-    {
-        std::lock_guard<std::mutex> lk(lm->ctx->mu);
-        DeviceGuard dg_(lm->ctx->device);
-        (void)hipStreamSynchronize(lm->ctx->stream);
-        lm->buf.release();
-        lm->pin.release();
-    }
+    release_handle_buffers(lm->ctx, lm->buf, lm->pin);
     delete lm;
 }
 
@@ -465,15 +403,15 @@ int plslam_local_map_form(plslam_local_map* lm, const plslam_map_index* map, int
     memcpy(h + C_WORDS, row, (size_t)nk * 4);
     PLSLAM_HIP_CHECK(hipMemsetAsync(lm->d.kf_local, 0, lm->zero_bytes, s));
     PLSLAM_HIP_CHECK(hipMemcpyAsync(lm->row, h + C_WORDS, (size_t)nk * 4, hipMemcpyHostToDevice, s));
-    const KindD P = kind_d(map->points, 0), L = kind_d(map->lines, 1);
-    hipLaunchKernelGGL(k_lm_kf_flags, dim3(tiles(nk)), dim3(LM_NT), 0, s, nk, anchor_kf, map->kf_valid, (const int32_t*)lm->row,
+    const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
+    hipLaunchKernelGGL(k_lm_kf_flags, dim3(map_tiles(nk)), dim3(MAP_TILE), 0, s, nk, anchor_kf, map->kf_valid, (const int32_t*)lm->row,
                        min_lm_cov_graph, min_kf_local_map, lm->d.kf_local);
     const int64_t nfeat = (int64_t)P.n_feat + L.n_feat;
     if (nfeat > 0)
-        hipLaunchKernelGGL(k_lm_feat_flags, dim3(tiles(nfeat)), dim3(LM_NT), 0, s, nk, (const uint8_t*)lm->d.kf_local, P, L,
+        hipLaunchKernelGGL(k_lm_feat_flags, dim3(map_tiles(nfeat)), dim3(MAP_TILE), 0, s, nk, (const uint8_t*)lm->d.kf_local, P, L,
                            lm->d.pt_local, lm->d.ls_local);
     const Publish pub{lm->cnt + C_FORM_DONE, lm->cnt, (int32_t*)lm->pin.dev, 3};
-    hipLaunchKernelGGL(k_lm_count_flags, dim3(tiles((int64_t)nk + P.n + L.n)), dim3(LM_NT), 0, s, (const uint8_t*)lm->d.kf_local, nk,
+    hipLaunchKernelGGL(k_lm_count_flags, dim3(map_tiles((int64_t)nk + P.n + L.n)), dim3(MAP_TILE), 0, s, (const uint8_t*)lm->d.kf_local, nk,
                        (const uint8_t*)lm->d.pt_local, P.n, (const uint8_t*)lm->d.ls_local, L.n, lm->cnt, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -492,10 +430,10 @@ int plslam_local_map_candidates(plslam_local_map* lm, const plslam_map_index* ma
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
     PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
-    const KindD P = kind_d(map->points, 0), L = kind_d(map->lines, 1);
+    const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
     if ((int64_t)P.n + L.n == 0) return PLSLAM_OK;
     StreamSyncOnError guard(s);
-    hipLaunchKernelGGL(k_lm_candidates, dim3(tiles((int64_t)P.n + L.n)), dim3(LM_NT), 0, s, P, L, (const uint8_t*)lm->d.pt_local,
+    hipLaunchKernelGGL(k_lm_candidates, dim3(map_tiles((int64_t)P.n + L.n)), dim3(MAP_TILE), 0, s, P, L, (const uint8_t*)lm->d.pt_local,
                        (const uint8_t*)lm->d.ls_local, kf2_idx, lm->d.pt_candidate, lm->d.ls_candidate);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -512,20 +450,20 @@ int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, p
     PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
     lm->gathered = lm->applied = false;
     StreamSyncOnError guard(s);
-    const KindD P = kind_d(map->points, 0), L = kind_d(map->lines, 1);
+    const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
     const int32_t nk = map->n_map_kf;
-    const unsigned wk = tiles(nk), wp = tiles(P.n), wl = tiles(L.n);
+    const unsigned wk = map_tiles(nk), wp = map_tiles(P.n), wl = map_tiles(L.n);
     uint32_t *part_k = lm->part, *part_pn = part_k + wk, *part_po = part_pn + wp, *part_ln = part_po + wp, *part_lo = part_ln + wl;
     PLSLAM_HIP_CHECK(hipMemsetAsync(lm->part, 0, lm->part_words * 4, s));
-    hipLaunchKernelGGL(k_lm_compact_kf, dim3(wk), dim3(LM_NT), 0, s, nk, map->kf_valid, (const uint8_t*)lm->d.kf_local, map->x_kf_w,
+    hipLaunchKernelGGL(k_lm_compact_kf, dim3(wk), dim3(MAP_TILE), 0, s, nk, map->kf_valid, (const uint8_t*)lm->d.kf_local, map->x_kf_w,
                        lm->d.kf_list, lm->kf_inv, lm->d.X_aux, lm->cnt, part_k);
-    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wp), dim3(LM_NT), 0, s, P, 0, (const uint8_t*)lm->d.pt_local, lm->d.pt_list, lm->pt_off,
+    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wp), dim3(MAP_TILE), 0, s, P, 0, (const uint8_t*)lm->d.pt_local, lm->d.pt_list, lm->pt_off,
                        lm->d.X_aux, lm->cnt, part_pn, part_po);
-    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wl), dim3(LM_NT), 0, s, L, 1, (const uint8_t*)lm->d.ls_local, lm->d.ls_list, lm->ls_off,
+    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wl), dim3(MAP_TILE), 0, s, L, 1, (const uint8_t*)lm->d.ls_local, lm->d.ls_list, lm->ls_off,
                        lm->d.X_aux, lm->cnt, part_ln, part_lo);
     const ExpandOut op{lm->d.pt_obs, lm->d.pt_lm_loc, lm->d.pt_kf_loc, lm->d.pt_pose_slot, lm->d.pt_obs_uv, lm->d.pt_list, lm->pt_off};
     const ExpandOut ol{lm->d.ls_obs, lm->d.ls_lm_loc, lm->d.ls_kf_loc, lm->d.ls_pose_slot, lm->d.ls_l_obs, lm->d.ls_list, lm->ls_off};
-    hipLaunchKernelGGL(k_lm_expand, dim3(tiles((int64_t)P.n_obs + L.n_obs)), dim3(LM_NT), 0, s, P, L, op, ol, nk,
+    hipLaunchKernelGGL(k_lm_expand, dim3(map_tiles((int64_t)P.n_obs + L.n_obs)), dim3(MAP_TILE), 0, s, P, L, op, ol, nk,
                        (const int32_t*)lm->kf_inv, (const int32_t*)lm->cnt, (int32_t*)lm->pin.dev);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
@@ -547,7 +485,7 @@ int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
     PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
-    const KindD P = kind_d(map->points, 0), L = kind_d(map->lines, 1);
+    const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
     counts->n_pt_removed = counts->n_ls_removed = 0;
     lm->h_cnt[C_PT_REM] = lm->h_cnt[C_LS_REM] = 0;
     if ((int64_t)P.n + L.n == 0) return PLSLAM_OK;
@@ -555,9 +493,10 @@ int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int
     // (the two counts and the ticket: C_PT_REM, C_LS_REM ... C_CULL_DONE are consecutive words)
     PLSLAM_HIP_CHECK(hipMemsetAsync(lm->cnt + C_PT_REM, 0, (C_CULL_DONE - C_PT_REM + 1) * 4, s));
     const Publish pub{lm->cnt + C_CULL_DONE, lm->cnt + C_PT_REM, (int32_t*)lm->pin.dev + C_PT_REM, 2};
-    hipLaunchKernelGGL(k_lm_cull, dim3(tiles((int64_t)P.n + L.n)), dim3(LM_NT), 0, s, P, L, map->n_map_kf, map->kf_valid,
-                       (const uint8_t*)lm->d.pt_local, (const uint8_t*)lm->d.ls_local, max_kf_idx, min_lm_obs, lm->d.pt_removed,
-                       lm->d.ls_removed, lm->cnt + C_PT_REM, pub);
+    hipLaunchKernelGGL(k_lm_cull, dim3(map_tiles((int64_t)P.n + L.n)), dim3(MAP_TILE), 0, s, P, L,
+                       CullKind{map->points.valid, map->points.feat_idx, lm->d.pt_removed},
+                       CullKind{map->lines.valid, map->lines.feat_idx, lm->d.ls_removed}, map->n_map_kf, map->kf_valid,
+                       (const uint8_t*)lm->d.pt_local, (const uint8_t*)lm->d.ls_local, max_kf_idx, min_lm_obs, lm->cnt + C_PT_REM, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
@@ -588,7 +527,7 @@ int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, cons
     const ApplyKind P{lm->d.pt_list, plan->x.Xw, dst->pt_X, dst->pt_inlier, lm->d.pt_moved, npt_l, lm->npt};
     const ApplyKind L{lm->d.ls_list, plan->x.Lw, dst->ls_X, dst->ls_inlier, lm->d.ls_moved, nls_l, lm->nls};
     const Publish pub{lm->cnt + C_APPLY_DONE, lm->cnt + C_PT_MOVED, (int32_t*)lm->pin.dev + C_PT_MOVED, 2};
-    hipLaunchKernelGGL(k_lm_apply_lba, dim3(tiles((int64_t)npt_l + nls_l)), dim3(LM_NT), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
+    hipLaunchKernelGGL(k_lm_apply_lba, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
@@ -615,13 +554,10 @@ int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffe
     PLSLAM_REQUIRE((!host->pt_moved && !host->ls_moved) || lm->applied, PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
-    hipStream_t s = lm->ctx->stream;
-    StreamSyncOnError guard(s);
     const plslam_local_map_buffers& d = lm->d;
     const int32_t* c = lm->h_cnt;
     const size_t nkf = (size_t)c[C_NKF], npt = (size_t)c[C_NPT], nls = (size_t)c[C_NLS], po = (size_t)c[C_PT_OBS], lo = (size_t)c[C_LS_OBS];
-    struct Item { void* dst; const void* src; size_t bytes; };
-    const Item items[] = {
+    const DownloadItem items[] = {
         {host->kf_local, d.kf_local, (size_t)lm->n_map_kf}, {host->pt_local, d.pt_local, (size_t)lm->npt},
         {host->ls_local, d.ls_local, (size_t)lm->nls}, {host->pt_candidate, d.pt_candidate, (size_t)lm->npt},
         {host->ls_candidate, d.ls_candidate, (size_t)lm->nls}, {host->pt_removed, d.pt_removed, (size_t)lm->npt},
@@ -631,11 +567,7 @@ int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffe
         {host->ls_lm_loc, d.ls_lm_loc, lo * 4}, {host->ls_kf_loc, d.ls_kf_loc, lo * 4}, {host->ls_pose_slot, d.ls_pose_slot, lo * 4},
         {host->pt_obs_uv, d.pt_obs_uv, po * 16}, {host->ls_l_obs, d.ls_l_obs, lo * 24},
         {host->X_aux, d.X_aux, (6 * nkf + 3 * npt + 6 * nls) * 8}, {host->pt_moved, d.pt_moved, npt}, {host->ls_moved, d.ls_moved, nls}};
-    for (const Item& it : items)
-        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    return PLSLAM_OK;
+    return download_items(items, lm->ctx->stream);
 }
 
 }  // extern "C"

@@ -19,34 +19,17 @@
 
 #include "common.hpp"
 #include "lookback_dev.hpp"
+#include "map_image_dev.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
 namespace {
 
-constexpr int MI_NT = 256;              // lanes per workgroup = items per look-back tile (plslam_amd/map_insert.py: LOOKBACK_TILE)
-constexpr int MI_NW = MI_NT / 64;
 constexpr unsigned MI_MAX_GRID = 4096;  // K66 strides over its items
 // the call counters (device words, mirrored in the page-locked block): four per kind
 enum { W_EV = 0, W_NEW, W_PAIRS, W_OBS, W_KIND = 4, W_WORDS = 8 };
 enum { MODE_KF2KF = 0, MODE_MAP2KF = 1 };
 
-struct SrcD {                           // one landmark kind of the source image
-    int32_t n, n_obs, n_feat, dl, dv;   // dl: doubles per landmark / feature position (3 / 6), dv: doubles per observation (2 / 3)
-    const uint8_t *valid, *inlier;
-    const double* X;
-    const int32_t *obs_ptr, *obs_kf;
-    const double* obs_val;
-    const int32_t *feat_ptr, *feat_idx;
-};
-struct DstD {                           // ... of the destination
-    uint8_t *valid, *inlier;
-    double* X;
-    int32_t *obs_ptr, *obs_kf;
-    double* obs_val;
-    int32_t* feat_idx;
-    int32_t cap, obs_cap;
-};
 struct CallD {                          // one kind's tables and scratch (device), carved from the handle's buffer
     int32_t mode, lines, n_map_kf, kf1, kf2, n_tab, n_prev, n_curr, e_cap;
     const double* T;                    // T_kf1_w, T_kf2_w: 2 x 16
@@ -56,37 +39,6 @@ struct CallD {                          // one kind's tables and scratch (device
     double* ev_dir;
 };
 
-// the length of a landmark's list in the source image, 0 where obs_ptr is not a list inside obs_kf
-__device__ __forceinline__ int32_t old_len(const SrcD& S, int32_t lm)
-{
-    const int32_t b = S.obs_ptr[lm], e = S.obs_ptr[lm + 1];
-    return b >= 0 && e > b && e <= S.n_obs ? e - b : 0;
-}
-// the features of a slot: [f0, f0 + nf) inside feat_idx, empty where feat_ptr is not
-__device__ __forceinline__ void slot_features(const SrcD& S, int32_t kf, int32_t& f0, int32_t& nf)
-{
-    f0 = nf = 0;
-    if (S.n_feat <= 0) return;
-    const int32_t b = S.feat_ptr[kf], e = S.feat_ptr[kf + 1];
-    if (b >= 0 && e > b && e <= S.n_feat) { f0 = b; nf = e - b; }
-}
-// Eigen's normalized(): v / sqrt(squaredNorm) where the squared norm is positive, else v itself; (x^2 + y^2) + z^2
-__device__ __forceinline__ void normalized3(const double v[3], double o[3])
-{
-    const double z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-    if (z > 0.0) {
-        const double s = sqrt(z);
-        o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
-    } else {
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-    }
-}
-// v / v.norm(): no guard (:311)
-__device__ __forceinline__ void over_norm3(const double v[3], double o[3])
-{
-    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    o[0] = v[0] / s; o[1] = v[1] / s; o[2] = v[2] / s;
-}
 // 0.5 * (sP + eP) of a line feature (6 doubles)
 __device__ __forceinline__ void midpoint(const double* __restrict__ se, double m[3])
 {
@@ -95,12 +47,12 @@ __device__ __forceinline__ void midpoint(const double* __restrict__ se, double m
 }
 
 // K63: the event list.  A lane per table entry.
-__global__ void __launch_bounds__(MI_NT)
-k_mi_events(SrcD S, CallD C, uint32_t* __restrict__ part_e, uint32_t* __restrict__ part_n, uint32_t* __restrict__ part_p)
+__global__ void __launch_bounds__(MAP_TILE)
+k_mi_events(MapKindSrc S, CallD C, uint32_t* __restrict__ part_e, uint32_t* __restrict__ part_n, uint32_t* __restrict__ part_p)
 {
-    __shared__ uint32_t s_e[MI_NW], s_n[MI_NW], s_p[MI_NW], s_before_e, s_before_n, s_before_p;
+    __shared__ uint32_t s_e[MAP_NW], s_n[MAP_NW], s_p[MAP_NW], s_before_e, s_before_n, s_before_p;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
-    const int32_t i1 = b * MI_NT + tid;
+    const int32_t i1 = b * MAP_TILE + tid;
     bool ev = false, nw = false;
     int32_t lm = -1, i2 = -1;
     uint32_t pairs = 0;
@@ -125,22 +77,14 @@ k_mi_events(SrcD S, CallD C, uint32_t* __restrict__ part_e, uint32_t* __restrict
     }
     if (ev) pairs = nw ? 1u : (uint32_t)old_len(S, lm);       // (a new landmark's pair: full_graph[kf2][kf1]++)
     const uint64_t me = __ballot(ev), mn = __ballot(nw);
-    uint32_t incl = pairs;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += t;
-    }
+    const uint32_t incl = wave_inclusive_sum(pairs);
     if (lane == 0) { s_e[wv] = (uint32_t)__popcll(me); s_n[wv] = (uint32_t)__popcll(mn); }
     if (lane == 63) s_p[wv] = incl;
-    __syncthreads();
-    uint32_t own_e = 0, in_e = 0, own_n = 0, in_n = 0, own_p = 0, in_p = 0;
-#pragma unroll
-    for (int w = 0; w < MI_NW; ++w) {
-        in_e += w < wv ? s_e[w] : 0u; own_e += s_e[w];
-        in_n += w < wv ? s_n[w] : 0u; own_n += s_n[w];
-        in_p += w < wv ? s_p[w] : 0u; own_p += s_p[w];
-    }
+    __syncthreads();                                            // (one barrier for the three chains)
+    uint32_t own_e, in_e, own_n, in_n, own_p, in_p;
+    waves_before_and_all<MAP_NW>(s_e, wv, in_e, own_e);
+    waves_before_and_all<MAP_NW>(s_n, wv, in_n, own_n);
+    waves_before_and_all<MAP_NW>(s_p, wv, in_p, own_p);
     const uint32_t before_e = lookback_exclusive(part_e, b, own_e, &s_before_e);
     const uint32_t before_n = lookback_exclusive(part_n, b, own_n, &s_before_n);
     const uint32_t before_p = lookback_exclusive(part_p, b, own_p, &s_before_p);
@@ -200,35 +144,21 @@ k_mi_events(SrcD S, CallD C, uint32_t* __restrict__ part_e, uint32_t* __restrict
 
 // K64: obs_ptr of the destination (an exclusive look-back scan of the new list lengths over n + n_new landmarks) and the
 // landmark rows: valid / inlier / X copied; a new landmark is valid, an inlier and X = T_kf1_w P (:297, :445-448).
-__global__ void __launch_bounds__(MI_NT)
-k_mi_ptr(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
+__global__ void __launch_bounds__(MAP_TILE)
+k_mi_ptr(MapKindSrc S, MapKindDst D, CallD C, uint32_t* __restrict__ part)
 {
-    __shared__ uint32_t s_o[MI_NW], s_before;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x;
-    const int32_t i = b * MI_NT + tid;
+    __shared__ uint32_t s_o[MAP_NW], s_before;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
+    const int32_t i = b * MAP_TILE + tid;
     int32_t n_new = C.cnt[W_NEW];
     if (n_new > D.cap - S.n) n_new = D.cap - S.n;
     const int32_t n2 = S.n + (n_new > 0 ? n_new : 0);
     uint32_t c = 0;
     if (i < S.n) c = (uint32_t)(old_len(S, i) + C.app_cnt[i]);
     else if (i < n2) c = 2u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_o[wv] = incl;
-    __syncthreads();
-    uint32_t own = 0, in = 0;
-#pragma unroll
-    for (int w = 0; w < MI_NW; ++w) {
-        in += w < wv ? s_o[w] : 0u;
-        own += s_o[w];
-    }
-    const uint32_t before = lookback_exclusive(part, b, own, &s_before);
+    const TileScan sc = lookback_offset<MAP_NW>(c, part, b, s_o, &s_before);
     if (i < n2) {
-        D.obs_ptr[i] = (int32_t)(before + in + incl - c);
+        D.obs_ptr[i] = (int32_t)sc.pos;
         if (i < S.n) {
             D.valid[i] = S.valid[i];
             D.inlier[i] = S.inlier[i];
@@ -242,8 +172,8 @@ k_mi_ptr(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
         }
     }
     if (b == (int)gridDim.x - 1 && tid == 0) {
-        D.obs_ptr[n2] = (int32_t)(before + own);
-        C.cnt[W_OBS] = (int32_t)(before + own);
+        D.obs_ptr[n2] = (int32_t)sc.upto;
+        C.cnt[W_OBS] = (int32_t)sc.upto;
     }
 }
 
@@ -251,10 +181,10 @@ k_mi_ptr(SrcD S, DstD D, CallD C, uint32_t* __restrict__ part)
 // lists share an offset with their successor: the last one at or below the lane owns it); inside the landmark's list the old
 // entries come first, verbatim, then the events' in event order: the k-th event that names the landmark, counted from the
 // landmark's first event (the atomics of K63 gave the count and the first event; the ORDER is the event list's).
-__global__ void __launch_bounds__(MI_NT)
-k_mi_obs(SrcD S, DstD D, CallD C)
+__global__ void __launch_bounds__(MAP_TILE)
+k_mi_obs(MapKindSrc S, MapKindDst D, CallD C)
 {
-    const int64_t t = (int64_t)blockIdx.x * MI_NT + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
     const int32_t total = C.cnt[W_OBS], n_ev = C.cnt[W_EV];
     int32_t n_new = C.cnt[W_NEW];
     if (n_new > D.cap - S.n) n_new = D.cap - S.n;
@@ -293,15 +223,15 @@ k_mi_obs(SrcD S, DstD D, CallD C)
 // a feature of keyframe 1 whose event made a landmark takes that landmark (its only writer); every other feature is copied.
 // A pair adds 1 to row_delta[the observing keyframe] unless that is keyframe 2 (:345, :508, :622, :742) -- int32 adds, exact in
 // any order; a new landmark's single pair is keyframe 1 (:320-321).
-__global__ void __launch_bounds__(MI_NT)
-k_mi_feat_rows(SrcD S, DstD D, CallD C, int32_t* __restrict__ row_delta)
+__global__ void __launch_bounds__(MAP_TILE)
+k_mi_feat_rows(MapKindSrc S, MapKindDst D, CallD C, int32_t* __restrict__ row_delta)
 {
     const int32_t n_ev = C.cnt[W_EV];
-    const int64_t n_items = (int64_t)S.n_feat + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * MI_NT;
+    const int64_t n_items = (int64_t)S.n_feat + C.cnt[W_PAIRS], stride = (int64_t)gridDim.x * MAP_TILE;
     int32_t f1_0, nf1, f2_0, nf2;
     slot_features(S, C.kf2, f2_0, nf2);
     slot_features(S, C.kf1, f1_0, nf1);
-    for (int64_t t = (int64_t)blockIdx.x * MI_NT + threadIdx.x; t < n_items; t += stride) {
+    for (int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x; t < n_items; t += stride) {
         if (t < S.n_feat) {
             const int32_t f = (int32_t)t;
             int32_t v = S.feat_idx[f];
@@ -326,36 +256,18 @@ k_mi_feat_rows(SrcD S, DstD D, CallD C, int32_t* __restrict__ row_delta)
 }
 
 // K67: the call's last kernel: the counters and row_delta to the page-locked block
-__global__ void __launch_bounds__(MI_NT)
+__global__ void __launch_bounds__(MAP_TILE)
 k_mi_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ row_delta, int32_t n_map_kf, int32_t* __restrict__ pinned)
 {
-    for (int32_t i = (int32_t)threadIdx.x; i < W_WORDS + n_map_kf; i += MI_NT) pinned[i] = i < W_WORDS ? cnt[i] : row_delta[i - W_WORDS];
+    for (int32_t i = (int32_t)threadIdx.x; i < W_WORDS + n_map_kf; i += MAP_TILE) pinned[i] = i < W_WORDS ? cnt[i] : row_delta[i - W_WORDS];
 }
 
-bool src_kind_ok(const plslam_map_landmarks& L)
-{
-    return L.n >= 0 && L.n_obs >= 0 && L.n_obs < (1 << 30) && L.n_feat >= 0 &&
-           (L.n == 0 || (L.valid && L.inlier && L.X && L.obs_ptr)) && (L.n_obs == 0 || (L.n > 0 && L.obs_kf && L.obs_val)) &&
-           (L.n_feat == 0 || (L.feat_ptr && L.feat_idx));
-}
-bool dst_kind_ok(const plslam_map_landmarks& D, const plslam_map_landmarks& S)
-{
-    const void* d[] = {D.valid, D.inlier, D.X, D.obs_ptr, D.obs_kf, D.obs_val, D.feat_idx};
-    const void* s[] = {S.valid, S.inlier, S.X, S.obs_ptr, S.obs_kf, S.obs_val, S.feat_idx, S.feat_ptr};
-    for (const void* p : d) {
-        if (!p) return false;
-        for (const void* q : s)
-            if (p == q) return false;
-    }
-    return D.feat_ptr != nullptr;
-}
 bool kind_args_ok(const plslam_map_insert_kind* k, int mode)
 {
     if (!k || !k->table || k->n_table == 0) return !k || k->n_table >= 0;
     if (k->n_table < 0 || k->n_curr < 0 || (k->n_curr > 0 && (!k->P2 || !k->obs2))) return false;
     return mode == MODE_MAP2KF || (k->n_prev >= 0 && (k->n_prev == 0 || (k->P1 && k->obs1)));
 }
-unsigned tiles(int64_t n) { return (unsigned)(n > 0 ? (n + MI_NT - 1) / MI_NT : 1); }
 
 }  // namespace
 }  // namespace plslam
@@ -387,12 +299,12 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
 {
     // ---- validate everything, then commit once ----
     PLSLAM_REQUIRE(mi && src && dst && T2 && row_delta && counts && (mode == MODE_MAP2KF || T1), PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(src->n_map_kf >= 1 && src->kf_valid && src->x_kf_w && src_kind_ok(src->points) && src_kind_ok(src->lines),
+    PLSLAM_REQUIRE(src->n_map_kf >= 1 && src->kf_valid && src->x_kf_w && map_src_kind_ok(src->points) && map_src_kind_ok(src->lines),
                    PLSLAM_EINVAL);
     PLSLAM_REQUIRE(kf2 >= 0 && kf2 < src->n_map_kf && (mode == MODE_MAP2KF || (kf1 >= 0 && kf1 < src->n_map_kf && kf1 != kf2)),
                    PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(dst->map.kf_valid && dst->map.x_kf_w && dst_kind_ok(dst->map.points, src->points) &&
-                       dst_kind_ok(dst->map.lines, src->lines) && kind_args_ok(points, mode) && kind_args_ok(lines, mode),
+    PLSLAM_REQUIRE(dst->map.kf_valid && dst->map.x_kf_w && map_dst_kind_ok(dst->map.points, src->points) &&
+                       map_dst_kind_ok(dst->map.lines, src->lines) && kind_args_ok(points, mode) && kind_args_ok(lines, mode),
                    PLSLAM_EINVAL);
     const plslam_map_landmarks* S[2] = {&src->points, &src->lines};
     const int32_t cap[2] = {dst->pt_cap, dst->ls_cap}, obs_cap[2] = {dst->pt_obs_cap, dst->ls_obs_cap};
@@ -418,7 +330,7 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
     const size_t o_cnt = c.take(W_WORDS * 4), o_row = c.take((size_t)nk * 4);
     for (int k = 0; k < 2; ++k) {
         KindPlan& P = K[k];
-        P.w_tab = tiles(P.n_tab); P.w_lm = tiles((int64_t)S[k]->n + P.m);
+        P.w_tab = map_tiles(P.n_tab); P.w_lm = map_tiles((int64_t)S[k]->n + P.m);
         P.o_app = c.take((size_t)S[k]->n * 4 + 4); P.o_win = c.take((size_t)P.n_curr * 4 + 4);
         P.o_part = c.take((3 * (size_t)P.w_tab + P.w_lm) * 4);
     }
@@ -483,9 +395,8 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         plslam_map_landmarks& B = *Dk[k];
         if (A.n_feat > 0 && B.feat_ptr != A.feat_ptr)
             PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)B.feat_ptr, A.feat_ptr, ((size_t)nk + 1) * 4, hipMemcpyDeviceToDevice, s));
-        const SrcD Sd{A.n, A.n_obs, A.n_feat, P.dl, P.dv, A.valid, A.inlier, A.X, A.obs_ptr, A.obs_kf, A.obs_val, A.feat_ptr, A.feat_idx};
-        const DstD Dd{B.valid, (uint8_t*)B.inlier, (double*)B.X, (int32_t*)B.obs_ptr, (int32_t*)B.obs_kf, (double*)B.obs_val, B.feat_idx,
-                      cap[k], obs_cap[k]};
+        const MapKindSrc Sd = map_kind_src(A, k);
+        const MapKindDst Dd = map_kind_dst(B, cap[k], obs_cap[k]);
         CallD C{};
         C.mode = mode; C.lines = k; C.n_map_kf = nk; C.kf1 = mode == MODE_KF2KF ? kf1 : -1; C.kf2 = kf2;
         C.n_tab = P.n_tab; C.n_prev = P.n_prev; C.n_curr = P.n_curr; C.e_cap = P.m;
@@ -496,16 +407,16 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         C.new_ev = (int32_t*)(d + P.o_new); C.app_cnt = (int32_t*)(d + P.o_app); C.head = (int32_t*)(d + P.o_head);
         C.feat_win = (int32_t*)(d + P.o_win); C.cnt = cnt + W_KIND * k; C.ev_dir = (double*)(d + P.o_dir);
         uint32_t* part = (uint32_t*)(d + P.o_part);
-        hipLaunchKernelGGL(k_mi_events, dim3(P.w_tab), dim3(MI_NT), 0, s, Sd, C, part, part + P.w_tab, part + 2 * P.w_tab);
-        hipLaunchKernelGGL(k_mi_ptr, dim3(P.w_lm), dim3(MI_NT), 0, s, Sd, Dd, C, part + 3 * P.w_tab);
+        hipLaunchKernelGGL(k_mi_events, dim3(P.w_tab), dim3(MAP_TILE), 0, s, Sd, C, part, part + P.w_tab, part + 2 * P.w_tab);
+        hipLaunchKernelGGL(k_mi_ptr, dim3(P.w_lm), dim3(MAP_TILE), 0, s, Sd, Dd, C, part + 3 * P.w_tab);
         const int64_t n_out = (int64_t)A.n_obs + (mode == MODE_KF2KF ? 2 : 1) * (int64_t)P.m;
-        if (n_out > 0) hipLaunchKernelGGL(k_mi_obs, dim3(tiles(n_out)), dim3(MI_NT), 0, s, Sd, Dd, C);
-        const unsigned g = tiles((int64_t)A.n_feat + A.n_obs + P.m);
-        hipLaunchKernelGGL(k_mi_feat_rows, dim3(g < MI_MAX_GRID ? g : MI_MAX_GRID), dim3(MI_NT), 0, s, Sd, Dd, C, row);
+        if (n_out > 0) hipLaunchKernelGGL(k_mi_obs, dim3(map_tiles(n_out)), dim3(MAP_TILE), 0, s, Sd, Dd, C);
+        const unsigned g = map_tiles((int64_t)A.n_feat + A.n_obs + P.m);
+        hipLaunchKernelGGL(k_mi_feat_rows, dim3(g < MI_MAX_GRID ? g : MI_MAX_GRID), dim3(MAP_TILE), 0, s, Sd, Dd, C, row);
         (k ? mi->d.ls_ev : mi->d.pt_ev) = C.ev;
         (k ? mi->d.ls_dir : mi->d.pt_dir) = C.ev_dir;
     }
-    hipLaunchKernelGGL(k_mi_publish, dim3(1), dim3(MI_NT), 0, s, (const int32_t*)cnt, (const int32_t*)row, nk, (int32_t*)mi->pin.dev);
+    hipLaunchKernelGGL(k_mi_publish, dim3(1), dim3(MAP_TILE), 0, s, (const int32_t*)cnt, (const int32_t*)row, nk, (int32_t*)mi->pin.dev);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
@@ -541,13 +452,7 @@ int plslam_map_insert_create(plslam_ctx* ctx, plslam_map_insert** out)
 void plslam_map_insert_destroy(plslam_map_insert* mi)
 {
     if (!mi) return;
-    {
-        std::lock_guard<std::mutex> lk(mi->ctx->mu);
-        DeviceGuard dg_(mi->ctx->device);
-        (void)hipStreamSynchronize(mi->ctx->stream);
-        mi->buf.release();
-        mi->pin.release();
-    }
+    release_handle_buffers(mi->ctx, mi->buf, mi->pin);
     delete mi;
 }
 
@@ -577,16 +482,9 @@ int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_ev
     PLSLAM_REQUIRE(mi && host && mi->done, PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(mi->ctx->mu);
     DeviceGuard dg_(mi->ctx->device);
-    hipStream_t s = mi->ctx->stream;
-    StreamSyncOnError guard(s);
-    struct Item { void* dst; const void* src; size_t bytes; };
-    const Item items[] = {{host->pt_ev, mi->d.pt_ev, (size_t)mi->n_ev[0] * 16}, {host->pt_dir, mi->d.pt_dir, (size_t)mi->n_ev[0] * 48},
-                          {host->ls_ev, mi->d.ls_ev, (size_t)mi->n_ev[1] * 16}, {host->ls_dir, mi->d.ls_dir, (size_t)mi->n_ev[1] * 48}};
-    for (const Item& it : items)
-        if (it.dst && it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    return PLSLAM_OK;
+    const DownloadItem items[] = {{host->pt_ev, mi->d.pt_ev, (size_t)mi->n_ev[0] * 16}, {host->pt_dir, mi->d.pt_dir, (size_t)mi->n_ev[0] * 48},
+                                  {host->ls_ev, mi->d.ls_ev, (size_t)mi->n_ev[1] * 16}, {host->ls_dir, mi->d.ls_dir, (size_t)mi->n_ev[1] * 48}};
+    return download_items(items, mi->ctx->stream);
 }
 
 }  // extern "C"

@@ -11,10 +11,9 @@ import ctypes as C
 import numpy as np
 
 from .capi import Context, _check, _p
-from .local_map import FEAT_NULL
-from .map_insert import DeviceMapImage
+from .local_map import FEAT_NULL, LOOKBACK_TILE  # noqa: F401 (LOOKBACK_TILE: for the case tables)
+from .map_insert import DeviceMapImage, _pose
 
-LOOKBACK_TILE = 256       # plslam_amd/csrc/lc_fuse.hip: LF_NT, the items one workgroup of the obs_ptr scan takes
 MAX_TUPLES = 65536        # include/plslam_hip.h: PLSLAM_LC_FUSE_MAX_TUPLES
 MAX_LEVEL = 64            # include/plslam_hip.h: PLSLAM_LC_FUSE_MAX_LEVEL
 
@@ -128,15 +127,6 @@ class LcFuse:
 
 
 # ---- the seeded generators ----------------------------------------------------------------------------------------------------
-def _pose(rng):
-    q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
-    if np.linalg.det(q) < 0:
-        q[:, 0] = -q[:, 0]
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = q, rng.uniform(-2.0, 2.0, 3)
-    return T
-
-
 def pack_loop_closure(m, lc_idx, points=None, lines=None, seed=1) -> dict:
     """explicit tuples -> the call's arguments.  lc_idx: rows (kf_prev, kf_curr, flag); points / lines: per entry a list of
     tuples (lm_idx0, lm_ldx0, lm_idx1, lm_ldx1), or None for no tuple of the kind.  The features' values (P0, obs0, P1, obs1) and

@@ -12,9 +12,8 @@ import ctypes as C
 import numpy as np
 
 from .capi import Context, _check, _p
-from .local_map import FEAT_NULL, DeviceMapIndex, MapIndex
+from .local_map import FEAT_NULL, LOOKBACK_TILE, DeviceMapIndex, MapIndex  # noqa: F401 (LOOKBACK_TILE: for the case tables)
 
-LOOKBACK_TILE = 256       # plslam_amd/csrc/map_insert.hip: MI_NT, the items one workgroup of a scan takes
 MAX_TABLE = 65536         # include/plslam_hip.h: PLSLAM_MAP_INSERT_MAX_TABLE
 
 _vp, _i32 = C.c_void_p, C.c_int32

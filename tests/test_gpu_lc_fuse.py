@@ -82,8 +82,11 @@ def test_cases_equal_the_restatement(ctx, name):
 def test_the_tile_the_cases_are_built_around_is_the_kernels():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "csrc", "lc_fuse.hip")).read()
-    assert int(re.search(r"constexpr int LF_NT = (\d+);", src).group(1)) == LF.LOOKBACK_TILE == CS.T
+    import local_map_cases
+    import map_insert_cases
+    src = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "csrc", "map_image_dev.hpp")).read()
+    tile = int(re.search(r"constexpr int MAP_TILE = (\d+);", src).group(1))
+    assert tile == LM.LOOKBACK_TILE == MI.LOOKBACK_TILE == LF.LOOKBACK_TILE == CS.T == map_insert_cases.T == local_map_cases.T
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "..", "include", "plslam_hip.h")).read()
     assert int(re.search(r"#define PLSLAM_LC_FUSE_MAX_LEVEL (\d+)", hdr).group(1)) == LF.MAX_LEVEL == CS.L
     assert int(re.search(r"#define PLSLAM_LC_FUSE_MAX_TUPLES (\d+)", hdr).group(1)) == LF.MAX_TUPLES

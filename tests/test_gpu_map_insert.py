@@ -78,8 +78,12 @@ def test_cases_equal_the_restatement(ctx, name):
 def test_the_tile_the_cases_are_built_around_is_the_kernels():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(MI.__file__)), "csrc", "map_insert.hip")).read()
-    assert int(re.search(r"constexpr int MI_NT = (\d+);", src).group(1)) == MI.LOOKBACK_TILE == CS.T
+    import lc_fuse_cases
+    import local_map_cases
+    from plslam_amd import lc_fuse as LF
+    src = open(os.path.join(os.path.dirname(os.path.abspath(MI.__file__)), "csrc", "map_image_dev.hpp")).read()
+    tile = int(re.search(r"constexpr int MAP_TILE = (\d+);", src).group(1))
+    assert tile == LM.LOOKBACK_TILE == MI.LOOKBACK_TILE == LF.LOOKBACK_TILE == CS.T == lc_fuse_cases.T == local_map_cases.T
 
 
 def test_two_hundred_thousand_landmarks(ctx):

@@ -125,6 +125,39 @@ struct Carver {
     size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
 };
 
+// an array inside a carved buffer: where it starts and how many bytes of it are data (what an upload or a download copies;
+// the slack the carving leaves behind it is not counted)
+template <class T>
+struct Arr {
+    T* p = nullptr;
+    size_t bytes = 0;
+    operator T*() const { return p; }
+};
+
+// carves arrays out of the block at `base` in the order they are taken (Carver's alignment); base = nullptr: only the
+// total is wanted (the buffer is reserved after its size is known, and carved again over its address)
+struct ArrCarver {
+    char* base;
+    Carver c{};
+    size_t size() const { return c.off; }
+    template <class T> Arr<T> take(size_t bytes, size_t slack = 0) { return {reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + c.take(bytes + slack)), bytes}; }
+};
+
+// The upload of a plan's host-built lists into its carved arrays: each array's data bytes from the host vector behind it,
+// enqueued on s (nothing is waited for).  The caller holds the context's lock and has selected its device.
+struct UploadItem {
+    void* dst;
+    size_t bytes;
+    const void* src;
+    template <class T> UploadItem(const Arr<T>& a, const void* host) : dst(a.p), bytes(a.bytes), src(host) {}
+};
+template <size_t N> int upload_items(const UploadItem (&items)[N], hipStream_t s)
+{
+    for (const UploadItem& it : items)
+        if (it.bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(it.dst, it.src, it.bytes, hipMemcpyHostToDevice, s));
+    return PLSLAM_OK;
+}
+
 }  // namespace plslam
 
 struct plslam_ctx {
@@ -158,7 +191,7 @@ struct plslam_ctx {
     plslam::DevBuf lc_args;                         // plslam_relpose_robust_gn_batched_dev: K54's argument table
     std::vector<char> lc_args_h;                    // ... and its host image (pageable: staged by the copy call itself)
     int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
-    plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (pgo.hip)
+    plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (lc_correct.hip)
 };
 
 namespace plslam {

@@ -12,40 +12,38 @@
 //                              chunk's sum of W_o1^T Y_o2, pair after pair
 //   K30 k_gba_blocks           a workgroup per covisible block (k1 >= k2): S(k1,k2) = [H_pose + lambda diag]delta - chunk sums
 //   K31 k_gba_rhs              a workgroup per keyframe: b_k = g_k - sum_o W_o^T t_lm(o)
-//   K32 k_ldlt_diag            one workgroup: L D L^T of the 32 x 32 diagonal tile (pivots that are zero / not finite counted)
-//   K33 k_ldlt_panel           a workgroup per row tile below it: L_ik = A_ik L_kk^-T D^-1 (and X_ik = L_ik D kept)
-//   K34 k_ldlt_update          a workgroup per lower tile of the trailing matrix: A_ij -= X_ik L_jk^T on v_mfma_f64_16x16x4_f64
-//   K35 k_ldlt_fwd             per tile column: L y = b (+ the D scaling), the rows below updated in parallel
-//   K36 k_ldlt_bwd             per tile row, last first: L^T x = z, the rows above updated in parallel
+//   K32-K36                    the dense blocked L D L^T of S and its triangular solves: ldlt_dense.hip, through ldlt_dense.hpp
 //   K37 k_gba_backsub<DL>      a lane per landmark: dxj = Vj'^-1 (gj - sum_o W_o dp[kf(o)]), X += dx when the step is taken
 //   K38 k_gba_pose             a lane per optimised keyframe: x <- logmap(expmap(x) inverse(expmap(dp))), its estimate slot
 //   K39 k_gba_stats            ||DX||^2 over all N unknowns, singular landmarks, bad pivots: 24 bytes for the host
 // Every sum has a fixed shape (no floating-point atomics): two runs give the same bits.  Phases are ordered by kernel
 // boundaries only -- no grid barrier, no device-scope fence.
+//
+// The lists the kernels walk are host work (gba_lists.hpp).  The plan's buffers are named ONCE: each is carved in one function
+// (carve_stat, carve_work), which fills a view of typed pointers with the bytes behind each; every launch site, upload and
+// download reads the views.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <vector>
 
 #include "common.hpp"
+#include "gba_lists.hpp"
+#include "ldlt_dense.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
 namespace {
 
-constexpr int GBA_CHUNK = 64;   // observation pairs per chunk of K29
-constexpr int LT = 32;          // LDL^T tile edge
-typedef double dvec4_t __attribute__((ext_vector_type(4)));
+// the host lists hold pairs of int32 (gba_lists.hpp has no HIP type); K29 reads the same bytes as int2
+static_assert(sizeof(GbaPair) == sizeof(int2) && alignof(GbaPair) <= alignof(int2), "GbaPair is uploaded as int2");
 
 struct GbaStats {               // what crosses to the host per solve
     double dx_sumsq;
     int32_t n_singular, n_bad_pivots;
 };
-struct GbaBlock { int32_t k1, k2, c0, c1; };          // covisible block (k1 >= k2) and its chunk range
-struct GbaChunk { int32_t blk, line, p0, np; };       // chunk: block, kind (1 = lines), first pair, pair count
 
 // ---- K26 ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -206,14 +204,6 @@ k_gba_blocks(const GbaBlock* __restrict__ blocks, const double* __restrict__ par
     S[(6 * (int64_t)B.k1 + a) * ld + 6 * (int64_t)B.k2 + b] = v;
 }
 
-// the padding of the matrix beyond n: identity, so that every tile is full
-__global__ void __launch_bounds__(256)
-k_pad_diag(double* __restrict__ S, int64_t ld, int32_t n, int32_t npad)
-{
-    const int i = n + blockIdx.x * 256 + threadIdx.x;
-    if (i < npad) S[(int64_t)i * ld + i] = 1.0;
-}
-
 // ---- K31: b_k = g_k - sum over the keyframe's observations of W_o^T t_lm(o) ---------------------------------------------------
 template <int DL>
 __device__ __forceinline__ void gba_rhs_term(const double* __restrict__ W, const double* __restrict__ tv, int o, int j, double (&acc)[6])
@@ -252,8 +242,6 @@ k_gba_rhs(const int32_t* __restrict__ kp_ptr, const int32_t* __restrict__ kp_obs
     }
     if (i < 6) b[6 * (size_t)k + i] = g[6 * (size_t)k + i] - red[i][0];
 }
-
-#include "ldlt_dense_dev.hpp"
 
 // ---- K37: landmark steps ----------------------------------------------------------------------------------------------------
 template <int DL>
@@ -366,6 +354,24 @@ k_gba_stats(const double* __restrict__ part, int32_t npart, const int32_t* __res
     }
 }
 
+struct GbaStatView {               // `stat`: the lists of gba_lists.hpp -- uploaded once
+    Arr<GbaBlock> blk;
+    Arr<GbaChunk> chk;
+    Arr<int2> pair;
+    Arr<int32_t> plm, pkf, llm, lkf;                  // per observation: landmark, optimised keyframe
+    Arr<int32_t> kpp, kpo, klp, klo;                  // keyframe -> observations (points, lines)
+    Arr<int32_t> lpp, lpo, llp, llo;                  // landmark -> observations by optimised keyframes (points, lines)
+};
+struct GbaWorkView {               // `work`: what a solve computes
+    Arr<double> Vp, tp, Vl, tl;                       // landmark inverses and Vj'^-1 gj (points, lines)
+    Arr<int32_t> sing, sing_pt, sing_ls;              // singular flags: sing = the points' directly followed by the lines'
+    Arr<double> Yp, Yl, part;                         // Y_o; the chunk sums of K29
+    Arr<double> P, w, z, dp;                          // the L D L^T's panel, b, z and the pose steps
+    Arr<int32_t> bad;                                 // bad pivots per tile
+    Arr<double> ss_part;                              // partials of ||DX||^2: pose workgroups, point workgroups, line workgroups
+    Arr<GbaStats> stats;
+    Arr<double> hmax, x;                              // K26's result; the pose parameters x_kf
+};
 
 }  // namespace
 }  // namespace plslam
@@ -380,21 +386,73 @@ struct plslam_gba_plan {
     int32_t nblk = 0, nchunk = 0, nt = 0;
     std::vector<int32_t> kf_list;           // map index of optimised keyframe k
     DevBuf stat, work, Sbuf;
-    // static lists (stat)
-    size_t oBlk = 0, oChk = 0, oPair = 0, oPlm = 0, oPkf = 0, oLlm = 0, oLkf = 0, oKpp = 0, oKpo = 0, oKlp = 0, oKlo = 0,
-           oLpp = 0, oLpo = 0, oLlp = 0, oLlo = 0;
-    // per-iteration arrays (work)
-    size_t oVp = 0, oTp = 0, oVl = 0, oTl = 0, oSp = 0, oSl = 0, oYp = 0, oYl = 0, oPart = 0, oP = 0, oW = 0, oZ = 0, oDp = 0,
-           oBad = 0, oSsPart = 0, oStats = 0, oHmax = 0, oX = 0;
-    int32_t nss = 0;                         // partials of ||DX||^2: pose workgroups, point workgroups, line workgroups
+    GbaStatView st;
+    GbaWorkView wk;
+
+    // workgroups of K38 / K37<3> / K37<6>: each leaves one partial of ||DX||^2
+    int nwk() const { return (nkf + 255) / 256; }
+    int nwp() const { return (npt + 255) / 256; }
+    int nwl() const { return (nls + 255) / 256; }
+    void release() { stat.release(); work.release(); Sbuf.release(); }
 };
 
 namespace {
 
+size_t carve_stat(plslam_gba_plan* G, const GbaLists& L, char* base)
+{
+    GbaStatView& v = G->st;
+    ArrCarver c{base};
+    v.blk = c.take<GbaBlock>(L.blks.size() * sizeof(GbaBlock));
+    v.chk = c.take<GbaChunk>(L.chks.size() * sizeof(GbaChunk), 16);
+    v.pair = c.take<int2>(L.pairs.size() * sizeof(int2), 8);
+    v.plm = c.take<int32_t>(L.plm.size() * 4, 4);
+    v.pkf = c.take<int32_t>(L.pkf.size() * 4, 4);
+    v.llm = c.take<int32_t>(L.llm.size() * 4, 4);
+    v.lkf = c.take<int32_t>(L.lkf.size() * 4, 4);
+    v.kpp = c.take<int32_t>(L.kpp.size() * 4);
+    v.kpo = c.take<int32_t>(L.kpo.size() * 4, 4);
+    v.klp = c.take<int32_t>(L.klp.size() * 4);
+    v.klo = c.take<int32_t>(L.klo.size() * 4, 4);
+    v.lpp = c.take<int32_t>(L.lpp.size() * 4);
+    v.lpo = c.take<int32_t>(L.lpo.size() * 4, 4);
+    v.llp = c.take<int32_t>(L.llp.size() * 4);
+    v.llo = c.take<int32_t>(L.llo.size() * 4, 4);
+    return c.size();
+}
+
+size_t carve_work(plslam_gba_plan* G, char* base)
+{
+    GbaWorkView& v = G->wk;
+    ArrCarver c{base};
+    const size_t npt = (size_t)G->npt, nls = (size_t)G->nls, np = (size_t)G->np, nl = (size_t)G->nl, npad = (size_t)G->npad;
+    v.Vp = c.take<double>(npt * 72, 8);
+    v.tp = c.take<double>(npt * 24, 8);
+    v.Vl = c.take<double>(nls * 288, 8);
+    v.tl = c.take<double>(nls * 48, 8);
+    // the one deliberate adjacency: K39 counts the singular landmarks of both kinds in one pass over npt + nls flags, so the
+    // lines' flags directly follow the points'
+    v.sing = c.take<int32_t>((npt + nls) * 4, 8);
+    v.sing_pt = {v.sing.p, npt * 4};
+    v.sing_ls = {v.sing.p + npt, nls * 4};
+    v.Yp = c.take<double>(np * 144, 8);
+    v.Yl = c.take<double>(nl * 288, 8);
+    v.part = c.take<double>((size_t)G->nchunk * 288, 8);
+    v.P = c.take<double>(npad * LT * 8);
+    v.w = c.take<double>(npad * 8);
+    v.z = c.take<double>(npad * 8);
+    v.dp = c.take<double>(npad * 8);
+    v.bad = c.take<int32_t>((size_t)G->nt * 4, 4);
+    v.ss_part = c.take<double>((size_t)(G->nwk() + G->nwp() + G->nwl()) * 8, 8);
+    v.stats = c.take<GbaStats>(sizeof(GbaStats));
+    v.hmax = c.take<double>(8);
+    v.x = c.take<double>((size_t)G->nkf * 48);
+    return c.size();
+}
+
 int gba_fail(plslam_gba_plan* G, int rc)
 {
     if (G->lba) plslam_lba_plan_destroy(G->lba);
-    G->stat.release(); G->work.release(); G->Sbuf.release();
+    G->release();
     delete G;
     return rc;
 }
@@ -406,52 +464,50 @@ int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t
     plslam_lba_state st;
     int rc;
     if ((rc = plslam_lba_plan_device_blocks(G->lba, &B)) || (rc = plslam_lba_plan_device_state(G->lba, &st))) return rc;
-    char* d = G->stat.as<char>();
-    char* wk = G->work.as<char>();
-    auto I32 = [&](size_t o) { return (const int32_t*)(d + o); };
-    auto D = [&](size_t o) { return (double*)(wk + o); };
+    const GbaStatView& l = G->st;
+    const GbaWorkView& w = G->wk;
     double* S = G->Sbuf.as<double>();
     const int32_t nkf = G->nkf, npt = G->npt, nls = G->nls;
     const double* g_pt = B.g + 6 * (size_t)nkf;
     const double* g_ls = g_pt + 3 * (size_t)npt;
     if (npt)
-        hipLaunchKernelGGL(k_gba_landmarks<3>, dim3((npt + 255) / 256), dim3(256), 0, s, B.H_pt, g_pt, npt, lambda, D(G->oVp),
-                           D(G->oTp), (int32_t*)(wk + G->oSp));
+        hipLaunchKernelGGL(k_gba_landmarks<3>, dim3((npt + 255) / 256), dim3(256), 0, s, B.H_pt, g_pt, npt, lambda, w.Vp.p, w.tp.p,
+                           w.sing_pt.p);
     if (nls)
-        hipLaunchKernelGGL(k_gba_landmarks<6>, dim3((nls + 255) / 256), dim3(256), 0, s, B.H_ls, g_ls, nls, lambda, D(G->oVl),
-                           D(G->oTl), (int32_t*)(wk + G->oSl));
+        hipLaunchKernelGGL(k_gba_landmarks<6>, dim3((nls + 255) / 256), dim3(256), 0, s, B.H_ls, g_ls, nls, lambda, w.Vl.p, w.tl.p,
+                           w.sing_ls.p);
     if (G->np)
-        hipLaunchKernelGGL(k_gba_cross<3>, dim3((G->np + 255) / 256), dim3(256), 0, s, I32(G->oPlm), I32(G->oPkf), G->np,
-                           (const double*)D(G->oVp), B.W_pt, D(G->oYp));
+        hipLaunchKernelGGL(k_gba_cross<3>, dim3((G->np + 255) / 256), dim3(256), 0, s, (const int32_t*)l.plm, (const int32_t*)l.pkf,
+                           G->np, (const double*)w.Vp, B.W_pt, w.Yp.p);
     if (G->nl)
-        hipLaunchKernelGGL(k_gba_cross<6>, dim3((G->nl + 255) / 256), dim3(256), 0, s, I32(G->oLlm), I32(G->oLkf), G->nl,
-                           (const double*)D(G->oVl), B.W_ls, D(G->oYl));
+        hipLaunchKernelGGL(k_gba_cross<6>, dim3((G->nl + 255) / 256), dim3(256), 0, s, (const int32_t*)l.llm, (const int32_t*)l.lkf,
+                           G->nl, (const double*)w.Vl, B.W_ls, w.Yl.p);
     PLSLAM_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)G->npad * (size_t)G->npad * 8, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(D(G->oW), 0, (size_t)G->npad * 8, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(w.w, 0, w.w.bytes, s));
     if (G->nchunk)
-        hipLaunchKernelGGL(k_gba_pairs, dim3(G->nchunk), dim3(GBA_CHUNK), 0, s, (const GbaChunk*)(d + G->oChk),
-                           (const int2*)(d + G->oPair), B.W_pt, (const double*)D(G->oYp), B.W_ls, (const double*)D(G->oYl),
-                           D(G->oPart));
-    hipLaunchKernelGGL(k_gba_blocks, dim3(G->nblk), dim3(64), 0, s, (const GbaBlock*)(d + G->oBlk), (const double*)D(G->oPart),
-                       B.H_pose, lambda, S, G->npad);
-    if (G->npad > G->n)
-        hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, G->npad, (int32_t)G->n, (int32_t)G->npad);
-    hipLaunchKernelGGL(k_gba_rhs, dim3(nkf), dim3(64), 0, s, I32(G->oKpp), I32(G->oKpo), I32(G->oKlp), I32(G->oKlo), I32(G->oPlm),
-                       I32(G->oLlm), B.W_pt, (const double*)D(G->oTp), B.W_ls, (const double*)D(G->oTl), B.g, D(G->oW));
-    if ((rc = ldlt_enqueue(S, G->npad, (int32_t)G->n, D(G->oP), D(G->oW), D(G->oZ), D(G->oDp), (int32_t*)(wk + G->oBad), s))) return rc;
-    const int nwp = (npt + 255) / 256, nwl = (nls + 255) / 256, nwk = (nkf + 255) / 256;
-    double* part = D(G->oSsPart);
-    hipLaunchKernelGGL(k_gba_pose, dim3(nwk), dim3(256), 0, s, nkf, (const double*)D(G->oDp), (int32_t)apply, D(G->oX),
+        hipLaunchKernelGGL(k_gba_pairs, dim3(G->nchunk), dim3(GBA_CHUNK), 0, s, (const GbaChunk*)l.chk, (const int2*)l.pair, B.W_pt,
+                           (const double*)w.Yp, B.W_ls, (const double*)w.Yl, w.part.p);
+    hipLaunchKernelGGL(k_gba_blocks, dim3(G->nblk), dim3(64), 0, s, (const GbaBlock*)l.blk, (const double*)w.part, B.H_pose, lambda,
+                       S, G->npad);
+    ldlt_pad_diag_enqueue(S, G->npad, (int32_t)G->n, s);
+    hipLaunchKernelGGL(k_gba_rhs, dim3(nkf), dim3(64), 0, s, (const int32_t*)l.kpp, (const int32_t*)l.kpo, (const int32_t*)l.klp,
+                       (const int32_t*)l.klo, (const int32_t*)l.plm, (const int32_t*)l.llm, B.W_pt, (const double*)w.tp, B.W_ls,
+                       (const double*)w.tl, B.g, w.w.p);
+    if ((rc = ldlt_enqueue(S, G->npad, (int32_t)G->n, w.P, w.w, w.z, w.dp, w.bad, s))) return rc;
+    const int nwp = G->nwp(), nwl = G->nwl(), nwk = G->nwk();
+    double* part = w.ss_part;
+    hipLaunchKernelGGL(k_gba_pose, dim3(nwk), dim3(256), 0, s, nkf, (const double*)w.dp, (int32_t)apply, w.x.p,
                        st.T_kf_w + 16 * (size_t)G->n_map, part);
     if (npt)
-        hipLaunchKernelGGL(k_gba_backsub<3>, dim3(nwp), dim3(256), 0, s, I32(G->oLpp), I32(G->oLpo), I32(G->oPkf), npt, B.W_pt,
-                           (const double*)D(G->oVp), g_pt, (const double*)D(G->oDp), (int32_t)apply, st.Xw, part + nwk);
+        hipLaunchKernelGGL(k_gba_backsub<3>, dim3(nwp), dim3(256), 0, s, (const int32_t*)l.lpp, (const int32_t*)l.lpo,
+                           (const int32_t*)l.pkf, npt, B.W_pt, (const double*)w.Vp, g_pt, (const double*)w.dp, (int32_t)apply, st.Xw,
+                           part + nwk);
     if (nls)
-        hipLaunchKernelGGL(k_gba_backsub<6>, dim3(nwl), dim3(256), 0, s, I32(G->oLlp), I32(G->oLlo), I32(G->oLkf), nls, B.W_ls,
-                           (const double*)D(G->oVl), g_ls, (const double*)D(G->oDp), (int32_t)apply, st.Lw, part + nwk + nwp);
-    // the singular flags of points and lines lie back to back (oSp, oSl carved contiguously)
-    hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)part, nwk + nwp + nwl, (const int32_t*)(wk + G->oSp),
-                       npt + nls, (const int32_t*)(wk + G->oBad), G->nt, (GbaStats*)(wk + G->oStats));
+        hipLaunchKernelGGL(k_gba_backsub<6>, dim3(nwl), dim3(256), 0, s, (const int32_t*)l.llp, (const int32_t*)l.llo,
+                           (const int32_t*)l.lkf, nls, B.W_ls, (const double*)w.Vl, g_ls, (const double*)w.dp, (int32_t)apply, st.Lw,
+                           part + nwk + nwp);
+    hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)part, nwk + nwp + nwl, (const int32_t*)w.sing, npt + nls,
+                       (const int32_t*)w.bad, G->nt, w.stats.p);
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }
@@ -460,6 +516,7 @@ int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t
 
 extern "C" {
 
+// check the arguments the lists do not cover, plan (gba_lists.hpp), carve and upload, return
 int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf, const int32_t* kf_list, int32_t npt, int32_t nls, const int32_t* pt_obs,
                            const double* pt_obs_uv, int32_t n_pt_obs, const int32_t* ls_obs, const double* ls_l_obs,
                            int32_t n_ls_obs, plslam_gba_plan** out)
@@ -475,23 +532,11 @@ int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th
     // 32-bit addressing: observation blocks (DL x 6 doubles each), landmark blocks and pair lists are indexed with int32
     PLSLAM_REQUIRE((int64_t)n_pt_obs * 18 < INT32_MAX && (int64_t)n_ls_obs * 36 < INT32_MAX &&
                    (int64_t)npt * 9 < INT32_MAX && (int64_t)nls * 36 < INT32_MAX, PLSLAM_EINVAL);
-    for (int32_t k = 0; k < nkf; ++k) PLSLAM_REQUIRE(kf_list[k] >= 0 && kf_list[k] < n_map_kf, PLSLAM_EINVAL);
-    std::vector<int32_t> plm(n_pt_obs), pkf(n_pt_obs), pslot(n_pt_obs), llm(n_ls_obs), lkf(n_ls_obs), lslot(n_ls_obs);
-    // Vector6i columns: 0 landmark map index, 1 landmark local index, 2 observation index, 3 keyframe map index, 4 keyframe
-    // local index (-1: keyframe 0, not optimised), 5 inlier flag
-    for (int32_t o = 0; o < n_pt_obs; ++o) {
-        const int32_t* v = pt_obs + 6 * (size_t)o;
-        PLSLAM_REQUIRE(v[1] >= 0 && v[1] < npt && v[3] >= 0 && v[3] < n_map_kf && v[4] >= -1 && v[4] < nkf, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(v[4] < 0 || kf_list[v[4]] == v[3], PLSLAM_EINVAL);
-        plm[o] = v[1]; pkf[o] = v[4];
-        pslot[o] = v[4] >= 0 ? n_map_kf + v[4] : v[3];      // points of optimised keyframes read the estimate (:2411-2416)
-    }
-    for (int32_t o = 0; o < n_ls_obs; ++o) {
-        const int32_t* v = ls_obs + 6 * (size_t)o;
-        PLSLAM_REQUIRE(v[1] >= 0 && v[1] < nls && v[3] >= 0 && v[3] < n_map_kf && v[4] >= -1 && v[4] < nkf, PLSLAM_EINVAL);
-        PLSLAM_REQUIRE(v[4] < 0 || kf_list[v[4]] == v[3], PLSLAM_EINVAL);
-        llm[o] = v[1]; lkf[o] = v[4];
-        lslot[o] = v[3];                                     // lines always read the stored pose (:2523)
+    GbaLists L;
+    int rc = gba_lists_build(n_map_kf, nkf, kf_list, npt, nls, pt_obs, n_pt_obs, ls_obs, n_ls_obs, &L);
+    if (rc) {
+        set_last_error("plslam_gba_plan_create: %s", L.why);
+        return rc;
     }
     plslam_gba_plan* G = new (std::nothrow) plslam_gba_plan();
     PLSLAM_REQUIRE(G != nullptr, PLSLAM_ENOMEM);
@@ -500,115 +545,27 @@ int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th
     G->n = 6 * (int64_t)nkf;
     G->npad = pad_to_tile(G->n);
     G->nt = (int32_t)(G->npad / LT);
-    int rc = plslam_lba_plan_create(ctx, K, homog_th, n_map_kf + nkf, nkf, npt, nls, plm.data(), pslot.data(), pkf.data(),
-                                    pt_obs_uv, n_pt_obs, llm.data(), lslot.data(), lkf.data(), ls_l_obs, n_ls_obs, &G->lba);
+    G->nblk = (int32_t)L.blks.size(); G->nchunk = (int32_t)L.chks.size();
+    rc = plslam_lba_plan_create(ctx, K, homog_th, n_map_kf + nkf, nkf, npt, nls, L.plm.data(), L.pslot.data(), L.pkf.data(),
+                                pt_obs_uv, n_pt_obs, L.llm.data(), L.lslot.data(), L.lkf.data(), ls_l_obs, n_ls_obs, &G->lba);
     if (rc) return gba_fail(G, rc);
-
-    // landmark -> its observations by optimised keyframes, list order; keyframe -> its observations, list order
-    auto csr = [](const std::vector<int32_t>& key, const std::vector<int32_t>& kf, int32_t nkey, std::vector<int32_t>& ptr,
-                  std::vector<int32_t>& ids) {
-        ptr.assign(nkey + 1, 0);
-        for (size_t o = 0; o < key.size(); ++o) if (kf[o] >= 0) ++ptr[key[o] + 1];
-        for (int32_t i = 0; i < nkey; ++i) ptr[i + 1] += ptr[i];
-        ids.assign(ptr[nkey], 0);
-        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (size_t o = 0; o < key.size(); ++o) if (kf[o] >= 0) ids[fill[key[o]]++] = (int32_t)o;
-    };
-    std::vector<int32_t> lpp, lpo, llp, llo, kpp, kpo, klp, klo;
-    csr(plm, pkf, npt, lpp, lpo);
-    csr(llm, lkf, nls, llp, llo);
-    csr(pkf, pkf, nkf, kpp, kpo);
-    csr(lkf, lkf, nkf, klp, klo);
-
-    // covisible blocks: every ordered pair (o1, o2) of a landmark's observations with kf(o1) >= kf(o2) falls in lower block
-    // (kf(o1), kf(o2)); blocks sorted by (k1, k2), a block's point pairs before its line pairs, each in landmark order
-    struct Pr { int64_t key; int32_t line, o1, o2; };
-    std::vector<Pr> prs;
-    auto add_pairs = [&](const std::vector<int32_t>& ptr, const std::vector<int32_t>& ids, const std::vector<int32_t>& kf, int line,
-                         int32_t nlm) {
-        for (int32_t j = 0; j < nlm; ++j)
-            for (int32_t a = ptr[j]; a < ptr[j + 1]; ++a)
-                for (int32_t b = ptr[j]; b < ptr[j + 1]; ++b) {
-                    const int32_t o1 = ids[a], o2 = ids[b];
-                    if (kf[o1] >= kf[o2]) prs.push_back({(int64_t)kf[o1] * nkf + kf[o2], line, o1, o2});
-                }
-    };
-    add_pairs(lpp, lpo, pkf, 0, npt);
-    add_pairs(llp, llo, lkf, 1, nls);
-    for (int32_t k = 0; k < nkf; ++k) prs.push_back({(int64_t)k * nkf + k, 2, -1, -1});   // every diagonal block exists
-    std::stable_sort(prs.begin(), prs.end(), [](const Pr& x, const Pr& y) { return x.key != y.key ? x.key < y.key : x.line < y.line; });
-    std::vector<GbaBlock> blks;
-    std::vector<GbaChunk> chks;
-    std::vector<int2> pairs;
-    pairs.reserve(prs.size());
-    for (size_t i = 0; i < prs.size();) {
-        size_t e = i;
-        while (e < prs.size() && prs[e].key == prs[i].key) ++e;
-        GbaBlock B{(int32_t)(prs[i].key / nkf), (int32_t)(prs[i].key % nkf), (int32_t)chks.size(), 0};
-        for (size_t q = i; q < e;) {
-            if (prs[q].line == 2) { ++q; continue; }
-            size_t r = q;
-            while (r < e && prs[r].line == prs[q].line && r - q < (size_t)GBA_CHUNK) ++r;
-            chks.push_back({(int32_t)blks.size(), prs[q].line, (int32_t)pairs.size(), (int32_t)(r - q)});
-            for (size_t u = q; u < r; ++u) pairs.push_back(make_int2(prs[u].o1, prs[u].o2));
-            q = r;
-        }
-        B.c1 = (int32_t)chks.size();
-        blks.push_back(B);
-        i = e;
-    }
-    if (pairs.size() >= (size_t)INT32_MAX || chks.size() * 36 >= (size_t)INT32_MAX) return gba_fail(G, PLSLAM_EINVAL);
-    prs.clear(); prs.shrink_to_fit();
-    G->nblk = (int32_t)blks.size(); G->nchunk = (int32_t)chks.size();
-
-    Carver cs;
-    G->oBlk = cs.take(blks.size() * sizeof(GbaBlock)); G->oChk = cs.take(chks.size() * sizeof(GbaChunk) + 16);
-    G->oPair = cs.take(pairs.size() * 8 + 8);
-    G->oPlm = cs.take(plm.size() * 4 + 4); G->oPkf = cs.take(pkf.size() * 4 + 4);
-    G->oLlm = cs.take(llm.size() * 4 + 4); G->oLkf = cs.take(lkf.size() * 4 + 4);
-    G->oKpp = cs.take(kpp.size() * 4); G->oKpo = cs.take(kpo.size() * 4 + 4); G->oKlp = cs.take(klp.size() * 4);
-    G->oKlo = cs.take(klo.size() * 4 + 4); G->oLpp = cs.take(lpp.size() * 4); G->oLpo = cs.take(lpo.size() * 4 + 4);
-    G->oLlp = cs.take(llp.size() * 4); G->oLlo = cs.take(llo.size() * 4 + 4);
-    const size_t np = (size_t)n_pt_obs, nl = (size_t)n_ls_obs;
-    const int nwp = (npt + 255) / 256, nwl = (nls + 255) / 256, nwk = (nkf + 255) / 256;
-    G->nss = nwp + nwl + nwk;
-    Carver cw;
-    G->oVp = cw.take((size_t)npt * 72 + 8); G->oTp = cw.take((size_t)npt * 24 + 8);
-    G->oVl = cw.take((size_t)nls * 288 + 8); G->oTl = cw.take((size_t)nls * 48 + 8);
-    G->oSp = cw.take(0);                                  // point flags, then line flags, back to back
-    cw.off += ((size_t)npt + nls) * 4;
-    G->oSl = G->oSp + (size_t)npt * 4;
-    cw.take(8);
-    G->oYp = cw.take(np * 144 + 8); G->oYl = cw.take(nl * 288 + 8);
-    G->oPart = cw.take(chks.size() * 288 + 8);
-    G->oP = cw.take((size_t)G->npad * LT * 8); G->oW = cw.take((size_t)G->npad * 8); G->oZ = cw.take((size_t)G->npad * 8);
-    G->oDp = cw.take((size_t)G->npad * 8); G->oBad = cw.take((size_t)G->nt * 4 + 4);
-    G->oSsPart = cw.take((size_t)G->nss * 8 + 8); G->oStats = cw.take(sizeof(GbaStats)); G->oHmax = cw.take(8);
-    G->oX = cw.take((size_t)nkf * 48);
-    if ((rc = G->stat.reserve(cs.off + 256)) || (rc = G->work.reserve(cw.off + 256)) ||
+    if ((rc = G->stat.reserve(carve_stat(G, L, nullptr) + 256)) || (rc = G->work.reserve(carve_work(G, nullptr) + 256)) ||
         (rc = G->Sbuf.reserve((size_t)G->npad * (size_t)G->npad * 8)))
         return gba_fail(G, rc);
+    carve_stat(G, L, G->stat.as<char>());
+    carve_work(G, G->work.as<char>());
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         DeviceGuard dg_(ctx->device);
         hipStream_t s = ctx->stream;
-        char* d = G->stat.as<char>();
-        auto up = [&](size_t off, const void* src, size_t bytes) -> int {
-            if (bytes) PLSLAM_HIP_CHECK(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s));
-            return PLSLAM_OK;
-        };
-        if ((rc = up(G->oBlk, blks.data(), blks.size() * sizeof(GbaBlock))) ||
-            (rc = up(G->oChk, chks.data(), chks.size() * sizeof(GbaChunk))) || (rc = up(G->oPair, pairs.data(), pairs.size() * 8)) ||
-            (rc = up(G->oPlm, plm.data(), np * 4)) || (rc = up(G->oPkf, pkf.data(), np * 4)) ||
-            (rc = up(G->oLlm, llm.data(), nl * 4)) || (rc = up(G->oLkf, lkf.data(), nl * 4)) ||
-            (rc = up(G->oKpp, kpp.data(), kpp.size() * 4)) || (rc = up(G->oKpo, kpo.data(), kpo.size() * 4)) ||
-            (rc = up(G->oKlp, klp.data(), klp.size() * 4)) || (rc = up(G->oKlo, klo.data(), klo.size() * 4)) ||
-            (rc = up(G->oLpp, lpp.data(), lpp.size() * 4)) || (rc = up(G->oLpo, lpo.data(), lpo.size() * 4)) ||
-            (rc = up(G->oLlp, llp.data(), llp.size() * 4)) || (rc = up(G->oLlo, llo.data(), llo.size() * 4))) {
-            (void)hipStreamSynchronize(s);
-            return gba_fail(G, rc);
-        }
-        if (hipStreamSynchronize(s) != hipSuccess) return gba_fail(G, PLSLAM_EHIP);
+        const GbaStatView& st = G->st;
+        const UploadItem ups[] = {{st.blk, L.blks.data()}, {st.chk, L.chks.data()}, {st.pair, L.pairs.data()},
+                                  {st.plm, L.plm.data()}, {st.pkf, L.pkf.data()}, {st.llm, L.llm.data()}, {st.lkf, L.lkf.data()},
+                                  {st.kpp, L.kpp.data()}, {st.kpo, L.kpo.data()}, {st.klp, L.klp.data()}, {st.klo, L.klo.data()},
+                                  {st.lpp, L.lpp.data()}, {st.lpo, L.lpo.data()}, {st.llp, L.llp.data()}, {st.llo, L.llo.data()}};
+        rc = upload_items(ups, s);
+        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = PLSLAM_EHIP;
+        if (rc) return gba_fail(G, rc);
     }
     *out = G;
     return PLSLAM_OK;
@@ -638,17 +595,16 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
     plslam_lba_blocks B;
     if ((rc = plslam_lba_plan_device_blocks(G->lba, &B))) return rc;
     hipStream_t s = (hipStream_t)B.stream;
-    char* wk = G->work.as<char>();
+    const GbaWorkView& wk = G->wk;
     double hmax = 0.0;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         DeviceGuard dg2_(ctx->device);
         StreamSyncOnError guard(s);
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(wk + G->oX, x_kf, (size_t)nkf * 48, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_gba_hmax, dim3(1), dim3(256), 0, s, B.H_pose, nkf, B.H_pt, G->npt, B.H_ls, G->nls,
-                           (double*)(wk + G->oHmax));
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(wk.x, x_kf, wk.x.bytes, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_gba_hmax, dim3(1), dim3(256), 0, s, B.H_pose, nkf, B.H_pt, G->npt, B.H_ls, G->nls, wk.hmax.p);
         PLSLAM_HIP_CHECK(hipGetLastError());
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(&hmax, wk + G->oHmax, 8, hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(&hmax, wk.hmax, 8, hipMemcpyDeviceToHost, s));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
         guard.dismiss();
     }
@@ -662,7 +618,7 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
         StreamSyncOnError guard(s);
         int r = gba_solve_enqueue(G, lambda, apply, s);
         if (r) return r;
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(&st, wk + G->oStats, sizeof(GbaStats), hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(&st, wk.stats, sizeof(GbaStats), hipMemcpyDeviceToHost, s));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
         guard.dismiss();
         if (trace) {
@@ -696,7 +652,7 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
         std::lock_guard<std::mutex> lk(ctx->mu);
         DeviceGuard dg4_(ctx->device);
         StreamSyncOnError guard(s);
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(x_kf_out, wk + G->oX, (size_t)nkf * 48, hipMemcpyDeviceToHost, s));
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(x_kf_out, wk.x, wk.x.bytes, hipMemcpyDeviceToHost, s));
         if (T_out)
             PLSLAM_HIP_CHECK(hipMemcpyAsync(T_out, ls.T_kf_w + 16 * (size_t)n_map, (size_t)nkf * 128, hipMemcpyDeviceToHost, s));
         if (G->npt) PLSLAM_HIP_CHECK(hipMemcpyAsync(Xw_out, ls.Xw, (size_t)G->npt * 24, hipMemcpyDeviceToHost, s));
@@ -718,47 +674,10 @@ void plslam_gba_plan_destroy(plslam_gba_plan* G)
         std::lock_guard<std::mutex> lk(G->ctx->mu);
         DeviceGuard dg_(G->ctx->device);
         (void)hipStreamSynchronize(G->ctx->stream);
-        G->stat.release(); G->work.release(); G->Sbuf.release();
+        G->release();
     }
     if (G->lba) plslam_lba_plan_destroy(G->lba);
     delete G;
-}
-
-int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots)
-{
-    PLSLAM_REQUIRE(ctx && n >= 1 && A && b && x && n <= 6 * PLSLAM_GBA_MAX_KEYFRAMES, PLSLAM_EINVAL);
-    const int64_t npad = pad_to_tile(n);
-    const int nt = (int)(npad / LT);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard dg_(ctx->device);
-    hipStream_t s = ctx->stream;
-    DevBuf buf;
-    Carver c;
-    const size_t oS = c.take((size_t)npad * npad * 8), oP = c.take((size_t)npad * LT * 8), oW = c.take((size_t)npad * 8),
-                 oZ = c.take((size_t)npad * 8), oX = c.take((size_t)npad * 8), oB = c.take((size_t)nt * 4),
-                 oR = c.take(sizeof(GbaStats));
-    int rc = buf.reserve(c.off);
-    if (rc) return rc;
-    ReleaseAfterSync rel{buf, s};
-    char* d = buf.as<char>();
-    double* S = (double*)(d + oS);
-    PLSLAM_HIP_CHECK(hipMemsetAsync(S, 0, (size_t)npad * npad * 8, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d + oW, 0, (size_t)npad * 8, s));
-    PLSLAM_HIP_CHECK(hipMemcpy2DAsync(S, (size_t)npad * 8, A, (size_t)n * 8, (size_t)n * 8, n, hipMemcpyHostToDevice, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oW, b, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, npad, n, (int32_t)npad);
-    if ((rc = ldlt_enqueue(S, npad, n, (double*)(d + oP), (double*)(d + oW), (double*)(d + oZ), (double*)(d + oX),
-                           (int32_t*)(d + oB), s)))
-        return rc;
-    hipLaunchKernelGGL(k_gba_stats, dim3(1), dim3(256), 0, s, (const double*)nullptr, 0, (const int32_t*)nullptr, 0,
-                       (const int32_t*)(d + oB), nt, (GbaStats*)(d + oR));
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    GbaStats st{};
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(x, d + oX, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(&st, d + oR, sizeof(GbaStats), hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    if (n_bad_pivots) *n_bad_pivots = st.n_bad_pivots;
-    return PLSLAM_OK;
 }
 
 }  // extern "C"

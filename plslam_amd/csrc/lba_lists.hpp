@@ -21,19 +21,23 @@ constexpr int POSE_CHUNK = 64;
 // stable CSR lists (host, O(nobs)): observations per landmark and per keyframe, list order; keyframe
 // lists hold points first, then lines (global ids: points [0, n_pt_obs), lines n_pt_obs + o)
 struct CsrLists { std::vector<int32_t> ptp, pti, lsp, lsi, kfp, kfi; };
+// one stable list: the observations o < n by key[o] in [0, nkeys), list order; keep != nullptr: only those with keep[o] >= 0
+// (the global BA's lists, gba_lists.hpp: the observations by optimised keyframes)
+inline void csr_by_key(const int32_t* key, int32_t n, int32_t nkeys, std::vector<int32_t>& ptr, std::vector<int32_t>& ids,
+                       const int32_t* keep = nullptr)
+{
+    ptr.assign((size_t)nkeys + 1, 0);
+    for (int32_t o = 0; o < n; ++o) if (!keep || keep[o] >= 0) ++ptr[key[o] + 1];
+    for (int32_t k = 0; k < nkeys; ++k) ptr[k + 1] += ptr[k];
+    ids.assign((size_t)ptr[nkeys], 0);
+    std::vector<int32_t> pos(ptr.begin(), ptr.end() - 1);
+    for (int32_t o = 0; o < n; ++o) if (!keep || keep[o] >= 0) ids[pos[key[o]]++] = o;
+}
 inline void build_csr(const int32_t* pt_lm, const int32_t* pt_kf, int32_t np, const int32_t* ls_lm,
                       const int32_t* ls_kf, int32_t nl, int32_t nkf, int32_t npt, int32_t nls, CsrLists& c)
 {
-    auto by = [](const int32_t* key, int32_t n, int32_t nkeys, std::vector<int32_t>& ptr, std::vector<int32_t>& ids) {
-        ptr.assign((size_t)nkeys + 1, 0);
-        for (int32_t o = 0; o < n; ++o) ++ptr[key[o] + 1];
-        for (int32_t k = 0; k < nkeys; ++k) ptr[k + 1] += ptr[k];
-        ids.assign((size_t)ptr[nkeys], 0);
-        std::vector<int32_t> pos(ptr.begin(), ptr.end() - 1);
-        for (int32_t o = 0; o < n; ++o) ids[pos[key[o]]++] = o;
-    };
-    by(pt_lm, np, npt, c.ptp, c.pti);
-    by(ls_lm, nl, nls, c.lsp, c.lsi);
+    csr_by_key(pt_lm, np, npt, c.ptp, c.pti);
+    csr_by_key(ls_lm, nl, nls, c.lsp, c.lsi);
     c.kfp.assign((size_t)nkf + 1, 0);
     for (int32_t o = 0; o < np; ++o) if (pt_kf[o] >= 0) ++c.kfp[pt_kf[o] + 1];
     for (int32_t o = 0; o < nl; ++o) if (ls_kf[o] >= 0) ++c.kfp[ls_kf[o] + 1];

@@ -2,7 +2,8 @@
 // state, downloads) and lba_schur.hip (the Schur step on the blocks an iteration left on the device).  Internal.
 //
 // The plan's buffers are named ONCE: each is carved in one function (lba_plan.hip: carve_*; lba_schur.hip: carve_schur), which
-// fills a view of typed pointers with the bytes behind each; every launch site, upload and download reads the views.
+// fills a view of typed pointers with the bytes behind each (Arr, ArrCarver: common.hpp); every launch site, upload and
+// download reads the views.
 #pragma once
 
 #include "lba_blocks_dev.hpp"
@@ -10,24 +11,6 @@
 struct plslam_lba_plan;
 
 namespace plslam {
-
-// an array inside a carved buffer: where it starts and how many bytes of it are data (what an upload or a download copies;
-// the slack the carving leaves behind it is not counted)
-template <class T>
-struct Arr {
-    T* p = nullptr;
-    size_t bytes = 0;
-    operator T*() const { return p; }
-};
-
-// carves arrays out of the block at `base` in the order they are taken (Carver's alignment); base = nullptr: only the
-// total is wanted (the buffer is reserved after its size is known, and carved again over its address)
-struct ArrCarver {
-    char* base;
-    Carver c{};
-    size_t size() const { return c.off; }
-    template <class T> Arr<T> take(size_t bytes, size_t slack = 0) { return {reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + c.take(bytes + slack)), bytes}; }
-};
 
 struct LbaStatView {               // `stat`: the observation lists, the observations, the CSR lists -- uploaded once
     Arr<int32_t> pt_lm, pt_slot, pt_kf;

@@ -1,7 +1,20 @@
-// ldlt_dense_dev.hpp -- the dense right-looking fp64 L D L^T of the global bundle adjustment (K32-K36) and its enqueue
-// function, shared by gba.hip and, as the comparison path of the loop-closure pose graph, pgo.hip.  Included INSIDE the
-// includer's anonymous namespace in plslam, after it defines LT (the tile edge, 32) and dvec4_t (4 x double ext vector).
-#pragma once
+// ldlt_dense.hip -- the dense right-looking fp64 L D L^T of the global bundle adjustment (gba.hip) and, as the comparison path of
+// the loop-closure pose graph, of pgo.hip; compiled once, used through ldlt_dense.hpp.
+//   K32 k_ldlt_diag            one workgroup: L D L^T of the 32 x 32 diagonal tile (pivots that are zero / not finite counted)
+//   K33 k_ldlt_panel           a workgroup per row tile below it: L_ik = A_ik L_kk^-T D^-1 (and X_ik = L_ik D kept)
+//   K34 k_ldlt_update          a workgroup per lower tile of the trailing matrix: A_ij -= X_ik L_jk^T on v_mfma_f64_16x16x4_f64
+//   K35 k_ldlt_fwd             per tile column: L y = b (+ the D scaling), the rows below updated in parallel
+//   K36 k_ldlt_bwd             per tile row, last first: L^T x = z, the rows above updated in parallel
+// and the two small kernels around a solve: the identity padding of S (k_pad_diag) and the sum of the per-tile counts of bad
+// pivots (k_count_bad).  Every sum has a fixed shape; phases are ordered by kernel boundaries only.
+#include <hip/hip_runtime.h>
+
+#include "ldlt_dense.hpp"
+
+namespace plslam {
+namespace {
+
+typedef double dvec4_t __attribute__((ext_vector_type(4)));
 
 // ---- K32-K34: right-looking blocked L D L^T of the lower triangle, in place (strict lower: L, diagonal: D) --------------------
 __global__ void __launch_bounds__(256)
@@ -161,10 +174,25 @@ k_ldlt_bwd(const double* __restrict__ S, int64_t ld, int32_t k, double* __restri
     }
 }
 
-// ---- host side of the LDL^T: the matrix S (npad x npad, row-major, lower triangle read) is factored in place and
-// S x = b solved; w, z: npad doubles of workspace (w holds b on entry and is overwritten); P: npad x 32 doubles; n <= npad: the
-// order of the system itself, whose bad pivots badp counts per tile -------------------------------------------------------------
-inline int64_t pad_to_tile(int64_t n) { return (n + LT - 1) / LT * LT; }   // the npad of ldlt_enqueue
+// the padding of the matrix beyond n: identity, so that every tile is full
+__global__ void __launch_bounds__(256)
+k_pad_diag(double* __restrict__ S, int64_t ld, int32_t n, int32_t npad)
+{
+    const int i = n + blockIdx.x * 256 + threadIdx.x;
+    if (i < npad) S[(int64_t)i * ld + i] = 1.0;
+}
+__global__ void __launch_bounds__(256)
+k_count_bad(const int32_t* __restrict__ badp, int32_t nt, int32_t* __restrict__ nbad)
+{
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int i = 0; i < nt; ++i) n += badp[i];
+        *nbad = n;
+    }
+}
+
+}  // namespace
+
 int ldlt_enqueue(double* S, int64_t npad, int32_t n, double* P, double* w, double* z, double* x, int32_t* badp, hipStream_t s)
 {
     const int nt = (int)(npad / LT);
@@ -179,5 +207,68 @@ int ldlt_enqueue(double* S, int64_t npad, int32_t n, double* P, double* w, doubl
     for (int k = 0; k < nt; ++k) hipLaunchKernelGGL(k_ldlt_fwd, dim3(nt - k), dim3(64), 0, s, (const double*)S, npad, k, w, z);
     for (int k = nt - 1; k >= 0; --k) hipLaunchKernelGGL(k_ldlt_bwd, dim3(k + 1), dim3(64), 0, s, (const double*)S, npad, k, z, x);
     PLSLAM_HIP_CHECK(hipGetLastError());
+    return PLSLAM_OK;
+}
+
+void ldlt_pad_diag_enqueue(double* S, int64_t npad, int32_t n, hipStream_t s)
+{
+    if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(1), dim3(256), 0, s, S, npad, n, (int32_t)npad);
+}
+
+void ldlt_count_bad_enqueue(const int32_t* badp, int32_t nt, int32_t* nbad, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_count_bad, dim3(1), dim3(64), 0, s, badp, nt, nbad);
+}
+
+}  // namespace plslam
+
+using namespace plslam;
+
+namespace {
+
+struct DenseSolveView { Arr<double> S, P, w, z, x; Arr<int32_t> badp, nbad; };
+
+size_t carve_dense_solve(DenseSolveView& v, int64_t npad, char* base)
+{
+    ArrCarver c{base};
+    const size_t np8 = (size_t)npad * 8;
+    v.S = c.take<double>((size_t)npad * np8);
+    v.P = c.take<double>(np8 * LT);
+    v.w = c.take<double>(np8);
+    v.z = c.take<double>(np8);
+    v.x = c.take<double>(np8);
+    v.badp = c.take<int32_t>((size_t)(npad / LT) * 4);
+    v.nbad = c.take<int32_t>(4);
+    return c.size();
+}
+
+}  // namespace
+
+extern "C" int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots)
+{
+    PLSLAM_REQUIRE(ctx && n >= 1 && A && b && x && n <= 6 * PLSLAM_GBA_MAX_KEYFRAMES, PLSLAM_EINVAL);
+    const int64_t npad = pad_to_tile(n);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard dg_(ctx->device);
+    hipStream_t s = ctx->stream;
+    DevBuf buf;
+    DenseSolveView v;
+    int rc = buf.reserve(carve_dense_solve(v, npad, nullptr));
+    if (rc) return rc;
+    ReleaseAfterSync rel{buf, s};
+    carve_dense_solve(v, npad, buf.as<char>());
+    PLSLAM_HIP_CHECK(hipMemsetAsync(v.S, 0, v.S.bytes, s));
+    PLSLAM_HIP_CHECK(hipMemsetAsync(v.w, 0, v.w.bytes, s));
+    PLSLAM_HIP_CHECK(hipMemcpy2DAsync(v.S, (size_t)npad * 8, A, (size_t)n * 8, (size_t)n * 8, n, hipMemcpyHostToDevice, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(v.w, b, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    ldlt_pad_diag_enqueue(v.S, npad, n, s);
+    if ((rc = ldlt_enqueue(v.S, npad, n, v.P, v.w, v.z, v.x, v.badp, s))) return rc;
+    ldlt_count_bad_enqueue(v.badp, (int32_t)(npad / LT), v.nbad, s);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    int32_t nb = 0;
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(x, v.x, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(&nb, v.nbad, 4, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    if (n_bad_pivots) *n_bad_pivots = nb;
     return PLSLAM_OK;
 }

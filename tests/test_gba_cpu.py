@@ -173,7 +173,8 @@ def _run(name, max_iters=15, lambda_lm=0.00001):
 
 
 def plan_layout(m):
-    """The covisible blocks of plslam_gba_plan_create, restated from its comment: every ordered pair (o1, o2) of a landmark's
+    """The covisible blocks of the GBA plan (plslam_amd/csrc/gba_lists.hpp), restated from its comment -- tests/test_gba_lists_cpu.py
+    holds the lists the planner really builds against this: every ordered pair (o1, o2) of a landmark's
     observations by optimised keyframes with kf(o1) >= kf(o2) falls in lower block (kf(o1), kf(o2)); a block's point pairs
     come before its line pairs; a chunk holds at most 64 pairs of one kind; every diagonal block exists.
     -> {(k1, k2): (point pairs, line pairs, [chunk sizes])}"""

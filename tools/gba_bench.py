@@ -2,7 +2,8 @@
 trajectory-shaped maps -- G1: 400 keyframes, 40 k points, 6 k lines, 4 observations per landmark, one loop; G2: 1500 keyframes,
 150 k points, 20 k lines -- and, at G1, the time of the numpy restatement of the same loop (tests/gba_ref.py: a restatement,
 not the reference).  Prints one JSON line: median milliseconds per whole call (plan creation excluded).  The per-phase device
-split comes from a kernel trace of this tool (rocprofv3 --kernel-trace --stats), grouped by the kernel names of gba.hip.
+split comes from a kernel trace of this tool (rocprofv3 --kernel-trace --stats), grouped by the kernel names of gba.hip and
+ldlt_dense.hip.
 
     python tools/gba_bench.py [--reps 3] [--no-restatement]
 """

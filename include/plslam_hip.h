@@ -437,6 +437,11 @@ int plslam_match_plan_add_stereo_gates(plslam_match_plan* plan, const plslam_ste
 int plslam_match_plan_set_wire16(plslam_match_plan* plan, const int32_t* table32, int16_t* table16, size_t n_entries);
 
 /* ---- K3/K4: local-BA residual + Jacobian rows ------------------------------------------- */
+/* Both kinds of row, every entry point: std::max(homogTh, x) is computed as (homogTh > x ? homogTh : x), so a NaN x (a landmark
+ * at depth zero, a NaN / inf input) gives a NaN row as in the reference, while a NaN homogTh -- where libstdc++'s std::max
+ * returns the NaN -- is passed over and the rows stay finite: on purpose, a threshold that is not a number is no configuration
+ * of the reference.  An entry that is not a number is stored as ONE NaN, 0x7FF8000000000000: which NaN an operation hands on
+ * (sign, payload) is the hardware's choice and differs between the GPU and a host. */
 /* Point rows: the per-observation body of MapHandler::levMarquardtOptimizationLBA,
  * src/mapHandler.cpp:1358-1407 (first pass) == :1587-1642 (iteration pass; the caller
  * supplies poses/landmarks from X).  fp64, no FMA contraction, reference operation order.
@@ -726,7 +731,11 @@ int plslam_map2kf_match_lines(plslam_ctx* ctx, const plslam_cam* K, const double
  * ratio nnr_grid (Config::minRatio12P() for BOTH kinds); then, exactly as in the plain drivers,
  * StVO::match(nnr) replaces its result when |Q| > min_matches && matches < min_matches (:594-598,
  * :709-713).  *used_match (may be NULL) reports whether that happened.  fm == NULL or !fm->enabled is the
- * plain driver.  kf_seg: n_kf x 4 doubles = stereo_ls[i]->spl, ->epl (lines only). */
+ * plain driver.  kf_seg: n_kf x 4 doubles = stereo_ls[i]->spl, ->epl (lines only).
+ * PRECONDITION (as in the reference's getLineCoords): kf_seg holds PIXELS of the image.  The grid of the windowed matcher is
+ * filled on the host by walking every Bresenham cell between the two end points times inv_width / inv_height, whether it lies
+ * in the grid or not: a coordinate of 1e19 keeps the call busy for 2^31 cells.  Finite values of the image's size are expected;
+ * the entry points do not clamp them. */
 typedef struct plslam_fast_matching {
     int32_t enabled;              /* SlamConfig::fastMatching() */
     int32_t grid_cols, grid_rows; /* GRID_COLS (64), GRID_ROWS (48) */

@@ -380,7 +380,21 @@ void plo_logmap_se3(const double T[16], double x[6])
 /* ------------------------------------------------------------------------------------ */
 /* LBA rows                                                                              */
 /* ------------------------------------------------------------------------------------ */
-static inline double dmax(double a, double b) { return a > b ? a : b; } /* std::max(a,b) */
+/* std::max(homogTh, x) for every x, NaN included (a NaN x is handed on, as libstdc++'s a < b ? b : a does).  NOT std::max for
+ * a NaN homogTh: that one is passed over here and the rows stay finite, where the reference's would be NaN -- on purpose, and
+ * what the kernels (dmax_gt, lba_rows_dev.hpp) have always computed; a NaN threshold is no configuration of the reference. */
+static inline double dmax(double a, double b) { return a > b ? a : b; }
+
+/* A row entry that is not a number is ONE NaN, the positive quiet one: which NaN an operation generates or hands on (sign,
+ * payload) is left to the implementation by IEEE 754 and differs between this host and the GPU (lba_rows_dev.hpp one_nan). */
+static inline double one_nan(double x)
+{
+    if (x != x) {
+        const uint64_t q = 0x7FF8000000000000ull;
+        memcpy(&x, &q, sizeof(x));
+    }
+    return x;
+}
 
 /* stvo-pl PinholeStereoCamera::projection [RECALL]: u = cx + fx*X/Z, v = cy + fy*Y/Z */
 static inline void project(const plo_cam* K, const double P[3], double uv[2])
@@ -434,11 +448,11 @@ void plo_lba_point_rows(const plo_cam* K, double th, const double* T_kf_w, const
         const double a = K->fx * dx, b = K->fy * dy;             /* :1388-1389 */
         jac6(a, b, k, G, Jc);                                    /* :1392-1397 */
         const double den = dmax(th, nrm);
-        for (int c = 0; c < 6; ++c) J_pose[6 * (size_t)o + c] = Jc[c] / den;   /* :1398 */
+        for (int c = 0; c < 6; ++c) J_pose[6 * (size_t)o + c] = one_nan(Jc[c] / den);   /* :1398 */
         for (int j = 0; j < 3; ++j)                                            /* :1404 */
-            J_lm[3 * (size_t)o + j] = (Jc[0] * R[j] + Jc[1] * R[3 + j] + Jc[2] * R[6 + j]) / den;
-        r[o] = nrm;
-        w[o] = 1.0 / (1.0 + nrm * nrm);                          /* robustWeightCauchy :1407 */
+            J_lm[3 * (size_t)o + j] = one_nan((Jc[0] * R[j] + Jc[1] * R[3 + j] + Jc[2] * R[6 + j]) / den);
+        r[o] = one_nan(nrm);
+        w[o] = one_nan(1.0 / (1.0 + nrm * nrm));                 /* robustWeightCauchy :1407 */
     }
 }
 
@@ -470,13 +484,13 @@ void plo_lba_line_rows(const plo_cam* K, double th_in, int compat, const double*
         for (int j = 0; j < 3; ++j) {
             const double vp = JP[0] * R[j] + JP[1] * R[3 + j] + JP[2] * R[6 + j];
             const double vq = JQ[0] * R[j] + JQ[1] * R[3 + j] + JQ[2] * R[6 + j];
-            J_lm[6 * (size_t)o + j] = vp * e0 / den;             /* :1486 */
-            J_lm[6 * (size_t)o + 3 + j] = vq * e1 / den;         /* :1506 */
+            J_lm[6 * (size_t)o + j] = one_nan(vp * e0 / den);            /* :1486 */
+            J_lm[6 * (size_t)o + 3 + j] = one_nan(vq * e1 / den);        /* :1506 */
         }
         for (int c = 0; c < 6; ++c)
-            J_pose[6 * (size_t)o + c] = (JP[c] * e0 + JQ[c] * e1) / den;       /* :1509 */
-        r[o] = nrm;
-        w[o] = 1.0 / (1.0 + nrm * nrm);                          /* :1516 */
+            J_pose[6 * (size_t)o + c] = one_nan((JP[c] * e0 + JQ[c] * e1) / den);       /* :1509 */
+        r[o] = one_nan(nrm);
+        w[o] = one_nan(1.0 / (1.0 + nrm * nrm));                 /* :1516 */
     }
 }
 

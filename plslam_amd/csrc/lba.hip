@@ -213,6 +213,7 @@ int launch_line_rows(const plslam_cam& K, double th, int compat, const double* T
                      double* Jp, double* Jl, double* r, double* w, hipStream_t s, int32_t n_pose_slots)
 {
     if (nobs <= 0) return PLSLAM_OK;
+    if (compat) th = 0.0000001;                              // (the iteration pass's threshold is a literal, :1698 - :1741)
     hipLaunchKernelGGL(k_line_rows, dim3((nobs + 255) / 256), dim3(256), 0, s, cam_d(K), th, compat, T,
                        Lw, lobs, lm, kf, nobs, Jp, Jl, r, w, n_pose_slots);
     PLSLAM_HIP_CHECK(hipGetLastError());

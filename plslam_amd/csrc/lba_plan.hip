@@ -93,7 +93,8 @@ k_lba_rows_cross(const LbaIterArgs A)
             wave_store_rows<18>(A.Wp + 18 * (size_t)o0, w18, slabs[wave], lane, valid);
         } else {
             double outl[6], outp[6];
-            line_row(A.K, A.th, T12, LM6, LM6 + 3, ob3[0], ob3[1], ob3[2], outl, outp, nrm, wgt);
+            // (the iteration pass's line rows take a literal for homogTh, :1698 - :1741; its point rows do not, :1616 - :1637)
+            line_row(A.K, A.compat_iter ? 0.0000001 : A.th, T12, LM6, LM6 + 3, ob3[0], ob3[1], ob3[2], outl, outp, nrm, wgt);
             wave_store_rows<6>(A.lJl + 6 * (size_t)o0, outl, slabs[wave], lane, valid);
             wave_store_rows<6>(A.lJp + 6 * (size_t)o0, outp, slabs[wave], lane, valid);
             if (o < nobs) {

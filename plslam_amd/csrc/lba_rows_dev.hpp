@@ -13,6 +13,12 @@ struct CamD { double fx, fy, cx, cy; double width, height; };
 // not dmax_std: the comparison the other way round (a NaN in `a` gives b here, a there) -- what these rows have always computed
 __device__ __forceinline__ double dmax_gt(double a, double b) { return a > b ? a : b; }
 
+// A row entry that is not a number is stored as ONE NaN, the positive quiet one.  Which NaN an operation generates or hands on
+// (sign, payload) is the implementation's choice under IEEE 754: the GPU generates 0x7FF8..., the checker's host 0xFFF8..., and a
+// subtraction done as an addition with a negated operand turns the sign of a NaN that passes through it.  With this the rows of
+// the device and of the restatement are the same words also where they are not numbers.
+__device__ __forceinline__ double one_nan(double x) { return x != x ? __longlong_as_double(0x7FF8000000000000LL) : x; }
+
 // stvo-pl PinholeStereoCamera::projection: u = cx + fx*X/Z, v = cy + fy*Y/Z
 __device__ __forceinline__ void project(const CamD& K, const double P[3], double& u, double& v)
 {
@@ -177,11 +183,11 @@ __device__ __forceinline__ void point_row(const CamD& K, double th, const double
     jac6(a, b, k, G, Jc);
     const double den = dmax_gt(th, nrm);
 #pragma unroll
-    for (int c = 0; c < 6; ++c) out6[c] = Jc[c] / den;
+    for (int c = 0; c < 6; ++c) out6[c] = one_nan(Jc[c] / den);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) out3[j] = (Jc[0] * R[j] + Jc[1] * R[3 + j] + Jc[2] * R[6 + j]) / den;
-    nrm_out = nrm;
-    w_out = 1.0 / (1.0 + nrm * nrm);
+    for (int j = 0; j < 3; ++j) out3[j] = one_nan((Jc[0] * R[j] + Jc[1] * R[3 + j] + Jc[2] * R[6 + j]) / den);
+    nrm_out = one_nan(nrm);
+    w_out = one_nan(1.0 / (1.0 + nrm * nrm));
 }
 
 // One line row (:1436-1516; compat = the iteration pass's quirks, :1668-1772): J_lm (6), J_pose (6), r, w.
@@ -209,13 +215,13 @@ __device__ __forceinline__ void line_row(const CamD& K, double th, const double*
     for (int j = 0; j < 3; ++j) {
         const double vp = JP[0] * R[j] + JP[1] * R[3 + j] + JP[2] * R[6 + j];
         const double vq = JQ[0] * R[j] + JQ[1] * R[3 + j] + JQ[2] * R[6 + j];
-        outl[j] = vp * e0 / den;
-        outl[3 + j] = vq * e1 / den;
+        outl[j] = one_nan(vp * e0 / den);
+        outl[3 + j] = one_nan(vq * e1 / den);
     }
 #pragma unroll
-    for (int c = 0; c < 6; ++c) outp[c] = (JP[c] * e0 + JQ[c] * e1) / den;
-    nrm_out = nrm;
-    w_out = 1.0 / (1.0 + nrm * nrm);
+    for (int c = 0; c < 6; ++c) outp[c] = one_nan((JP[c] * e0 + JQ[c] * e1) / den);
+    nrm_out = one_nan(nrm);
+    w_out = one_nan(1.0 / (1.0 + nrm * nrm));
 }
 
 }  // namespace plslam

@@ -12,8 +12,11 @@
 // No atomics, nothing scheduling-dependent (as everywhere in this file): the pairs (o1, o2) of observations of one landmark that
 // fall into block (k1 <= k2) of S are listed ONCE per plan on the host, sorted by block; a block's sum is a fixed-shape two-level
 // sum -- chunks of SCH_CHUNK pairs sequentially in list order, then the chunk partials in chunk order -- and the lower triangle
-// is the mirror of the upper one.
-//   K19 k_schur_landmarks<DL>   a lane per landmark: Vj' inverse (closed form 3x3 / Gauss-Jordan 6x6), tj = Vj'^-1 gj
+// is the mirror of the upper one, block by block (inside a DIAGONAL block all 36 entries are summed, each over its own products:
+// S(a,b) and S(b,a) there agree to rounding, not to the bit).  A sequential program in this order reproduces every word of S, b,
+// the steps and their sum of squares: tests/lba_schur_ref.py is one, tests/test_gpu_lba_schur_edges.py compares with it.
+//   K19 k_schur_landmarks       a lane per landmark: Vj' inverse (Gauss-Jordan without pivoting, 3x3 and 6x6 alike: schur_landmark
+//                               in lba_blocks_dev.hpp), tj = Vj'^-1 gj
 //   K20 k_schur_partials        a lane per (block, chunk, entry of the 6x6 block): sum over the chunk's pairs of W1^T Vinv W2
 //   K21 (in K20's launch)       a lane per (keyframe, chunk, entry of b): sum over the chunk's observations of W^T tj
 //   K22 k_schur_finish          a lane per (block, entry) / (keyframe, entry): chunk partials -> S (both triangles), b

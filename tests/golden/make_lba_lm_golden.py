@@ -19,9 +19,37 @@ from plslam_amd import synth  # noqa: E402
 CFG = dict(homog_th=1e-7, lambda_lm=0.00001, lambda_k=10.0, max_iters=15, min_err_change=1e-7, min_err=1e-7)   # config/config/config.yaml:28-30, 101-106
 
 
-def problem(n_kf_map, n_pt, n_ls, obs, seed, sigma_lm, sigma_pose):
+def _fixed_heavy(lm, n_kf, seed):
+    """every landmark seen twice: once by key frame 0 and once by another one -- half the observations by the key frame that is
+    not optimised.  The observations are drawn again as synth.local_map draws them (projection + N(0, 1 px))."""
+    rng = np.random.Generator(np.random.PCG64(seed + 2000))
+    K = synth.EUROC
+    T = lm["T_kf_w"].reshape(-1, 4, 4)
+
+    def project(k, X):
+        Ti = np.linalg.inv(T[k])
+        Xc = X @ Ti[:3, :3].T + Ti[:3, 3]
+        return np.stack([K["cx"] + K["fx"] * Xc[:, 0] / Xc[:, 2], K["cy"] + K["fy"] * Xc[:, 1] / Xc[:, 2]], axis=1)
+    for lmk, kfk in (("pt_lm", "pt_kf"), ("ls_lm", "ls_kf")):
+        n = lm[lmk].size // 2
+        lm[kfk] = np.stack([np.zeros(n, np.int32), 1 + rng.integers(0, n_kf - 1, n).astype(np.int32)], 1).reshape(-1)
+    for k in range(n_kf):
+        s = lm["pt_kf"] == k
+        lm["obs_uv"][s] = project(k, lm["Xw"][lm["pt_lm"][s]]) + rng.standard_normal((int(s.sum()), 2))
+        s = lm["ls_kf"] == k
+        n = int(s.sum())
+        p = project(k, lm["Lw"][lm["ls_lm"][s], :3]) + rng.standard_normal((n, 2))
+        q = project(k, lm["Lw"][lm["ls_lm"][s], 3:]) + rng.standard_normal((n, 2))
+        ln = np.cross(np.concatenate([p, np.ones((n, 1))], 1), np.concatenate([q, np.ones((n, 1))], 1))
+        lm["l_obs"][s] = ln / np.sqrt(ln[:, 0:1] ** 2 + ln[:, 1:2] ** 2)
+    return lm
+
+
+def problem(n_kf_map, n_pt, n_ls, obs, seed, sigma_lm, sigma_pose, fixed_heavy=False):
     """Key frame 0 of the map is never optimised (src/mapHandler.cpp:1231); the others are the local ones, kf_loc = index - 1."""
     lm = synth.local_map(n_kf=n_kf_map, n_pt=n_pt, n_ls=n_ls, obs_per_lm=obs, seed=seed)
+    if fixed_heavy:
+        lm = _fixed_heavy(lm, n_kf_map, seed)
     rng = np.random.Generator(np.random.PCG64(seed + 1000))
     x = np.stack([O.logmap_se3(T) for T in lm["T_kf_w"].reshape(-1, 4, 4)])
     x[1:] += sigma_pose * rng.standard_normal((n_kf_map - 1, 6)) * np.array([1, 1, 1, 0.2, 0.2, 0.2])
@@ -47,6 +75,9 @@ CASES = {      # name -> problem arguments
     "reject": dict(n_kf_map=5, n_pt=120, n_ls=40, obs=3, seed=61, sigma_lm=0.8, sigma_pose=0.3),
     "reject_later": dict(n_kf_map=5, n_pt=120, n_ls=40, obs=3, seed=74, sigma_lm=1.5, sigma_pose=0.15),
     "points_only": dict(n_kf_map=4, n_pt=90, n_ls=0, obs=3, seed=5, sigma_lm=0.05, sigma_pose=0.01),
+    # landmark blocks without rank (two views: rank 2 of 3 and of 6), and half the observations by the key frame that is not optimised
+    "two_views": dict(n_kf_map=5, n_pt=90, n_ls=30, obs=2, seed=1, sigma_lm=0.05, sigma_pose=0.01),
+    "fixed_heavy": dict(n_kf_map=5, n_pt=90, n_ls=30, obs=2, seed=1, sigma_lm=0.05, sigma_pose=0.01, fixed_heavy=True),
 }
 
 
@@ -63,8 +94,18 @@ def main():
             out[f"{name}_{k}"] = np.asarray(v)
         for k, v in r.items():
             out[f"{name}_ref_{k}"] = np.asarray(v)
+        if not all(np.isfinite(np.asarray(r[k], np.float64)).all() for k in ("X", "lam", "err_last")):
+            raise SystemExit(f"{name}: the reference's run left a non-finite value")
     out["cfg"] = np.array([CFG[k] for k in ("homog_th", "lambda_lm", "lambda_k", "max_iters", "min_err_change", "min_err")], np.float64)
-    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "lba_lm_golden.npz"), **out)
+    path = os.path.join(ROOT, "tests", "golden", "lba_lm_golden.npz")
+    if os.path.exists(path):                   # a regeneration leaves every array that was there byte for byte as it was
+        old = np.load(path)
+        for k in old.files:
+            a, b = old[k], out[k]
+            if a.dtype != b.dtype or a.shape != b.shape or a.tobytes() != b.tobytes():
+                raise SystemExit(f"{k} would change: not written")
+        print(f"{len(old.files)} arrays of the fixture as it was: byte-identical; {len(out) - len(old.files)} new")
+    np.savez_compressed(path, **out)
 
 
 if __name__ == "__main__":

@@ -269,7 +269,6 @@ def _preload_shared_hip_runtime() -> None:
 
 
 # every entry point returns an int status except these (load() gives each name of ABI_SYMBOLS its return type from here).
-# plslam_lc_batch_destroy is void in the header and is bound as int, as it has been since it was added; its value is not read.
 _RESTYPES = {
     "plslam_strerror": C.c_char_p, "plslam_last_error": C.c_char_p,
     "plslam_pinned_alloc": C.c_void_p, "plslam_pinned_free": None,
@@ -278,6 +277,7 @@ _RESTYPES = {
     "plslam_grid_plan_destroy": None, "plslam_match_pipeline_destroy": None, "plslam_bow_vocab_destroy": None,
     "plslam_bow_db_destroy": None, "plslam_gba_plan_destroy": None, "plslam_pgo_plan_destroy": None,
     "plslam_local_map_destroy": None, "plslam_map_insert_destroy": None, "plslam_lc_fuse_destroy": None,
+    "plslam_lc_batch_destroy": None,
 }
 
 

@@ -6,13 +6,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gn_cam.hpp"   // GnCam
 #include "se3_dev.hpp"
 
 namespace plslam {
 
 constexpr int GN_TERMS = 21 + 6 + 1;       // upper triangle of H, g, e
-
-struct GnCam { double fx, fy, cx, cy; };
 
 __device__ __forceinline__ void jac6(double fgz2, double a, double b, double gx, double gy, double gz, double J[6])
 {

@@ -231,6 +231,36 @@ def C_sizeof():
     return ctypes.sizeof(plslam_amd.LcResult)
 
 
+def test_one_record_as_both_keyframes_is_uploaded_once_and_equals_the_dev_form(ctx):
+    """kf0 and kf1 the same record: the host form's image holds it once and both device records point into it.  257 points: one
+    row past the gather's 256-row chunk; 3 lines."""
+    torch = pytest.importorskip("torch")
+    kf, _, _ = LC.keyframe_pair(83, 257, 3)
+    p = LC.params()
+    host = ctx.loop_closure_verify(p, kf, kf)
+    assert host[0]["common_pt"] == 257 and host[0]["common_ls"] == 3          # every feature is its own nearest neighbour
+    dev = torch.device("cuda:0")
+    t = {k: torch.from_numpy(np.ascontiguousarray(kf[k])).to(dev) for k in ("pdesc", "P", "pl", "pt_idx", "ldesc", "sPeP", "le", "ls_idx")}
+    rec = dict({k: v.data_ptr() for k, v in t.items()}, n_pt=257, n_ls=3)
+    res = torch.zeros(C_sizeof(), dtype=torch.uint8, device=dev)
+    pc = torch.zeros((257, 4), dtype=torch.int32, device=dev)
+    pi = torch.zeros(257, dtype=torch.uint8, device=dev)
+    lcr = torch.zeros((3, 4), dtype=torch.int32, device=dev)
+    li = torch.zeros(3, dtype=torch.uint8, device=dev)
+    s = torch.cuda.Stream(dev)
+    ctx.loop_closure_verify_dev(p, rec, rec, res.data_ptr(), pc.data_ptr(), pi.data_ptr(), lcr.data_ptr(), li.data_ptr(),
+                                stream=s.cuda_stream)
+    s.synchronize()
+    r = plslam_amd.LcResult.from_buffer_copy(res.cpu().numpy().tobytes()).as_dict()
+    for k, v in host[0].items():
+        if k in ("clk_total", "clk_serial"):
+            continue
+        assert np.array_equal(np.asarray(r[k]), np.asarray(v), equal_nan=True), k
+    assert np.array_equal(pc.cpu().numpy(), host[1]) and np.array_equal(pi.cpu().numpy().astype(bool), host[2])
+    assert np.array_equal(lcr.cpu().numpy(), host[3]) and np.array_equal(li.cpu().numpy().astype(bool), host[4])
+    assert np.array_equal(host[1][:, 1], np.arange(257)) and np.array_equal(host[1][:, 3], np.arange(257))
+
+
 def test_relpose_robust_gn_alone(ctx):
     kf0, kf1, _ = LC.keyframe_pair(91, 1500, 200)
     prm = LC.params_dict(LC.params())

@@ -119,12 +119,6 @@ struct ReleaseAfterSync {
     }
 };
 
-// carve several arrays out of one scratch buffer (slices aligned as align256 says: match_tables.hpp)
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
-};
-
 // an array inside a carved buffer: where it starts and how many bytes of it are data (what an upload or a download copies;
 // the slack the carving leaves behind it is not counted)
 template <class T>
@@ -324,28 +318,13 @@ int launch_merge_partials(const SymDesc* d_sym, const BlockDesc* d_blocks, int n
 
 int scan_rows_per_block(int variant, int block_threads);
 
-// dst[i] = src[idx[i]] for rows of row_bytes (a multiple of 8) bytes  (map2kf.hip)
-int launch_gather_rows(const void* src, const int32_t* idx, int32_t n, int32_t row_bytes, void* dst,
-                       hipStream_t s);
-
-// --- LBA rows + gates (lba.hip) --------------------------------------------------------------
+// --- LBA rows (lba.hip; the gates and the visibility kernels: map2kf_dev.hpp) ------------------
 int launch_point_rows(const plslam_cam& K, double th, const double* T, const double* Xw,
                       const double* uv, const int32_t* lm, const int32_t* kf, int32_t nobs,
                       double* Jp, double* Jl, double* r, double* w, hipStream_t s, int32_t n_pose_slots = 0);
 int launch_line_rows(const plslam_cam& K, double th, int compat, const double* T, const double* Lw,
                      const double* lobs, const int32_t* lm, const int32_t* kf, int32_t nobs,
                      double* Jp, double* Jl, double* r, double* w, hipStream_t s, int32_t n_pose_slots = 0);
-int launch_point_gate(const plslam_cam& K, const double* Twf16, const double* Xw, const int32_t* m12,
-                      int32_t nq, const double* pl, double th, uint8_t* mask, int32_t* count,
-                      hipStream_t s);
-int launch_line_gate(const plslam_cam& K, const double* Twf16, const double* Lw, const int32_t* m12,
-                     int32_t nq, const double* le, double th, uint8_t* mask, int32_t* count,
-                     hipStream_t s);
-int launch_visible(const plslam_cam& K, const double* Twf16, const double* X, int32_t n, int lines,
-                   uint8_t* vis, hipStream_t s);
-// cells (n x [1|2] x 2 int32) of the projected landmarks in grid units; lines: also dir1 (n x 2)
-int launch_project_cells(const plslam_cam& K, const double* Twf16, const double* X, int32_t n, int lines, double inv_w,
-                         double inv_h, int32_t* cells, double* dir1, hipStream_t s);
 
 // --- stereo gates (stereo_gates.hip) -------------------------------------------------------------
 int launch_stereo_gates(const plslam_stereo_gate_problem* d_gates, const BlockDesc* d_blocks, int nblocks, hipStream_t s);

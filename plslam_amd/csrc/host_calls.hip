@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <new>
 
+#include "map2kf_dev.hpp"   // the gates and the visibility pre-filter
 #include "match_plan.hpp"
 
 using namespace plslam;

@@ -9,6 +9,10 @@
 namespace plslam {
 
 struct CamD { double fx, fy, cx, cy; double width, height; };
+inline CamD cam_d(const plslam_cam& K)      // (host: what the launchers of lba.hip and map2kf_kernels.hip hand their kernels)
+{
+    return CamD{K.fx, K.fy, K.cx, K.cy, (double)K.width, (double)K.height};
+}
 
 // not dmax_std: the comparison the other way round (a NaN in `a` gives b here, a there) -- what these rows have always computed
 __device__ __forceinline__ double dmax_gt(double a, double b) { return a > b ? a : b; }

@@ -1,5 +1,5 @@
 // lookback_dev.hpp -- the decoupled look-back the stable compactions and offset scans share, the tile scan that stands in front of
-// it, and the bisection that finds an item's segment in the offsets such a scan leaves.  Its users: lba.hip k_visible_compact;
+// it, and the bisection that finds an item's segment in the offsets such a scan leaves.  Its users: map2kf_kernels.hip k_visible_compact;
 // local_map.hip K59 (the keyframe list), K60 (the landmark lists and their observation offsets); map_insert.hip K63 (events, new
 // landmarks, pairs), K64 (the new obs_ptr); lc_fuse.hip K70 (the new obs_ptr); lba_plan_dev.hip K81 (the pair enumeration; K82
 // uses the tile scan alone).  One copy: a change here moves every list that is built with it.

@@ -74,6 +74,11 @@ struct SymDesc {
 
 // every area and every packed table starts on a multiple of 256 bytes
 constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+// carve several arrays out of one scratch buffer (slices aligned as align256 says)
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
+};
 
 // the kernels index these tables with fixed strides: a reordered or resized field must not slip through
 static_assert(sizeof(ScanDesc) == 32, "ScanDesc layout");

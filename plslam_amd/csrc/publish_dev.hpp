@@ -1,4 +1,4 @@
-// publish_dev.hpp -- the counters of a call's LAST kernel (lba.hip: the gates of the map <-> keyframe drivers; local_map.hip: K57,
+// publish_dev.hpp -- the counters of a call's LAST kernel (map2kf_kernels.hip: the gates of the map <-> keyframe drivers; local_map.hip: K57,
 // K62, K84): every wave adds its ballot to a device word and WAITS for the atomic (a returning one) before the workgroup's barrier;
 // one lane then counts the workgroup in, and the workgroup that finishes last copies the words to the page-locked block the host
 // reads -- a launch less at the end of a call that is bound by its launches.  One copy: the memory order of this ticket (relaxed

@@ -2,7 +2,7 @@
 // rigid transform of a point, 3x3 products, the inverse of a pose, and stvo-pl's SE(3) maps (expmap_se3 / logmap_se3 /
 // inverse_se3, auxiliar.cpp), their theta < 1e-6 branches included.  Every includer is built with -ffp-contract=off and every
 // expression keeps the reference's order of operations (sums left to right).  Used by the row kernels (pose_gn_dev.hpp,
-// lba_rows_dev.hpp, lba.hip), the stereo gates, K25 (loop_closure.hip), the global BA (gba.hip), the pose graph
+// lba_rows_dev.hpp, lba.hip, map2kf_kernels.hip), the stereo gates, K25 (loop_closure.hip), the global BA (gba.hip), the pose graph
 // (pgo.hip, under g2o's maps in g2o_dev.hpp) and the map correction (lc_correct.hip).
 #pragma once
 

@@ -1,4 +1,4 @@
-"""Named inputs that put the map<->keyframe visibility pre-filter and gates (plslam_amd/csrc/lba.hip: inside(), k_visible,
+"""Named inputs that put the map<->keyframe visibility pre-filter and gates (plslam_amd/csrc/map2kf_kernels.hip: inside(), k_visible,
 k_visible_compact, K5 k_point_gate, K6 k_line_gate; specification = the oracle's restatement, oracle/plslam_oracle.c inside /
 plo_map2kf_point_gate / plo_map2kf_line_gate, of src/mapHandler.cpp:549-551, :650-655, :601-613, :716-729) ON their
 thresholds, for tests/test_map_gate_cases_cpu.py (which checks from the input and a Python restatement alone that each class

@@ -1355,8 +1355,9 @@ int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffe
  * event order.  Deviation: an event that names a PLSLAM_FEAT_NULL feature, or an i1 / i2 beyond the keyframe's features or the
  * arrays given, is SKIPPED (the reference throws, :285-288, or reads out of bounds).
  * row_delta[n_map_kf] (HOST, int32, overwritten): the increment of full_graph[kf2][.] and of full_graph[.][kf2]; full_graph
- * stays with the caller.  Also with the caller: hasRefinement's matched_pt / matched_ls, --matches, map_*_kf_idx, desc_list /
- * dir_list / pts_list -- driven by the event records (plslam_map_insert_events).
+ * stays with the caller.  Also with the caller: hasRefinement's matched_pt / matched_ls, --matches and map_*_kf_idx -- driven by
+ * the event records (plslam_map_insert_events).  desc_list / dir_list / pts_list and the representative descriptor follow the
+ * insert on the device: plslam_map_insert_carry (below, plslam_map_lists).
  * All arithmetic fp64 without contraction: R p + t as ((r0 p0 + r1 p1) + r2 p2) + t, the norm as sqrt((x^2 + y^2) + z^2).
  *
  * plslam_map_insert_kind: HOST arrays of one landmark kind; a NULL struct or table = no entry of that kind (the kind's image is
@@ -1389,12 +1390,17 @@ typedef struct plslam_map_insert_counts {
  * n_events x 6 doubles: the direction of the new landmark's FIRST observation (zeros for an existing landmark), then that of the
  * kf2 observation -- new point: P3d.normalized() (:299), then P3d / P3d.norm() (:311); existing point: p3d.normalized() (:338);
  * map2kf point: R normalized(P) + t (:608, :618: the translation added to a direction is the reference's); lines: the
- * transformed midpoint, normalised (:449-450, :463-465, :496-498, :734-736).  Device pointers (valid until the next insert /
- * destroy, ordered on `stream`) or, for download, HOST pointers (NULL = skip; `stream` ignored). */
+ * transformed midpoint, normalised (:449-450, :463-465, :496-498, :734-736).
+ * obs_src[dst n_obs] int32 (appended behind `stream`: the struct's prefix is unchanged), the encoding of plslam_lc_fuse_buffers:
+ * >= 0 the source observation now at that position; -1 - (2 e + w): event e (its row in ev) made it, w = 0 the keyframe-1
+ * observation of a new landmark, w = 1 the keyframe-2 observation.
+ * Device pointers (valid until the next insert / destroy, ordered on `stream`) or, for download, HOST pointers (NULL = skip;
+ * `stream` ignored). */
 typedef struct plslam_map_insert_events {
     int32_t *pt_ev, *ls_ev;
     double *pt_dir, *ls_dir;
     void* stream;
+    int32_t *pt_obs_src, *ls_obs_src;
 } plslam_map_insert_events;
 typedef struct plslam_map_insert plslam_map_insert;
 int plslam_map_insert_create(plslam_ctx* ctx, plslam_map_insert** out);
@@ -1445,7 +1451,8 @@ int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_ev
  * names its indices in [0, n), acted or not); a level above PLSLAM_LC_FUSE_MAX_LEVEL -> PLSLAM_ERANGE with dst untouched.  So
  * is a call whose graph increments number 2^30 (event, pair) items or more (A / B: the list's length, D: len(a) x len(b)).
  * A run that fails after validation (PLSLAM_ENOMEM, PLSLAM_EHIP, the two refusals above) invalidates the previous run's records.
- * With the caller stay desc_list / dir_list / pts_list (one gather by obs_src; so the pts quirk of :4626 never reaches the call),
+ * desc_list / dir_list / pts_list follow on the device with plslam_lc_fuse_carry (below: one gather by obs_src from the per-tuple
+ * rows the caller gathers, so the pts quirk of :4626 stays with whoever gathers).  With the caller stay
  * map_*_kf_idx (push ev's landmark to the anchor's list for C, erase the dead landmark from the anchor's for D) and full_graph.
  * Arithmetic as plslam_map_insert_*: fp64 without contraction, R p + t as ((r0 p0 + r1 p1) + r2 p2) + t, the norm as
  * sqrt((x^2 + y^2) + z^2), the division per component.
@@ -1492,6 +1499,69 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
                        const plslam_lc_fuse_kind* lines, int32_t* graph_delta, plslam_lc_fuse_counts* counts);
 int plslam_lc_fuse_device_buffers(plslam_lc_fuse* lf, plslam_lc_fuse_buffers* out);
 int plslam_lc_fuse_download(plslam_lc_fuse* lf, const plslam_lc_fuse_buffers* host);
+
+/* ---- desc_list / dir_list / pts_list and the representative descriptor in the device-resident map ----------------------- */
+/* The per-observation side lists of MapPoint / MapLine (include/mapFeatures.h) in the observation order of plslam_map_index, and
+ * what MapPoint::updateAverageDescDir (src/mapFeatures.cpp:51-84, :121-157) derives from desc_list.  The reference runs it inside
+ * every addMapPointObservation / addMapLineObservation (:41-49, :110-119) and behind every push of a fusion
+ * (src/mapHandler.cpp:4515, :4663); the carries below refresh exactly those landmarks (K85-K88, KERNELS.md).
+ * med_obs_dir is NOT kept: the reference's average accumulates into an uninitialised vector (src/mapFeatures.cpp:88-91), which
+ * plslam_median_desc_batched declines to reproduce as well.
+ *
+ * plslam_map_lists_kind: DEVICE pointers, caller-owned; row o belongs to observation o of the image (obs_kf[o]).  Alignment: desc,
+ * med_desc and pts 16 bytes, dir 8, med_idx 4 (the kernels move the 32-byte rows as two 16-byte words). */
+typedef struct plslam_map_lists_kind {
+    uint8_t* desc;       /* n_obs x 32: desc_list                                                       */
+    double*  dir;        /* n_obs x 3 : dir_list (plslam_lc_landmarks.dirs with dir_ptr = obs_ptr)        */
+    double*  pts;        /* n_obs x 4 : pts_list, lines only (may be NULL: not carried); NULL for points  */
+    int32_t* med_idx;    /* n: position of the representative inside the landmark's list, -1 = empty list */
+    uint8_t* med_desc;   /* n x 32: the d_med_desc of plslam_map2kf_match_*_dev                           */
+    uint8_t* refreshed;  /* n, may be NULL: 1 where this call recomputed med_idx / med_desc               */
+} plslam_map_lists_kind;
+typedef struct plslam_map_lists { plslam_map_lists_kind points, lines; } plslam_map_lists;
+/* The keyframes' rows of one kind for plslam_map_insert_carry (DEVICE): desc1 n_prev x 32 (kf2kf only), desc2 n_curr x 32 -- the
+ * rows the _dev kf <-> kf drivers hold; lines: pts1 / pts2 x 4 (spl, epl).  desc 16-byte aligned, pts 16. */
+typedef struct plslam_map_insert_rows {
+    const uint8_t *desc1, *desc2;
+    const double *pts1, *pts2;
+} plslam_map_insert_rows;
+/* The per-tuple rows of one kind for plslam_lc_fuse_carry (DEVICE): desc0 / desc1 m x 32, lines pts0 / pts1 m x 4, gathered by the
+ * caller exactly as P0 / P1 of plslam_lc_fuse_kind. */
+typedef struct plslam_lc_fuse_rows {
+    const uint8_t *desc0, *desc1;
+    const double *pts0, *pts1;
+} plslam_lc_fuse_rows;
+/* All three calls ENQUEUE on the context's stream and do not synchronise: the insert / run in front of them has synchronised and
+ * left its counts on the host, so every size is known.
+ *
+ * plslam_map_lists_refresh: med_idx / med_desc of every landmark of both kinds recomputed from lists->desc with map's obs_ptr as
+ *   offsets (the rule of plslam_median_desc_batched); refreshed, where given, becomes 1.  For the first upload.
+ * plslam_map_insert_carry: after a successful plslam_map_insert_kf2kf / _map2kf on mi, with that call's images.
+ * plslam_lc_fuse_carry: after a successful plslam_lc_fuse_run on lf, with that call's images.
+ * Both carries, per kind and per destination observation j with s = obs_src[j]:
+ *   s >= 0               desc / dir / pts rows copied verbatim from row s of src_lists
+ *   s = -1 - (2 e + w)   event / tuple e made the observation: desc (pts) is the keyframe's row -- insert: desc1[i1] for w = 0,
+ *                        desc2[i2] for w = 1 (i1, i2 of the event record); fuse: desc0[e] / desc1[e]; dir is columns
+ *                        3 w .. 3 w + 2 of the event's direction record
+ * then per destination landmark: TOUCHED (it is new, its list's length changed or its valid flag changed -- every acted event
+ * lengthens one surviving landmark or empties a dead one) -> med_idx / med_desc recomputed from its destination list: element
+ * int(1 + 0.5 (n - 1)) of each sorted row of distances, the smallest value wins, the first row on ties; one observation gives 0, an
+ * empty list -1 and zero bytes; refreshed = 1.  UNTOUCHED -> med_idx / med_desc copied verbatim from src_lists, whatever is
+ * stored there (the reference does not recompute an untouched landmark); refreshed = 0.
+ * Rows beyond the destination's n_obs / n are not written.  The destination lists have the capacities of plslam_map_insert_dst.
+ * A kind's lines.pts is carried when src_lists, dst_lists and (where the kind has events) the rows all give it, and not at all
+ * when none does.
+ * PLSLAM_EINVAL, nothing launched or written: NULL arguments; no successful insert / run on the handle (a failed one invalidates
+ * the records); src_map / dst_map counts that are not the ones the handle's last call read and produced; a kind that has events
+ * (fuse: tuples) but lacks its rows; pts given by some and not all of src_lists, dst_lists and the rows; a destination list
+ * pointer equal to a source list pointer; a misaligned pointer; a list that is not memory of the context's device. */
+int plslam_map_lists_refresh(plslam_ctx* ctx, const plslam_map_index* map, const plslam_map_lists* lists);
+int plslam_map_insert_carry(plslam_map_insert* mi, const plslam_map_index* src_map, const plslam_map_lists* src_lists,
+                            const plslam_map_index* dst_map, const plslam_map_lists* dst_lists,
+                            const plslam_map_insert_rows* points, const plslam_map_insert_rows* lines);
+int plslam_lc_fuse_carry(plslam_lc_fuse* lf, const plslam_map_index* src_map, const plslam_map_lists* src_lists,
+                         const plslam_map_index* dst_map, const plslam_map_lists* dst_lists,
+                         const plslam_lc_fuse_rows* points, const plslam_lc_fuse_rows* lines);
 
 #ifdef __cplusplus
 }

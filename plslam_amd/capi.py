@@ -68,6 +68,7 @@ ABI_SYMBOLS = (
     "plslam_map_insert_device_buffers", "plslam_map_insert_download",
     "plslam_lc_fuse_create", "plslam_lc_fuse_destroy", "plslam_lc_fuse_run", "plslam_lc_fuse_device_buffers",
     "plslam_lc_fuse_download",
+    "plslam_map_lists_refresh", "plslam_map_insert_carry", "plslam_lc_fuse_carry",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -459,6 +460,10 @@ def load() -> C.CDLL:
     L.plslam_lc_fuse_run.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.plslam_lc_fuse_device_buffers.argtypes = [vp, vp]
     L.plslam_lc_fuse_download.argtypes = [vp, vp]
+    # the side lists of the device-resident map (plslam_amd/map_lists.py)
+    L.plslam_map_lists_refresh.argtypes = [vp, vp, vp]
+    L.plslam_map_insert_carry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.plslam_lc_fuse_carry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         getattr(L, name).restype = _RESTYPES.get(name, C.c_int)
     _lib = L

@@ -186,6 +186,7 @@ struct plslam_ctx {
     std::vector<char> lc_args_h;                    // ... and its host image (pageable: staged by the copy call itself)
     int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
     plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (lc_correct.hip)
+    plslam::DevBuf lists_scratch;                   // the carries' chain words and touched-landmark lists (map_lists.hip)
 };
 
 namespace plslam {

@@ -30,6 +30,7 @@
 #include "lc_fuse_plan.hpp"
 #include "lookback_dev.hpp"
 #include "map_image_dev.hpp"
+#include "map_lists_plan.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
@@ -423,7 +424,15 @@ struct plslam_lc_fuse {
     bool done = false;
     plslam_lc_fuse_buffers d = {};
     int32_t m[2] = {0, 0}, n_obs[2] = {0, 0}, nk = 0;
+    ListsRecords lists;                          // what plslam_lc_fuse_carry needs of the last run
 };
+
+const ListsRecords* plslam::lc_fuse_lists_records(plslam_lc_fuse* lf, plslam_ctx** ctx)
+{
+    if (!lf) return nullptr;
+    *ctx = lf->ctx;
+    return &lf->lists;
+}
 
 extern "C" {
 
@@ -485,6 +494,7 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
     DeviceGuard dg_(lf->ctx->device);
     hipStream_t s = lf->ctx->stream;
     lf->done = false;
+    lf->lists.valid = false;
     if ((rc = lf->buf.reserve(c.off + 256))) return rc;
     const size_t res_bytes = align256((W_WORDS + (graph_delta ? (size_t)nk * nk : 0)) * 4);
     if ((rc = lf->pin.reserve(res_bytes + P.stage_bytes))) return rc;
@@ -564,12 +574,18 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
         (k ? lf->d.ls_ev : lf->d.pt_ev) = C[k].ev;
         (k ? lf->d.ls_dir : lf->d.pt_dir) = C[k].ev_dir;
         (k ? lf->d.ls_obs_src : lf->d.pt_obs_src) = C[k].obs_src;
+        ListsKindRecords& R = lf->lists.k[k];
+        R = ListsKindRecords{};
+        R.src_n = S[k]->n; R.src_obs = S[k]->n_obs; R.dst_n = Dk[k]->n; R.dst_obs = Dk[k]->n_obs;
+        R.n_ev = P.k[k].m; R.bound[0] = R.bound[1] = P.k[k].m; R.ev_stride = 0; R.need_side0 = 1;
+        R.ev = C[k].ev; R.dir = C[k].ev_dir; R.obs_src = C[k].obs_src;
     }
     dst->map.n_map_kf = nk;
     lf->nk = nk;
     lf->d.graph_delta = graph;
     lf->d.stream = (void*)s;
     lf->done = true;
+    lf->lists.valid = true;
     return PLSLAM_OK;
 }
 

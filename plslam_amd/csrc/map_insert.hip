@@ -7,8 +7,8 @@
 //       directions; integer atomics COUNT the appended observations per landmark and keep the smallest / largest event number
 //       per landmark / per keyframe-2 feature -- none of them decides an order
 //   K64 the new obs_ptr: a look-back scan over n + n_new landmarks; valid / inlier / X copied, the new rows computed
-//   K65 obs_kf / obs_val: a lane per OUTPUT observation, its landmark by bisection (K61); the old entry copied or the event's
-//       written -- the k-th event of a landmark is found by walking the event list from the landmark's first event, in event order
+//   K65 obs_kf / obs_val / obs_src: a lane per OUTPUT observation, its landmark by bisection (K61); the old entry copied or the
+//       event's written; obs_src says which (the records plslam_map_insert_carry gathers the side lists by) -- the k-th event of a landmark is found by walking the event list from the landmark's first event, in event order
 //   K66 feat_idx (copy; the last event of a keyframe-2 feature wins; a new landmark's keyframe-1 feature) and row_delta: a lane
 //       per (event, old observation), int32 atomic adds
 //   K67 the counts and row_delta to the page-locked block the host reads
@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "lookback_dev.hpp"
 #include "map_image_dev.hpp"
+#include "map_lists_plan.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
@@ -35,7 +36,7 @@ struct CallD {                          // one kind's tables and scratch (device
     const double* T;                    // T_kf1_w, T_kf2_w: 2 x 16
     const int32_t* tab;
     const double *P1, *o1, *P2, *o2;
-    int32_t *i1_lm, *ev, *pair_off, *new_ev, *app_cnt, *head, *feat_win, *cnt;
+    int32_t *i1_lm, *ev, *pair_off, *new_ev, *app_cnt, *head, *feat_win, *cnt, *obs_src;
     double* ev_dir;
 };
 
@@ -192,7 +193,7 @@ k_mi_obs(MapKindSrc S, MapKindDst D, CallD C)
     if (t >= total || t >= D.obs_cap || n2 <= 0) return;
     const int32_t j = (int32_t)t;
     const int32_t lm = segment_of(D.obs_ptr, n2, j), o = j - D.obs_ptr[lm];
-    int32_t kf = -1;
+    int32_t kf = -1, tag = INT32_MIN;                           // (tag: an event beyond every list unless found below)
     const double* val = nullptr;
     if (lm < S.n) {
         const int32_t ol = old_len(S, lm);
@@ -200,6 +201,7 @@ k_mi_obs(MapKindSrc S, MapKindDst D, CallD C)
             const size_t src = (size_t)S.obs_ptr[lm] + o;
             kf = S.obs_kf[src];
             val = S.obs_val + (size_t)S.dv * src;
+            tag = (int32_t)src;
         } else {
             int32_t k = o - ol, e = C.head[lm];
             for (; e >= 0 && e < n_ev; ++e)
@@ -207,14 +209,18 @@ k_mi_obs(MapKindSrc S, MapKindDst D, CallD C)
             if (e >= 0 && e < n_ev) {
                 kf = C.kf2;
                 val = C.o2 + (size_t)S.dv * C.ev[4 * (size_t)e + 2];
+                tag = -1 - (2 * e + 1);
             }
         }
     } else {
-        const int32_t* rec = C.ev + 4 * (size_t)C.new_ev[lm - S.n];
+        const int32_t e = C.new_ev[lm - S.n];
+        const int32_t* rec = C.ev + 4 * (size_t)e;
         kf = o == 0 ? C.kf1 : C.kf2;
         val = o == 0 ? C.o1 + (size_t)S.dv * rec[1] : C.o2 + (size_t)S.dv * rec[2];
+        tag = -1 - (2 * e + (o == 0 ? 0 : 1));
     }
     D.obs_kf[j] = kf;
+    C.obs_src[j] = tag;
     for (int w = 0; w < S.dv; ++w) D.obs_val[(size_t)S.dv * j + w] = val ? val[w] : 0.0;
 }
 
@@ -281,6 +287,7 @@ struct plslam_map_insert {
     bool done = false;
     plslam_map_insert_events d = {};
     int32_t n_ev[2] = {0, 0};
+    ListsRecords lists;                          // what plslam_map_insert_carry needs of the last insert
 };
 
 namespace {
@@ -289,7 +296,7 @@ struct KindPlan {                                // one kind of one call, host s
     const plslam_map_insert_kind* in = nullptr;  // nullptr: no table
     int32_t n_tab = 0, n_prev = 0, n_curr = 0, m = 0, dl = 3, dv = 2;
     size_t o_tab, o_P1, o_o1, o_P2, o_o2;        // in the staged block
-    size_t o_i1lm, o_ev, o_dir, o_pair, o_new, o_app, o_head, o_win, o_part;
+    size_t o_i1lm, o_ev, o_dir, o_pair, o_new, o_app, o_head, o_win, o_part, o_osrc;
     unsigned w_tab = 1, w_lm = 1;
 };
 
@@ -350,10 +357,13 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         P.o_i1lm = c.take((size_t)P.n_tab * 4 + 4); P.o_ev = c.take((size_t)P.m * 16 + 16); P.o_dir = c.take((size_t)P.m * 48 + 48);
         P.o_pair = c.take((size_t)P.m * 4 + 4); P.o_new = c.take((size_t)P.m * 4 + 4);
     }
+    for (int k = 0; k < 2; ++k)                                  // (behind everything else: the layout in front is unchanged)
+        K[k].o_osrc = c.take(((size_t)S[k]->n_obs + (mode == MODE_KF2KF ? 2 : 1) * (size_t)K[k].m) * 4 + 4);
     std::lock_guard<std::mutex> lk(mi->ctx->mu);
     DeviceGuard dg_(mi->ctx->device);
     hipStream_t s = mi->ctx->stream;
     mi->done = false;
+    mi->lists.valid = false;
     int rc = mi->buf.reserve(c.off + 256);
     if (rc) return rc;
     const size_t res_bytes = align256((W_WORDS + (size_t)nk) * 4);
@@ -406,6 +416,7 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         C.i1_lm = (int32_t*)(d + P.o_i1lm); C.ev = (int32_t*)(d + P.o_ev); C.pair_off = (int32_t*)(d + P.o_pair);
         C.new_ev = (int32_t*)(d + P.o_new); C.app_cnt = (int32_t*)(d + P.o_app); C.head = (int32_t*)(d + P.o_head);
         C.feat_win = (int32_t*)(d + P.o_win); C.cnt = cnt + W_KIND * k; C.ev_dir = (double*)(d + P.o_dir);
+        C.obs_src = (int32_t*)(d + P.o_osrc);
         uint32_t* part = (uint32_t*)(d + P.o_part);
         hipLaunchKernelGGL(k_mi_events, dim3(P.w_tab), dim3(MAP_TILE), 0, s, Sd, C, part, part + P.w_tab, part + 2 * P.w_tab);
         hipLaunchKernelGGL(k_mi_ptr, dim3(P.w_lm), dim3(MAP_TILE), 0, s, Sd, Dd, C, part + 3 * P.w_tab);
@@ -415,6 +426,7 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         hipLaunchKernelGGL(k_mi_feat_rows, dim3(g < MI_MAX_GRID ? g : MI_MAX_GRID), dim3(MAP_TILE), 0, s, Sd, Dd, C, row);
         (k ? mi->d.ls_ev : mi->d.pt_ev) = C.ev;
         (k ? mi->d.ls_dir : mi->d.pt_dir) = C.ev_dir;
+        (k ? mi->d.ls_obs_src : mi->d.pt_obs_src) = C.obs_src;
     }
     hipLaunchKernelGGL(k_mi_publish, dim3(1), dim3(MAP_TILE), 0, s, (const int32_t*)cnt, (const int32_t*)row, nk, (int32_t*)mi->pin.dev);
     PLSLAM_HIP_CHECK(hipGetLastError());
@@ -430,14 +442,28 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
         Dk[k]->n = S[k]->n + w[W_NEW];
         Dk[k]->n_obs = w[W_OBS];
         Dk[k]->n_feat = S[k]->n_feat;
+        ListsKindRecords& R = mi->lists.k[k];
+        R = ListsKindRecords{};
+        R.src_n = S[k]->n; R.src_obs = S[k]->n_obs; R.dst_n = Dk[k]->n; R.dst_obs = Dk[k]->n_obs;
+        R.n_ev = w[W_EV]; R.bound[0] = K[k].n_prev; R.bound[1] = K[k].n_curr; R.ev_stride = 4; R.need_side0 = mode == MODE_KF2KF;
+        R.ev = k ? mi->d.ls_ev : mi->d.pt_ev; R.dir = k ? mi->d.ls_dir : mi->d.pt_dir;
+        R.obs_src = k ? mi->d.ls_obs_src : mi->d.pt_obs_src;
     }
     dst->map.n_map_kf = nk;
     mi->d.stream = (void*)s;
     mi->done = true;
+    mi->lists.valid = true;
     return PLSLAM_OK;
 }
 
 }  // namespace
+
+const ListsRecords* plslam::map_insert_lists_records(plslam_map_insert* mi, plslam_ctx** ctx)
+{
+    if (!mi) return nullptr;
+    *ctx = mi->ctx;
+    return &mi->lists;
+}
 
 extern "C" {
 
@@ -483,7 +509,9 @@ int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_ev
     std::lock_guard<std::mutex> lk(mi->ctx->mu);
     DeviceGuard dg_(mi->ctx->device);
     const DownloadItem items[] = {{host->pt_ev, mi->d.pt_ev, (size_t)mi->n_ev[0] * 16}, {host->pt_dir, mi->d.pt_dir, (size_t)mi->n_ev[0] * 48},
-                                  {host->ls_ev, mi->d.ls_ev, (size_t)mi->n_ev[1] * 16}, {host->ls_dir, mi->d.ls_dir, (size_t)mi->n_ev[1] * 48}};
+                                  {host->ls_ev, mi->d.ls_ev, (size_t)mi->n_ev[1] * 16}, {host->ls_dir, mi->d.ls_dir, (size_t)mi->n_ev[1] * 48},
+                                  {host->pt_obs_src, mi->d.pt_obs_src, (size_t)mi->lists.k[0].dst_obs * 4},
+                                  {host->ls_obs_src, mi->d.ls_obs_src, (size_t)mi->lists.k[1].dst_obs * 4}};
     return download_items(items, mi->ctx->stream);
 }
 

@@ -12,36 +12,26 @@
 // directly the query matrix of the map<->keyframe matcher (mapHandler.cpp:545-561).
 //
 // K12 k_row_medians: one lane per (landmark, observation) = one row of conf.  The k-th order
-//   statistic of the row is found by bisection on the value range [0,256] (lists of up to 16
-//   observations keep the row in a lane-private LDS column; longer ones recompute the distances
-//   per probe: 9 x n XOR+popcount distances per lane, rows come from L1/L2) and the
+//   statistic of the row is found by bisection on the value range [0,256] (median_desc_dev.hpp, shared
+//   with K87 of map_lists.hip: lists of up to 16 observations keep the row in a lane-private LDS
+//   column; longer ones recompute the distances per probe, rows come from L1/L2) and the
 //   row's key (value << 23 | i) is folded into the landmark's slot with atomicMin -- min over keys
 //   is exactly "smallest value, then smallest i", independent of execution order.
 // K13 k_select_median: decodes the slot in place (idempotent, so no ordering between the lanes that
 //   read it is needed) and gathers the winner's 32 bytes.
 #include "common.hpp"
+#include "median_desc_dev.hpp"
 
 namespace plslam {
 namespace {
 
-constexpr uint32_t IDX_BITS = 23, IDX_MASK = (1u << IDX_BITS) - 1u;
-constexpr int ROW_CACHE = 16;      // lists up to this long keep their distance row in LDS
+constexpr uint32_t IDX_MASK = MEDIAN_IDX_MASK;
 
-// (not mfma_h_common.hpp's hamming256 of four vector registers: the builtin, so that the compiler selects the popcount for a
-// row it reads from memory -- the asm form pins v_bcnt_u32_b32 and its operand order)
-__device__ __forceinline__ int hamming256(const uint32_t (&q)[8], const uint32_t* __restrict__ t)
+__global__ __launch_bounds__(MEDIAN_NT) void k_row_medians(const uint32_t* __restrict__ desc,
+                                                           const int32_t* __restrict__ off, int32_t n_lm,
+                                                           int32_t total, uint32_t* __restrict__ slot)
 {
-    int d = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) d += __popc(q[w] ^ t[w]);
-    return d;
-}
-
-__global__ __launch_bounds__(256) void k_row_medians(const uint32_t* __restrict__ desc,
-                                                     const int32_t* __restrict__ off, int32_t n_lm,
-                                                     int32_t total, uint32_t* __restrict__ slot)
-{
-    __shared__ uint16_t row_cache[ROW_CACHE][256];      // 8 KB
+    __shared__ uint16_t row_cache[MEDIAN_ROW_CACHE][MEDIAN_NT];      // 8 KB
     const int32_t t = (int32_t)(blockIdx.x * 256u + threadIdx.x);
     if (t >= total) return;
     // landmark of observation t: the last l with off[l] <= t (skips empty lists)
@@ -55,32 +45,8 @@ __global__ __launch_bounds__(256) void k_row_medians(const uint32_t* __restrict_
         slot[lo] = 0u;
         return;
     }
-    const int32_t k = 1 + ((n - 1) >> 1);          // == int(1 + 0.5*(n-1)) for n >= 1
-    uint32_t q[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) q[w] = desc[(int64_t)t * 8 + w];
-    const uint32_t* rows = desc + (int64_t)s * 8;
-    // smallest v with #{j : d(i,j) <= v} >= k+1  ==  sorted(row)[k]
-    int32_t vlo = 0, vhi = 256;
-    if (n <= ROW_CACHE) {
-        // the usual case: the row of conf lives in this lane's LDS column (lane-private, no barrier)
-        for (int32_t j = 0; j < n; ++j) row_cache[j][threadIdx.x] = (uint16_t)hamming256(q, rows + (int64_t)j * 8);
-        while (vlo < vhi) {
-            const int32_t mid = (vlo + vhi) >> 1;
-            int32_t cnt = 0;
-            for (int32_t j = 0; j < n; ++j) cnt += (int32_t)row_cache[j][threadIdx.x] <= mid;
-            if (cnt >= k + 1) vhi = mid; else vlo = mid + 1;
-        }
-    } else {
-        // long lists: recompute the distances per probe instead of storing n of them
-        while (vlo < vhi) {
-            const int32_t mid = (vlo + vhi) >> 1;
-            int32_t cnt = 0;
-            for (int32_t j = 0; j < n; ++j) cnt += hamming256(q, rows + (int64_t)j * 8) <= mid;
-            if (cnt >= k + 1) vhi = mid; else vlo = mid + 1;
-        }
-    }
-    atomicMin(slot + lo, ((uint32_t)vlo << IDX_BITS) | (uint32_t)(t - s));
+    // the row's order statistic and key: median_desc_dev.hpp
+    atomicMin(slot + lo, median_row_key(desc, s, n, t - s, row_cache));
 }
 
 __global__ __launch_bounds__(256) void k_select_median(const uint32_t* __restrict__ desc,

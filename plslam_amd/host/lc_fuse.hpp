@@ -2,8 +2,8 @@
 // MapHandler::loopClosureFuseLandmarks (src/mapHandler.cpp:4412-4687) over the pair of device images map_insert.hpp's MapImages
 // keeps.  pack() turns lc_idx_list / lc_pt_idxs / lc_ls_idxs and the keyframes' features, as the reference holds them, into the
 // call's arrays; Fuser::run() fuses from the current image into the other one; apply() brings the caller's own containers up to
-// date from the records: full_graph, map_points_kf_idx / map_lines_kf_idx and, by one gather, any per-observation list
-// (desc_list, dir_list, pts_list).  No PL-SLAM type here.
+// date from the records: full_graph, map_points_kf_idx / map_lines_kf_idx and, by one gather, any per-observation list the
+// caller still keeps on the host (desc_list, dir_list, pts_list on the device: map_lists.hpp's MapLists::carry).  No PL-SLAM type here.
 #pragma once
 
 #include <algorithm>
@@ -119,6 +119,7 @@ public:
         check(plslam_lc_fuse_download(lf_, &h), "lc_fuse_download");
         return out;
     }
+    plslam_lc_fuse* handle() const { return lf_; }              // (whose records describe the last run: map_lists.hpp)
 
 private:
     plslam_lc_fuse* lf_ = nullptr;

@@ -2,8 +2,8 @@
 // keeps the CSR image of the map (plslam_map_index) on the device in TWO copies with room to grow and runs the insertion loops of
 // MapHandler::matchKF2KFPoints / Lines (src/mapHandler.cpp:280-360, :428-527) and matchMap2KFPoints / Lines (:601-629, :716-749)
 // from one into the other, so that the image never travels: index() is what plslam_local_map_* take next.  The caller keeps
-// full_graph (row_delta), desc_list / dir_list / pts_list and map_*_kf_idx (the events).  No PL-SLAM type here; the HIP runtime is
-// used for the images' device memory only.
+// full_graph (row_delta) and map_*_kf_idx (the events); desc_list / dir_list / pts_list follow on the device with map_lists.hpp's
+// MapLists::carry.  No PL-SLAM type here; the HIP runtime is used for the images' device memory only.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -64,6 +64,9 @@ public:
 
     // the image the calls read next (device pointers)
     const plslam_map_index& index() const { return img_[cur_].d.map; }
+    // the image the last insert / pingpong READ, and the handle whose records describe that call (map_lists.hpp)
+    const plslam_map_index& previous() const { return img_[1 - cur_].d.map; }
+    plslam_map_insert* handle() const { return mi_; }
 
     // uploads a host image (every keyframe slot, kf2 included, is in it)
     void upload(const HostImage& h)

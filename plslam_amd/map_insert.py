@@ -38,7 +38,8 @@ class MapInsertCounts(C.Structure):
 
 
 class MapInsertEvents(C.Structure):
-    _fields_ = [("pt_ev", _vp), ("ls_ev", _vp), ("pt_dir", _vp), ("ls_dir", _vp), ("stream", _vp)]
+    _fields_ = [("pt_ev", _vp), ("ls_ev", _vp), ("pt_dir", _vp), ("ls_dir", _vp), ("stream", _vp), ("pt_obs_src", _vp),
+                ("ls_obs_src", _vp)]
 
 
 def insert_bounds(m, kf, mode: str) -> dict:
@@ -145,6 +146,7 @@ class MapInsert:
         _check(self._L.plslam_map_insert_create(ctx.handle, C.byref(h)), "plslam_map_insert_create")
         self._h = h
         self._n_ev = (0, 0)
+        self._n_obs = (0, 0)
 
     def _call(self, mode, src, dst: DeviceMapImage, kf) -> dict:
         ks, keep = [], []
@@ -168,6 +170,7 @@ class MapInsert:
         for kind, kc in (("points", c.points), ("lines", c.lines)):
             out[kind] = dict(n_events=kc.n_events, n_new=kc.n_new, n_appended=kc.n_appended, n_skipped=kc.n_skipped)
         self._n_ev = (c.points.n_events, c.lines.n_events)
+        self._n_obs = (dst.struct.points.n_obs, dst.struct.lines.n_obs)
         return out
 
     def kf2kf(self, src, dst: DeviceMapImage, kf) -> dict:
@@ -185,13 +188,15 @@ class MapInsert:
         return {k: (getattr(b, k) or 0) for k, _ in MapInsertEvents._fields_}
 
     def download(self) -> dict:
-        """the event records of the last insert: dict(points / lines: dict(ev (n, 4) int32, dir (n, 6) float64))"""
+        """the records of the last insert: dict(points / lines: dict(ev (n, 4) int32, dir (n, 6) float64, obs_src (n_obs,) int32))"""
         out, b = {}, MapInsertEvents()
-        for kind, tag, n in (("points", "pt", self._n_ev[0]), ("lines", "ls", self._n_ev[1])):
-            out[kind] = dict(ev=np.zeros((n, 4), np.int32), dir=np.zeros((n, 6), np.float64))
+        for kind, tag, n, n_obs in (("points", "pt", self._n_ev[0], self._n_obs[0]), ("lines", "ls", self._n_ev[1], self._n_obs[1])):
+            out[kind] = dict(ev=np.zeros((n, 4), np.int32), dir=np.zeros((n, 6), np.float64), obs_src=np.zeros(n_obs, np.int32))
             if n:
                 setattr(b, tag + "_ev", _p(out[kind]["ev"]))
                 setattr(b, tag + "_dir", _p(out[kind]["dir"]))
+            if n_obs:
+                setattr(b, tag + "_obs_src", _p(out[kind]["obs_src"]))
         _check(self._L.plslam_map_insert_download(self._h, C.addressof(b)), "plslam_map_insert_download")
         return out
 

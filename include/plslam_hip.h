@@ -1161,6 +1161,54 @@ int plslam_gba_optimize(plslam_gba_plan* plan, double lambda_lba_lm, double lamb
                         const double* T_kf_w, const double* x_kf, const double* Xw, const double* Lw, double* x_kf_out,
                         double* T_out, double* Xw_out, double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result);
 void plslam_gba_plan_destroy(plslam_gba_plan* plan);
+/* The same plan built ON THE DEVICE from DEVICE columns (additive within 5; K89-K96, KERNELS.md): plslam_gba_plan_create's
+ * signature with d_kf_list (nkf), d_pt_obs (n x 6), d_pt_obs_uv (n x 2), d_ls_obs (n x 6), d_ls_l_obs (n x 3) as device pointers
+ * -- what plslam_local_map_form_all + plslam_local_map_gather leave in plslam_local_map_buffers (kf_list, pt_obs, pt_obs_uv, ls_obs,
+ * ls_l_obs) -- read on the context's stream.  Every list gba_lists_build makes on the host -- the per-observation arrays, the four
+ * CSR lists, the covisible blocks, their chunks of at most 64 pairs and the compact pair list -- is built on the device, equal
+ * entry for entry (plslam_gba_plan_lists shows them); the inner LBA plan is plslam_lba_plan_create_dev with n_pose_slots =
+ * n_map_kf + nkf and first_estimate_slot = n_map_kf.  The plan keeps no host copy of any list but kf_list (downloaded once).
+ * The checks are the host call's, made on the device: a column out of range, kf_list[v4] != v3, a kf_list entry out of range give
+ * PLSLAM_EINVAL and no plan, and no kernel follows a bad index.  Refused before anything is launched, as the host call refuses
+ * them: nkf < 1, nkf > PLSLAM_GBA_MAX_KEYFRAMES, homog_th != 1e-7, NULL or negative arguments, the 32-bit size limits; also
+ * n_map_kf < 1 and observations of a kind with no landmark (rows the host builder refuses one by one).
+ * PLSLAM_ERANGE: 2^30 or more observation pairs (the look-back's sums are 30-bit words, as for the LBA plan's device-built lists;
+ * the host builder's limit is INT32_MAX pairs, PLSLAM_EINVAL) -- refused after the count, before any pair is emitted.  36 x the
+ * chunk count at or above INT32_MAX: PLSLAM_EINVAL like the host, refused when the chunk total is known (behind the emit, before
+ * anything is carved from it).
+ * Synchronisations: the inner LBA plan's one, plus TWO here (the pair total, from which the scratch is carved; the block and
+ * chunk totals, from which the solve's buffers are).  The last layout kernel is enqueued behind the second one on the context's
+ * stream, which every later call of the plan uses.  Every plslam_gba_* call works on the plan. */
+int plslam_gba_plan_create_dev(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf,
+                               const int32_t* d_kf_list, int32_t npt, int32_t nls, const int32_t* d_pt_obs,
+                               const double* d_pt_obs_uv, int32_t n_pt_obs, const int32_t* d_ls_obs, const double* d_ls_l_obs,
+                               int32_t n_ls_obs, plslam_gba_plan** out);
+/* The lists of a plan of either kind, device -> host: a debugging aid (what the tests compare).  plslam_gba_plan_list_sizes gives
+ * the lengths.  plslam_gba_plan_lists: HOST pointers, NULL = skip.
+ *   blk (nblk x 4 int32: k1, k2, c0, c1), chk (nchunk x 4: block, kind, first pair, pair count), pair (n_pairs x 2: o1, o2);
+ *   plm / pkf (n_pt_obs), llm / lkf (n_ls_obs): landmark local index, keyframe local index or -1;
+ *   kpp / klp (nkf + 1), kpo (n_kpo), klo (n_klo): optimised keyframe -> its observations;
+ *   lpp (npt + 1) / lpo (n_lpo), llp (nls + 1) / llo (n_llo): landmark -> its observations by optimised keyframes. */
+typedef struct plslam_gba_list_sizes {
+    int32_t nkf, npt, nls, n_pt_obs, n_ls_obs;
+    int32_t nblk, nchunk, n_pairs, n_lpo, n_llo, n_kpo, n_klo;
+} plslam_gba_list_sizes;
+typedef struct plslam_gba_lists {
+    int32_t *blk, *chk, *pair;
+    int32_t *plm, *pkf, *llm, *lkf;
+    int32_t *kpp, *kpo, *klp, *klo, *lpp, *lpo, *llp, *llo;
+} plslam_gba_lists;
+int plslam_gba_plan_list_sizes(plslam_gba_plan* plan, plslam_gba_list_sizes* out);
+int plslam_gba_plan_lists(plslam_gba_plan* plan, const plslam_gba_lists* host);
+/* plslam_gba_optimize's loop -- one shared body, the same kernels, the same bits -- on state that lives on the device: d_x_kf
+ * (nkf x 6), d_Xw (npt x 3), d_Lw (nls x 6) are DEVICE pointers (for the gather: X_aux, X_aux + 6 nkf, X_aux + 6 nkf + 3 npt),
+ * copied device to device into the plan's state on the context's stream.  T_kf_w (n_map_kf x 16) stays a HOST pointer: poses stay
+ * with the host, as everywhere in this library.  x_kf_out, T_out (may be NULL), trace and result come back to the host; the
+ * landmarks stay resident in the plan (plslam_local_map_apply_gba writes them into the map image).  Works on a plan of either
+ * kind, as plslam_gba_optimize does. */
+int plslam_gba_optimize_dev(plslam_gba_plan* plan, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba,
+                            const double* T_kf_w, const double* d_x_kf, const double* d_Xw, const double* d_Lw, double* x_kf_out,
+                            double* T_out, plslam_gba_solve* trace, plslam_gba_result* result);
 int plslam_dense_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots);
 
 /* ---- K40-K53: loop-closure correction (MapHandler::loopClosureOptimizationCovGraphG2O, src/mapHandler.cpp:4185-4410, up to
@@ -1334,6 +1382,19 @@ typedef struct plslam_local_map_lba_dst {
 } plslam_local_map_lba_dst;
 int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, const plslam_local_map_lba_dst* dst, double moved_th,
                                plslam_local_map_counts* counts);
+/* The flags of globalBundleAdjustment's gather (:1995-2092: localBundleAdjustment's gather without the ->local tests):
+ * kf_local[i] = kf_valid[i], pt_local = valid, ls_local = valid; counts: the three form fields; the handle is formed.
+ * plslam_local_map_gather then yields the GBA's kf_list (every non-NULL keyframe but slot 0), pt_list, ls_list, the Vector6i
+ * rows, pt_obs_uv, ls_l_obs and X_aux, order for order.  form_all OVERWRITES the flags of the last plslam_local_map_form: a
+ * plslam_local_map_cull or plslam_local_map_candidates afterwards needs a new form. */
+int plslam_local_map_form_all(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts);
+/* The write-back of globalBundleAdjustment (:2681-2697) from the GBA plan's RESIDENT landmarks into the image, after gather on the
+ * handle: X[pt_list[i]] = Xw[i], X[ls_list[i]] = Lw[i], verbatim copies.  No moved test; inlier is not touched (dst's inlier
+ * pointers are ignored and may be NULL).  x_kf_w is not written: the reference stores only T_kf_w = expmap_se3(X) (:2676-2680),
+ * which is plslam_gba_optimize's T_out.  One launch on the context's stream, one synchronisation.
+ * PLSLAM_EINVAL: no gather has run on the handle; the plan's npt / nls differ from the gather's counts; no optimize has run on the
+ * plan; the plan belongs to another context. */
+int plslam_local_map_apply_gba(plslam_local_map* lm, plslam_gba_plan* plan, const plslam_local_map_lba_dst* dst);
 int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out);
 int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffers* host);
 

@@ -59,11 +59,12 @@ ABI_SYMBOLS = (
     "plslam_lc_batch_create", "plslam_lc_batch_destroy", "plslam_lc_batch_verify", "plslam_lc_batch_verify_dev",
     "plslam_relpose_robust_gn_batched_dev",
     "plslam_gba_plan_create", "plslam_gba_optimize", "plslam_gba_plan_destroy", "plslam_dense_ldlt_solve",
+    "plslam_gba_plan_create_dev", "plslam_gba_plan_list_sizes", "plslam_gba_plan_lists", "plslam_gba_optimize_dev",
     "plslam_pgo_plan_create", "plslam_pgo_optimize", "plslam_pgo_plan_destroy", "plslam_lc_correct_map",
     "plslam_lc_correct_map_dev", "plslam_envelope_ldlt_solve",
     "plslam_local_map_create", "plslam_local_map_destroy", "plslam_local_map_form", "plslam_local_map_candidates",
     "plslam_local_map_gather", "plslam_local_map_cull", "plslam_local_map_device_buffers", "plslam_local_map_download",
-    "plslam_local_map_apply_lba",
+    "plslam_local_map_apply_lba", "plslam_local_map_form_all", "plslam_local_map_apply_gba",
     "plslam_map_insert_create", "plslam_map_insert_destroy", "plslam_map_insert_kf2kf", "plslam_map_insert_map2kf",
     "plslam_map_insert_device_buffers", "plslam_map_insert_download",
     "plslam_lc_fuse_create", "plslam_lc_fuse_destroy", "plslam_lc_fuse_run", "plslam_lc_fuse_device_buffers",
@@ -84,6 +85,20 @@ class GbaSolve(C.Structure):
     """plslam_gba_solve: one record per solve of plslam_gba_optimize"""
     _fields_ = [("lambda_", C.c_double), ("err_raw", C.c_double), ("err", C.c_double), ("dx_norm", C.c_double),
                 ("n_singular", C.c_int32), ("n_bad_pivots", C.c_int32), ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GbaListSizes(C.Structure):
+    """plslam_gba_list_sizes"""
+    _fields_ = [(k, C.c_int32) for k in ("nkf", "npt", "nls", "n_pt_obs", "n_ls_obs", "nblk", "nchunk", "n_pairs", "n_lpo", "n_llo",
+                                         "n_kpo", "n_klo")]
+
+
+GBA_LIST_NAMES = ("blk", "chk", "pair", "plm", "pkf", "llm", "lkf", "kpp", "kpo", "klp", "klo", "lpp", "lpo", "llp", "llo")
+
+
+class GbaLists(C.Structure):
+    """plslam_gba_lists: host pointers, NULL = skip"""
+    _fields_ = [(k, C.c_void_p) for k in GBA_LIST_NAMES]
 
 
 class GbaResult(C.Structure):
@@ -430,6 +445,10 @@ def load() -> C.CDLL:
     L.plslam_gba_plan_create.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(vp)]
     L.plslam_gba_optimize.argtypes = [vp, f64, f64, i32] + [vp] * 8 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)]
     L.plslam_gba_plan_destroy.argtypes = [vp]
+    L.plslam_gba_plan_create_dev.argtypes = [vp, C.POINTER(Cam), f64, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, C.POINTER(vp)]
+    L.plslam_gba_plan_list_sizes.argtypes = [vp, C.POINTER(GbaListSizes)]
+    L.plslam_gba_plan_lists.argtypes = [vp, vp]
+    L.plslam_gba_optimize_dev.argtypes = [vp, f64, f64, i32] + [vp] * 6 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)]
     L.plslam_dense_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32)]
     L.plslam_pgo_plan_create.argtypes = [vp, C.POINTER(PgoParams), i32, vp, vp, i32, vp, C.POINTER(vp)]
     L.plslam_pgo_optimize.argtypes = [vp] + [vp] * 7 + [C.POINTER(PgoTrial), i32, C.POINTER(PgoResult)]
@@ -447,6 +466,8 @@ def load() -> C.CDLL:
     L.plslam_local_map_device_buffers.argtypes = [vp, vp]
     L.plslam_local_map_download.argtypes = [vp, vp]
     L.plslam_local_map_apply_lba.argtypes = [vp, vp, vp, f64, vp]
+    L.plslam_local_map_form_all.argtypes = [vp, vp, vp]
+    L.plslam_local_map_apply_gba.argtypes = [vp, vp, vp]
     # the map insertion (plslam_amd/map_insert.py): structs by address, host arrays as pointers
     L.plslam_map_insert_create.argtypes = [vp, C.POINTER(vp)]
     L.plslam_map_insert_destroy.argtypes = [vp]
@@ -1573,6 +1594,43 @@ class GbaPlan:
                                               C.byref(h)), "plslam_gba_plan_create")
         self._h = h
 
+    @classmethod
+    def from_device(cls, ctx: Context, cam: Cam, n_map_kf, nkf, d_kf_list, npt, nls, d_pt_obs, d_pt_uv, n_pt_obs, d_ls_obs, d_ls_l,
+                    n_ls_obs, homog_th=1e-7):
+        """plslam_gba_plan_create_dev: the same plan from DEVICE columns (addresses as ints), e.g. what LocalMap.form_all +
+        .gather leave in LocalMap.device_buffers(): kf_list, pt_obs, pt_obs_uv, ls_obs, ls_l_obs."""
+        self = cls.__new__(cls)
+        self._L, self._ctx, self._h = ctx._L, ctx, None
+        self.dims = (int(n_map_kf), int(nkf), int(npt), int(nls))
+        h = C.c_void_p()
+        _check(self._L.plslam_gba_plan_create_dev(ctx.handle, C.byref(cam), float(homog_th), int(n_map_kf), int(nkf),
+                                                  d_kf_list or None, int(npt), int(nls), d_pt_obs or None, d_pt_uv or None,
+                                                  int(n_pt_obs), d_ls_obs or None, d_ls_l or None, int(n_ls_obs), C.byref(h)),
+               "plslam_gba_plan_create_dev")
+        self._h = h
+        return self
+
+    def lists(self) -> dict:
+        """The plan's lists as host arrays (plslam_gba_plan_lists): blk (nblk, 4), chk (nchunk, 4), pair (n, 2), plm / pkf /
+        llm / lkf and the eight CSR arrays -- of a host-built or a device-built plan."""
+        z = GbaListSizes()
+        _check(self._L.plslam_gba_plan_list_sizes(self._h, C.byref(z)), "plslam_gba_plan_list_sizes")
+        shape = dict(blk=(z.nblk, 4), chk=(z.nchunk, 4), pair=(z.n_pairs, 2), plm=(z.n_pt_obs,), pkf=(z.n_pt_obs,), llm=(z.n_ls_obs,),
+                     lkf=(z.n_ls_obs,), kpp=(z.nkf + 1,), kpo=(z.n_kpo,), klp=(z.nkf + 1,), klo=(z.n_klo,), lpp=(z.npt + 1,),
+                     lpo=(z.n_lpo,), llp=(z.nls + 1,), llo=(z.n_llo,))
+        out, b = {}, GbaLists()
+        for k in GBA_LIST_NAMES:
+            out[k] = np.zeros(shape[k], np.int32)
+            setattr(b, k, _p(out[k]) if out[k].size else None)
+        _check(self._L.plslam_gba_plan_lists(self._h, C.addressof(b)), "plslam_gba_plan_lists")
+        return out
+
+    def _result(self, tr, res, **state) -> dict:
+        trace = [dict(lam=t.lambda_, err_raw=t.err_raw, err=t.err, dx_norm=t.dx_norm, n_singular=t.n_singular,
+                      n_bad_pivots=t.n_bad_pivots, accepted=bool(t.accepted)) for t in tr[:res.n_solves]]
+        return dict(state, trace=trace, iters=res.iters, n_solves=res.n_solves, stop_reason=res.stop_reason, err=res.err,
+                    err_prev=res.err_prev, lam=res.lambda_, hmax=res.hmax)
+
     def optimize(self, T_kf_w, x_kf, Xw, Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15) -> dict:
         """The LM loop -> dict(x_kf (nkf, 6), T (nkf, 4, 4), Xw (npt, 3), Lw (nls, 6), trace (one dict per solve), iters,
         n_solves, stop_reason, err, err_prev, lam, hmax)."""
@@ -1585,10 +1643,21 @@ class GbaPlan:
         res = GbaResult()
         _check(self._L.plslam_gba_optimize(self._h, float(lambda_lm), float(lambda_k), int(max_iters), _p(T), _p(x), _p(X),
                                            _p(Lm), _p(xo), _p(To), _p(Xo), _p(Lo), tr, C.byref(res)), "plslam_gba_optimize")
-        trace = [dict(lam=t.lambda_, err_raw=t.err_raw, err=t.err, dx_norm=t.dx_norm, n_singular=t.n_singular,
-                      n_bad_pivots=t.n_bad_pivots, accepted=bool(t.accepted)) for t in tr[:res.n_solves]]
-        return dict(x_kf=xo, T=To, Xw=Xo, Lw=Lo, trace=trace, iters=res.iters, n_solves=res.n_solves,
-                    stop_reason=res.stop_reason, err=res.err, err_prev=res.err_prev, lam=res.lambda_, hmax=res.hmax)
+        return self._result(tr, res, x_kf=xo, T=To, Xw=Xo, Lw=Lo)
+
+    def optimize_dev(self, T_kf_w, d_x_kf, d_Xw, d_Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15) -> dict:
+        """plslam_gba_optimize_dev: the same loop with x_kf / Xw / Lw as DEVICE addresses (for the gather: X_aux, X_aux + 48 nkf,
+        X_aux + 48 nkf + 24 npt bytes); T_kf_w stays a host array.  -> optimize's dict without Xw / Lw: the landmarks stay
+        resident in the plan (LocalMap.apply_gba writes them into the map image)."""
+        n_map, nkf, _, _ = self.dims
+        T = _arr(T_kf_w, np.float64, (n_map, 16))
+        xo, To = np.empty((nkf, 6)), np.empty((nkf, 4, 4))
+        tr = (GbaSolve * max(int(max_iters), 1))()
+        res = GbaResult()
+        _check(self._L.plslam_gba_optimize_dev(self._h, float(lambda_lm), float(lambda_k), int(max_iters), _p(T), d_x_kf or None,
+                                               d_Xw or None, d_Lw or None, _p(xo), _p(To), tr, C.byref(res)),
+               "plslam_gba_optimize_dev")
+        return self._result(tr, res, x_kf=xo, T=To)
 
     def close(self) -> None:
         # a plan is destroyed before its context: once the context is closed the handle is only dropped

@@ -1,5 +1,6 @@
-// distribute_dev.hpp -- the stable distribution the device-built LBA plan makes its lists with (lba_plan_dev.hip: landmarks by
-// lm_loc, the keyframe list by kf_loc, the Schur pairs by block).  One copy: a change here moves every list that is built with it.
+// distribute_dev.hpp -- the stable distribution the device-built plans make their lists with (lba_plan_dev.hip: landmarks by
+// lm_loc, the keyframe list by kf_loc, the Schur pairs by block; gba_plan_dev.hip: the four CSR lists, the covisible pairs by
+// block and kind).  One copy: a change here moves every list that is built with it.
 //
 // Items 0 .. n-1 carry integer keys in [-1, nkeys).  The result is build_csr's inner by(...) (lba_lists.hpp): ids[ptr[k] .. ptr[k+1])
 // are the items of key k IN THEIR ORIGINAL ORDER, items of key -1 are left out.  A key of -1 sorts as the value nkeys, behind
@@ -45,6 +46,16 @@ struct DistPass {
     uint32_t* table;           // DIST_RADIX x ntiles words
     int32_t n, ntiles, nkeys, shift;
 };
+
+// the distribution's scratch: two key buffers and an id buffer of `cap` items, the table for dist_tiles(cap) tiles
+struct DistScratch { int32_t *key_a, *key_b, *id_tmp; uint32_t* table; };
+
+// (distribute.hip: the kernels K75-K78 and their launches)
+// ids_out[ptr_out[k] .. ptr_out[k + 1]): the items of key k in their order; ptr_out: nkeys + 1 words.  Enqueued on s.
+void dist_enqueue(hipStream_t s, const int32_t* key_in, int32_t n, int32_t nkeys, int32_t* ids_out, int32_t* ptr_out, const DistScratch& w);
+// The passes alone, for a caller that reads the segments off the sorted keys itself (no ptr over all nkeys keys): ids_out as
+// above; returns where the n sorted keys lie -- key_in itself (n == 0) or one of the scratch's key buffers.
+const int32_t* dist_sort_enqueue(hipStream_t s, const int32_t* key_in, int32_t n, int32_t nkeys, int32_t* ids_out, const DistScratch& w);
 
 #if defined(__HIPCC__)
 

@@ -19,9 +19,11 @@
 // Every sum has a fixed shape (no floating-point atomics): two runs give the same bits.  Phases are ordered by kernel
 // boundaries only -- no grid barrier, no device-scope fence.
 //
-// The lists the kernels walk are host work (gba_lists.hpp).  The plan's buffers are named ONCE: each is carved in one function
-// (carve_stat, carve_work), which fills a view of typed pointers with the bytes behind each; every launch site, upload and
-// download reads the views.
+// The lists the kernels walk are host work (gba_lists.hpp) or built on the device (gba_plan_dev.hip); the plan object is in
+// gba_plan.hpp.  The plan's buffers are named ONCE: each is carved in one function (gba_carve_stat, gba_carve_pairs,
+// gba_carve_work), which fills a view of typed pointers with the bytes behind each; every launch site, upload and download reads
+// the views.  The LM loop is ONE body (gba_optimize) behind plslam_gba_optimize (host state) and plslam_gba_optimize_dev (device
+// state: the landmarks stay resident in the LBA plan, plslam_local_map_apply_gba writes them into the map image).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,20 +32,13 @@
 #include <vector>
 
 #include "common.hpp"
-#include "gba_lists.hpp"
+#include "gba_plan.hpp"
+#include "lba_plan.hpp"
 #include "ldlt_dense.hpp"
 #include "se3_dev.hpp"
 
 namespace plslam {
 namespace {
-
-// the host lists hold pairs of int32 (gba_lists.hpp has no HIP type); K29 reads the same bytes as int2
-static_assert(sizeof(GbaPair) == sizeof(int2) && alignof(GbaPair) <= alignof(int2), "GbaPair is uploaded as int2");
-
-struct GbaStats {               // what crosses to the host per solve
-    double dx_sumsq;
-    int32_t n_singular, n_bad_pivots;
-};
 
 // ---- K26 ----------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -354,73 +349,44 @@ k_gba_stats(const double* __restrict__ part, int32_t npart, const int32_t* __res
     }
 }
 
-struct GbaStatView {               // `stat`: the lists of gba_lists.hpp -- uploaded once
-    Arr<GbaBlock> blk;
-    Arr<GbaChunk> chk;
-    Arr<int2> pair;
-    Arr<int32_t> plm, pkf, llm, lkf;                  // per observation: landmark, optimised keyframe
-    Arr<int32_t> kpp, kpo, klp, klo;                  // keyframe -> observations (points, lines)
-    Arr<int32_t> lpp, lpo, llp, llo;                  // landmark -> observations by optimised keyframes (points, lines)
-};
-struct GbaWorkView {               // `work`: what a solve computes
-    Arr<double> Vp, tp, Vl, tl;                       // landmark inverses and Vj'^-1 gj (points, lines)
-    Arr<int32_t> sing, sing_pt, sing_ls;              // singular flags: sing = the points' directly followed by the lines'
-    Arr<double> Yp, Yl, part;                         // Y_o; the chunk sums of K29
-    Arr<double> P, w, z, dp;                          // the L D L^T's panel, b, z and the pose steps
-    Arr<int32_t> bad;                                 // bad pivots per tile
-    Arr<double> ss_part;                              // partials of ||DX||^2: pose workgroups, point workgroups, line workgroups
-    Arr<GbaStats> stats;
-    Arr<double> hmax, x;                              // K26's result; the pose parameters x_kf
-};
-
 }  // namespace
 }  // namespace plslam
 
 using namespace plslam;
 
-struct plslam_gba_plan {
-    plslam_ctx* ctx = nullptr;
-    plslam_lba_plan* lba = nullptr;
-    int32_t n_map = 0, nkf = 0, npt = 0, nls = 0, np = 0, nl = 0;
-    int64_t n = 0, npad = 0;
-    int32_t nblk = 0, nchunk = 0, nt = 0;
-    std::vector<int32_t> kf_list;           // map index of optimised keyframe k
-    DevBuf stat, work, Sbuf;
-    GbaStatView st;
-    GbaWorkView wk;
+namespace plslam {
 
-    // workgroups of K38 / K37<3> / K37<6>: each leaves one partial of ||DX||^2
-    int nwk() const { return (nkf + 255) / 256; }
-    int nwp() const { return (npt + 255) / 256; }
-    int nwl() const { return (nls + 255) / 256; }
-    void release() { stat.release(); work.release(); Sbuf.release(); }
-};
-
-namespace {
-
-size_t carve_stat(plslam_gba_plan* G, const GbaLists& L, char* base)
+size_t gba_carve_stat(plslam_gba_plan* G, const GbaListRoom& r, char* base)
 {
     GbaStatView& v = G->st;
     ArrCarver c{base};
-    v.blk = c.take<GbaBlock>(L.blks.size() * sizeof(GbaBlock));
-    v.chk = c.take<GbaChunk>(L.chks.size() * sizeof(GbaChunk), 16);
-    v.pair = c.take<int2>(L.pairs.size() * sizeof(int2), 8);
-    v.plm = c.take<int32_t>(L.plm.size() * 4, 4);
-    v.pkf = c.take<int32_t>(L.pkf.size() * 4, 4);
-    v.llm = c.take<int32_t>(L.llm.size() * 4, 4);
-    v.lkf = c.take<int32_t>(L.lkf.size() * 4, 4);
-    v.kpp = c.take<int32_t>(L.kpp.size() * 4);
-    v.kpo = c.take<int32_t>(L.kpo.size() * 4, 4);
-    v.klp = c.take<int32_t>(L.klp.size() * 4);
-    v.klo = c.take<int32_t>(L.klo.size() * 4, 4);
-    v.lpp = c.take<int32_t>(L.lpp.size() * 4);
-    v.lpo = c.take<int32_t>(L.lpo.size() * 4, 4);
-    v.llp = c.take<int32_t>(L.llp.size() * 4);
-    v.llo = c.take<int32_t>(L.llo.size() * 4, 4);
+    const size_t np = (size_t)G->np, nl = (size_t)G->nl;
+    v.plm = c.take<int32_t>(np * 4, 4);
+    v.pkf = c.take<int32_t>(np * 4, 4);
+    v.llm = c.take<int32_t>(nl * 4, 4);
+    v.lkf = c.take<int32_t>(nl * 4, 4);
+    v.kpp = c.take<int32_t>(((size_t)G->nkf + 1) * 4);
+    v.kpo = c.take<int32_t>(r.kpo * 4, 4);
+    v.klp = c.take<int32_t>(((size_t)G->nkf + 1) * 4);
+    v.klo = c.take<int32_t>(r.klo * 4, 4);
+    v.lpp = c.take<int32_t>(((size_t)G->npt + 1) * 4);
+    v.lpo = c.take<int32_t>(r.lpo * 4, 4);
+    v.llp = c.take<int32_t>(((size_t)G->nls + 1) * 4);
+    v.llo = c.take<int32_t>(r.llo * 4, 4);
     return c.size();
 }
 
-size_t carve_work(plslam_gba_plan* G, char* base)
+size_t gba_carve_pairs(plslam_gba_plan* G, const GbaListRoom& r, char* base)
+{
+    GbaStatView& v = G->st;
+    ArrCarver c{base};
+    v.blk = c.take<GbaBlock>(r.nblk * sizeof(GbaBlock));
+    v.chk = c.take<GbaChunk>(r.nchunk * sizeof(GbaChunk), 16);
+    v.pair = c.take<int2>(r.npair * sizeof(int2), 8);
+    return c.size();
+}
+
+size_t gba_carve_work(plslam_gba_plan* G, char* base)
 {
     GbaWorkView& v = G->wk;
     ArrCarver c{base};
@@ -451,6 +417,10 @@ size_t carve_work(plslam_gba_plan* G, char* base)
 
 int gba_fail(plslam_gba_plan* G, int rc)
 {
+    {
+        DeviceGuard dg_(G->ctx->device);
+        (void)hipStreamSynchronize(G->ctx->stream);        // (a device-built plan: its builders may still read the scratch)
+    }
     if (G->lba) plslam_lba_plan_destroy(G->lba);
     G->release();
     delete G;
@@ -458,7 +428,7 @@ int gba_fail(plslam_gba_plan* G, int rc)
 }
 
 // one damped solve on the blocks the LBA plan left on the device: Schur complement, LDL^T, landmark and pose steps, stats
-int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t s)
+static int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t s)
 {
     plslam_lba_blocks B;
     plslam_lba_state st;
@@ -512,14 +482,9 @@ int gba_solve_enqueue(plslam_gba_plan* G, double lambda, bool apply, hipStream_t
     return PLSLAM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-// check the arguments the lists do not cover, plan (gba_lists.hpp), carve and upload, return
-int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf, const int32_t* kf_list, int32_t npt, int32_t nls, const int32_t* pt_obs,
-                           const double* pt_obs_uv, int32_t n_pt_obs, const int32_t* ls_obs, const double* ls_l_obs,
-                           int32_t n_ls_obs, plslam_gba_plan** out)
+int gba_plan_args_ok(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf, const void* kf_list, int32_t npt,
+                     int32_t nls, const void* pt_obs, const void* pt_obs_uv, int32_t n_pt_obs, const void* ls_obs, const void* ls_l_obs,
+                     int32_t n_ls_obs, plslam_gba_plan** out)
 {
     PLSLAM_REQUIRE(ctx && K && out && n_map_kf >= 0 && nkf >= 1 && npt >= 0 && nls >= 0 && n_pt_obs >= 0 && n_ls_obs >= 0,
                    PLSLAM_EINVAL);
@@ -532,28 +497,50 @@ int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th
     // 32-bit addressing: observation blocks (DL x 6 doubles each), landmark blocks and pair lists are indexed with int32
     PLSLAM_REQUIRE((int64_t)n_pt_obs * 18 < INT32_MAX && (int64_t)n_ls_obs * 36 < INT32_MAX &&
                    (int64_t)npt * 9 < INT32_MAX && (int64_t)nls * 36 < INT32_MAX, PLSLAM_EINVAL);
+    return PLSLAM_OK;
+}
+
+void gba_plan_dims(plslam_gba_plan* G, plslam_ctx* ctx, int32_t n_map_kf, int32_t nkf, int32_t npt, int32_t nls, int32_t n_pt_obs,
+                   int32_t n_ls_obs)
+{
+    G->ctx = ctx; G->n_map = n_map_kf; G->nkf = nkf; G->npt = npt; G->nls = nls; G->np = n_pt_obs; G->nl = n_ls_obs;
+    G->n = 6 * (int64_t)nkf;
+    G->npad = pad_to_tile(G->n);
+    G->nt = (int32_t)(G->npad / LT);
+}
+
+}  // namespace plslam
+
+extern "C" {
+
+// check the arguments the lists do not cover, plan (gba_lists.hpp), carve and upload, return
+int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th, int32_t n_map_kf, int32_t nkf, const int32_t* kf_list, int32_t npt, int32_t nls, const int32_t* pt_obs,
+                           const double* pt_obs_uv, int32_t n_pt_obs, const int32_t* ls_obs, const double* ls_l_obs,
+                           int32_t n_ls_obs, plslam_gba_plan** out)
+{
+    int rc = gba_plan_args_ok(ctx, K, homog_th, n_map_kf, nkf, kf_list, npt, nls, pt_obs, pt_obs_uv, n_pt_obs, ls_obs, ls_l_obs, n_ls_obs, out);
+    if (rc) return rc;
     GbaLists L;
-    int rc = gba_lists_build(n_map_kf, nkf, kf_list, npt, nls, pt_obs, n_pt_obs, ls_obs, n_ls_obs, &L);
+    rc = gba_lists_build(n_map_kf, nkf, kf_list, npt, nls, pt_obs, n_pt_obs, ls_obs, n_ls_obs, &L);
     if (rc) {
         set_last_error("plslam_gba_plan_create: %s", L.why);
         return rc;
     }
     plslam_gba_plan* G = new (std::nothrow) plslam_gba_plan();
     PLSLAM_REQUIRE(G != nullptr, PLSLAM_ENOMEM);
-    G->ctx = ctx; G->n_map = n_map_kf; G->nkf = nkf; G->npt = npt; G->nls = nls; G->np = n_pt_obs; G->nl = n_ls_obs;
+    gba_plan_dims(G, ctx, n_map_kf, nkf, npt, nls, n_pt_obs, n_ls_obs);
     G->kf_list.assign(kf_list, kf_list + nkf);
-    G->n = 6 * (int64_t)nkf;
-    G->npad = pad_to_tile(G->n);
-    G->nt = (int32_t)(G->npad / LT);
-    G->nblk = (int32_t)L.blks.size(); G->nchunk = (int32_t)L.chks.size();
+    G->nblk = (int32_t)L.blks.size(); G->nchunk = (int32_t)L.chks.size(); G->npair = (int64_t)L.pairs.size();
     rc = plslam_lba_plan_create(ctx, K, homog_th, n_map_kf + nkf, nkf, npt, nls, L.plm.data(), L.pslot.data(), L.pkf.data(),
                                 pt_obs_uv, n_pt_obs, L.llm.data(), L.lslot.data(), L.lkf.data(), ls_l_obs, n_ls_obs, &G->lba);
     if (rc) return gba_fail(G, rc);
-    if ((rc = G->stat.reserve(carve_stat(G, L, nullptr) + 256)) || (rc = G->work.reserve(carve_work(G, nullptr) + 256)) ||
-        (rc = G->Sbuf.reserve((size_t)G->npad * (size_t)G->npad * 8)))
+    const GbaListRoom room{L.lpo.size(), L.llo.size(), L.kpo.size(), L.klo.size(), L.blks.size(), L.chks.size(), L.pairs.size()};
+    if ((rc = G->stat.reserve(gba_carve_stat(G, room, nullptr) + 256)) || (rc = G->pairbuf.reserve(gba_carve_pairs(G, room, nullptr) + 256)) ||
+        (rc = G->work.reserve(gba_carve_work(G, nullptr) + 256)) || (rc = G->Sbuf.reserve((size_t)G->npad * (size_t)G->npad * 8)))
         return gba_fail(G, rc);
-    carve_stat(G, L, G->stat.as<char>());
-    carve_work(G, G->work.as<char>());
+    gba_carve_stat(G, room, G->stat.as<char>());
+    gba_carve_pairs(G, room, G->pairbuf.as<char>());
+    gba_carve_work(G, G->work.as<char>());
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         DeviceGuard dg_(ctx->device);
@@ -571,12 +558,16 @@ int plslam_gba_plan_create(plslam_ctx* ctx, const plslam_cam* K, double homog_th
     return PLSLAM_OK;
 }
 
-int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba, const double* T_kf_w,
-                        const double* x_kf, const double* Xw, const double* Lw, double* x_kf_out, double* T_out, double* Xw_out,
+}  // extern "C"
+
+// The LM loop both entry points run.  dev: Xw / Lw are DEVICE pointers, copied device to device into the LBA plan's resident
+// state, and the landmarks stay there (no Xw_out / Lw_out); otherwise they are host pointers and go up with the poses.
+static int gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba, const double* T_kf_w,
+                        const double* x_kf, bool dev, const double* Xw, const double* Lw, double* x_kf_out, double* T_out, double* Xw_out,
                         double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result)
 {
-    PLSLAM_REQUIRE(G && x_kf && x_kf_out && (G->n_map == 0 || T_kf_w) && (G->npt == 0 || (Xw && Xw_out)) &&
-                   (G->nls == 0 || (Lw && Lw_out)), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(G && x_kf && x_kf_out && (G->n_map == 0 || T_kf_w) && (G->npt == 0 || (Xw && (dev || Xw_out))) &&
+                   (G->nls == 0 || (Lw && (dev || Lw_out))), PLSLAM_EINVAL);
     PLSLAM_REQUIRE(lambda_lba_k != 0.0, PLSLAM_EINVAL);
     plslam_ctx* ctx = G->ctx;
     DeviceGuard dg_(ctx->device);
@@ -590,7 +581,28 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
     if (n_map) std::memcpy(T.data(), T_kf_w, (size_t)n_map * 128);
     for (int32_t k = 0; k < nkf; ++k) std::memcpy(&T[16 * (size_t)(n_map + k)], &T_kf_w[16 * (size_t)G->kf_list[k]], 128);
     double err_raw = 0.0;
-    int rc = plslam_lba_plan_iterate_dev(G->lba, T.data(), Xw, Lw, PLSLAM_LBA_COMPAT_GBA, nullptr, &err_raw);
+    int rc;
+    G->optimized = false;
+    if (!dev) rc = plslam_lba_plan_iterate_dev(G->lba, T.data(), Xw, Lw, PLSLAM_LBA_COMPAT_GBA, nullptr, &err_raw);
+    else {
+        // the same first pass on the same state: the landmarks device to device, the poses up, then the resident iteration
+        plslam_lba_plan* P = G->lba;
+        {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            DeviceGuard dg1_(ctx->device);
+            hipStream_t s1 = ctx->stream;
+            StreamSyncOnError guard(s1);
+            if (G->npt) PLSLAM_HIP_CHECK(hipMemcpyAsync(P->x.Xw, Xw, P->x.Xw.bytes, hipMemcpyDeviceToDevice, s1));
+            if (G->nls) PLSLAM_HIP_CHECK(hipMemcpyAsync(P->x.Lw, Lw, P->x.Lw.bytes, hipMemcpyDeviceToDevice, s1));
+            if (P->n_slots) {
+                memcpy(P->hx.T, T.data(), P->hx.T.bytes);
+                PLSLAM_HIP_CHECK(hipMemcpyAsync(P->x.T, P->hx.T, P->x.T.bytes, hipMemcpyHostToDevice, s1));
+            }
+            guard.dismiss();                                // (the resident iteration below synchronises the same stream)
+            P->state_valid = true;
+        }
+        rc = plslam_lba_plan_iterate_resident(P, PLSLAM_LBA_COMPAT_GBA, &err_raw);
+    }
     if (rc) return rc;
     plslam_lba_blocks B;
     if ((rc = plslam_lba_plan_device_blocks(G->lba, &B))) return rc;
@@ -601,7 +613,7 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
         std::lock_guard<std::mutex> lk(ctx->mu);
         DeviceGuard dg2_(ctx->device);
         StreamSyncOnError guard(s);
-        PLSLAM_HIP_CHECK(hipMemcpyAsync(wk.x, x_kf, wk.x.bytes, hipMemcpyHostToDevice, s));
+        PLSLAM_HIP_CHECK(hipMemcpyAsync(wk.x, x_kf, wk.x.bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_gba_hmax, dim3(1), dim3(256), 0, s, B.H_pose, nkf, B.H_pt, G->npt, B.H_ls, G->nls, wk.hmax.p);
         PLSLAM_HIP_CHECK(hipGetLastError());
         PLSLAM_HIP_CHECK(hipMemcpyAsync(&hmax, wk.hmax, 8, hipMemcpyDeviceToHost, s));
@@ -655,8 +667,8 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
         PLSLAM_HIP_CHECK(hipMemcpyAsync(x_kf_out, wk.x, wk.x.bytes, hipMemcpyDeviceToHost, s));
         if (T_out)
             PLSLAM_HIP_CHECK(hipMemcpyAsync(T_out, ls.T_kf_w + 16 * (size_t)n_map, (size_t)nkf * 128, hipMemcpyDeviceToHost, s));
-        if (G->npt) PLSLAM_HIP_CHECK(hipMemcpyAsync(Xw_out, ls.Xw, (size_t)G->npt * 24, hipMemcpyDeviceToHost, s));
-        if (G->nls) PLSLAM_HIP_CHECK(hipMemcpyAsync(Lw_out, ls.Lw, (size_t)G->nls * 48, hipMemcpyDeviceToHost, s));
+        if (G->npt && Xw_out) PLSLAM_HIP_CHECK(hipMemcpyAsync(Xw_out, ls.Xw, (size_t)G->npt * 24, hipMemcpyDeviceToHost, s));
+        if (G->nls && Lw_out) PLSLAM_HIP_CHECK(hipMemcpyAsync(Lw_out, ls.Lw, (size_t)G->nls * 48, hipMemcpyDeviceToHost, s));
         PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
         guard.dismiss();
     }
@@ -664,7 +676,27 @@ int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_
         result->iters = iters; result->n_solves = nsol; result->stop_reason = stop; result->reserved = 0;
         result->err = err; result->err_prev = err_prev; result->lambda = lambda; result->hmax = hmax;
     }
+    G->optimized = true;
     return PLSLAM_OK;
+}
+
+extern "C" {
+
+int plslam_gba_optimize(plslam_gba_plan* G, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba, const double* T_kf_w,
+                        const double* x_kf, const double* Xw, const double* Lw, double* x_kf_out, double* T_out, double* Xw_out,
+                        double* Lw_out, plslam_gba_solve* trace, plslam_gba_result* result)
+{
+    PLSLAM_REQUIRE(G && (G->npt == 0 || Xw_out) && (G->nls == 0 || Lw_out), PLSLAM_EINVAL);
+    return gba_optimize(G, lambda_lba_lm, lambda_lba_k, max_iters_lba, T_kf_w, x_kf, false, Xw, Lw, x_kf_out, T_out, Xw_out, Lw_out, trace,
+                        result);
+}
+
+int plslam_gba_optimize_dev(plslam_gba_plan* G, double lambda_lba_lm, double lambda_lba_k, int32_t max_iters_lba, const double* T_kf_w,
+                            const double* d_x_kf, const double* d_Xw, const double* d_Lw, double* x_kf_out, double* T_out,
+                            plslam_gba_solve* trace, plslam_gba_result* result)
+{
+    return gba_optimize(G, lambda_lba_lm, lambda_lba_k, max_iters_lba, T_kf_w, d_x_kf, true, d_Xw, d_Lw, x_kf_out, T_out, nullptr, nullptr,
+                        trace, result);
 }
 
 void plslam_gba_plan_destroy(plslam_gba_plan* G)

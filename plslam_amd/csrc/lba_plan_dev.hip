@@ -5,8 +5,9 @@
 //                           made safe, so no later kernel follows a bad index), the slot rewrite, the stored columns, the keys of
 //                           the keyframe list
 //   K75 k_dist_hist / K76 k_dist_scan / K77 k_dist_scatter / K78 k_dist_ptr
-//                           the stable distribution (distribute_dev.hpp), used three times for the plan -- points by lm_loc, lines
-//                           by lm_loc, the keyframe list by kf_loc -- and once for the Schur pairs by 2 block + kind
+//                           the stable distribution (distribute_dev.hpp; the kernels and dist_enqueue: distribute.hip), used three
+//                           times for the plan -- points by lm_loc, lines by lm_loc, the keyframe list by kf_loc -- and once for
+//                           the Schur pairs by 2 block + kind
 //   K79 k_lbp_pair_count    a lane per position of the landmark lists: the pairs (o1, .) it starts; their sum in 64 bits
 //   K80 k_lbp_publish       max_chunks reduced from kf_ptr; status and counts to the page-locked block the host reads
 //   K81 k_lbp_pair_emit     enumeration offsets (the look-back of lookback_dev.hpp over K79's counts), then key and pair of every
@@ -70,60 +71,6 @@ k_lbp_validate(const LbpValidateArgs A)
 #pragma unroll
         for (int w = 0; w < 3; ++w) g_(A.o_lobs)[3 * (size_t)o + w] = g_(A.lobs)[3 * (size_t)o + w];
     }
-}
-
-__global__ void __launch_bounds__(DIST_NT)
-k_dist_hist(const DistPass A)
-{
-    __shared__ uint32_t s_cnt[DIST_RADIX];
-    dist_hist_tile(A, (int)blockIdx.x, s_cnt);
-}
-
-__global__ void __launch_bounds__(DIST_SCAN_NT)
-k_dist_scan(uint32_t* __restrict__ table, int64_t words)
-{
-    __shared__ uint32_t s_w[DIST_SCAN_NT / 64 + 1];
-    dist_scan_table(table, words, s_w);
-}
-
-__global__ void __launch_bounds__(DIST_NT)
-k_dist_scatter(const DistPass A)
-{
-    __shared__ uint32_t s_cnt[DIST_NW][DIST_RADIX], s_base[DIST_RADIX];
-    dist_scatter_tile(A, (int)blockIdx.x, s_cnt, s_base);
-}
-
-__global__ void __launch_bounds__(LBP_NT)
-k_dist_ptr(const int32_t* __restrict__ sorted_key, int32_t n, int32_t nkeys, int32_t* __restrict__ ptr)
-{
-    const int64_t k = (int64_t)blockIdx.x * LBP_NT + threadIdx.x;
-    if (k <= nkeys) ptr[k] = dist_ptr_of(sorted_key, n, nkeys, (int32_t)k);
-}
-
-// the distribution's scratch: two key buffers and an id buffer of `cap` items, the table for dist_tiles(cap) tiles
-struct DistScratch { int32_t *key_a, *key_b, *id_tmp; uint32_t* table; };
-
-// ids_out[ptr_out[k] .. ptr_out[k + 1]): the items of key k in their order; ptr_out: nkeys + 1 words.  Enqueued on s.
-void dist_enqueue(hipStream_t s, const int32_t* key_in, int32_t n, int32_t nkeys, int32_t* ids_out, int32_t* ptr_out, const DistScratch& w)
-{
-    const int passes = dist_passes(nkeys);
-    const int32_t ntiles = dist_tiles(n);
-    const int32_t* sorted = key_in;
-    if (n > 0) {
-        const int32_t* ids_in = nullptr;
-        for (int p = 0; p < passes; ++p) {
-            DistPass A{};
-            A.key_in = sorted; A.id_in = ids_in;
-            A.key_out = (p & 1) ? w.key_b : w.key_a;
-            A.id_out = ((passes - 1 - p) & 1) ? w.id_tmp : ids_out;        // the last pass writes the list itself
-            A.table = w.table; A.n = n; A.ntiles = ntiles; A.nkeys = nkeys; A.shift = 8 * p;
-            hipLaunchKernelGGL(k_dist_hist, dim3(ntiles), dim3(DIST_NT), 0, s, A);
-            hipLaunchKernelGGL(k_dist_scan, dim3(1), dim3(DIST_SCAN_NT), 0, s, w.table, (int64_t)DIST_RADIX * ntiles);
-            hipLaunchKernelGGL(k_dist_scatter, dim3(ntiles), dim3(DIST_NT), 0, s, A);
-            sorted = A.key_out; ids_in = A.id_out;
-        }
-    }
-    hipLaunchKernelGGL(k_dist_ptr, dim3(wgs((int64_t)nkeys + 1, LBP_NT)), dim3(LBP_NT), 0, s, sorted, n, nkeys, ptr_out);
 }
 
 // the lists as the pair kernels read them

@@ -6,12 +6,15 @@
 //                                                   lookback_dev.hpp), K61 a lane per output observation
 //   removeBadMapLandmarks               :2705-2786  K62
 //   the write-back of the local BA      :1828-1855  K84 from an LBA plan's resident landmarks into the image
+//   the gather of globalBundleAdjustment :1995-2092 K97 every flag set (form_all), then K59-K61 as they are
+//   the write-back of the global BA     :2681-2697  K84 with the moved test switched off, from a GBA plan's resident landmarks
 // Every output is an integer, a flag or a verbatim copy of a double: bit-exact against the sequential loops (tests/local_map_ref.py).
 // Each entry point: the context's lock, device and stream; one synchronisation; counts through page-locked memory written by the
 // call's last kernel.  Every index read from the image is range-checked before it is used as an address.
 #include <cstring>
 
 #include "common.hpp"
+#include "gba_plan.hpp"
 #include "lba_plan.hpp"
 #include "lookback_dev.hpp"
 #include "map_image_dev.hpp"
@@ -258,6 +261,9 @@ k_lm_cull(MapKindSrc P, MapKindSrc L, CullKind wp, CullKind wl, int32_t n_map_kf
 // from 0 (no contraction: the build's -ffp-contract=off), sqrt(s2) > th.  inlier is only ever cleared; X is copied verbatim.
 // A listed landmark occurs once in its list: no two lanes touch the same landmark, in place on the image is safe.
 struct ApplyKind { const int32_t* list; const double* Xnew; double* X; uint8_t* inlier; uint8_t* moved; int32_t n_list, n; };
+// TEST = false: the write-back of globalBundleAdjustment (:2681-2697) -- the copy alone: no moved test, inlier and moved untouched,
+// nothing counted
+template <bool TEST>
 __global__ void __launch_bounds__(MAP_TILE)
 k_lm_apply_lba(ApplyKind P, ApplyKind L, double th, int32_t* __restrict__ cnt, Publish pub)
 {
@@ -278,17 +284,34 @@ k_lm_apply_lba(ApplyKind P, ApplyKind L, double th, int32_t* __restrict__ cnt, P
             double s2 = 0.0;
             for (int a = 0; a < dl; ++a) {
                 const double v = Xnew[(size_t)dl * i + a];
-                const double d = v - X[(size_t)dl * j + a];
-                s2 += d * d;
+                if (TEST) {
+                    const double d = v - X[(size_t)dl * j + a];
+                    s2 += d * d;
+                }
                 X[(size_t)dl * j + a] = v;
             }
-            mv = sqrt(s2) > th;
-            if (mv) inlier[j] = 0;
+            if (TEST) {
+                mv = sqrt(s2) > th;
+                if (mv) inlier[j] = 0;
+            }
         }
-        (lines ? L.moved : P.moved)[i] = mv ? 1 : 0;
-        ok[lines ? 1 : 0] = mv;
+        if (TEST) {
+            (lines ? L.moved : P.moved)[i] = mv ? 1 : 0;
+            ok[lines ? 1 : 0] = mv;
+        }
     }
-    count_and_publish<2>(ok, cnt, pub);
+    if (TEST) count_and_publish<2>(ok, cnt, pub);
+}
+
+// K97: the flags of the global BA's gather: every non-NULL keyframe, every non-NULL landmark (:1995-2092 have no ->local test)
+__global__ void __launch_bounds__(MAP_TILE)
+k_lm_all_flags(int32_t nkf, const uint8_t* __restrict__ kf_valid, int32_t npt, const uint8_t* __restrict__ pt_valid, int32_t nls,
+               const uint8_t* __restrict__ ls_valid, uint8_t* __restrict__ kf_local, uint8_t* __restrict__ pt_local, uint8_t* __restrict__ ls_local)
+{
+    const int64_t t = (int64_t)blockIdx.x * MAP_TILE + threadIdx.x;
+    if (t < nkf) kf_local[t] = kf_valid[t] != 0 ? 1 : 0;
+    else if (t < (int64_t)nkf + npt) pt_local[t - nkf] = pt_valid[t - nkf] != 0 ? 1 : 0;
+    else if (t < (int64_t)nkf + npt + nls) ls_local[t - nkf - npt] = ls_valid[t - nkf - npt] != 0 ? 1 : 0;
 }
 
 bool map_ok(const plslam_map_index* m)
@@ -527,13 +550,66 @@ int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, cons
     const ApplyKind P{lm->d.pt_list, plan->x.Xw, dst->pt_X, dst->pt_inlier, lm->d.pt_moved, npt_l, lm->npt};
     const ApplyKind L{lm->d.ls_list, plan->x.Lw, dst->ls_X, dst->ls_inlier, lm->d.ls_moved, nls_l, lm->nls};
     const Publish pub{lm->cnt + C_APPLY_DONE, lm->cnt + C_PT_MOVED, (int32_t*)lm->pin.dev + C_PT_MOVED, 2};
-    hipLaunchKernelGGL(k_lm_apply_lba, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
+    hipLaunchKernelGGL(k_lm_apply_lba<true>, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
     const int32_t* h = lm->pin.as<int32_t>();
     counts->n_pt_moved = lm->h_cnt[C_PT_MOVED] = h[C_PT_MOVED];
     counts->n_ls_moved = lm->h_cnt[C_LS_MOVED] = h[C_LS_MOVED];
+    return PLSLAM_OK;
+}
+
+int plslam_local_map_form_all(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts)
+{
+    PLSLAM_REQUIRE(lm && map_ok(map) && counts, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(lm->ctx->mu);
+    DeviceGuard dg_(lm->ctx->device);
+    hipStream_t s = lm->ctx->stream;
+    lm->formed = lm->gathered = lm->applied = false;
+    int rc = lm_layout(lm, map);
+    if (rc) return rc;
+    PLSLAM_REQUIRE(lm->pin.dev, PLSLAM_ENOTSUP);               // the counters are written where the host reads them
+    StreamSyncOnError guard(s);
+    const int32_t nk = map->n_map_kf, npt = map->points.n, nls = map->lines.n;
+    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->d.kf_local, 0, lm->zero_bytes, s));
+    const unsigned tiles = map_tiles((int64_t)nk + npt + nls);
+    hipLaunchKernelGGL(k_lm_all_flags, dim3(tiles), dim3(MAP_TILE), 0, s, nk, map->kf_valid, npt, (const uint8_t*)map->points.valid, nls,
+                       (const uint8_t*)map->lines.valid, lm->d.kf_local, lm->d.pt_local, lm->d.ls_local);
+    const Publish pub{lm->cnt + C_FORM_DONE, lm->cnt, (int32_t*)lm->pin.dev, 3};
+    hipLaunchKernelGGL(k_lm_count_flags, dim3(tiles), dim3(MAP_TILE), 0, s, (const uint8_t*)lm->d.kf_local, nk,
+                       (const uint8_t*)lm->d.pt_local, npt, (const uint8_t*)lm->d.ls_local, nls, lm->cnt, pub);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    const int32_t* h = lm->pin.as<int32_t>();
+    memset(lm->h_cnt, 0, sizeof lm->h_cnt);
+    for (int k = C_KF_LOCAL; k <= C_LS_LOCAL; ++k) lm->h_cnt[k] = h[k];
+    counts->n_kf_local = h[C_KF_LOCAL]; counts->n_pt_local = h[C_PT_LOCAL]; counts->n_ls_local = h[C_LS_LOCAL];
+    lm->formed = true;
+    return PLSLAM_OK;
+}
+
+int plslam_local_map_apply_gba(plslam_local_map* lm, plslam_gba_plan* plan, const plslam_local_map_lba_dst* dst)
+{
+    PLSLAM_REQUIRE(lm && plan && dst && plan->ctx == lm->ctx && plan->lba, PLSLAM_EINVAL);
+    std::lock_guard<std::mutex> lk(lm->ctx->mu);
+    DeviceGuard dg_(lm->ctx->device);
+    hipStream_t s = lm->ctx->stream;
+    PLSLAM_REQUIRE(lm->formed && lm->gathered, PLSLAM_EINVAL);
+    const int32_t npt_l = lm->h_cnt[C_NPT], nls_l = lm->h_cnt[C_NLS];
+    PLSLAM_REQUIRE(plan->npt == npt_l && plan->nls == nls_l && plan->optimized, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE((npt_l == 0 || dst->pt_X) && (nls_l == 0 || dst->ls_X), PLSLAM_EINVAL);
+    if ((int64_t)npt_l + nls_l == 0) return PLSLAM_OK;
+    StreamSyncOnError guard(s);
+    const plslam_lba_plan* P_ = plan->lba;
+    const ApplyKind P{lm->d.pt_list, P_->x.Xw, dst->pt_X, nullptr, nullptr, npt_l, lm->npt};
+    const ApplyKind L{lm->d.ls_list, P_->x.Lw, dst->ls_X, nullptr, nullptr, nls_l, lm->nls};
+    hipLaunchKernelGGL(k_lm_apply_lba<false>, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, 0.0, (int32_t*)nullptr,
+                       Publish{nullptr, nullptr, nullptr, 0});
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
     return PLSLAM_OK;
 }
 

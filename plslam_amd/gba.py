@@ -102,6 +102,44 @@ def trajectory_map(n_kf=400, n_pt=40000, n_ls=6000, obs_per_lm=4, loop=True, see
                 x_kf=x_est[1:].copy(), Xw=Xw, Lw=Lw, pt_obs=pt_obs, pt_uv=uv, ls_obs=ls_obs, ls_l=l_obs, npt=n_pt, nls=n_ls)
 
 
+def map_image(m):
+    """The arrays of a plslam_map_index (the dict plslam_amd.local_map.DeviceMapIndex takes) whose global-BA gather
+    (LocalMap.form_all + .gather) gives back a trajectory_map-shaped dict m: kf_list, the six Vector6i columns, pt_uv, ls_l, Xw, Lw.
+
+    Every landmark is valid and an inlier, landmark j of the image is local landmark j; kf_valid marks kf_list plus slot 0;
+    obs_ptr counts column 1; x_kf_w holds x_kf at the optimised slots (NaN elsewhere: nothing reads it).  No features: the GBA
+    gather reads none.  Precondition (asserted): the rows are grouped by ascending landmark local index, column 0 equals column 1,
+    column 2 counts from 0 within the landmark and column 4 is the position of column 3 in kf_list, or -1."""
+    n_map = int(m["n_map_kf"])
+    kf_list = np.asarray(m["kf_list"], np.int32)
+    assert kf_list.size and (np.diff(kf_list) > 0).all() and kf_list[0] >= 1 and kf_list[-1] < n_map, "kf_list: ascending slots above 0"
+    kf_valid = np.zeros(n_map, np.uint8)
+    kf_valid[0] = 1
+    kf_valid[kf_list] = 1
+    inv = np.full(n_map, -1, np.int32)
+    inv[kf_list] = np.arange(kf_list.size, dtype=np.int32)
+    x_kf_w = np.full((n_map, 6), np.nan)
+    x_kf_w[kf_list] = np.asarray(m["x_kf"], np.float64).reshape(-1, 6)
+
+    def kind(obs, val, X, dv):
+        obs = np.asarray(obs, np.int32).reshape(-1, 6)
+        n = X.shape[0]
+        lm = obs[:, 1]
+        assert ((lm >= 0) & (lm < n)).all() and (np.diff(lm) >= 0).all(), "rows grouped by ascending landmark local index"
+        assert (obs[:, 0] == lm).all(), "landmark map index == local index"
+        obs_ptr = np.zeros(n + 1, np.int32)
+        obs_ptr[1:] = np.cumsum(np.bincount(lm, minlength=n))
+        assert (obs[:, 2] == np.arange(obs.shape[0]) - obs_ptr[lm]).all(), "column 2 counts within the landmark"
+        assert ((obs[:, 3] >= 0) & (obs[:, 3] < n_map)).all() and (obs[:, 4] == inv[obs[:, 3]]).all(), "column 4 is kf_list's position"
+        assert (obs[:, 5] == 1).all()
+        return dict(n=n, valid=np.ones(n, np.uint8), inlier=np.ones(n, np.uint8), X=np.asarray(X, np.float64).copy(), obs_ptr=obs_ptr,
+                    obs_kf=obs[:, 3].copy(), obs_val=np.asarray(val, np.float64).reshape(-1, dv).copy(),
+                    feat_ptr=np.zeros(n_map + 1, np.int32), feat_idx=np.zeros(0, np.int32))
+
+    return dict(n_map_kf=n_map, kf_valid=kf_valid, x_kf_w=x_kf_w, points=kind(m["pt_obs"], m["pt_uv"], np.asarray(m["Xw"]).reshape(-1, 3), 2),
+                lines=kind(m["ls_obs"], m["ls_l"], np.asarray(m["Lw"]).reshape(-1, 6), 3))
+
+
 def covisible_blocks(m):
     """The set of lower covisible keyframe blocks (k1 >= k2, local indices) the map's observations produce."""
     out = set()

@@ -1,7 +1,8 @@
 // gba.hpp -- header-only drop-in for MapHandler::globalBundleAdjustment (src/mapHandler.cpp:1995-2099) on the C ABI's
 // global bundle adjustment (plslam_gba_*, include/plslam_hip.h).  The caller describes its map with plain arrays (no PL-SLAM
 // types here); gba::run builds the lists as :1995-2099 does, runs levMarquardtOptimizationGBA on the device and writes back
-// as :2674-2702 does (T_kf_w of every optimised keyframe, point3D, line3D; no inlier marking).
+// as :2674-2702 does (T_kf_w of every optimised keyframe, point3D, line3D; no inlier marking).  gba::runResident is the same
+// optimisation on a map that lives on the device (plslam_map_index): gather, plan, loop and write-back without the host.
 #pragma once
 
 #include <stdexcept>
@@ -90,6 +91,48 @@ inline int run(plslam_ctx* ctx, const plslam_cam& cam, const Params& prm, std::v
         for (int a = 0; a < 3; ++a) pts[pmap[j]].X[a] = X_out[3 * (size_t)j + a];
     for (int32_t j = 0; j < nls; ++j)
         for (int a = 0; a < 6; ++a) lns[lmap[j]].X[a] = L_out[6 * (size_t)j + a];
+    if (trace) trace->assign(tr.begin(), tr.begin() + res.n_solves);
+    return res.n_solves;
+}
+
+// The resident route: the same optimisation for a caller whose map lives on the device as a plslam_map_index (host/local_map.hpp:
+// LocalMapIndex).  Nothing but the poses crosses to the host: the gather (plslam_local_map_form_all + _gather), the plan
+// (plslam_gba_plan_create_dev), the loop (plslam_gba_optimize_dev) and the write-back of the landmarks into the image
+// (plslam_local_map_apply_gba) run on the device.  form_all overwrites the handle's local flags: a cull or a candidate mask
+// afterwards needs a new form.
+//   T_all    the stored T_kf_w of every map slot (n_map_kf x 16, row-major; NULL slots: anything) -- poses stay with the host
+//   dst      where the landmarks go: the image's own X arrays (LocalMapIndex::writeBackDst())
+//   kf_list  out: the map index of every optimised keyframe; T_out (nkf x 16): what :2676-2680 store as T_kf_w; x_out (nkf x 6)
+// returns the number of solves; trace (optional) receives one record per solve
+inline int runResident(plslam_ctx* ctx, const plslam_cam& cam, const Params& prm, plslam_local_map* lm, const plslam_map_index& map,
+                       const plslam_local_map_lba_dst& dst, const std::vector<double>& T_all, std::vector<int32_t>& kf_list,
+                       std::vector<double>& T_out, std::vector<double>& x_out, std::vector<plslam_gba_solve>* trace = nullptr)
+{
+    if (T_all.size() != (size_t)map.n_map_kf * 16) throw std::runtime_error("[gba] runResident: T_all is n_map_kf x 16");
+    plslam_local_map_counts c{};
+    check(plslam_local_map_form_all(lm, &map, &c), "plslam_local_map_form_all");
+    check(plslam_local_map_gather(lm, &map, &c), "plslam_local_map_gather");
+    plslam_local_map_buffers b{};
+    check(plslam_local_map_device_buffers(lm, &b), "plslam_local_map_device_buffers");
+    plslam_gba_plan* plan = nullptr;
+    check(plslam_gba_plan_create_dev(ctx, &cam, prm.homog_th, map.n_map_kf, c.nkf, b.kf_list, c.npt, c.nls, b.pt_obs, b.pt_obs_uv, c.n_pt_obs,
+                                     b.ls_obs, b.ls_l_obs, c.n_ls_obs, &plan),
+          "plslam_gba_plan_create_dev");
+    kf_list.assign((size_t)c.nkf, 0);
+    x_out.assign((size_t)c.nkf * 6, 0.0);
+    T_out.assign((size_t)c.nkf * 16, 0.0);
+    std::vector<plslam_gba_solve> tr((size_t)(prm.max_iters_lba > 1 ? prm.max_iters_lba : 1));
+    plslam_gba_result res{};
+    const double* X = b.X_aux;
+    int rc = plslam_gba_optimize_dev(plan, prm.lambda_lba_lm, prm.lambda_lba_k, prm.max_iters_lba, T_all.data(), X, X + 6 * (size_t)c.nkf,
+                                     X + 6 * (size_t)c.nkf + 3 * (size_t)c.npt, x_out.data(), T_out.data(), tr.data(), &res);
+    const char* where = "plslam_gba_optimize_dev";
+    if (rc == PLSLAM_OK) { rc = plslam_local_map_apply_gba(lm, plan, &dst); where = "plslam_local_map_apply_gba"; }
+    plslam_gba_plan_destroy(plan);
+    check(rc, where);
+    plslam_local_map_buffers h{};
+    h.kf_list = kf_list.data();
+    check(plslam_local_map_download(lm, &h), "plslam_local_map_download");
     if (trace) trace->assign(tr.begin(), tr.begin() + res.n_solves);
     return res.n_solves;
 }

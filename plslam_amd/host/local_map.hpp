@@ -160,11 +160,44 @@ public:
     // caller keeps them (plslam_local_map_download: pt_moved / ls_moved).
     int applyLba(plslam_lba_plan* plan, double moved_th = 0.01)
     {
+        const plslam_local_map_lba_dst d = writeBackDst();
+        check(plslam_local_map_apply_lba(lm_, plan, &d, moved_th, &counts_), "apply_lba");
+        return counts_.n_pt_moved + counts_.n_ls_moved;
+    }
+    // The gather of globalBundleAdjustment() (:1995-2092) left ON THE DEVICE: every non-NULL keyframe but slot 0, every non-NULL
+    // landmark with all its observations.  formAll() overwrites the flags of the last formLocalMap(): removeBadMapLandmarks() or
+    // candidates() afterwards need a new formLocalMap().  The lists stay in the handle's device buffers (deviceBuffers()) for
+    // plslam_gba_plan_create_dev -- PLSLAM::gba::runResident (host/gba.hpp) takes them from there.
+    void formAll() { check(plslam_local_map_form_all(lm_, &map_, &counts_), "form_all"); }
+    void gatherResident() { check(plslam_local_map_gather(lm_, &map_, &counts_), "gather"); }
+    plslam_local_map_buffers deviceBuffers()
+    {
+        plslam_local_map_buffers b{};
+        check(plslam_local_map_device_buffers(lm_, &b), "device_buffers");
+        return b;
+    }
+    // where the write-backs put the landmarks: the image's own X (and inlier) arrays, this object's device memory
+    plslam_local_map_lba_dst writeBackDst() const
+    {
         plslam_local_map_lba_dst d{};
         d.pt_X = const_cast<double*>(map_.points.X); d.pt_inlier = const_cast<uint8_t*>(map_.points.inlier);
         d.ls_X = const_cast<double*>(map_.lines.X); d.ls_inlier = const_cast<uint8_t*>(map_.lines.inlier);
-        check(plslam_local_map_apply_lba(lm_, plan, &d, moved_th, &counts_), "apply_lba");
-        return counts_.n_pt_moved + counts_.n_ls_moved;
+        return d;
+    }
+    // the write-back of globalBundleAdjustment() (:2681-2697) from the GBA plan's resident landmarks into the image, in place,
+    // after gatherResident() on this handle: point3D / line3D <- the estimate; no moved test, inlier untouched
+    void applyGba(plslam_gba_plan* plan)
+    {
+        const plslam_local_map_lba_dst d = writeBackDst();
+        check(plslam_local_map_apply_gba(lm_, plan, &d), "apply_gba");
+    }
+    // the image's landmarks, device -> host (n x 3 points, n x 6 lines): what a write-back left there
+    void downloadLandmarks(std::vector<double>& pts_X, std::vector<double>& lns_X) const
+    {
+        pts_X.assign(3 * (size_t)map_.points.n, 0.0);
+        lns_X.assign(6 * (size_t)map_.lines.n, 0.0);
+        if (!pts_X.empty()) hip_check(hipMemcpy(pts_X.data(), map_.points.X, pts_X.size() * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (!lns_X.empty()) hip_check(hipMemcpy(lns_X.data(), map_.lines.X, lns_X.size() * 8, hipMemcpyDeviceToHost), "hipMemcpy");
     }
     const plslam_local_map_counts& counts() const { return counts_; }
 

@@ -108,6 +108,16 @@ class LocalMap:
         self._counts = dict(n_kf_local=c.n_kf_local, n_pt_local=c.n_pt_local, n_ls_local=c.n_ls_local)
         return dict(self._counts)
 
+    def form_all(self, index: DeviceMapIndex) -> dict:
+        """The flags of the GLOBAL bundle adjustment's gather (:1995-2092): every non-NULL keyframe and landmark.  It overwrites
+        the flags of the last form: cull / candidates afterwards need a new form."""
+        c = LocalMapCounts()
+        _check(self._L.plslam_local_map_form_all(self._h, C.addressof(index.struct), C.addressof(c)), "plslam_local_map_form_all")
+        s = index.struct
+        self._dims = dict(kf=s.n_map_kf, pt=s.points.n, ls=s.lines.n)
+        self._counts = dict(n_kf_local=c.n_kf_local, n_pt_local=c.n_pt_local, n_ls_local=c.n_ls_local)
+        return dict(self._counts)
+
     def candidates(self, index: DeviceMapIndex, kf2_idx: int) -> None:
         _check(self._L.plslam_local_map_candidates(self._h, C.addressof(index.struct), int(kf2_idx)), "plslam_local_map_candidates")
 
@@ -133,6 +143,12 @@ class LocalMap:
         _check(self._L.plslam_local_map_apply_lba(self._h, plan._h, C.addressof(dst), float(moved_th), C.addressof(c)),
                "plslam_local_map_apply_lba")
         return dict(n_pt_moved=c.n_pt_moved, n_ls_moved=c.n_ls_moved)
+
+    def apply_gba(self, plan, index: DeviceMapIndex) -> None:
+        """The write-back of the global BA (:2681-2697) from the GbaPlan's resident landmarks into `index`'s own X arrays, in
+        place: every listed landmark takes the plan's estimate; inlier is not touched."""
+        dst = LocalMapLbaDst(index.ptr("points.X"), None, index.ptr("lines.X"), None)
+        _check(self._L.plslam_local_map_apply_gba(self._h, plan._h, C.addressof(dst)), "plslam_local_map_apply_gba")
 
     def device_buffers(self) -> dict:
         b = LocalMapBuffers()

@@ -134,7 +134,9 @@ void plslam_ctx_destroy(plslam_ctx* ctx);
  * everything in LDS (the SLAM loop's 200 x 200 line problems) | 0 = the general kernels; identical tables),
  * "zero_copy_kb" (plslam_match_grid: n > 0 (default 64) = an upload image of at most n KB is read by the dense kernel where it
  * lies in page-locked host memory -- no copy command in front of the kernel: 57 -> 51 us per 200 x 200 call | -n = for the general
- * kernels too (measured neutral to slower: they read their inputs many times) | 0 = always copy; identical tables) */
+ * kernels too (measured neutral to slower: they read their inputs many times) | 0 = always copy; identical tables),
+ * "lba_loop_peek" (plslam_lba_plan_optimize_dev: 1 (default) = between two passes the host looks at the loop's stop word where
+ * the device writes it and stops enqueuing | 0 = all max_iters_lba passes are enqueued blindly; identical results) */
 int plslam_ctx_set_option(plslam_ctx* ctx, const char* key, int value);
 int plslam_ctx_get_option(plslam_ctx* ctx, const char* key, int* value);
 /* device facts for reports: CU count, max clock (kHz), LDS bytes per workgroup */
@@ -662,6 +664,51 @@ typedef struct plslam_lba_lists {
 } plslam_lba_lists;
 int plslam_lba_plan_list_sizes(plslam_lba_plan* plan, int prepare_schur, plslam_lba_list_sizes* out);
 int plslam_lba_plan_lists(plslam_lba_plan* plan, const plslam_lba_lists* host);
+
+/* ---- K98-K104: the whole LM loop of levMarquardtOptimizationLBA (src/mapHandler.cpp:1334-1812) in one call (additive within 5) --
+ * plslam_lba_plan_optimize_dev runs the loop that PLSLAM::LbaPlanSolver::optimizeResident (host/lba_rows.hpp) runs with two
+ * synchronisations per iteration, on the device: the reduced system is solved there (L D L^T without pivoting, one workgroup),
+ * the pose update x_k <- logmap(expmap(x_k) inverse(expmap(dp_k))) and the loop's decisions run there, and the loop's variables
+ * live in a control block in device memory.  Every kernel of a pass returns at once when the loop has ended, so the call
+ * enqueues passes without waiting and synchronises ONCE, at its end.
+ *   plan          of either kind, its landmarks resident: plslam_lba_plan_create_dev with d_Xw / d_Lw, or any plan an earlier
+ *                 plslam_lba_plan_iterate / _iterate_dev has filled; otherwise PLSLAM_EINVAL.  The landmarks stay in the plan:
+ *                 plslam_local_map_apply_lba or plslam_lba_plan_get_landmarks take them from there.
+ *   T_slots       n_pose_slots x 16 (host): the stored T_kf_w; the estimate slots first_estimate_slot + k must hold key frame k's
+ *                 stored T_kf_w on entry -- the first pass reads the slots as given (:1369), expmap(x) appears from the first
+ *                 update on (:1601)
+ *   x_kf          nkf x 6 (host); x_kf_out: nkf x 6; T_out: nkf x 16 = expmap_se3(x_kf_out) (:1822-1826), may be NULL
+ *   trace         max(max_iters_lba, 1) records, one per H / g build ([0] = the first pass), may be NULL
+ * The loop's quirks are the reference's: the first err is divided by two counters that are never incremented (+inf, or NaN);
+ * lambda0 = lambda_lba_lm * max |H(i,i)|; the first solve is always applied; later errs are divided by Npt + Nls; lambda GROWS on
+ * an applied step; ||DX|| is taken over all N unknowns, for a rejected step too; err_prev = err after a rejected step too.
+ * PLSLAM_EINVAL (nothing launched): a NULL plan, prm, T_slots, x_kf, x_kf_out or result; lambda_lba_k == 0; nkf < 1;
+ * first_estimate_slot < 0 or first_estimate_slot + nkf > n_pose_slots.
+ *   plslam_lba_reduced_ldlt_solve   the solve kernel alone: A (n x n, row-major, host; the lower triangle is read), b, x (n);
+ *                 *n_bad_pivots (may be NULL) counts the pivots that are <= 0 or not finite.  n <= 120 runs on one workgroup with
+ *                 A in LDS; larger systems go through the blocked L D L^T of plslam_dense_ldlt_solve on a padded copy. */
+#define PLSLAM_LBA_STOP_MAX_ITERS 0   /* iters == max_iters_lba                                                              */
+#define PLSLAM_LBA_STOP_ERR 1         /* |err - err_prev| < min_error_change || err < min_error (:1775)                       */
+#define PLSLAM_LBA_STOP_DX 2          /* ||DX|| < min_error_change (:1808)                                                    */
+#define PLSLAM_LBA_STOP_NOT_PD 3      /* a pivot of the reduced system was <= 0 or not finite: step NOT applied               */
+typedef struct plslam_lba_lm_params {
+    double lambda_lba_lm, lambda_lba_k;
+    int32_t max_iters_lba, reserved;
+    double min_error_change, min_error;
+} plslam_lba_lm_params;
+typedef struct plslam_lba_solve {      /* one per H / g build, [0] = the first pass */
+    double lambda, err_raw, err, dx_norm;
+    int32_t n_singular, n_bad_pivots;
+    int32_t applied, reserved;         /* 1, 0, or -1: stopped before the solve */
+} plslam_lba_solve;
+typedef struct plslam_lba_result {
+    int32_t iters, n_builds, stop_reason, n_enqueued_passes;
+    double err, err_prev, lambda, hmax;
+} plslam_lba_result;
+int plslam_lba_plan_optimize_dev(plslam_lba_plan* plan, const plslam_lba_lm_params* prm, const double* T_slots, const double* x_kf,
+                                 int32_t first_estimate_slot, double* x_kf_out, double* T_out, plslam_lba_solve* trace,
+                                 plslam_lba_result* result);
+int plslam_lba_reduced_ldlt_solve(plslam_ctx* ctx, int32_t n, const double* A, const double* b, double* x, int32_t* n_bad_pivots);
 
 /* ---- K17: pose-only Gauss-Newton system of the loop-closure relative pose ------------------------------- */
 /* The iteration body of MapHandler::computeRelativePoseGN (src/mapHandler.cpp:3324-3424) and of

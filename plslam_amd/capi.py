@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "plslam_lba_plan_set_poses", "plslam_lba_plan_host_state", "plslam_lba_plan_get_landmarks",
     "plslam_lba_plan_iterate_schur", "plslam_lba_plan_apply_step", "plslam_lba_point_rows_dev_n", "plslam_lba_line_rows_dev_n", "plslam_rccl_available",
     "plslam_lba_plan_blocks", "plslam_lba_plan_create_dev", "plslam_lba_plan_list_sizes", "plslam_lba_plan_lists",
+    "plslam_lba_plan_optimize_dev", "plslam_lba_reduced_ldlt_solve",
     "plslam_map2kf_point_gate", "plslam_map2kf_line_gate", "plslam_map_point_visible",
     "plslam_map_line_visible", "plslam_map2kf_match_points", "plslam_map2kf_match_lines",
     "plslam_map2kf_match_points_fast", "plslam_map2kf_match_lines_fast", "plslam_map2kf_match_points_dev", "plslam_map2kf_match_lines_dev",
@@ -79,6 +80,26 @@ LC_MAX_ITERS = 10000     # include/plslam_hip.h: PLSLAM_LC_MAX_ITERS
 LC_MAX_BATCH = 65536     # include/plslam_hip.h: PLSLAM_LC_MAX_BATCH
 GBA_MAX_KEYFRAMES = 4096  # include/plslam_hip.h: PLSLAM_GBA_MAX_KEYFRAMES
 GBA_STOP_MAX_ITERS, GBA_STOP_ERR, GBA_STOP_DX = 0, 1, 2
+LBA_STOP_MAX_ITERS, LBA_STOP_ERR, LBA_STOP_DX, LBA_STOP_NOT_PD = 0, 1, 2, 3
+LBA_SOLVE_MAX_N6 = 120   # plslam_amd/csrc/lba_lm_dev.hip: the largest reduced system the one-workgroup solve takes
+
+
+class LbaLmParams(C.Structure):
+    """plslam_lba_lm_params"""
+    _fields_ = [("lambda_lba_lm", C.c_double), ("lambda_lba_k", C.c_double), ("max_iters_lba", C.c_int32), ("reserved", C.c_int32),
+                ("min_error_change", C.c_double), ("min_error", C.c_double)]
+
+
+class LbaSolve(C.Structure):
+    """plslam_lba_solve: one record per H / g build of plslam_lba_plan_optimize_dev"""
+    _fields_ = [("lambda_", C.c_double), ("err_raw", C.c_double), ("err", C.c_double), ("dx_norm", C.c_double),
+                ("n_singular", C.c_int32), ("n_bad_pivots", C.c_int32), ("applied", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LbaResult(C.Structure):
+    """plslam_lba_result"""
+    _fields_ = [("iters", C.c_int32), ("n_builds", C.c_int32), ("stop_reason", C.c_int32), ("n_enqueued_passes", C.c_int32),
+                ("err", C.c_double), ("err_prev", C.c_double), ("lambda_", C.c_double), ("hmax", C.c_double)]
 
 
 class GbaSolve(C.Structure):
@@ -375,6 +396,8 @@ def load() -> C.CDLL:
                                              vp, vp, i32, C.POINTER(vp)]
     L.plslam_lba_plan_list_sizes.argtypes = [vp, C.c_int, vp]
     L.plslam_lba_plan_lists.argtypes = [vp, vp]
+    L.plslam_lba_plan_optimize_dev.argtypes = [vp, C.POINTER(LbaLmParams), vp, vp, i32, vp, vp, vp, C.POINTER(LbaResult)]
+    L.plslam_lba_reduced_ldlt_solve.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32)]
     for f in (L.plslam_map2kf_point_gate, L.plslam_map2kf_line_gate):
         f.argtypes = [vp, C.POINTER(Cam), vp, vp, vp, i32, vp, i32, f64, vp, C.POINTER(i32)]
     for f in (L.plslam_map_point_visible, L.plslam_map_line_visible):
@@ -576,6 +599,17 @@ class Context:
         v = C.c_int()
         _check(self._L.plslam_ctx_get_option(self._h, key.encode(), C.byref(v)), "plslam_ctx_get_option")
         return v.value
+
+    def lba_reduced_ldlt_solve(self, A, b):
+        """plslam_lba_reduced_ldlt_solve: the local BA's solve kernel alone -- x with (the lower triangle of A, mirrored) x = b by
+        L D L^T without pivoting -> (x, number of pivots that are <= 0 or not finite)."""
+        A = _arr(A, np.float64)
+        n = A.shape[0]
+        assert A.shape == (n, n)
+        bb = _arr(b, np.float64, (n,))
+        x, nb = np.empty(n), C.c_int32(0)
+        _check(self._L.plslam_lba_reduced_ldlt_solve(self._h, n, _p(A), _p(bb), _p(x), C.byref(nb)), "plslam_lba_reduced_ldlt_solve")
+        return x, int(nb.value)
 
     def device_info(self) -> dict:
         cu, clk, lds = C.c_int32(), C.c_int32(), C.c_int32()
@@ -1209,6 +1243,30 @@ class LbaPlan:
         _check(self._L.plslam_lba_plan_apply_step(self._h, _p(dp), _p(T) if T is not None else None, int(bool(apply)), _p(ss)),
                "plslam_lba_plan_apply_step")
         return float(ss[0])
+
+    def optimize_dev(self, T_slots, x_kf, first_estimate_slot, lambda_lm=1e-5, lambda_k=10.0, max_iters=15, min_error_change=1e-7,
+                     min_error=1e-7) -> dict:
+        """plslam_lba_plan_optimize_dev: the whole LM loop of the local BA on the device, one synchronisation.  T_slots
+        (n_pose_slots, 16): the stored T_kf_w, in the estimate slots too; x_kf (nkf, 6).  The landmarks must be resident and stay in
+        the plan (get_landmarks, LocalMap.apply_lba).  -> dict(x_kf (nkf, 6), T (nkf, 4, 4), the trace arrays lam / err_raw / err /
+        dx_norm / n_singular / n_bad_pivots / applied (one entry per H / g build), iters, n_builds, stop_reason,
+        n_enqueued_passes, err_last, err_prev, lam_last, hmax)."""
+        nkf, nslot = self.dims[0], self.dims[5]
+        T = _arr(T_slots, np.float64, (nslot, 16))
+        x = _arr(x_kf, np.float64, (nkf, 6))
+        prm = LbaLmParams(float(lambda_lm), float(lambda_k), int(max_iters), 0, float(min_error_change), float(min_error))
+        xo, To = np.empty((nkf, 6)), np.empty((nkf, 4, 4))
+        tr = (LbaSolve * max(int(max_iters), 1))()
+        res = LbaResult()
+        _check(self._L.plslam_lba_plan_optimize_dev(self._h, C.byref(prm), _p(T), _p(x), int(first_estimate_slot), _p(xo), _p(To),
+                                                    C.cast(tr, C.c_void_p), C.byref(res)), "plslam_lba_plan_optimize_dev")
+        rec = tr[:res.n_builds]
+        return dict(x_kf=xo, T=To, lam=np.array([t.lambda_ for t in rec]), err_raw=np.array([t.err_raw for t in rec]),
+                    err=np.array([t.err for t in rec]), dx_norm=np.array([t.dx_norm for t in rec]),
+                    n_singular=np.array([t.n_singular for t in rec], np.int32), n_bad_pivots=np.array([t.n_bad_pivots for t in rec], np.int32),
+                    applied=np.array([t.applied for t in rec], np.int32), iters=res.iters, n_builds=res.n_builds,
+                    stop_reason=res.stop_reason, n_enqueued_passes=res.n_enqueued_passes, err_last=res.err, err_prev=res.err_prev,
+                    lam_last=res.lambda_, hmax=res.hmax)
 
     def get_landmarks(self):
         """The resident landmarks (after backsub(apply=True)) -> (Xw (npt, 3), Lw (nls, 6)); also refreshes the page-locked images

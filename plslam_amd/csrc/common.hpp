@@ -184,6 +184,7 @@ struct plslam_ctx {
     hipEvent_t lc_ev[2] = {nullptr, nullptr};       // ... its fences with a caller's stream (the _dev forms)
     plslam::DevBuf lc_args;                         // plslam_relpose_robust_gn_batched_dev: K54's argument table
     std::vector<char> lc_args_h;                    // ... and its host image (pageable: staged by the copy call itself)
+    int lba_loop_peek = 1;                          // plslam_lba_plan_optimize_dev: 1 = the host looks at the mapped stop word between two passes and stops enqueuing, 0 = every pass is enqueued
     int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
     plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (lc_correct.hip)
     plslam::DevBuf lists_scratch;                   // the carries' chain words and touched-landmark lists (map_lists.hip)

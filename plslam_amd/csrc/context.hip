@@ -187,6 +187,7 @@ const OptionDesc kOptions[] = {
     {"split_target", &plslam_ctx::split_target, nullptr, 0, 64},
     {"split_min_tiles", &plslam_ctx::split_min_tiles, nullptr, 0, 64},
     {"post_workgroups", &plslam_ctx::post_workgroups, nullptr, 0, INT32_MAX},
+    {"lba_loop_peek", &plslam_ctx::lba_loop_peek, nullptr, 0, 1},
     {"pgo_solver", &plslam_ctx::pgo_solver, nullptr, 0, 1},                   // measurement tools only: 1 = the pose graph on the dense L D L^T
 };
 const OptionDesc* find_option(const char* key, bool to_write)

@@ -35,7 +35,7 @@
 #include "gba_plan.hpp"
 #include "lba_plan.hpp"
 #include "ldlt_dense.hpp"
-#include "se3_dev.hpp"
+#include "pose_step_dev.hpp"
 
 namespace plslam {
 namespace {
@@ -297,19 +297,10 @@ k_gba_pose(int32_t nkf, const double* __restrict__ dp, int32_t apply, double* __
 #pragma unroll
         for (int a = 0; a < 6; ++a) { d[a] = dp[6 * (size_t)k + a]; ss += d[a] * d[a]; x[a] = xkf[6 * (size_t)k + a]; }
         if (apply) {
-            double Tp[16], E[16], Ei[16], Tc[16];
-            expmap_se3(x, Tp);
-            expmap_se3(d, E);
-            inverse_se3(E, Ei);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    Tc[4 * i + c] = Tp[4 * i] * Ei[c] + Tp[4 * i + 1] * Ei[4 + c] + Tp[4 * i + 2] * Ei[8 + c] + Tp[4 * i + 3] * Ei[12 + c];
-            logmap_se3(Tc, x);
+            double Tp[16];
+            pose_step_se3(d, x, Tp);
 #pragma unroll
             for (int a = 0; a < 6; ++a) xkf[6 * (size_t)k + a] = x[a];
-            expmap_se3(x, Tp);
 #pragma unroll
             for (int i = 0; i < 16; ++i) Test[16 * (size_t)k + i] = Tp[i];
         }

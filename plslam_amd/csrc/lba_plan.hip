@@ -31,8 +31,7 @@ struct LbaIterArgs {
     double *pJp, *pJl, *pr, *pw, *lJp, *lJl, *lr, *lw, *Wp, *Wl, *err_part;   // err_part[nbp + nbl]
 };
 
-__global__ void __launch_bounds__(256)
-k_lba_rows_cross(const LbaIterArgs A)
+__device__ __forceinline__ void lba_rows_cross_wg(const LbaIterArgs& A)
 {
     // (a slab holds a wave's 64 rows of up to 18 doubles: the cross blocks leave through it too -- written lane by lane they were 18 /
     // 36 instructions of 64 scattered 8-byte stores each)
@@ -125,6 +124,18 @@ k_lba_rows_cross(const LbaIterArgs A)
     }
     if (threadIdx.x == 0) A.err_part[blockIdx.x] = red[0];
 }
+__global__ void __launch_bounds__(256)
+k_lba_rows_cross(const LbaIterArgs A)
+{
+    lba_rows_cross_wg(A);
+}
+// plslam_lba_plan_optimize_dev (lba_lm_dev.hip): the same pass behind the loop's stop word -- a pass enqueued behind the stop changes nothing
+__global__ void __launch_bounds__(256)
+k_lba_rows_cross_lm(const LbaIterArgs A, const LbaLmCtl* __restrict__ ctl)
+{
+    if (ctl->stop != LM_RUNNING) return;
+    lba_rows_cross_wg(A);
+}
 
 // One lane per landmark, 64 landmarks per workgroup (a wave: the 2 000 lines of C3 were 8 workgroups of 256 on 8 CUs).  The blocks
 // leave through an LDS slab in runs (wave_store_rows): a lane storing its own 36 doubles word by word is 36 instructions of 64
@@ -185,8 +196,7 @@ __device__ __forceinline__ void landmark_block(int l0 /* the wave's first landma
     }
 }
 
-__global__ void __launch_bounds__(256)
-k_lba_blocks(const LbaBlockArgs A)
+__device__ __forceinline__ void lba_blocks_wg(const LbaBlockArgs& A)
 {
     __shared__ __attribute__((aligned(16))) double slab[64 * 36];
     const int b = blockIdx.x;
@@ -236,9 +246,30 @@ k_lba_blocks(const LbaBlockArgs A)
 }
 
 __global__ void __launch_bounds__(256)
+k_lba_blocks(const LbaBlockArgs A)
+{
+    lba_blocks_wg(A);
+}
+// ... with the damping read from the loop's control block (the landmark inverses of the fused form)
+__global__ void __launch_bounds__(256)
+k_lba_blocks_lm(LbaBlockArgs A, const LbaLmCtl* __restrict__ ctl)
+{
+    if (ctl->stop != LM_RUNNING) return;
+    A.lambda = ctl->lambda;
+    lba_blocks_wg(A);
+}
+
+__global__ void __launch_bounds__(256)
 k_lba_finish(const LbaBlockArgs A)
 {
     __shared__ double red[256];
+    lba_finish_wg<256>(A, (int)blockIdx.x, red);
+}
+__global__ void __launch_bounds__(256)
+k_lba_finish_lm(const LbaBlockArgs A, const LbaLmCtl* __restrict__ ctl)
+{
+    __shared__ double red[256];
+    if (ctl->stop != LM_RUNNING) return;
     lba_finish_wg<256>(A, (int)blockIdx.x, red);
 }
 
@@ -259,7 +290,7 @@ LbaBlockArgs lba_block_args(plslam_lba_plan* P)
 }
 
 int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw, const double* Lw, int compat_flags, bool upload,
-                     double fused_lambda)
+                     double fused_lambda, const LbaLmCtl* ctl)
 {
     plslam_ctx* ctx = P->ctx;
     hipStream_t s = ctx->stream;
@@ -286,7 +317,8 @@ int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw,
     A.np = P->np; A.nl = P->nl; A.nbp = nbp; A.nbl = nbl; A.n_slots = P->n_slots;
     A.pJp = R.pJp; A.pJl = R.pJl; A.pr = R.pr; A.pw = R.pw; A.lJp = R.lJp; A.lJl = R.lJl; A.lr = R.lr; A.lw = R.lw;
     A.Wp = O.W_pt; A.Wl = O.W_ls; A.err_part = O.err_part;
-    if (nbp + nbl > 0) hipLaunchKernelGGL(k_lba_rows_cross, dim3(nbp + nbl), dim3(256), 0, s, A);
+    if (nbp + nbl > 0 && ctl) hipLaunchKernelGGL(k_lba_rows_cross_lm, dim3(nbp + nbl), dim3(256), 0, s, A, ctl);
+    else if (nbp + nbl > 0) hipLaunchKernelGGL(k_lba_rows_cross, dim3(nbp + nbl), dim3(256), 0, s, A);
     LbaBlockArgs B = lba_block_args(P);
     const bool fused = fused_lambda >= 0.0;
     if (fused) {
@@ -296,9 +328,12 @@ int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw,
         B.nsing = C.tail.sing + P->schur_parity;
     }
     const int32_t nchunk_wgs = (P->nkf * P->max_chunks + 3) / 4;
-    if (B.nb3 + B.nb6 + nchunk_wgs > 0)
+    if (B.nb3 + B.nb6 + nchunk_wgs > 0 && ctl)
+        hipLaunchKernelGGL(k_lba_blocks_lm, dim3(B.nb3 + B.nb6 + nchunk_wgs), dim3(256), 0, s, B, ctl);
+    else if (B.nb3 + B.nb6 + nchunk_wgs > 0)
         hipLaunchKernelGGL(k_lba_blocks, dim3(B.nb3 + B.nb6 + nchunk_wgs), dim3(256), 0, s, B);
-    if (!fused) hipLaunchKernelGGL(k_lba_finish, dim3(P->nkf + 1), dim3(256), 0, s, B);
+    if (!fused && ctl) hipLaunchKernelGGL(k_lba_finish_lm, dim3(P->nkf + 1), dim3(256), 0, s, B, ctl);
+    else if (!fused) hipLaunchKernelGGL(k_lba_finish, dim3(P->nkf + 1), dim3(256), 0, s, B);
     PLSLAM_HIP_CHECK(hipGetLastError());
     P->blocks_valid = true;
     P->blocks_gba = (compat_flags & PLSLAM_LBA_COMPAT_GBA) != 0;

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "lba_blocks_dev.hpp"
+#include "lba_lm_ctl.hpp"
 
 struct plslam_lba_plan;
 
@@ -61,8 +62,17 @@ LbaBlockArgs lba_block_args(plslam_lba_plan* P);
 // fused_lambda >= 0 (plslam_lba_plan_iterate_schur; the Schur step's buffers exist): the landmark inverses for that damping are
 // written by the blocks' launch, and the last stage (K10) is NOT launched here -- it rides in the Schur partials' launch
 // (lba_schur.hip: lba_schur_enqueue(fused)), which the caller enqueues next
+// ctl (plslam_lba_plan_optimize_dev): every kernel returns at once when the loop's stop word is set, and the fused form reads the
+// damping from the control block (fused_lambda >= 0 then only says "fused")
 int lba_plan_enqueue(plslam_lba_plan* P, const double* T_kf_w, const double* Xw, const double* Lw, int compat_flags, bool upload = true,
-                     double fused_lambda = -1.0);
+                     double fused_lambda = -1.0, const LbaLmCtl* ctl = nullptr);
+// (lba_schur.hip) the Schur step's launches on the blocks of the last iteration (fused: of the iteration whose last stage rides in
+// the partials' launch); no copy, no synchronisation; *par_out = the counter word of singular landmarks this call counts in.
+// ctl: behind the stop word, the damping from the control block, S and b left on the device (sc.tail) for the device's solve
+int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bool fused = false, const LbaLmCtl* ctl = nullptr);
+// (lba_schur.hip) the back-substitution of the dp the device's solve left in sc.dp, applied when the control block says so
+int lba_backsub_enqueue_lm(plslam_lba_plan* P, const LbaLmCtl* ctl);
+int lba_backsub_wgs(const plslam_lba_plan* P);      // its workgroups: one sum of squares each in sc.dx_part
 // (lba_schur.hip) on first use: the pair lists (lba_lists.hpp), the Schur buffers carved and the lists uploaded -- or, for a plan
 // whose lists were built on the device (plslam_lba_plan_create_dev), lba_schur_prepare_dev
 int lba_schur_prepare(plslam_lba_plan* P);
@@ -126,11 +136,16 @@ struct plslam_lba_plan {
     bool schur_ready = false, schur_done = false;
     int schur_parity = 0;              // which of the two counters of singular landmarks the next plslam_lba_plan_schur counts in
     int32_t nblk = 0, schur_chunks = 0;
+    // ---- plslam_lba_plan_optimize_dev (lba_lm_dev.hip): the loop's control block, x_kf, the solve's scratch | their images
+    plslam::DevBuf lm;
+    plslam::HostBuf lm_pin;
+    int32_t lm_trace_cap = 0;          // trace records the two blocks have room for (0: not laid out yet)
 
     size_t n_unknowns() const { return 6 * (size_t)nkf + 3 * (size_t)npt + 6 * (size_t)nls; }
     void release()
     {
         stat.release(); dyn.release(); rows.release(); out.release(); pin_in.release(); pin_out.release();
         schur.release(); schur_pin.release(); aux.release(); aux_schur.release(); pin_cnt.release();
+        lm.release(); lm_pin.release();
     }
 };

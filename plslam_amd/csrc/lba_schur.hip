@@ -46,6 +46,23 @@ k_schur_landmarks(const double* __restrict__ H_pt, const double* __restrict__ g_
     }
 }
 
+// (plslam_lba_plan_optimize_dev, lba_lm_dev.hip: the same kernels behind the loop's stop word, the damping read from its control block)
+__global__ void __launch_bounds__(256)
+k_schur_landmarks_lm(const double* __restrict__ H_pt, const double* __restrict__ g_pt, int32_t npt, const double* __restrict__ H_ls,
+                     const double* __restrict__ g_ls, int32_t nls, int32_t nb3, const LbaLmCtl* __restrict__ ctl, double* __restrict__ Vp,
+                     double* __restrict__ tp, double* __restrict__ Vl, double* __restrict__ tl, int32_t* __restrict__ nsing)
+{
+    if (ctl->stop != LM_RUNNING) return;
+    const double lambda = ctl->lambda;
+    if ((int)blockIdx.x < nb3) {
+        const int j = blockIdx.x * 256 + threadIdx.x;
+        if (j < npt) schur_landmark<3>(H_pt, g_pt, j, lambda, Vp, tp, nsing);
+    } else {
+        const int j = ((int)blockIdx.x - nb3) * 256 + threadIdx.x;
+        if (j < nls) schur_landmark<6>(H_ls, g_ls, j, lambda, Vl, tl, nsing);
+    }
+}
+
 // W_pt[o]: 3 x 6 (landmark row x, pose column a), W_ls[o]: 6 x 6.  Entry (a, b) of W1^T Vinv W2 = sum_x sum_y W1[x][a] Vinv[x][y] W2[y][b].
 // A workgroup = one chunk of SCH_CHUNK pairs: lane i computes the whole 6 x 6 contribution of pair i (its loads are one round
 // trip: a first form with a lane per entry walking the chunk was a chain of 64 dependent round trips, 177 us per call at C3),
@@ -373,6 +390,15 @@ k_schur_partials(SchurPartArgs A, int32_t npart)
     schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, (int)blockIdx.x * SCH_WAVES + wv, npart);
 }
 
+__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES)
+k_schur_partials_lm(SchurPartArgs A, int32_t npart, const LbaLmCtl* __restrict__ ctl)
+{
+    __shared__ __attribute__((aligned(16))) double sch_lds[SCH_WAVES * SCH_TILE_DOUBLES];
+    if (ctl->stop != LM_RUNNING) return;
+    const int wv = (int)threadIdx.x >> 6;
+    schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, (int)blockIdx.x * SCH_WAVES + wv, npart);
+}
+
 // plslam_lba_plan_iterate_schur: the Schur partials and, in the SAME launch, the iteration's last stage (K10: keyframe blocks and err
 // from their partials) -- the two are independent (the partials read W and the landmark inverses, K22 behind them reads H_pose /
 // g_pose), so the iteration's third launch rides in the Schur step's second.  The last stage's workgroups come FIRST (a wave each;
@@ -390,9 +416,23 @@ k_schur_partials_lba_finish(SchurPartArgs A, const LbaBlockArgs B, int32_t npart
     schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, ((int)blockIdx.x - nF) * SCH_WAVES + wv, npart);
 }
 
+__global__ void __launch_bounds__(SCH_CHUNK * SCH_WAVES)
+k_schur_partials_lba_finish_lm(SchurPartArgs A, const LbaBlockArgs B, int32_t npart, const LbaLmCtl* __restrict__ ctl)
+{
+    __shared__ __attribute__((aligned(16))) double sch_lds[SCH_WAVES * SCH_TILE_DOUBLES];
+    if (ctl->stop != LM_RUNNING) return;
+    const int wv = (int)threadIdx.x >> 6;
+    const int nF = B.nkf + 1;
+    if ((int)blockIdx.x < nF) {
+        if (wv == 0) lba_finish_wg<SCH_CHUNK>(B, (int)blockIdx.x, sch_lds);
+        return;
+    }
+    schur_partials_item(reinterpret_cast<double (*)[37]>(sch_lds + wv * SCH_TILE_DOUBLES), A, ((int)blockIdx.x - nF) * SCH_WAVES + wv, npart);
+}
+
 // block B = (k1 <= k2) in row-major upper-triangle order; S is (6 nkf) x (6 nkf) row-major, b follows it
-__global__ void __launch_bounds__(64)
-k_schur_finish(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ kf_ptr, const double* __restrict__ spart,
+__device__ __forceinline__ void
+schur_finish_wg(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ kf_ptr, const double* __restrict__ spart,
                const double* __restrict__ bpart, const double* __restrict__ H_pose, const double* __restrict__ g_pose,
                int32_t nkf, int32_t nblk, int32_t schur_chunks, int32_t pose_chunks, double lambda, double* __restrict__ S,
                double* __restrict__ bvec, int32_t* __restrict__ next_sing, const double* __restrict__ err_src, double* __restrict__ err_dst,
@@ -443,6 +483,27 @@ k_schur_finish(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ 
         }
         bvec[6 * k + e] = g_pose[6 * k + e] - acc;
     }
+}
+__global__ void __launch_bounds__(64)
+k_schur_finish(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ kf_ptr, const double* __restrict__ spart,
+               const double* __restrict__ bpart, const double* __restrict__ H_pose, const double* __restrict__ g_pose,
+               int32_t nkf, int32_t nblk, int32_t schur_chunks, int32_t pose_chunks, double lambda, double* __restrict__ S,
+               double* __restrict__ bvec, int32_t* __restrict__ next_sing, const double* __restrict__ err_src, double* __restrict__ err_dst,
+               const int32_t* __restrict__ sing_cur, int32_t* __restrict__ sing_out)
+{
+    schur_finish_wg(blk_ptr, kf_ptr, spart, bpart, H_pose, g_pose, nkf, nblk, schur_chunks, pose_chunks, lambda, S, bvec, next_sing, err_src,
+                    err_dst, sing_cur, sing_out);
+}
+__global__ void __launch_bounds__(64)
+k_schur_finish_lm(const int32_t* __restrict__ blk_ptr, const int32_t* __restrict__ kf_ptr, const double* __restrict__ spart,
+                  const double* __restrict__ bpart, const double* __restrict__ H_pose, const double* __restrict__ g_pose,
+                  int32_t nkf, int32_t nblk, int32_t schur_chunks, int32_t pose_chunks, const LbaLmCtl* __restrict__ ctl,
+                  double* __restrict__ S, double* __restrict__ bvec, int32_t* __restrict__ next_sing, const double* __restrict__ err_src,
+                  double* __restrict__ err_dst, const int32_t* __restrict__ sing_cur)
+{
+    if (ctl->stop != LM_RUNNING) return;
+    schur_finish_wg(blk_ptr, kf_ptr, spart, bpart, H_pose, g_pose, nkf, nblk, schur_chunks, pose_chunks, ctl->lambda, S, bvec, next_sing,
+                    err_src, err_dst, sing_cur, nullptr);
 }
 
 // A lane per (landmark, row x of its step): the row's share of sum_o W_o dp[kf(o)] in list order, the DL shares of a landmark
@@ -499,14 +560,27 @@ struct SchurBackArgs {
     double *dx_pt, *dx_ls, *X, *L, *part;              // X / L = nullptr: do not apply; part: a sum of squares per workgroup
     int32_t npt, nls, nwg_pt;
 };
-__global__ void __launch_bounds__(BACK_WG)
-k_schur_backsub(SchurBackArgs A)
+__device__ __forceinline__ void schur_backsub_item(const SchurBackArgs& A)
 {
     __shared__ double sh[BACK_WG];
     if ((int)blockIdx.x < A.nwg_pt)
         schur_backsub_wg<3>(sh, (int)blockIdx.x, A.pt_ptr, A.pt_obs, A.pt_kf, A.npt, A.W_pt, A.Vp, A.tp, A.dp, A.dx_pt, A.X, A.part + blockIdx.x);
     else
         schur_backsub_wg<6>(sh, (int)blockIdx.x - A.nwg_pt, A.ls_ptr, A.ls_obs, A.ls_kf, A.nls, A.W_ls, A.Vl, A.tl, A.dp, A.dx_ls, A.L, A.part + blockIdx.x);
+}
+
+__global__ void __launch_bounds__(BACK_WG)
+k_schur_backsub(SchurBackArgs A)
+{
+    schur_backsub_item(A);
+}
+// the step is taken only when the control block says so: a rejected step leaves Xw / Lw untouched
+__global__ void __launch_bounds__(BACK_WG)
+k_schur_backsub_lm(SchurBackArgs A, const LbaLmCtl* __restrict__ ctl)
+{
+    if (ctl->stop != LM_RUNNING) return;
+    if (ctl->apply != 1) { A.X = nullptr; A.L = nullptr; }
+    schur_backsub_item(A);
 }
 
 // max over all diagonal entries of |H(i,i)| (a maximum: exact whatever the order)
@@ -622,7 +696,8 @@ extern "C" int plslam_lba_plan_diag_max(plslam_lba_plan* P, double* hmax)
 
 // the Schur step's three launches on the blocks of the last iteration (no copy, no synchronisation); *par = the counter word of
 // singular landmarks this call counts in
-static int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bool fused = false)
+namespace plslam {
+int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bool fused, const LbaLmCtl* ctl)
 {
     int rc = lba_schur_prepare(P);
     if (rc) return rc;
@@ -634,7 +709,10 @@ static int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bo
     int32_t* sing2 = C.tail.sing;
     const int par = P->schur_parity;
     const int32_t nb3 = (P->npt + 255) / 256, nb6 = (P->nls + 255) / 256;
-    if (nb3 + nb6 > 0 && !fused)                          // (fused: the iteration's blocks launch has written them)
+    if (nb3 + nb6 > 0 && !fused && ctl)
+        hipLaunchKernelGGL(k_schur_landmarks_lm, dim3(nb3 + nb6), dim3(256), 0, s, O.H_pt, O.g + n6, P->npt, O.H_ls,
+                           O.g + n6 + 3 * (size_t)P->npt, P->nls, nb3, ctl, C.Vp, C.tp, C.Vl, C.tl, sing2 + par);
+    else if (nb3 + nb6 > 0 && !fused)                     // (fused: the iteration's blocks launch has written them)
         hipLaunchKernelGGL(k_schur_landmarks, dim3(nb3 + nb6), dim3(256), 0, s, O.H_pt, O.g + n6, P->npt, O.H_ls,
                            O.g + n6 + 3 * (size_t)P->npt, P->nls, nb3, lambda, C.Vp, C.tp, C.Vl, C.tl, sing2 + par);
     SchurPartArgs A{};
@@ -643,13 +721,21 @@ static int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bo
     A.spart = C.spart; A.bpart = C.bpart;
     A.nblk = P->nblk; A.schur_chunks = P->schur_chunks; A.nkf = P->nkf; A.pose_chunks = P->max_chunks; A.n_pt_obs = P->np;
     const int32_t npart_wgs = P->nblk * P->schur_chunks + P->nkf * P->max_chunks;
-    if (fused)
+    if (fused && ctl)
+        hipLaunchKernelGGL(k_schur_partials_lba_finish_lm, dim3(npart_wgs + P->nkf + 1), dim3(SCH_CHUNK), 0, s, A, lba_block_args(P), npart_wgs, ctl);
+    else if (fused)
         hipLaunchKernelGGL(k_schur_partials_lba_finish, dim3(npart_wgs + P->nkf + 1), dim3(SCH_CHUNK), 0, s, A, lba_block_args(P), npart_wgs);
+    else if (npart_wgs > 0 && ctl)
+        hipLaunchKernelGGL(k_schur_partials_lm, dim3(npart_wgs), dim3(SCH_CHUNK), 0, s, A, npart_wgs, ctl);
     else if (npart_wgs > 0)
         hipLaunchKernelGGL(k_schur_partials, dim3(npart_wgs), dim3(SCH_CHUNK), 0, s, A, npart_wgs);
     // S, b, err and this call's counter: written where the host reads them (the page-locked image, mapped) when it can be -- no
     // copy behind the kernel; otherwise beside the partials on the device, and lba_schur_fetch copies
-    const SchurTail& to = P->schur_mapped ? P->simg_dev.tail : C.tail;
+    const SchurTail& to = P->schur_mapped && !ctl ? P->simg_dev.tail : C.tail;
+    if (ctl)
+        hipLaunchKernelGGL(k_schur_finish_lm, dim3(P->nblk + P->nkf), dim3(64), 0, s, C.blk_ptr, S.kf_ptr, C.spart, C.bpart, O.H_pose, O.g,
+                           P->nkf, P->nblk, P->schur_chunks, P->max_chunks, ctl, to.S, to.b, sing2 + (par ^ 1), O.err, to.err, sing2 + par);
+    else
     hipLaunchKernelGGL(k_schur_finish, dim3(P->nblk + P->nkf), dim3(64), 0, s, C.blk_ptr, S.kf_ptr, C.spart, C.bpart, O.H_pose, O.g, P->nkf,
                        P->nblk, P->schur_chunks, P->max_chunks, lambda, to.S, to.b, sing2 + (par ^ 1), O.err, to.err, sing2 + par,
                        P->schur_mapped ? to.sing + par : nullptr);
@@ -658,6 +744,7 @@ static int lba_schur_enqueue(plslam_lba_plan* P, double lambda, int* par_out, bo
     *par_out = par;
     return PLSLAM_OK;
 }
+}  // namespace plslam
 
 // S, b and the counter behind them: one copy, one synchronisation
 static int lba_schur_fetch(plslam_lba_plan* P, int par, double* S, double* b, int32_t* n_singular, double* err = nullptr)
@@ -714,19 +801,39 @@ extern "C" int plslam_lba_plan_iterate_schur(plslam_lba_plan* P, int compat_flag
     return lba_schur_fetch(P, par, S, b, n_singular, err);    // (err rides behind S and b: k_schur_finish put it there)
 }
 
-// dp up, the back-substitution (and the landmark update when `apply`) into the stream; no synchronisation
-static int lba_backsub_enqueue(plslam_lba_plan* P, const double* dpose, int apply, double* part_out = nullptr)
+// the back-substitution's arguments from the plan's views
+static SchurBackArgs backsub_args(plslam_lba_plan* P, int apply, double* part_out)
 {
-    hipStream_t s = P->ctx->stream;
     const LbaStatView& S = P->st; const LbaOutView& O = P->o; const LbaSchurView& C = P->sc;
-    memcpy(P->simg.dp, dpose, C.dp.bytes);
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(C.dp, P->simg.dp, C.dp.bytes, hipMemcpyHostToDevice, s));
     SchurBackArgs A{};
     A.pt_ptr = S.pt_ptr; A.pt_obs = S.pt_ids; A.pt_kf = S.pt_kf; A.ls_ptr = S.ls_ptr; A.ls_obs = S.ls_ids; A.ls_kf = S.ls_kf;
     A.W_pt = O.W_pt; A.W_ls = O.W_ls; A.Vp = C.Vp; A.Vl = C.Vl; A.tp = C.tp; A.tl = C.tl;
     A.dp = C.dp; A.dx_pt = C.dx; A.dx_ls = C.dx + 3 * (size_t)P->npt; A.part = part_out ? part_out : C.dx_part.p;
     A.X = apply ? P->x.Xw.p : nullptr; A.L = apply ? P->x.Lw.p : nullptr;
     A.npt = P->npt; A.nls = P->nls; A.nwg_pt = (P->npt + BACK_WG / 3 - 1) / (BACK_WG / 3);
+    return A;
+}
+
+namespace plslam {
+int lba_backsub_enqueue_lm(plslam_lba_plan* P, const LbaLmCtl* ctl)
+{
+    const SchurBackArgs A = backsub_args(P, 1, nullptr);
+    const int32_t nwg = (int32_t)backsub_wgs(P);
+    if (nwg > 0) hipLaunchKernelGGL(k_schur_backsub_lm, dim3(nwg), dim3(BACK_WG), 0, P->ctx->stream, A, ctl);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    return PLSLAM_OK;
+}
+int lba_backsub_wgs(const plslam_lba_plan* P) { return (int)backsub_wgs(P); }
+}  // namespace plslam
+
+// dp up, the back-substitution (and the landmark update when `apply`) into the stream; no synchronisation
+static int lba_backsub_enqueue(plslam_lba_plan* P, const double* dpose, int apply, double* part_out = nullptr)
+{
+    hipStream_t s = P->ctx->stream;
+    const LbaSchurView& C = P->sc;
+    memcpy(P->simg.dp, dpose, C.dp.bytes);
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(C.dp, P->simg.dp, C.dp.bytes, hipMemcpyHostToDevice, s));
+    const SchurBackArgs A = backsub_args(P, apply, part_out);
     const int32_t nwg = (int32_t)backsub_wgs(P);
     if (nwg > 0) hipLaunchKernelGGL(k_schur_backsub, dim3(nwg), dim3(BACK_WG), 0, s, A);
     PLSLAM_HIP_CHECK(hipGetLastError());

@@ -315,7 +315,7 @@ public:
         std::vector<double> err, lambda;       // err as the reference normalises it; lambda used by that build's solve (0: none)
         std::vector<int> applied;              // 1: the step was applied, 0: rejected (err > err_prev), -1: stopped before the solve
         int iters = 0;                         // the reference's `iters` when its loop ends
-        int stop = 0;                          // 0 max_iters reached, 1 |err - err_prev| / err test, 2 ||DX|| test
+        int stop = 0;                          // 0 max_iters reached, 1 |err - err_prev| / err test, 2 ||DX|| test (optimizeOnDevice: 3 not positive definite)
         int n_singular = 0;                    // landmarks whose damped block was not positive definite in any solve
     };
     void optimize(LbaProblem& p, std::vector<double>& x_kf, int32_t first_estimate_slot, const LmParams& prm, const Se3Maps& maps,
@@ -334,6 +334,40 @@ public:
         if (T_slots.size() != (size_t)nslots_ * 16) throw std::runtime_error("[LbaPlanSolver::optimizeResident] one 4 x 4 per pose slot");
         lmLoop(T_slots, x_kf, first_estimate_slot, prm, maps, trace, [&]() { setPoses(T_slots); return iterateResident(false); });
     }
+    // The same loop in ONE call and ONE synchronisation (plslam_lba_plan_optimize_dev): the reduced system is solved on the device,
+    // the pose update and the loop's decisions run there, so no Se3Maps are needed.  The plan's landmarks must be resident (as for
+    // optimizeResident).  T_slots: one 4 x 4 per pose slot, the stored T_kf_w -- in the estimate slots first_estimate_slot + k too:
+    // the first pass reads the slots as given (:1369), expmap(X_k) appears there from the first update on (:1601); they are NOT
+    // written back into T_slots (T_kf, when given, receives nkf x 16: expmap of the final x_kf, :1822-1826).  Fills the same LmTrace.
+    // A reduced system that is not positive definite ends the loop with tr.stop = 3 and the step not applied (optimizeResident throws).
+    void optimizeOnDevice(std::vector<double>& x_kf, const std::vector<double>& T_slots, int32_t first_estimate_slot, const LmParams& prm,
+                          LmTrace* trace = nullptr, std::vector<double>* T_kf = nullptr)
+    {
+        if (T_slots.size() != (size_t)nslots_ * 16 || x_kf.size() != 6 * (size_t)nkf_)
+            throw std::runtime_error("[LbaPlanSolver::optimizeOnDevice] one 4 x 4 per pose slot, 6 doubles per optimised key frame");
+        plslam_lba_lm_params q{};
+        q.lambda_lba_lm = prm.lambda_lba_lm; q.lambda_lba_k = prm.lambda_lba_k; q.max_iters_lba = prm.max_iters_lba;
+        q.min_error_change = prm.min_error_change; q.min_error = prm.min_error;
+        lm_records_.resize((size_t)(prm.max_iters_lba > 1 ? prm.max_iters_lba : 1));
+        x_out_.resize(x_kf.size());
+        if (T_kf) T_kf->resize((size_t)nkf_ * 16);
+        plslam_lba_result res{};
+        check(plslam_lba_plan_optimize_dev(plan_, &q, T_slots.data(), x_kf.data(), first_estimate_slot, x_out_.data(),
+                                           T_kf ? T_kf->data() : nullptr, lm_records_.data(), &res), "plslam_lba_plan_optimize_dev");
+        x_kf = x_out_;
+        last_result_ = res;
+        if (trace) {
+            *trace = LmTrace();
+            for (int32_t i = 0; i < res.n_builds; ++i) {
+                const plslam_lba_solve& r = lm_records_[(size_t)i];
+                trace->err.push_back(r.err); trace->lambda.push_back(r.lambda); trace->applied.push_back(r.applied);
+                trace->n_singular += r.n_singular;
+            }
+            trace->iters = res.iters; trace->stop = res.stop_reason;
+        }
+    }
+    const plslam_lba_result& lastDeviceResult() const { return last_result_; }      // of the last optimizeOnDevice
+
     // the reference's write-back test (:1822-1846): landmark i is flagged when its estimate moved by more than `th` (0.01)
     static void movedLandmarks(const std::vector<double>& before, const std::vector<double>& after, int dim, double th, std::vector<uint8_t>& moved)
     {
@@ -456,7 +490,9 @@ private:
     }
     plslam_lba_plan* plan_ = nullptr;
     int32_t nkf_, npt_ = 0, nls_ = 0, nslots_ = 0;
-    std::vector<double> S_;
+    std::vector<double> S_, x_out_;
+    std::vector<plslam_lba_solve> lm_records_;
+    plslam_lba_result last_result_{};
 };
 
 }  // namespace PLSLAM

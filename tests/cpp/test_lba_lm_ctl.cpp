@@ -98,6 +98,23 @@ int main(int argc, char** argv)
         pass(c, p, 1e5, {1.0, 1.0, 1.0, 0}, tr);       // behind the stop: nothing
         report("schedule_reject_then_stop", a && b && d && tr.size() == 4 && c.n_builds == 4);
     }
+    {   // min_error_change = 0: the loop goes on behind a rejection -- the same err again is NOT above err_prev, the retry is applied
+        // at lambda / k, and lambda grows again behind it; a second rejection and retry follow the same schedule
+        LbaLmCtl c; lm_init(c); std::vector<Rec> tr; LbaLmPrm p = prm(15); p.min_error_change = 0.0;
+        const double l0 = 1e-5 * 1e5, l1 = l0 * 10.0, l2 = l1 / 10.0, l3 = l2 * 10.0, l4 = l3 / 10.0, l5 = l4 * 10.0;
+        pass(c, p, 1e5, {1.0, 1.0, 1.0, 0}, tr);
+        pass(c, p, 1e5, {300.0, 1.0, 1.0, 0}, tr);     // applied, lambda x 10
+        pass(c, p, 1e5, {310.0, 1.0, 1.0, 0}, tr);     // 3.1 > 3: rejected, lambda / 10
+        const bool a = tr[2].applied == 0 && tr[2].lambda == l1 && c.lambda == l2 && c.err_prev == 3.1 && c.stop == LM_RUNNING;
+        pass(c, p, 1e5, {310.0, 1.0, 1.0, 0}, tr);     // the same err: |0| < 0 is false, 3.1 > 3.1 is false -- applied at l2, lambda x 10
+        const bool b = tr[3].applied == 1 && tr[3].lambda == l2 && c.lambda == l3 && c.err_prev == 3.1 && c.iters == 4 && c.stop == LM_RUNNING;
+        pass(c, p, 1e5, {320.0, 1.0, 1.0, 0}, tr);     // rejected again
+        pass(c, p, 1e5, {320.0, 1.0, 1.0, 0}, tr);     // ... and retried
+        const bool d = tr[4].applied == 0 && tr[4].lambda == l3 && tr[5].applied == 1 && tr[5].lambda == l4 && c.lambda == l5 && c.iters == 6 &&
+                       c.err_prev == 3.2 && c.stop == LM_RUNNING;
+        pass(c, p, 1e5, {315.0, 1.0, 1.0, 0}, tr);     // a descent behind it: applied at l5
+        report("schedule_reject_then_retry", a && b && d && tr[6].applied == 1 && tr[6].lambda == l5 && c.lambda == l5 * 10.0 && c.n_builds == 7);
+    }
     {   // err < min_error
         LbaLmCtl c; lm_init(c); std::vector<Rec> tr; const LbaLmPrm p = prm(15);
         pass(c, p, 1.0, {1.0, 1.0, 1.0, 0}, tr);

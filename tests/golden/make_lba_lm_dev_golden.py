@@ -48,11 +48,15 @@ def flow(r, cfg):
     return stop, applied
 
 
-def far_from_thresholds(p, cfg, r):
+def far_from_thresholds(p, cfg, r, equal_behind_a_rejection=False):
+    """equal_behind_a_rejection (make_lba_lm_dev_edges_golden.py): with min_error_change = 0 the build behind a rejected step
+    recomputes the state it had, so its err EQUALS the one before, bit for bit; such a pair is left out of the :1786 gap -- only
+    when it is exactly equal, and only behind a rejection"""
     mec, me = cfg["min_err_change"], cfg["min_err"]
     stop, applied = flow(r, cfg)
     e = list(r["err"])
-    pairs = [(e[i], e[i - 1]) for i in range(1, len(e))]
+    exempt = [equal_behind_a_rejection and mec == 0 and i >= 2 and applied[i - 1] == 0 and e[i] == e[i - 1] for i in range(len(e))]
+    pairs = [(e[i], e[i - 1]) for i in range(1, len(e)) if not exempt[i]]
     builds = pairs + ([(r["err_last"], r["err_prev"])] if stop == 1 else [])
     for a, b in builds:                                                   # :1775
         if np.isfinite(b) and abs(abs(a - b) - mec) < GAP * mec:

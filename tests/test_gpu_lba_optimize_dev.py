@@ -21,7 +21,8 @@ from plslam_amd.capi import EINVAL, LbaPlan, PlslamError
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = {"lm": os.path.join(ROOT, "tests", "golden", "lba_lm_golden.npz"), "dev": os.path.join(ROOT, "tests", "golden", "lba_lm_dev_golden.npz")}
+GOLD = {"lm": os.path.join(ROOT, "tests", "golden", "lba_lm_golden.npz"), "dev": os.path.join(ROOT, "tests", "golden", "lba_lm_dev_golden.npz"),
+        "edges": os.path.join(ROOT, "tests", "golden", "lba_lm_dev_edges_golden.npz")}     # (tests/test_gpu_lba_optimize_dev_edges.py)
 CASES = [("lm", n) for n in ("main", "reject", "reject_later", "points_only", "two_views", "fixed_heavy")] + \
         [("dev", n) for n in ("first_only", "main_3", "lines_only", "one_kf", "wide", "dx_stop")]
 IDS = [n for _, n in CASES]
@@ -42,7 +43,11 @@ def _cam():
 
 def _problem(which, name):
     g = _gold(which)
-    a = lambda k: g[f"{name}_{k}"]                                              # noqa: E731
+    src, case = g, name
+    if f"{name}_problem" in g:                 # "<fixture file>:<case>": the problem's arrays are stored there, once
+        fixture, case = str(g[f"{name}_problem"]).split(":")
+        src = _gold({os.path.basename(v): k for k, v in GOLD.items()}[fixture])
+    a = lambda k: src[f"{case}_{k}"]                                            # noqa: E731
     cfg = g[f"{name}_cfg"] if f"{name}_cfg" in g else g["cfg"]
     n_map, nkf = int(a("n_kf_map")), int(a("nkf"))
     # pose slots: the stored T_kf_w of every key frame, then the estimate slots -- which hold the stored poses on entry (:1369)
@@ -145,6 +150,10 @@ def _first_solve_cond(p):
 # ---- 3. every case of both fixtures against the reference's stored run -----------------------------------------------------------
 @pytest.mark.parametrize("which,name", CASES, ids=IDS)
 def test_the_loop_on_the_device_equals_the_references_own_text(ctx, which, name):
+    _equals_the_references_own_text(ctx, which, name)
+
+
+def _equals_the_references_own_text(ctx, which, name):
     p = _problem(which, name)
     p["name"] = name
     got, ref = _run_cached(ctx, which, name), p["ref"]
@@ -157,8 +166,8 @@ def test_the_loop_on_the_device_equals_the_references_own_text(ctx, which, name)
     assert got["applied"][solved].tolist() == ref_applied
     n_solves, iters = len(e), int(ref["iters"])
     ref_stop = 0 if iters >= p["prm"]["max_iters"] else 1 if n_solves == iters else 2
-    if which == "dev":
-        assert ref_stop == int(_gold("dev")[f"{name}_ref_stop"])
+    if which != "lm":
+        assert ref_stop == int(_gold(which)[f"{name}_ref_stop"]) and ref_applied == _gold(which)[f"{name}_ref_applied"].tolist()
     assert got["stop_reason"] == ref_stop
     assert (got["applied"][-1] == -1) == (ref_stop == 1) and (got["applied"][:-1] >= 0).all()
     if name.startswith("reject"):
@@ -246,7 +255,9 @@ def _spd(n, seed):
     return (A + A.T) / 2, rng.standard_normal(n)
 
 
-@pytest.mark.parametrize("n", [6, 54, capi.LBA_SOLVE_MAX_N6, capi.LBA_SOLVE_MAX_N6 + 6])
+# 84 | 90: the one-workgroup solve either side of 64 kB of LDS; 120 | 121: its last size and the padded route's first, n no multiple
+# of 6; 126, 128, 129, 160: on and either side of the 32-wide tile the padded copy is rounded to
+@pytest.mark.parametrize("n", [1, 6, 54, 84, 90, capi.LBA_SOLVE_MAX_N6, capi.LBA_SOLVE_MAX_N6 + 1, capi.LBA_SOLVE_MAX_N6 + 6, 128, 129, 160])
 def test_reduced_ldlt_solve_against_numpy(ctx, n):
     assert capi.LBA_SOLVE_MAX_N6 == 120
     A, b = _spd(n, 100 + n)

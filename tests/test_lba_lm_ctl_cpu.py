@@ -1,7 +1,9 @@
 """The control logic of plslam_lba_plan_optimize_dev (plslam_amd/csrc/lba_lm_ctl.hpp: what its control kernels run on one lane)
 without a GPU: tests/cpp/test_lba_lm_ctl.cpp is compiled with g++ alone against plslam_amd/csrc and include.  Its hand cases run
 once, every case one test here.  The same program replays every recorded run of the reference's own text -- the six cases of
-tests/golden/lba_lm_golden.npz and the six of tests/golden/lba_lm_dev_golden.npz: it is fed the errs the fixtures store (times
+tests/golden/lba_lm_golden.npz, the six of tests/golden/lba_lm_dev_golden.npz and the eleven of
+tests/golden/lba_lm_dev_edges_golden.npz (whose two retry runs are the first to take lm_on_step through lambda / k and then
+lambda * k): it is fed the errs the fixtures store (times
 Npt + Nls: the raw sums the device hands the function) and must give the reference's iters, its applied / rejected pattern, its
 lambda schedule (each lambda the one before times or over lambda_k, exactly) and its stop reason, and must stop consuming builds by
 itself.  The fixtures do not store ||DX|| (the text does not hand it out): the replay feeds a step far above the threshold for
@@ -16,11 +18,15 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HAND = ["first_pass", "first_pass_zero_sum_is_nan", "max_iters_1", "max_iters_0", "schedule_reject_then_stop", "min_error", "dx_test",
+HAND = ["first_pass", "first_pass_zero_sum_is_nan", "max_iters_1", "max_iters_0", "schedule_reject_then_stop", "schedule_reject_then_retry",
+        "min_error", "dx_test",
         "not_positive_definite", "runs_out"]
 SANITIZE = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
 GOLDEN = [("lba_lm_golden.npz", n) for n in ("main", "reject", "reject_later", "points_only", "two_views", "fixed_heavy")] + \
-         [("lba_lm_dev_golden.npz", n) for n in ("first_only", "main_3", "lines_only", "one_kf", "wide", "dx_stop")]
+         [("lba_lm_dev_golden.npz", n) for n in ("first_only", "main_3", "lines_only", "one_kf", "wide", "dx_stop")] + \
+         [("lba_lm_dev_edges_golden.npz", n) for n in ("n84", "n90", "n120", "n120_dx", "wide_max", "wide_dx", "wide_reject", "wide_retry",
+                                                       "retry", "iters0", "iters2")]
+RETRY = ("wide_retry", "retry")
 
 
 def _build(exe, extra):
@@ -79,7 +85,11 @@ def _case_file(path, fixture, name):
     cfg = g[f"{name}_cfg"] if f"{name}_cfg" in g.files else g["cfg"]
     lam_lm, lam_k, max_iters, mec, me = float(cfg[1]), float(cfg[2]), int(cfg[3]), float(cfg[4]), float(cfg[5])
     e, lam, iters = g[f"{name}_ref_err"], g[f"{name}_ref_lam"], int(g[f"{name}_ref_iters"])
-    n_lm = float(g[f"{name}_Xw"].shape[0] + g[f"{name}_Lw"].shape[0])
+    src, case = g, name
+    if f"{name}_problem" in g.files:                   # "<fixture file>:<case>": where the problem's arrays are stored
+        src, case = str(g[f"{name}_problem"]).split(":")
+        src = np.load(os.path.join(ROOT, "tests", "golden", src))
+    n_lm = float(src[f"{case}_Xw"].shape[0] + src[f"{case}_Lw"].shape[0])
     stop = 0 if iters >= max_iters else 1 if len(e) == iters else 2
     builds = [(1.0 if i == 0 else float(e[i]) * n_lm, 0.5, 0.0 if (stop == 2 and i == len(e) - 1) else 0.5) for i in range(len(e))]
     if stop == 2:
@@ -123,6 +133,10 @@ def test_lba_lm_ctl_replays_the_references_run(exe, exe_san, tmp_path, fixture, 
     assert len(got_lam) < 2 or got_lam[1] == got_lam[0]
     for i in range(2, len(got_lam)):                   # times lambda_k behind an applied step, over it behind a rejected one: exactly
         assert got_lam[i] == (got_lam[i - 1] * k if applied[i - 1] == 1 else got_lam[i - 1] / k)
+    if name in RETRY:                                  # lambda / k behind a rejection, the SAME err, the retry applied, lambda * k
+        rej = [i for i in range(len(applied) - 2) if applied[i] == 0]
+        assert rej and all(applied[i + 1] == 1 and B[i + 1][1] == B[i][1] for i in rej)
+        assert all(got_lam[i + 1] == got_lam[i] / k and got_lam[i + 2] == got_lam[i + 1] * k for i in rej)
     assert abs(R["lam"] - want["lam_last"]) <= 1e-12 * want["lam_last"]
     assert np.isinf(B[0][1]) and np.allclose([b[1] for b in B[1:]], e[1:], rtol=1e-15, atol=0)
     if len(B) > 1:

@@ -48,7 +48,8 @@ extern "C" {
  * plslam_local_map_* with plslam_map_index / plslam_map_landmarks / plslam_local_map_buffers / plslam_local_map_counts; the map
  * insertion plslam_map_insert_* with plslam_map_insert_kind / _dst / _counts / _events; the loop-closure landmark fusion
  * plslam_lc_fuse_* with plslam_lc_fuse_kind / _counts / _buffers; the device-built LBA plan plslam_lba_plan_create_dev with
- * plslam_lba_plan_list_sizes / _lists, and plslam_local_map_apply_lba (plslam_local_map_buffers / _counts grew at the END).
+ * plslam_lba_plan_list_sizes / _lists, and plslam_local_map_apply_lba (plslam_local_map_buffers / _counts grew at the END); the
+ * loop-closure correction on the map image plslam_lc_correct_image with plslam_lc_image_dst / plslam_lc_image_counts.
  * Clients compare plslam_abi_version() with the value they were compiled against. */
 #define PLSLAM_ABI_VERSION 5
 #define PLSLAM_DESC_BYTES 32
@@ -1405,7 +1406,7 @@ int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, p
 /* removeBadMapLandmarks (:2705-2786): a valid landmark with observations is removed when !local && max_kf_idx - obs_kf[first] >
  * 10 and (!inlier || n_obs < min_lm_obs).  In place on the index: valid cleared; in keyframe obs_kf[first] the FIRST feature whose
  * feat_idx equals the landmark becomes -1 (a later duplicate stays).  Erasing from map_*_kf_idx stays with the caller, driven by
- * the removed masks.  Deviations: a NULL first-observer keyframe or a NULL feature (:2720-2723) is skipped; an empty observation
+ * the removed masks (a caller that corrects with plslam_lc_correct_image keeps no such lists).  Deviations: a NULL first-observer keyframe or a NULL feature (:2720-2723) is skipped; an empty observation
  * list is not culled.  After form on the same map; counts: the cull fields. */
 int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int32_t max_kf_idx, int32_t min_lm_obs,
                           plslam_local_map_counts* counts);
@@ -1561,7 +1562,8 @@ int plslam_map_insert_download(plslam_map_insert* mi, const plslam_map_insert_ev
  * A run that fails after validation (PLSLAM_ENOMEM, PLSLAM_EHIP, the two refusals above) invalidates the previous run's records.
  * desc_list / dir_list / pts_list follow on the device with plslam_lc_fuse_carry (below: one gather by obs_src from the per-tuple
  * rows the caller gathers, so the pts quirk of :4626 stays with whoever gathers).  With the caller stay
- * map_*_kf_idx (push ev's landmark to the anchor's list for C, erase the dead landmark from the anchor's for D) and full_graph.
+ * map_*_kf_idx (push ev's landmark to the anchor's list for C, erase the dead landmark from the anchor's for D; not needed by a
+ * caller that corrects with plslam_lc_correct_image) and full_graph.
  * Arithmetic as plslam_map_insert_*: fp64 without contraction, R p + t as ((r0 p0 + r1 p1) + r2 p2) + t, the norm as
  * sqrt((x^2 + y^2) + z^2), the division per component.
  *
@@ -1670,6 +1672,38 @@ int plslam_map_insert_carry(plslam_map_insert* mi, const plslam_map_index* src_m
 int plslam_lc_fuse_carry(plslam_lc_fuse* lf, const plslam_map_index* src_map, const plslam_map_lists* src_lists,
                          const plslam_map_index* dst_map, const plslam_map_lists* dst_lists,
                          const plslam_lc_fuse_rows* points, const plslam_lc_fuse_rows* lines);
+
+/* ---- the loop-closure map correction on the device-resident map, without anchor lists ------------------------------------ */
+/* src/mapHandler.cpp:4306-4355 / :4364-4397 over plslam_map_index (K105-K107, KERNELS.md).  In the code the reference runs,
+ * map_points_kf_idx[k] / map_lines_kf_idx[k] is at any time the ascending list of the valid landmarks whose FIRST observation is
+ * keyframe k (pushed on creation only, :299-311, :461, :4472-4477, :4619; erased at kf_obs_list[0] only, :2717-2777, :4521-4529,
+ * :4669-4676; no live code removes a first observation): a landmark has one anchor, and the image names it.  So landmark j of a
+ * kind is CORRECTED when valid[j], [obs_ptr[j], obs_ptr[j + 1]) is a non-empty list inside obs_kf, k = obs_kf[obs_ptr[j]] is in
+ * [0, n_map_kf) and corrected[k]; then X[j] (both end points of a line), med_dir[j] (where given) and every row of its list in
+ * dir (where given; dir_ptr = obs_ptr) become R p + t with T_corr[k], ((r0 p0 + r1 p1) + r2 p2) + t without contraction, the
+ * translation added to the directions as the reference does.  Everything else is left as it is.  The result is that of
+ * plslam_lc_correct_map_dev given those lists, bit for bit.  A port that revives the observation removal of :1857-1979 or
+ * removeRedundantKFs breaks the first-observer rule and must keep the lists and use plslam_lc_correct_map_dev.
+ * A row of dir finds its landmark by bisection of obs_ptr (ascending, as every call on the image leaves it); a row that lies in
+ * no landmark's list, or in the list of a landmark that is not corrected, is not touched.
+ *
+ * T_corr[n_map_kf x 16] and corrected[n_map_kf] (HOST): what plslam_pgo_optimize returns.  x_kf_w_new (HOST, n_map_kf x 6, may be
+ * NULL): its x_out; where it and dst->x_kf_w are given, the rows of the corrected slots are written into dst->x_kf_w (:4310,
+ * :4358) and no other row.  dst: WRITABLE device pointers, 8-byte aligned; in place on the image (pt_X = map->points.X, ...) is
+ * the normal use.  A NULL *_dir or *_med_dir: that array is not carried (med_obs_dir is not part of plslam_map_lists).
+ * counts (may be NULL): the corrected landmarks and the transformed dir rows per kind.  One staged upload, one launch sequence on the context's
+ * stream, one synchronisation; the counts come back through page-locked memory.
+ * PLSLAM_EINVAL, nothing launched or written: a NULL ctx / map / T_corr / corrected / dst, n_map_kf < 1, a kind of the
+ * image whose counts and arrays do not agree, a kind with n > 0 and a NULL *_X, a misaligned destination.
+ * Every index read from the image is range-checked on the device before it is used as an address. */
+typedef struct plslam_lc_image_dst {        /* WRITABLE device pointers, caller-owned; in place on the image is the normal use */
+    double *pt_X, *pt_dir, *pt_med_dir;     /* n x 3, n_obs x 3 (plslam_map_lists_kind.dir), n x 3                              */
+    double *ls_X, *ls_dir, *ls_med_dir;     /* n x 6, n_obs x 3, n x 3                                                          */
+    double *x_kf_w;                         /* n_map_kf x 6: the image's x_kf_w, or NULL                                        */
+} plslam_lc_image_dst;
+typedef struct plslam_lc_image_counts { int32_t n_pt, n_ls, n_pt_dirs, n_ls_dirs; } plslam_lc_image_counts;
+int plslam_lc_correct_image(plslam_ctx* ctx, const plslam_map_index* map, const double* T_corr, const uint8_t* corrected,
+                            const double* x_kf_w_new, const plslam_lc_image_dst* dst, plslam_lc_image_counts* counts);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,7 @@ ABI_SYMBOLS = (
     "plslam_lc_fuse_create", "plslam_lc_fuse_destroy", "plslam_lc_fuse_run", "plslam_lc_fuse_device_buffers",
     "plslam_lc_fuse_download",
     "plslam_map_lists_refresh", "plslam_map_insert_carry", "plslam_lc_fuse_carry",
+    "plslam_lc_correct_image",
 )
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -155,6 +156,15 @@ class LcLandmarks(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_anchor", C.c_int32), ("n_dir", C.c_int32), ("anchor_ptr", C.c_void_p),
                 ("anchor_idx", C.c_void_p), ("valid", C.c_void_p), ("X", C.c_void_p), ("med_dir", C.c_void_p),
                 ("dir_ptr", C.c_void_p), ("dirs", C.c_void_p)]
+
+
+class LcImageDst(C.Structure):
+    """plslam_lc_image_dst: writable device pointers (None: that array is not carried)"""
+    _fields_ = [(k, C.c_void_p) for k in ("pt_X", "pt_dir", "pt_med_dir", "ls_X", "ls_dir", "ls_med_dir", "x_kf_w")]
+
+
+class LcImageCounts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_pt", "n_ls", "n_pt_dirs", "n_ls_dirs")]
 
 
 class Cam(C.Structure):
@@ -508,6 +518,8 @@ def load() -> C.CDLL:
     L.plslam_map_lists_refresh.argtypes = [vp, vp, vp]
     L.plslam_map_insert_carry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.plslam_lc_fuse_carry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    # the loop-closure correction on the map image (plslam_amd/pgo.py: correct_image)
+    L.plslam_lc_correct_image.argtypes = [vp, vp, vp, vp, vp, C.POINTER(LcImageDst), C.POINTER(LcImageCounts)]
     for name in ABI_SYMBOLS:
         getattr(L, name).restype = _RESTYPES.get(name, C.c_int)
     _lib = L

@@ -188,6 +188,7 @@ struct plslam_ctx {
     int pgo_solver = 0;                             // pgo plans created from now on: 0 = envelope L D L^T, 1 = the dense one (comparison)
     plslam::DevBuf pgo_scratch;                     // the map correction's per-landmark lists (lc_correct.hip)
     plslam::DevBuf lists_scratch;                   // the carries' chain words and touched-landmark lists (map_lists.hip)
+    plslam::HostBuf lc_image_pin;                   // plslam_lc_correct_image: its counts, then its staged block (lc_correct_image.hip)
 };
 
 namespace plslam {

@@ -157,6 +157,7 @@ void plslam_ctx_destroy(plslam_ctx* ctx)
     ctx->lc_in.release(); ctx->lc_out.release(); ctx->lc_tab.release(); ctx->lc_args.release();
     ctx->pgo_scratch.release();
     ctx->lists_scratch.release();
+    ctx->lc_image_pin.release();
     for (hipEvent_t& e : ctx->lc_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);

@@ -133,7 +133,8 @@ template <class Graph> inline void apply_graph(const Fused& f, Graph& full_graph
         for (size_t j = 0; j < n; ++j) full_graph[i][j] += f.graph_delta[i * n + j];
 }
 // map_points_kf_idx / map_lines_kf_idx: a new landmark goes to its anchor's list (:4477, :4619), a fused one leaves the list of
-// its first observer (:4521-4529), in event order
+// its first observer (:4521-4529), in event order.  Only for a caller that still keeps the containers: pgo::runResident
+// (plslam_lc_correct_image) reads the anchor from the image and needs none.
 inline void apply_kf_idx(const KindRecords& r, std::vector<std::vector<int>>& map_kf_idx)
 {
     for (size_t t = 0; t < r.ev.size() / 6; ++t) {

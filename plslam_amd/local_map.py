@@ -188,6 +188,27 @@ class LocalMap:
             pass
 
 
+def anchor_lists(m, kind):
+    """The reference's map_points_kf_idx / map_lines_kf_idx (kind = "points" / "lines") derived from an image dict: slot k lists,
+    ascending, the valid landmarks with a non-empty observation list whose FIRST observer is k -- what the containers hold at any
+    time in the code the reference runs ("Loop-closure correction on the image").  A first observer outside
+    [0, n_map_kf) is listed nowhere.  -> (anchor_ptr (n_map_kf + 1,) int32, anchor_idx int32): plslam_lc_landmarks' CSR."""
+    K, nk = m[kind], int(m["n_map_kf"])
+    valid, ptr = np.asarray(K["valid"]).reshape(-1), np.asarray(K["obs_ptr"], np.int64).reshape(-1)
+    obs_kf = np.asarray(K["obs_kf"], np.int64).reshape(-1)
+    n = valid.size
+    b, e = ptr[:n], ptr[1:n + 1]
+    ok = (valid != 0) & (b >= 0) & (e > b) & (e <= obs_kf.size)
+    first = np.full(n, -1, np.int64)
+    first[ok] = obs_kf[b[ok]]
+    ok &= (first >= 0) & (first < nk)
+    j = np.flatnonzero(ok)
+    j = j[np.argsort(first[j], kind="stable")]                     # per slot ascending: new indices only grow
+    anchor_ptr = np.zeros(nk + 1, np.int32)
+    anchor_ptr[1:] = np.cumsum(np.bincount(first[j], minlength=nk))
+    return anchor_ptr, j.astype(np.int32)
+
+
 # ---- the seeded generator -----------------------------------------------------------------------------------------------------
 def _kind(rng, n_kf, n, dl, dv, kf_valid, max_obs, null_lm_frac, outlier_frac, n_unmatched, n_null_feat, n_dup, no_obs_frac):
     nobs = rng.integers(1, max_obs + 1, n) if n else np.zeros(0, np.int64)

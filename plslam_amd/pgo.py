@@ -5,8 +5,13 @@ back where keyframe k - period was.  The stored poses are the true relative moti
 odometry drift).  full_graph counts landmarks shared inside a window of consecutive keyframes, so that the nearest neighbours
 pass min_lm_cov_graph = 75 and farther ones do not.  Each loop closure (a, b) with b = a + period carries the true relative
 pose plus noise, as x with expmap_se3(x) = T_a^-1 T_b: the measurement of the loop edge (src/mapHandler.cpp:4276-4287).
-Landmarks are anchored to keyframe slots (map_points_kf_idx / map_lines_kf_idx) as CSR lists, each with a dir_list CSR."""
+Landmarks are anchored to keyframe slots (map_points_kf_idx / map_lines_kf_idx) as CSR lists, each with a dir_list CSR.
+
+correct_image is the binding of plslam_lc_correct_image: the same correction on a device-resident map image, which needs no
+anchor lists (a landmark's anchor is its first observer)."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
@@ -116,3 +121,24 @@ def anchored_landmarks(n_kf, n_lm, n_dir=4, seed=5, line=False, null_frac=0.02, 
     dptr[1:] = np.cumsum(nd)
     dirs = rng.standard_normal((int(dptr[-1]), 3))
     return dict(anchor_ptr=ptr, anchor_idx=idx, valid=valid, X=X, med_dir=med, dir_ptr=dptr, dirs=dirs)
+
+
+def correct_image(ctx, index, T_corr, corrected, x_kf_w=None, lists=None, med_dir=None) -> dict:
+    """plslam_lc_correct_image, in place on a device-resident map: index is a DeviceMapIndex / DeviceMapImage (its X arrays, and
+    its x_kf_w where x_kf_w -- the (n_map_kf, 6) x of PgoPlan.optimize -- is given), lists a DeviceMapLists whose dir rows are
+    carried (None: no dir), med_dir a dict(points=, lines=) of device addresses of (n, 3) arrays (None: not carried).  T_corr
+    (n_map_kf, 4, 4) and corrected (n_map_kf,) are host arrays, as PgoPlan.optimize returns them.
+    -> dict(n_pt, n_ls, n_pt_dirs, n_ls_dirs): the corrected landmarks and the transformed dir rows."""
+    from .capi import LcImageCounts, LcImageDst, _arr, _check, _p
+    n = int(index.struct.n_map_kf)
+    Tc = _arr(T_corr, np.float64, (n, 16))
+    co = _arr(np.asarray(corrected).astype(np.uint8), np.uint8, (n,))
+    xn = None if x_kf_w is None else _arr(x_kf_w, np.float64, (n, 6))
+    med = med_dir or {}
+    dst = LcImageDst(index.ptr("points.X"), lists.ptr("points.dir") if lists is not None else None, med.get("points"),
+                     index.ptr("lines.X"), lists.ptr("lines.dir") if lists is not None else None, med.get("lines"),
+                     index.ptr("x_kf_w") if xn is not None else None)
+    c = LcImageCounts()
+    _check(ctx._L.plslam_lc_correct_image(ctx.handle, C.addressof(index.struct), _p(Tc), _p(co), _p(xn), C.byref(dst), C.byref(c)),
+           "plslam_lc_correct_image")
+    return {k: getattr(c, k) for k, _ in LcImageCounts._fields_}

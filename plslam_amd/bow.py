@@ -1,4 +1,5 @@
-"""DBoW2 vocabularies for the bag-of-words entry points (capi.BowVocabulary).
+"""The bag-of-words entry points (plslam_bow_*, include/plslam_hip.h): the ctypes binding (BowVocabulary, BowDatabase) and the
+DBoW2 vocabularies it is fed with.
 
 ``load_vocabulary`` reads the files PL-SLAM loads at MapHandler construction (src/mapHandler.cpp:38-41 ->
 TemplatedVocabulary::load(filename), which opens them with cv::FileStorage): the YAML layout written by
@@ -11,13 +12,147 @@ the descent keeps the first child of that list on a distance tie.
 """
 from __future__ import annotations
 
+import ctypes as C
 import gzip
 import re
 from dataclasses import dataclass
 
 import numpy as np
 
-from .capi import BOW_NODE_DTYPE, BOW_WORD_DTYPE, BOW_L1_NORM, BOW_TF_IDF
+from ._lib import Handle, _arr, _check, _p, proto
+
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
+BOW_L1_NORM = 0
+BOW_MAX_SET = 16384      # include/plslam_hip.h: PLSLAM_BOW_MAX_SET
+
+# plslam_bow_node / plslam_bow_word as numpy records
+BOW_NODE_DTYPE = np.dtype([("node_id", np.int32), ("parent_id", np.int32), ("weight", np.float64), ("descriptor", np.uint8, 32)])
+BOW_WORD_DTYPE = np.dtype([("word_id", np.int32), ("node_id", np.int32)])
+
+
+class BowVocabDesc(C.Structure):
+    """plslam_bow_vocab_desc"""
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("scoring_type", C.c_int32), ("weighting_type", C.c_int32),
+                ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("nodes", C.c_void_p), ("words", C.c_void_p)]
+
+
+class BowPlStats(C.Structure):
+    """plslam_bow_pl_stats"""
+    _fields_ = [("n_pt", C.c_int32), ("n_ls", C.c_int32), ("std_pt", C.c_double), ("std_ls", C.c_double)]
+
+
+def _bow_stats(stats):
+    if stats is None:
+        return None
+    if isinstance(stats, BowPlStats):
+        return stats
+    n_pt, n_ls, std_pt, std_ls = stats
+    return BowPlStats(int(n_pt), int(n_ls), float(std_pt), float(std_ls))
+
+
+_vp, _i32 = C.c_void_p, C.c_int32
+proto("plslam_bow_vocab_create", [_vp, C.POINTER(BowVocabDesc), C.POINTER(_vp)])
+proto("plslam_bow_transform", [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_bow_transform_dev", [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_bow_vocab_destroy", [_vp], None)
+
+
+class BowVocabulary(Handle):
+    """plslam_bow_vocab: a DBoW2 vocabulary on the device (TemplatedVocabulary::load, TemplatedVocabulary.h:1437-1485).
+
+    voc: anything with the fields k, L, scoring_type, weighting_type, nodes (BOW_NODE_DTYPE records in file order) and words
+    (BOW_WORD_DTYPE records) -- the Vocabulary below."""
+
+    def __init__(self, ctx: Context, voc):
+        nodes = np.ascontiguousarray(voc.nodes, dtype=BOW_NODE_DTYPE)
+        words = np.ascontiguousarray(voc.words, dtype=BOW_WORD_DTYPE)
+        desc = BowVocabDesc(int(voc.k), int(voc.L), int(voc.scoring_type), int(voc.weighting_type), nodes.shape[0],
+                            words.shape[0], _p(nodes), _p(words))
+        h = C.c_void_p()
+        _check(ctx._L.plslam_bow_vocab_create(ctx.handle, C.byref(desc), C.byref(h)), "plslam_bow_vocab_create")
+        self._open(ctx, "plslam_bow_vocab_destroy", h)
+
+    def transform(self, desc, offsets):
+        """TemplatedVocabulary::transform over ragged sets -> (word_id[total], word_weight[total], bow_word[total],
+        bow_weight[total], bow_len[nsets]); set s's BowVector is bow_word / bow_weight[offsets[s] : offsets[s] + bow_len[s]]."""
+        d = _arr(desc, np.uint8, (-1, 32))
+        off = _arr(offsets, np.int32)
+        nsets = off.shape[0] - 1
+        total = d.shape[0]
+        word, weight = np.empty(total, np.int32), np.empty(total, np.float64)
+        bword, bweight = np.empty(total, np.int32), np.empty(total, np.float64)
+        blen = np.empty(max(nsets, 0), np.int32)
+        _check(self._L.plslam_bow_transform(self._h, _p(d), _p(off), nsets, _p(word), _p(weight), _p(bword), _p(bweight),
+                                            _p(blen)), "plslam_bow_transform")
+        return word, weight, bword, bweight, blen
+
+    def transform_dev(self, d_desc, d_offsets, nsets, total, max_set, d_word, d_weight, d_bow_word, d_bow_weight, d_bow_len,
+                      stream=None):
+        """Device-pointer form (addresses as ints); enqueues on `stream` (None = the context's stream), no sync."""
+        _check(self._L.plslam_bow_transform_dev(self._h, int(d_desc), int(d_offsets), int(nsets), int(total), int(max_set),
+                                                int(d_word), d_weight or None, int(d_bow_word), int(d_bow_weight),
+                                                int(d_bow_len), stream or None), "plslam_bow_transform_dev")
+
+
+proto("plslam_bow_db_create", [_vp, _vp, _vp, _i32, C.POINTER(_vp)])
+proto("plslam_bow_db_size", [_vp, C.POINTER(_i32)])
+proto("plslam_bow_db_insert", [_vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(BowPlStats), _vp, _vp])
+proto("plslam_bow_db_insert_dev", [_vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(BowPlStats), _vp, _vp])
+proto("plslam_bow_db_score", [_vp, _vp, _i32, _vp])
+proto("plslam_bow_db_destroy", [_vp], None)
+
+
+class BowDatabase(Handle):
+    """plslam_bow_db: the keyframes' BowVectors on the device and MapHandler::insertKFBowVector{P,L,PL}
+    (src/mapHandler.cpp:3007-3128).  vocab_p / vocab_l: BowVocabulary or None (the mode follows :196-201).  Close it before
+    its vocabularies."""
+
+    def __init__(self, ctx: Context, vocab_p, vocab_l, capacity_hint: int = 0):
+        self._voc = (vocab_p, vocab_l)          # kept alive as long as the database
+        h = C.c_void_p()
+        _check(ctx._L.plslam_bow_db_create(ctx.handle, vocab_p.handle if vocab_p else None,
+                                           vocab_l.handle if vocab_l else None, int(capacity_hint), C.byref(h)),
+               "plslam_bow_db_create")
+        self._open(ctx, "plslam_bow_db_destroy", h)
+
+    @property
+    def size(self) -> int:
+        n = C.c_int32()
+        _check(self._L.plslam_bow_db_size(self._h, C.byref(n)), "plslam_bow_db_size")
+        return n.value
+
+    def insert(self, kf_idx, pdesc=None, ldesc=None, stats=None, alive=None, conf_row=None):
+        """One keyframe: conf_row (float64, >= kf_idx + 1 entries, updated in place; None = a fresh NaN row) gets
+        score(new, i) for every alive i < kf_idx and the self score at kf_idx.  stats: (n_pt, n_ls, std_pt, std_ls), PL mode.
+        alive: kf_idx uint8 flags (None = all alive)."""
+        kf_idx = int(kf_idx)
+        pd = _arr(pdesc if pdesc is not None else np.zeros((0, 32), np.uint8), np.uint8, (-1, 32))
+        ld = _arr(ldesc if ldesc is not None else np.zeros((0, 32), np.uint8), np.uint8, (-1, 32))
+        al = _arr(np.ones(kf_idx, np.uint8) if alive is None else alive, np.uint8)
+        assert al.shape[0] >= kf_idx
+        row = np.full(kf_idx + 1, np.nan) if conf_row is None else conf_row
+        assert row.dtype == np.float64 and row.flags.c_contiguous and row.shape[0] >= kf_idx + 1
+        st = _bow_stats(stats)
+        _check(self._L.plslam_bow_db_insert(self._h, kf_idx, _p(pd), pd.shape[0], _p(ld), ld.shape[0],
+                                            C.byref(st) if st is not None else None, _p(al), _p(row)), "plslam_bow_db_insert")
+        return row
+
+    def insert_dev(self, kf_idx, d_pdesc, n_pdesc, d_ldesc, n_ldesc, stats, d_alive, d_conf_row):
+        """Device-pointer form (addresses as ints), enqueued on the context's stream, no sync."""
+        st = _bow_stats(stats)
+        _check(self._L.plslam_bow_db_insert_dev(self._h, int(kf_idx), d_pdesc or None, int(n_pdesc), d_ldesc or None,
+                                                int(n_ldesc), C.byref(st) if st is not None else None, d_alive or None,
+                                                int(d_conf_row)), "plslam_bow_db_insert_dev")
+
+    def score(self, queries):
+        """plslam_bow_db_score -> (nq, size) float64; NaN where a keyframe was never inserted."""
+        q = _arr(queries, np.int32)
+        out = np.empty((q.shape[0], self.size), np.float64)
+        _check(self._L.plslam_bow_db_score(self._h, _p(q), q.shape[0], _p(out)), "plslam_bow_db_score")
+        return out
+
+
+# ---- the vocabulary files -----------------------------------------------------------------------------------------------------
 
 
 @dataclass

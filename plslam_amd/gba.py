@@ -1,4 +1,5 @@
-"""Seeded map generator for the global bundle adjustment (plslam_gba_*): a trajectory-shaped map.
+"""The global bundle adjustment (plslam_gba_*, include/plslam_hip.h): the ctypes binding (GbaPlan, dense_ldlt_solve) and a seeded
+map generator, trajectory_map: a trajectory-shaped map.
 
 synth.local_map gives every landmark random keyframes, so every keyframe pair is covisible and the reduced camera system is
 dense.  Here the keyframes lie on a closed circular trajectory and each landmark is seen by a window of consecutive keyframes,
@@ -8,10 +9,150 @@ keyframe 0 is not optimised (its observations carry keyframe local index -1), ev
 observations, in landmark order."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
+from ._lib import Cam, Handle, _arr, _check, _p, proto
 from .synth import EUROC, se3_exp
 
+GBA_MAX_KEYFRAMES = 4096  # include/plslam_hip.h: PLSLAM_GBA_MAX_KEYFRAMES
+GBA_STOP_MAX_ITERS, GBA_STOP_ERR, GBA_STOP_DX = 0, 1, 2
+
+
+class GbaSolve(C.Structure):
+    """plslam_gba_solve: one record per solve of plslam_gba_optimize"""
+    _fields_ = [("lambda_", C.c_double), ("err_raw", C.c_double), ("err", C.c_double), ("dx_norm", C.c_double),
+                ("n_singular", C.c_int32), ("n_bad_pivots", C.c_int32), ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GbaListSizes(C.Structure):
+    """plslam_gba_list_sizes"""
+    _fields_ = [(k, C.c_int32) for k in ("nkf", "npt", "nls", "n_pt_obs", "n_ls_obs", "nblk", "nchunk", "n_pairs", "n_lpo", "n_llo",
+                                         "n_kpo", "n_klo")]
+
+
+GBA_LIST_NAMES = ("blk", "chk", "pair", "plm", "pkf", "llm", "lkf", "kpp", "kpo", "klp", "klo", "lpp", "lpo", "llp", "llo")
+
+
+class GbaLists(C.Structure):
+    """plslam_gba_lists: host pointers, NULL = skip"""
+    _fields_ = [(k, C.c_void_p) for k in GBA_LIST_NAMES]
+
+
+class GbaResult(C.Structure):
+    """plslam_gba_result"""
+    _fields_ = [("iters", C.c_int32), ("n_solves", C.c_int32), ("stop_reason", C.c_int32), ("reserved", C.c_int32),
+                ("err", C.c_double), ("err_prev", C.c_double), ("lambda_", C.c_double), ("hmax", C.c_double)]
+
+
+_vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
+for _name in ("plslam_gba_plan_create", "plslam_gba_plan_create_dev"):
+    proto(_name, [_vp, C.POINTER(Cam), _f64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, C.POINTER(_vp)])
+proto("plslam_gba_plan_list_sizes", [_vp, C.POINTER(GbaListSizes)])
+proto("plslam_gba_plan_lists", [_vp, _vp])
+proto("plslam_gba_optimize", [_vp, _f64, _f64, _i32] + [_vp] * 8 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)])
+proto("plslam_gba_optimize_dev", [_vp, _f64, _f64, _i32] + [_vp] * 6 + [C.POINTER(GbaSolve), C.POINTER(GbaResult)])
+proto("plslam_gba_plan_destroy", [_vp], None)
+proto("plslam_dense_ldlt_solve", [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i32)])
+
+
+class GbaPlan(Handle):
+    """plslam_gba_plan: the global bundle adjustment of the reference (levMarquardtOptimizationGBA) over one map.
+
+    pt_obs / ls_obs: the reference's Vector6i rows (n, 6) -- landmark map index, landmark local index, observation index,
+    keyframe map index, keyframe local index (-1: keyframe 0), inlier flag; pt_uv (n, 2) / ls_l (n, 3) the observations;
+    kf_list[k]: the map index of optimised keyframe k."""
+
+    def __init__(self, ctx: Context, cam: Cam, n_map_kf, kf_list, npt, nls, pt_obs, pt_uv, ls_obs, ls_l, homog_th=1e-7):
+        kl = _arr(kf_list, np.int32, (-1,))
+        po, lo = _arr(pt_obs, np.int32, (-1, 6)), _arr(ls_obs, np.int32, (-1, 6))
+        uv, ll = _arr(pt_uv, np.float64, (-1, 2)), _arr(ls_l, np.float64, (-1, 3))
+        self.dims = (int(n_map_kf), kl.shape[0], int(npt), int(nls))
+        h = C.c_void_p()
+        _check(ctx._L.plslam_gba_plan_create(ctx.handle, C.byref(cam), float(homog_th), int(n_map_kf), kl.shape[0], _p(kl),
+                                             int(npt), int(nls), _p(po), _p(uv), po.shape[0], _p(lo), _p(ll), lo.shape[0],
+                                             C.byref(h)), "plslam_gba_plan_create")
+        self._open(ctx, "plslam_gba_plan_destroy", h)
+
+    @classmethod
+    def from_device(cls, ctx: Context, cam: Cam, n_map_kf, nkf, d_kf_list, npt, nls, d_pt_obs, d_pt_uv, n_pt_obs, d_ls_obs, d_ls_l,
+                    n_ls_obs, homog_th=1e-7):
+        """plslam_gba_plan_create_dev: the same plan from DEVICE columns (addresses as ints), e.g. what LocalMap.form_all +
+        .gather leave in LocalMap.device_buffers(): kf_list, pt_obs, pt_obs_uv, ls_obs, ls_l_obs."""
+        self = cls.__new__(cls)
+        self.dims = (int(n_map_kf), int(nkf), int(npt), int(nls))
+        h = C.c_void_p()
+        _check(ctx._L.plslam_gba_plan_create_dev(ctx.handle, C.byref(cam), float(homog_th), int(n_map_kf), int(nkf),
+                                                 d_kf_list or None, int(npt), int(nls), d_pt_obs or None, d_pt_uv or None,
+                                                 int(n_pt_obs), d_ls_obs or None, d_ls_l or None, int(n_ls_obs), C.byref(h)),
+               "plslam_gba_plan_create_dev")
+        self._open(ctx, "plslam_gba_plan_destroy", h)
+        return self
+
+    def lists(self) -> dict:
+        """The plan's lists as host arrays (plslam_gba_plan_lists): blk (nblk, 4), chk (nchunk, 4), pair (n, 2), plm / pkf /
+        llm / lkf and the eight CSR arrays -- of a host-built or a device-built plan."""
+        z = GbaListSizes()
+        _check(self._L.plslam_gba_plan_list_sizes(self._h, C.byref(z)), "plslam_gba_plan_list_sizes")
+        shape = dict(blk=(z.nblk, 4), chk=(z.nchunk, 4), pair=(z.n_pairs, 2), plm=(z.n_pt_obs,), pkf=(z.n_pt_obs,), llm=(z.n_ls_obs,),
+                     lkf=(z.n_ls_obs,), kpp=(z.nkf + 1,), kpo=(z.n_kpo,), klp=(z.nkf + 1,), klo=(z.n_klo,), lpp=(z.npt + 1,),
+                     lpo=(z.n_lpo,), llp=(z.nls + 1,), llo=(z.n_llo,))
+        out, b = {}, GbaLists()
+        for k in GBA_LIST_NAMES:
+            out[k] = np.zeros(shape[k], np.int32)
+            setattr(b, k, _p(out[k]) if out[k].size else None)
+        _check(self._L.plslam_gba_plan_lists(self._h, C.addressof(b)), "plslam_gba_plan_lists")
+        return out
+
+    def _result(self, tr, res, **state) -> dict:
+        trace = [dict(lam=t.lambda_, err_raw=t.err_raw, err=t.err, dx_norm=t.dx_norm, n_singular=t.n_singular,
+                      n_bad_pivots=t.n_bad_pivots, accepted=bool(t.accepted)) for t in tr[:res.n_solves]]
+        return dict(state, trace=trace, iters=res.iters, n_solves=res.n_solves, stop_reason=res.stop_reason, err=res.err,
+                    err_prev=res.err_prev, lam=res.lambda_, hmax=res.hmax)
+
+    def optimize(self, T_kf_w, x_kf, Xw, Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15) -> dict:
+        """The LM loop -> dict(x_kf (nkf, 6), T (nkf, 4, 4), Xw (npt, 3), Lw (nls, 6), trace (one dict per solve), iters,
+        n_solves, stop_reason, err, err_prev, lam, hmax)."""
+        n_map, nkf, npt, nls = self.dims
+        T = _arr(T_kf_w, np.float64, (n_map, 16))
+        x = _arr(x_kf, np.float64, (nkf, 6))
+        X, Lm = _arr(Xw, np.float64, (npt, 3)), _arr(Lw, np.float64, (nls, 6))
+        xo, To, Xo, Lo = np.empty((nkf, 6)), np.empty((nkf, 4, 4)), np.empty((npt, 3)), np.empty((nls, 6))
+        tr = (GbaSolve * max(int(max_iters), 1))()
+        res = GbaResult()
+        _check(self._L.plslam_gba_optimize(self._h, float(lambda_lm), float(lambda_k), int(max_iters), _p(T), _p(x), _p(X),
+                                           _p(Lm), _p(xo), _p(To), _p(Xo), _p(Lo), tr, C.byref(res)), "plslam_gba_optimize")
+        return self._result(tr, res, x_kf=xo, T=To, Xw=Xo, Lw=Lo)
+
+    def optimize_dev(self, T_kf_w, d_x_kf, d_Xw, d_Lw, lambda_lm=0.00001, lambda_k=10.0, max_iters=15) -> dict:
+        """plslam_gba_optimize_dev: the same loop with x_kf / Xw / Lw as DEVICE addresses (for the gather: X_aux, X_aux + 48 nkf,
+        X_aux + 48 nkf + 24 npt bytes); T_kf_w stays a host array.  -> optimize's dict without Xw / Lw: the landmarks stay
+        resident in the plan (LocalMap.apply_gba writes them into the map image)."""
+        n_map, nkf, _, _ = self.dims
+        T = _arr(T_kf_w, np.float64, (n_map, 16))
+        xo, To = np.empty((nkf, 6)), np.empty((nkf, 4, 4))
+        tr = (GbaSolve * max(int(max_iters), 1))()
+        res = GbaResult()
+        _check(self._L.plslam_gba_optimize_dev(self._h, float(lambda_lm), float(lambda_k), int(max_iters), _p(T), d_x_kf or None,
+                                               d_Xw or None, d_Lw or None, _p(xo), _p(To), tr, C.byref(res)),
+               "plslam_gba_optimize_dev")
+        return self._result(tr, res, x_kf=xo, T=To)
+
+
+def dense_ldlt_solve(ctx: Context, A, b):
+    """plslam_dense_ldlt_solve: x with (the lower triangle of A, mirrored) x = b on the device -> (x, number of zero /
+    non-finite pivots)."""
+    A = _arr(A, np.float64)
+    n = A.shape[0]
+    assert A.shape == (n, n)
+    bb = _arr(b, np.float64, (n,))
+    x, nb = np.empty(n), C.c_int32(0)
+    _check(ctx._L.plslam_dense_ldlt_solve(ctx.handle, n, _p(A), _p(bb), _p(x), C.byref(nb)), "plslam_dense_ldlt_solve")
+    return x, int(nb.value)
+
+
+# ---- the seeded generator -----------------------------------------------------------------------------------------------------
 
 def trajectory_map(n_kf=400, n_pt=40000, n_ls=6000, obs_per_lm=4, loop=True, seed=11, noise_px=1.0, pose_noise=0.002,
                    n_unobserved=0, cam=EUROC, step=0.3):

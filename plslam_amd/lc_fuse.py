@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import Context, _check, _p
+from ._lib import Handle, _check, _p, proto
 from .local_map import FEAT_NULL, LOOKBACK_TILE  # noqa: F401 (LOOKBACK_TILE: for the case tables)
 from .map_insert import DeviceMapImage, _pose
 
@@ -54,14 +54,20 @@ def fuse_bounds(m, lc) -> dict:
     return out
 
 
-class LcFuse:
+proto("plslam_lc_fuse_create", [_vp, C.POINTER(_vp)])
+proto("plslam_lc_fuse_run", [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_lc_fuse_device_buffers", [_vp, _vp])
+proto("plslam_lc_fuse_download", [_vp, _vp])
+proto("plslam_lc_fuse_destroy", [_vp], None)
+
+
+class LcFuse(Handle):
     """plslam_lc_fuse: the handle that owns the scratch and the records of a run."""
 
     def __init__(self, ctx: Context):
-        self._L, self._ctx, self._h = ctx._L, ctx, None
         h = C.c_void_p()
-        _check(self._L.plslam_lc_fuse_create(ctx.handle, C.byref(h)), "plslam_lc_fuse_create")
-        self._h = h
+        _check(ctx._L.plslam_lc_fuse_create(ctx.handle, C.byref(h)), "plslam_lc_fuse_create")
+        self._open(ctx, "plslam_lc_fuse_destroy", h)
         self._shape = None
 
     def run(self, src, dst: DeviceMapImage, lc, graph: bool = True) -> dict:
@@ -113,17 +119,6 @@ class LcFuse:
                     setattr(b, f"{tag}_{f}", _p(out[kind][f]))
         _check(self._L.plslam_lc_fuse_download(self._h, C.addressof(b)), "plslam_lc_fuse_download")
         return out
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._ctx.handle:
-            self._L.plslam_lc_fuse_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- the seeded generators ----------------------------------------------------------------------------------------------------

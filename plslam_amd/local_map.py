@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import Context, _check, _p
+from ._lib import Handle, _check, _p, proto
 
 FEAT_NULL = -2            # include/plslam_hip.h: PLSLAM_FEAT_NULL
 LOOKBACK_TILE = 256       # plslam_amd/csrc/map_image_dev.hpp: MAP_TILE, the items one workgroup of a scan over the image takes
@@ -87,14 +87,27 @@ class DeviceMapIndex:
         return t.cpu().numpy()[:n].copy()
 
 
-class LocalMap:
+_f64 = C.c_double
+proto("plslam_local_map_create", [_vp, C.POINTER(_vp)])     # (every struct goes by address)
+proto("plslam_local_map_form", [_vp, _vp, _i32, _vp, _i32, _i32, _vp])
+proto("plslam_local_map_form_all", [_vp, _vp, _vp])
+proto("plslam_local_map_candidates", [_vp, _vp, _i32])
+proto("plslam_local_map_gather", [_vp, _vp, _vp])
+proto("plslam_local_map_cull", [_vp, _vp, _i32, _i32, _vp])
+proto("plslam_local_map_apply_lba", [_vp, _vp, _vp, _f64, _vp])
+proto("plslam_local_map_apply_gba", [_vp, _vp, _vp])
+proto("plslam_local_map_device_buffers", [_vp, _vp])
+proto("plslam_local_map_download", [_vp, _vp])
+proto("plslam_local_map_destroy", [_vp], None)
+
+
+class LocalMap(Handle):
     """plslam_local_map: the handle that owns the scratch and the outputs of form / candidates / gather / cull."""
 
     def __init__(self, ctx: Context):
-        self._L, self._ctx, self._h = ctx._L, ctx, None
         h = C.c_void_p()
-        _check(self._L.plslam_local_map_create(ctx.handle, C.byref(h)), "plslam_local_map_create")
-        self._h = h
+        _check(ctx._L.plslam_local_map_create(ctx.handle, C.byref(h)), "plslam_local_map_create")
+        self._open(ctx, "plslam_local_map_destroy", h)
         self._dims = None
         self._counts = {}
 
@@ -175,17 +188,6 @@ class LocalMap:
             setattr(b, k, _p(out[k]) if out[k].size else None)
         _check(self._L.plslam_local_map_download(self._h, C.addressof(b)), "plslam_local_map_download")
         return out
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._ctx.handle:
-            self._L.plslam_local_map_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def anchor_lists(m, kind):

@@ -1,11 +1,136 @@
-"""Loop-closure verification (K25 / K54, MapHandler::isLoopClosure): the parameter record with the shipped configuration's
-values, a seeded synthetic keyframe pair with known correspondences and a known relative pose, and a seeded batch of such pairs."""
+"""Loop-closure verification (K25 / K54, MapHandler::isLoopClosure): the records of the ABI and LcBatch (the single-pair calls are
+Context's and pack their keyframes with the two helpers here), the parameter record with the shipped configuration's values, a seeded synthetic keyframe pair with known correspondences and a known relative pose, and a seeded batch of such pairs."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
 from . import synth
-from .capi import Cam, LcParams
+from ._lib import Cam, Handle, _arr, _check, _p, proto
+
+LC_MAX_FEATURES = 16384  # include/plslam_hip.h: PLSLAM_LC_MAX_FEATURES
+LC_MAX_ITERS = 10000     # include/plslam_hip.h: PLSLAM_LC_MAX_ITERS
+LC_MAX_BATCH = 65536     # include/plslam_hip.h: PLSLAM_LC_MAX_BATCH
+
+
+class LcParams(C.Structure):
+    """plslam_lc_params (params() builds one from the shipped configuration)"""
+    _fields_ = [("cam", Cam), ("homog_th", C.c_double), ("min_ratio_12_p", C.c_float), ("min_ratio_12_l", C.c_float),
+                ("mutual", C.c_int32), ("has_points", C.c_int32), ("has_lines", C.c_int32), ("max_iters", C.c_int32),
+                ("max_iters_ref", C.c_int32), ("reserved", C.c_int32), ("lc_inlier_ratio", C.c_double),
+                ("lc_res", C.c_double), ("lc_unc", C.c_double), ("lc_inl", C.c_double), ("lc_trs", C.c_double),
+                ("lc_rot", C.c_double)]
+
+
+class LcKeyframe(C.Structure):
+    """plslam_lc_keyframe"""
+    _fields_ = [("pdesc", C.c_void_p), ("P", C.c_void_p), ("pl", C.c_void_p), ("pt_idx", C.c_void_p), ("n_pt", C.c_int32),
+                ("n_ls", C.c_int32), ("ldesc", C.c_void_p), ("sPeP", C.c_void_p), ("le", C.c_void_p), ("ls_idx", C.c_void_p)]
+
+
+class LcResult(C.Structure):
+    """plslam_lc_result"""
+    _fields_ = [(n, C.c_int32) for n in ("is_lc", "gn_ran", "common_pt", "common_ls", "n_pt_inliers", "n_ls_inliers", "iters_1",
+                                          "iters_2", "ok_res", "ok_unc", "ok_inl", "ok_trs", "ok_rot", "reserved")] + \
+              [(n, C.c_double) for n in ("inl_ratio_pt", "inl_ratio_ls", "e", "cov_eig", "ratio_inliers", "t", "r")] + \
+              [("x_inc", C.c_double * 6), ("T_inc", C.c_double * 16), ("pose_inc", C.c_double * 6), ("H", C.c_double * 36),
+               ("g", C.c_double * 6), ("clk_total", C.c_int64), ("clk_serial", C.c_int64)]
+
+    def as_dict(self):
+        """the record as plain Python values / numpy arrays (T_inc 4 x 4, H 6 x 6)"""
+        d = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            d[name] = np.ctypeslib.as_array(v).copy() if not isinstance(v, (int, float)) else v
+        d["T_inc"] = d["T_inc"].reshape(4, 4)
+        d["H"] = d["H"].reshape(6, 6)
+        return d
+
+
+def _lc_kf_arrays(kf):
+    """the host arrays of one keyframe dict (pdesc, P, pl, pt_idx, ldesc, sPeP, le, ls_idx), contiguous and typed"""
+    out = {"pdesc": _arr(kf["pdesc"], np.uint8, (-1, 32)), "P": _arr(kf["P"], np.float64, (-1, 3)),
+           "pl": _arr(kf["pl"], np.float64, (-1, 2)), "ldesc": _arr(kf["ldesc"], np.uint8, (-1, 32)),
+           "sPeP": _arr(kf["sPeP"], np.float64, (-1, 6)), "le": _arr(kf["le"], np.float64, (-1, 3))}
+    for k in ("pt_idx", "ls_idx"):
+        out[k] = None if kf.get(k) is None else _arr(kf[k], np.int32)
+    n_pt, n_ls = out["pdesc"].shape[0], out["ldesc"].shape[0]
+    for k, n in (("P", n_pt), ("pl", n_pt), ("pt_idx", n_pt), ("sPeP", n_ls), ("le", n_ls), ("ls_idx", n_ls)):
+        if out[k] is not None and out[k].shape[0] != n:
+            raise ValueError(f"keyframe array {k} has {out[k].shape[0]} rows, its descriptors {n}")
+    return out
+
+
+def _lc_kf_record(a):
+    # a: the arrays of _lc_kf_arrays (host) or of device tensors' addresses; the caller keeps them alive across the call
+    return LcKeyframe(_p(a["pdesc"]), _p(a["P"]), _p(a["pl"]), _p(a["pt_idx"]), a["P"].shape[0], a["sPeP"].shape[0],
+                      _p(a["ldesc"]), _p(a["sPeP"]), _p(a["le"]), _p(a["ls_idx"]))
+
+
+_vp, _i32 = C.c_void_p, C.c_int32
+proto("plslam_lc_batch_create", [_vp, C.POINTER(LcParams), _i32, C.POINTER(_vp)])
+proto("plslam_lc_batch_verify", [_vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), _i32, C.POINTER(LcResult), _vp, _vp, _vp, _vp])
+proto("plslam_lc_batch_verify_dev", [_vp, C.POINTER(LcKeyframe), C.POINTER(LcKeyframe), _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_lc_batch_destroy", [_vp], None)
+
+
+class LcBatch(Handle):
+    """plslam_lc_batch: isLoopClosure for up to max_pairs candidate pairs per call (K54), with `params` fixed."""
+
+    def __init__(self, ctx: Context, params: LcParams, max_pairs: int):
+        self.params = params
+        self.max_pairs = int(max_pairs)
+        h = C.c_void_p()
+        _check(ctx._L.plslam_lc_batch_create(ctx.handle, C.byref(params), self.max_pairs, C.byref(h)), "plslam_lc_batch_create")
+        self._open(ctx, "plslam_lc_batch_destroy", h)
+
+    def verify(self, pairs):
+        """pairs: a sequence of (kf0, kf1) keyframe dicts (Context.loop_closure_verify's).  A dict that appears several
+        times is packed and uploaded once.  -> one (result dict, pt_corr, pt_inlier, ls_corr, ls_inlier) per pair."""
+        B = len(pairs)
+        packed = {}
+
+        def rec(kf):
+            if id(kf) not in packed:
+                a = _lc_kf_arrays(kf)
+                packed[id(kf)] = (_lc_kf_record(a), a)
+            return packed[id(kf)][0]
+
+        r0 = (LcKeyframe * max(B, 1))(*(rec(p[0]) for p in pairs))
+        r1 = (LcKeyframe * max(B, 1))(*(rec(p[1]) for p in pairs))
+        rp = np.concatenate([[0], np.cumsum([r0[b].n_pt for b in range(B)])]).astype(np.int64)
+        rl = np.concatenate([[0], np.cumsum([r0[b].n_ls for b in range(B)])]).astype(np.int64)
+        pc, pi = np.zeros((int(rp[-1]), 4), np.int32), np.zeros(int(rp[-1]), np.uint8)
+        lc, li = np.zeros((int(rl[-1]), 4), np.int32), np.zeros(int(rl[-1]), np.uint8)
+        res = (LcResult * max(B, 1))()
+        _check(self._L.plslam_lc_batch_verify(self._h, r0, r1, B, res, _p(pc), _p(pi), _p(lc), _p(li)), "plslam_lc_batch_verify")
+        out = []
+        for b in range(B):
+            d = res[b].as_dict()
+            n, m = d["common_pt"], d["common_ls"]
+            out.append((d, pc[rp[b]:rp[b] + n], pi[rp[b]:rp[b] + n].astype(bool), lc[rl[b]:rl[b] + m],
+                        li[rl[b]:rl[b] + m].astype(bool)))
+        return out
+
+    def verify_dev(self, kf0_dev, kf1_dev, results_ptr, pt_corr_ptr, pt_inlier_ptr, ls_corr_ptr, ls_inlier_ptr, stream=None):
+        """Device-pointer form.  kf0_dev / kf1_dev: B dicts of device addresses each (Context.loop_closure_verify_dev's);
+        results_ptr: B x sizeof(LcResult) bytes; pair b's rows start at row sum(n_pt of kf0_dev[:b]) (n_ls for lines).
+        Enqueued behind `stream` (None = the context's stream), no synchronisation."""
+        B = len(kf0_dev)
+        if len(kf1_dev) != B:
+            raise ValueError("kf0_dev and kf1_dev differ in length")
+
+        def recs(ks):
+            return (LcKeyframe * max(B, 1))(*(
+                LcKeyframe(*(C.c_void_p(k.get(n) or 0) for n in ("pdesc", "P", "pl", "pt_idx")), int(k["n_pt"]), int(k["n_ls"]),
+                           *(C.c_void_p(k.get(n) or 0) for n in ("ldesc", "sPeP", "le", "ls_idx"))) for k in ks))
+
+        _check(self._L.plslam_lc_batch_verify_dev(self._h, recs(kf0_dev), recs(kf1_dev), B, C.c_void_p(results_ptr or 0),
+                                                  C.c_void_p(pt_corr_ptr or 0), C.c_void_p(pt_inlier_ptr or 0),
+                                                  C.c_void_p(ls_corr_ptr or 0), C.c_void_p(ls_inlier_ptr or 0),
+                                                  C.c_void_p(stream or 0)), "plslam_lc_batch_verify_dev")
+
 
 # config/config/config.yaml (SlamConfig) and the stvo-pl Config it loads (homog_th, min_ratio_12_*, best_lr_matches)
 DEFAULTS = dict(homog_th=1e-7, min_ratio_12_p=0.75, min_ratio_12_l=0.75, mutual=1, has_points=1, has_lines=1, max_iters=5,

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import Context, _check, _p
+from ._lib import Handle, _check, _p, proto
 from .local_map import FEAT_NULL, LOOKBACK_TILE, DeviceMapIndex, MapIndex  # noqa: F401 (LOOKBACK_TILE: for the case tables)
 
 MAX_TABLE = 65536         # include/plslam_hip.h: PLSLAM_MAP_INSERT_MAX_TABLE
@@ -137,14 +137,21 @@ def _kind_struct(k, mode):
     return s, keep
 
 
-class MapInsert:
+proto("plslam_map_insert_create", [_vp, C.POINTER(_vp)])
+proto("plslam_map_insert_kf2kf", [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_map_insert_map2kf", [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_map_insert_device_buffers", [_vp, _vp])
+proto("plslam_map_insert_download", [_vp, _vp])
+proto("plslam_map_insert_destroy", [_vp], None)
+
+
+class MapInsert(Handle):
     """plslam_map_insert: the handle that owns the scratch and the event records of kf2kf / map2kf."""
 
     def __init__(self, ctx: Context):
-        self._L, self._ctx, self._h = ctx._L, ctx, None
         h = C.c_void_p()
-        _check(self._L.plslam_map_insert_create(ctx.handle, C.byref(h)), "plslam_map_insert_create")
-        self._h = h
+        _check(ctx._L.plslam_map_insert_create(ctx.handle, C.byref(h)), "plslam_map_insert_create")
+        self._open(ctx, "plslam_map_insert_destroy", h)
         self._n_ev = (0, 0)
         self._n_obs = (0, 0)
 
@@ -199,17 +206,6 @@ class MapInsert:
                 setattr(b, tag + "_obs_src", _p(out[kind]["obs_src"]))
         _check(self._L.plslam_map_insert_download(self._h, C.addressof(b)), "plslam_map_insert_download")
         return out
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value and self._ctx.handle:
-            self._L.plslam_map_insert_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- the seeded generators ----------------------------------------------------------------------------------------------------

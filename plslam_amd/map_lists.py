@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import Context, _check
+from ._lib import _check, proto
 from .synth import random_desc
 
 _vp = C.c_void_p
@@ -35,6 +35,11 @@ class MapInsertRows(C.Structure):
 
 class LcFuseRows(C.Structure):
     _fields_ = [(k, _vp) for k in ("desc0", "desc1", "pts0", "pts1")]
+
+
+proto("plslam_map_lists_refresh", [_vp, _vp, _vp])
+proto("plslam_map_insert_carry", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
+proto("plslam_lc_fuse_carry", [_vp, _vp, _vp, _vp, _vp, _vp, _vp])
 
 
 def _fields_of(kind):

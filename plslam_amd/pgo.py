@@ -1,4 +1,5 @@
-"""Seeded generator for the loop-closure correction (plslam_pgo_*, plslam_lc_correct_map): a map whose stored poses drifted.
+"""The loop-closure correction (plslam_pgo_*, plslam_lc_correct_map, include/plslam_hip.h): the ctypes binding (PgoPlan,
+correct_map, correct_map_dev, envelope_ldlt_solve) and a seeded generator: a map whose stored poses drifted.
 
 The true keyframes run around a circle of `period` keyframes and carry on into a second lap, so that keyframe k >= period is
 back where keyframe k - period was.  The stored poses are the true relative motions composed with small errors (accumulated
@@ -15,9 +16,146 @@ import ctypes as C
 
 import numpy as np
 
+from ._lib import Handle, _arr, _check, _p, proto
 from .synth import se3_exp
 
+PGO_STOP_MAX_ITERS, PGO_STOP_TERMINATE = 0, 1
 
+
+class PgoParams(C.Structure):
+    """plslam_pgo_params"""
+    _fields_ = [("min_lm_ess_graph", C.c_int32), ("min_lm_cov_graph", C.c_int32), ("max_iters_pgo", C.c_int32),
+                ("max_trials", C.c_int32), ("lambda_init", C.c_double)]
+
+
+class PgoTrial(C.Structure):
+    """plslam_pgo_trial: one record per trial of plslam_pgo_optimize"""
+    _fields_ = [("iteration", C.c_int32), ("trial", C.c_int32), ("lambda_", C.c_double), ("chi", C.c_double),
+                ("chi_new", C.c_double), ("scale", C.c_double), ("rho", C.c_double), ("ok", C.c_int32), ("accepted", C.c_int32)]
+
+
+class PgoResult(C.Structure):
+    """plslam_pgo_result"""
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("stop_reason", C.c_int32), ("n_vertices", C.c_int32),
+                ("n_active", C.c_int32), ("n_edges", C.c_int32), ("n_lc_edges", C.c_int32), ("env_width", C.c_int32),
+                ("env_entries", C.c_int64), ("chi_initial", C.c_double), ("chi_final", C.c_double), ("lambda_", C.c_double)]
+
+
+class LcLandmarks(C.Structure):
+    """plslam_lc_landmarks"""
+    _fields_ = [("n", C.c_int32), ("n_anchor", C.c_int32), ("n_dir", C.c_int32), ("anchor_ptr", C.c_void_p),
+                ("anchor_idx", C.c_void_p), ("valid", C.c_void_p), ("X", C.c_void_p), ("med_dir", C.c_void_p),
+                ("dir_ptr", C.c_void_p), ("dirs", C.c_void_p)]
+
+
+class LcImageDst(C.Structure):
+    """plslam_lc_image_dst: writable device pointers (None: that array is not carried)"""
+    _fields_ = [(k, C.c_void_p) for k in ("pt_X", "pt_dir", "pt_med_dir", "ls_X", "ls_dir", "ls_med_dir", "x_kf_w")]
+
+
+class LcImageCounts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_pt", "n_ls", "n_pt_dirs", "n_ls_dirs")]
+
+
+_vp, _i32 = C.c_void_p, C.c_int32
+proto("plslam_pgo_plan_create", [_vp, C.POINTER(PgoParams), _i32, _vp, _vp, _i32, _vp, C.POINTER(_vp)])
+proto("plslam_pgo_optimize", [_vp] + [_vp] * 7 + [C.POINTER(PgoTrial), _i32, C.POINTER(PgoResult)])
+proto("plslam_pgo_plan_destroy", [_vp], None)
+proto("plslam_lc_correct_map", [_vp, _i32, _vp, _vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks)])
+proto("plslam_lc_correct_map_dev", [_vp, _i32, _vp, _vp, C.POINTER(LcLandmarks), C.POINTER(LcLandmarks), _vp])
+proto("plslam_lc_correct_image", [_vp, _vp, _vp, _vp, _vp, C.POINTER(LcImageDst), C.POINTER(LcImageCounts)])
+proto("plslam_envelope_ldlt_solve", [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)])
+
+
+def envelope_ldlt_solve(ctx: Context, A, b):
+    """plslam_envelope_ldlt_solve: x with (the lower triangle of A, mirrored) x = b by the envelope L D L^T, in the given
+    ordering -> (x, number of zero / non-finite pivots, envelope width)."""
+    A = _arr(A, np.float64)
+    n = A.shape[0]
+    assert A.shape == (n, n)
+    bb = _arr(b, np.float64, (n,))
+    x, nb, bw = np.empty(n), C.c_int32(0), C.c_int32(0)
+    _check(ctx._L.plslam_envelope_ldlt_solve(ctx.handle, n, _p(A), _p(bb), _p(x), C.byref(nb), C.byref(bw)),
+           "plslam_envelope_ldlt_solve")
+    return x, int(nb.value), int(bw.value)
+
+
+class PgoPlan(Handle):
+    """plslam_pgo_plan: the loop-closure pose graph of the reference (loopClosureOptimizationCovGraphG2O) over one map.
+
+    kf_valid (n,): 0 for a NULL keyframe slot; full_graph (n, n) int32; lc_idx (n_lc, 3)."""
+
+    def __init__(self, ctx: Context, kf_valid, full_graph, lc_idx, min_lm_ess_graph=75, min_lm_cov_graph=75, max_iters_pgo=100,
+                 lambda_init=1e-10, max_trials=10):
+        v = _arr(kf_valid, np.uint8, (-1,))
+        n = v.shape[0]
+        fg = _arr(full_graph, np.int32, (n, n))
+        lc = _arr(lc_idx, np.int32, (-1, 3))
+        self.n_map, self.n_lc = n, lc.shape[0]
+        self.params = PgoParams(int(min_lm_ess_graph), int(min_lm_cov_graph), int(max_iters_pgo), int(max_trials),
+                                float(lambda_init))
+        h = C.c_void_p()
+        _check(ctx._L.plslam_pgo_plan_create(ctx.handle, C.byref(self.params), n, _p(v), _p(fg), self.n_lc, _p(lc), C.byref(h)),
+               "plslam_pgo_plan_create")
+        self._open(ctx, "plslam_pgo_plan_destroy", h)
+
+    def optimize(self, T_kf_w, x_kf_w, lc_pose, trace_cap=4096) -> dict:
+        """-> dict(T (n, 4, 4), x (n, 6), T_corr (n, 4, 4), corrected (n,) bool, trace [dict per trial], and the result's
+        fields)."""
+        n = self.n_map
+        T = _arr(T_kf_w, np.float64, (n, 16))
+        x = _arr(x_kf_w, np.float64, (n, 6))
+        lp = _arr(lc_pose, np.float64, (self.n_lc, 6))
+        To, xo, Tc, co = np.empty((n, 4, 4)), np.empty((n, 6)), np.empty((n, 4, 4)), np.empty(n, np.uint8)
+        tr = (PgoTrial * max(int(trace_cap), 1))()
+        res = PgoResult()
+        _check(self._L.plslam_pgo_optimize(self._h, _p(T), _p(x), _p(lp), _p(To), _p(xo), _p(Tc), _p(co), tr, int(trace_cap),
+                                           C.byref(res)), "plslam_pgo_optimize")
+        trace = [dict(it=t.iteration, trial=t.trial, lam=t.lambda_, chi=t.chi, chi_new=t.chi_new, scale=t.scale, rho=t.rho,
+                      ok=bool(t.ok), accepted=bool(t.accepted)) for t in tr[:min(res.trials, int(trace_cap))]]
+        out = {f: getattr(res, f) for f, _ in PgoResult._fields_}
+        out["lam"] = out.pop("lambda_")
+        out.update(T=To, x=xo, T_corr=Tc, corrected=co.astype(bool), trace=trace)
+        return out
+
+
+def _landmarks(lm, dl):
+    """host arrays of one kind -> (LcLandmarks over them, the arrays kept alive and written in place)"""
+    a = dict(anchor_ptr=_arr(lm["anchor_ptr"], np.int32, (-1,)), anchor_idx=_arr(lm["anchor_idx"], np.int32, (-1,)),
+             valid=_arr(lm["valid"], np.uint8, (-1,)), X=np.array(lm["X"], np.float64).reshape(-1, dl),
+             med_dir=np.array(lm["med_dir"], np.float64).reshape(-1, 3), dir_ptr=_arr(lm["dir_ptr"], np.int32, (-1,)),
+             dirs=np.array(lm["dirs"], np.float64).reshape(-1, 3))
+    n = a["valid"].shape[0]
+    s = LcLandmarks(n, a["anchor_idx"].shape[0], a["dirs"].shape[0], _p(a["anchor_ptr"]), _p(a["anchor_idx"]), _p(a["valid"]),
+                    _p(a["X"]), _p(a["med_dir"]), _p(a["dir_ptr"]), _p(a["dirs"]))
+    return s, a
+
+
+def correct_map(ctx: Context, T_corr, corrected, points=None, lines=None):
+    """plslam_lc_correct_map on host arrays: points / lines are dicts (anchor_ptr, anchor_idx, valid, X, med_dir, dir_ptr,
+    dirs) as plslam_amd.pgo.anchored_landmarks makes them -> (points, lines) corrected copies (X, med_dir, dirs)."""
+    Tc = _arr(T_corr, np.float64, (-1, 16))
+    n_map = Tc.shape[0]
+    co = _arr(corrected, np.uint8, (n_map,))
+    sp = _landmarks(points, 3) if points is not None else None
+    sl = _landmarks(lines, 6) if lines is not None else None
+    _check(ctx._L.plslam_lc_correct_map(ctx.handle, n_map, _p(Tc), _p(co), C.byref(sp[0]) if sp else None,
+                                        C.byref(sl[0]) if sl else None), "plslam_lc_correct_map")
+    pick = lambda s: None if s is None else {k: s[1][k] for k in ("X", "med_dir", "dirs")}  # noqa: E731
+    return pick(sp), pick(sl)
+
+
+def correct_map_dev(ctx: Context, n_map_kf, T_corr_ptr, corrected_ptr, points=None, lines=None, stream=0) -> None:
+    """plslam_lc_correct_map_dev: points / lines are dicts of device pointers (ints) with the counts n, n_anchor, n_dir."""
+    def mk(d):
+        return None if d is None else C.byref(LcLandmarks(d["n"], d["n_anchor"], d["n_dir"], d["anchor_ptr"], d["anchor_idx"],
+                                                          d["valid"], d["X"], d["med_dir"], d["dir_ptr"], d["dirs"]))
+    _check(ctx._L.plslam_lc_correct_map_dev(ctx.handle, int(n_map_kf), C.c_void_p(T_corr_ptr), C.c_void_p(corrected_ptr),
+                                            mk(points), mk(lines), C.c_void_p(stream) if stream else None),
+           "plslam_lc_correct_map_dev")
+
+
+# ---- the seeded generator -----------------------------------------------------------------------------------------------------
 def _logmap(T):
     R = T[:3, :3]
     c = min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))
@@ -129,7 +267,6 @@ def correct_image(ctx, index, T_corr, corrected, x_kf_w=None, lists=None, med_di
     carried (None: no dir), med_dir a dict(points=, lines=) of device addresses of (n, 3) arrays (None: not carried).  T_corr
     (n_map_kf, 4, 4) and corrected (n_map_kf,) are host arrays, as PgoPlan.optimize returns them.
     -> dict(n_pt, n_ls, n_pt_dirs, n_ls_dirs): the corrected landmarks and the transformed dir rows."""
-    from .capi import LcImageCounts, LcImageDst, _arr, _check, _p
     n = int(index.struct.n_map_kf)
     Tc = _arr(T_corr, np.float64, (n, 16))
     co = _arr(np.asarray(corrected).astype(np.uint8), np.uint8, (n,))

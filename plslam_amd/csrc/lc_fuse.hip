@@ -23,6 +23,9 @@
 // Atomics count and select; none decides an order.  Every output is an integer, a flag, a verbatim copy of a double or a
 // fixed-order fp64 expression of correctly rounded operations.  Every index read from the image or a tuple is range-checked
 // before it is used as an address.
+// The host decisions -- the validation, the growth bounds, the layout of the handle's buffer, the packing of the staged block --
+// are lc_fuse_plan.hpp (no HIP in it; tests/cpp/test_lc_fuse_pack.cpp); the commit the fusion shares with the insert is
+// map_image.hpp's.
 #include <climits>
 #include <cstring>
 
@@ -41,7 +44,7 @@ constexpr unsigned LF_MAX_GRID = 4096;  // K72 / K73 stride over their items
 constexpr int LF_MAX_LEVEL = PLSLAM_LC_FUSE_MAX_LEVEL;
 static_assert(PLSLAM_LC_FUSE_MAX_TUPLES <= 64 * LF_RES_NT, "a resolve lane keeps its pending events in one 64-bit mask");
 // the call counters (device words, mirrored in the page-locked block): eight per kind, then the status word
-enum { W_A = 0, W_B, W_C, W_D, W_SKIP, W_OBS, W_PAIRS, W_KIND = 8, W_STATUS = 16, W_WORDS = 20 };
+enum { W_A = 0, W_B, W_C, W_D, W_SKIP, W_OBS, W_PAIRS, W_KIND = 8, W_STATUS = 16, W_WORDS = LC_FUSE_COUNTER_WORDS };
 // what a tuple can be from the source image alone
 enum { SC_OFF = 0, SC_A, SC_B, SC_C, SC_D, SC_SELF, SC_NONE };
 
@@ -386,12 +389,48 @@ k_lf_feat_graph(MapKindSrc S, MapKindDst D, CallD C, int32_t* __restrict__ graph
     }
 }
 
+// one kind's tables and scratch: every slice of the plan's layout as the typed pointer the kernels take
+CallD call_of(const LcFusePlan& P, int k, const uint8_t* kf_valid, char* d)
+{
+    const LcFuseKindPlan& K = P.k[k];
+    const char* st_ = d + P.stage_off;
+    int32_t* cnt = slice_at<int32_t>(d, P.d_cnt);
+    CallD C{};
+    C.lines = k; C.n_map_kf = P.nk; C.n_lc = P.n_lc; C.m = K.m; C.c_cap = K.cC;
+    C.kf_valid = kf_valid;
+    C.lc = slice_at<int32_t>(st_, P.o_lc); C.tup = slice_at<int32_t>(st_, K.o_tup); C.eptr = slice_at<int32_t>(st_, K.o_eptr);
+    C.T = slice_at<double>(st_, P.o_T);
+    C.P0 = slice_at<double>(st_, K.o_P0); C.o0 = slice_at<double>(st_, K.o_o0);
+    C.P1 = slice_at<double>(st_, K.o_P1); C.o1 = slice_at<double>(st_, K.o_o1);
+    C.cur_len = slice_at<int32_t>(d, K.d_len); C.killer = slice_at<int32_t>(d, K.d_killer); C.head = slice_at<int32_t>(d, K.d_head);
+    C.sc = slice_at<int32_t>(d, K.d_sc); C.fw0 = slice_at<int32_t>(d, K.d_fw0); C.fw1 = slice_at<int32_t>(d, K.d_fw1);
+    C.ev = slice_at<int32_t>(d, K.d_ev); C.ev_off = slice_at<int32_t>(d, K.d_off); C.pair_off = slice_at<int32_t>(d, K.d_pair);
+    C.new_ev = slice_at<int32_t>(d, K.d_nev); C.feat_win = slice_at<int32_t>(d, K.d_win); C.obs_src = slice_at<int32_t>(d, K.d_osrc);
+    C.cnt = cnt + W_KIND * k; C.status = cnt + W_STATUS; C.ev_dir = slice_at<double>(d, K.d_dir);
+    return C;
+}
+
 struct KfCopy {                          // what K73 copies from the source image where the destination has its own array
     int32_t nk;
     const uint8_t* kf_valid; uint8_t* kf_valid_d;
     const double* x; double* x_d;
     const int32_t* fp[2]; int32_t* fp_d[2];
 };
+
+// what K73 copies: the keyframe arrays and feat_ptr, where the destination has an array of its own
+KfCopy kf_copy_of(const plslam_map_index& src, const plslam_map_index& dst)
+{
+    const plslam_map_landmarks *S[2] = {&src.points, &src.lines}, *D[2] = {&dst.points, &dst.lines};
+    KfCopy kc{};
+    kc.nk = src.n_map_kf;
+    kc.kf_valid = src.kf_valid; kc.kf_valid_d = dst.kf_valid != src.kf_valid ? (uint8_t*)dst.kf_valid : nullptr;
+    kc.x = src.x_kf_w; kc.x_d = dst.x_kf_w != src.x_kf_w ? (double*)dst.x_kf_w : nullptr;
+    for (int k = 0; k < 2; ++k) {
+        kc.fp[k] = S[k]->feat_ptr;
+        kc.fp_d[k] = S[k]->n_feat > 0 && D[k]->feat_ptr != S[k]->feat_ptr ? (int32_t*)D[k]->feat_ptr : nullptr;
+    }
+    return kc;
+}
 
 // K73: the call's last kernel: the counters and the graph to the page-locked block; kf_valid / x_kf_w / feat_ptr copied
 __global__ void __launch_bounds__(MAP_TILE)
@@ -467,89 +506,41 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
     plslam_map_landmarks* Dk[2] = {&dst->map.points, &dst->map.lines};
     const int32_t cap[2] = {dst->pt_cap, dst->ls_cap}, obs_cap[2] = {dst->pt_obs_cap, dst->ls_obs_cap};
     const int32_t nk = P.nk;
-    // ---- the layout: [zeroed: counters, graph, per kind feat_win / part] [0x7f: head] [0xff: killer] [staged] [the rest] ----
-    struct KindOff { size_t win, part, head, killer, len, sc, fw0, fw1, ev, off, pair, nev, dir, osrc; unsigned w_lm; } O[2];
-    Carver c;
-    const size_t o_cnt = c.take(W_WORDS * 4), o_graph = c.take((size_t)nk * nk * 4);
-    for (int k = 0; k < 2; ++k) {
-        O[k].w_lm = map_tiles(P.k[k].need_lm);
-        O[k].win = c.take((size_t)S[k]->n_feat * 4 + 4);
-        O[k].part = c.take((size_t)O[k].w_lm * 4);
-    }
-    const size_t zero_bytes = c.off;
-    for (int k = 0; k < 2; ++k) O[k].head = c.take((size_t)S[k]->n * 4 + 4);
-    const size_t head_off = zero_bytes, head_bytes = c.off - head_off;
-    for (int k = 0; k < 2; ++k) O[k].killer = c.take((size_t)S[k]->n * 4 + 4);
-    const size_t killer_off = head_off + head_bytes, killer_bytes = c.off - killer_off;
-    const size_t stage_off = c.take(P.stage_bytes);
-    for (int k = 0; k < 2; ++k) {
-        const size_t m = (size_t)P.k[k].m;
-        O[k].len = c.take((size_t)P.k[k].need_lm * 4 + 4);
-        O[k].sc = c.take(m * 4 + 4); O[k].fw0 = c.take(m * 4 + 4); O[k].fw1 = c.take(m * 4 + 4);
-        O[k].ev = c.take(m * 24 + 24); O[k].off = c.take(m * 4 + 4); O[k].pair = c.take(m * 4 + 8);
-        O[k].nev = c.take((size_t)P.k[k].cC * 4 + 4); O[k].dir = c.take(m * 48 + 48);
-        O[k].osrc = c.take((size_t)obs_cap[k] * 4 + 4);
-    }
     std::lock_guard<std::mutex> lk(lf->ctx->mu);
     DeviceGuard dg_(lf->ctx->device);
     hipStream_t s = lf->ctx->stream;
     lf->done = false;
     lf->lists.valid = false;
-    if ((rc = lf->buf.reserve(c.off + 256))) return rc;
-    const size_t res_bytes = align256((W_WORDS + (graph_delta ? (size_t)nk * nk : 0)) * 4);
+    if ((rc = lf->buf.reserve(P.total + 256))) return rc;
+    const size_t res_bytes = P.res_bytes(graph_delta != nullptr);
     if ((rc = lf->pin.reserve(res_bytes + P.stage_bytes))) return rc;
     PLSLAM_REQUIRE(lf->pin.dev, PLSLAM_ENOTSUP);                 // the counters are written where the host reads them
     char* d = lf->buf.as<char>();
-    char* h = lf->pin.as<char>();
-    lc_fuse_pack(P, lc_idx, T_kf_w, h + res_bytes);
+    char* staged = lf->pin.as<char>() + res_bytes;
+    lc_fuse_pack(P, lc_idx, T_kf_w, staged);
     StreamSyncOnError guard(s);
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d, 0, zero_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d + head_off, 0x7f, head_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d + killer_off, 0xff, killer_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + stage_off, h + res_bytes, P.stage_bytes, hipMemcpyHostToDevice, s));
-    int32_t* cnt = (int32_t*)(d + o_cnt);
-    int32_t* graph = (int32_t*)(d + o_graph);
-    const char* st_ = d + stage_off;
+    for (const FillRegion& f : P.fill) PLSLAM_HIP_CHECK(hipMemsetAsync(d + f.off, f.byte, f.bytes, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + P.stage_off, staged, P.stage_bytes, hipMemcpyHostToDevice, s));
+    int32_t* cnt = slice_at<int32_t>(d, P.d_cnt);
+    int32_t* graph = slice_at<int32_t>(d, P.d_graph);
     MapKindSrc Sd[2];
     MapKindDst Dd[2];
     CallD C[2];
     for (int k = 0; k < 2; ++k) {
-        const LcFuseKindPlan& K = P.k[k];
-        const plslam_map_landmarks& A = *S[k];
-        plslam_map_landmarks& B = *Dk[k];
-        Sd[k] = map_kind_src(A, k);
-        Dd[k] = map_kind_dst(B, cap[k], obs_cap[k]);
-        CallD& Ck = C[k];
-        Ck = CallD{};
-        Ck.lines = k; Ck.n_map_kf = nk; Ck.n_lc = n_lc; Ck.m = K.m; Ck.c_cap = K.cC;
-        Ck.kf_valid = src->kf_valid;
-        Ck.lc = (const int32_t*)(st_ + P.o_lc); Ck.tup = (const int32_t*)(st_ + K.o_tup); Ck.eptr = (const int32_t*)(st_ + K.o_eptr);
-        Ck.T = (const double*)(st_ + P.o_T);
-        Ck.P0 = (const double*)(st_ + K.o_P0); Ck.o0 = (const double*)(st_ + K.o_o0);
-        Ck.P1 = (const double*)(st_ + K.o_P1); Ck.o1 = (const double*)(st_ + K.o_o1);
-        Ck.cur_len = (int32_t*)(d + O[k].len); Ck.killer = (int32_t*)(d + O[k].killer); Ck.head = (int32_t*)(d + O[k].head);
-        Ck.sc = (int32_t*)(d + O[k].sc); Ck.fw0 = (int32_t*)(d + O[k].fw0); Ck.fw1 = (int32_t*)(d + O[k].fw1);
-        Ck.ev = (int32_t*)(d + O[k].ev); Ck.ev_off = (int32_t*)(d + O[k].off); Ck.pair_off = (int32_t*)(d + O[k].pair);
-        Ck.new_ev = (int32_t*)(d + O[k].nev); Ck.feat_win = (int32_t*)(d + O[k].win); Ck.obs_src = (int32_t*)(d + O[k].osrc);
-        Ck.cnt = cnt + W_KIND * k; Ck.status = cnt + W_STATUS; Ck.ev_dir = (double*)(d + O[k].dir);
+        Sd[k] = map_kind_src(*S[k], k);
+        Dd[k] = map_kind_dst(*Dk[k], cap[k], obs_cap[k]);
+        C[k] = call_of(P, k, src->kf_valid, d);
     }
     // both kinds are resolved before anything of the destination is written: a refusal leaves it untouched
     for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_classify, dim3(map_tiles((int64_t)S[k]->n + P.k[k].m)), dim3(MAP_TILE), 0, s, Sd[k], C[k]);
     for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_lf_resolve, dim3(1), dim3(LF_RES_NT), 0, s, Sd[k], C[k]);
     for (int k = 0; k < 2; ++k) {
-        hipLaunchKernelGGL(k_lf_layout, dim3(O[k].w_lm), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k], (uint32_t*)(d + O[k].part));
+        hipLaunchKernelGGL(k_lf_layout, dim3(P.k[k].w_lm), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k], slice_at<uint32_t>(d, P.k[k].d_part));
         hipLaunchKernelGGL(k_lf_obs, dim3(map_tiles((int64_t)S[k]->n_obs + 2 * (int64_t)P.k[k].m)), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k]);
         const unsigned g = map_tiles((int64_t)S[k]->n_feat + S[k]->n_obs + 4 * (int64_t)P.k[k].m);
         hipLaunchKernelGGL(k_lf_feat_graph, dim3(g < LF_MAX_GRID ? g : LF_MAX_GRID), dim3(MAP_TILE), 0, s, Sd[k], Dd[k], C[k], graph);
     }
-    KfCopy kc{};
-    kc.nk = nk;
-    kc.kf_valid = src->kf_valid; kc.kf_valid_d = dst->map.kf_valid != src->kf_valid ? (uint8_t*)dst->map.kf_valid : nullptr;
-    kc.x = src->x_kf_w; kc.x_d = dst->map.x_kf_w != src->x_kf_w ? (double*)dst->map.x_kf_w : nullptr;
-    for (int k = 0; k < 2; ++k) {
-        kc.fp[k] = S[k]->feat_ptr;
-        kc.fp_d[k] = S[k]->n_feat > 0 && Dk[k]->feat_ptr != S[k]->feat_ptr ? (int32_t*)Dk[k]->feat_ptr : nullptr;
-    }
+    const KfCopy kc = kf_copy_of(*src, dst->map);
     const unsigned gp = map_tiles(graph_delta ? (int64_t)nk * nk : nk + 1);
     hipLaunchKernelGGL(k_lf_publish, dim3(gp < 256u ? gp : 256u), dim3(MAP_TILE), 0, s, (const int32_t*)cnt, (const int32_t*)graph, kc,
                        (int32_t*)lf->pin.dev, graph_delta ? 1 : 0);
@@ -563,29 +554,19 @@ int plslam_lc_fuse_run(plslam_lc_fuse* lf, const plslam_map_index* src, plslam_m
     }
     if (graph_delta) memcpy(graph_delta, r + W_WORDS, (size_t)nk * nk * 4);
     plslam_lc_fuse_kind_counts* out[2] = {&counts->points, &counts->lines};
+    MapCommitKind done[2];
     for (int k = 0; k < 2; ++k) {
         const int32_t* w = r + W_KIND * k;
         *out[k] = plslam_lc_fuse_kind_counts{w[W_A], w[W_B], w[W_C], w[W_D], w[W_C], w[W_D], w[W_SKIP]};
         lf->m[k] = P.k[k].m;
         lf->n_obs[k] = w[W_OBS] < obs_cap[k] ? w[W_OBS] : obs_cap[k];
-        Dk[k]->n = S[k]->n + w[W_C];
-        Dk[k]->n_obs = lf->n_obs[k];
-        Dk[k]->n_feat = S[k]->n_feat;
-        (k ? lf->d.ls_ev : lf->d.pt_ev) = C[k].ev;
-        (k ? lf->d.ls_dir : lf->d.pt_dir) = C[k].ev_dir;
-        (k ? lf->d.ls_obs_src : lf->d.pt_obs_src) = C[k].obs_src;
-        ListsKindRecords& R = lf->lists.k[k];
-        R = ListsKindRecords{};
-        R.src_n = S[k]->n; R.src_obs = S[k]->n_obs; R.dst_n = Dk[k]->n; R.dst_obs = Dk[k]->n_obs;
-        R.n_ev = P.k[k].m; R.bound[0] = R.bound[1] = P.k[k].m; R.ev_stride = 0; R.need_side0 = 1;
-        R.ev = C[k].ev; R.dir = C[k].ev_dir; R.obs_src = C[k].obs_src;
+        done[k] = MapCommitKind{w[W_C], lf->n_obs[k], P.k[k].m, {P.k[k].m, P.k[k].m}, C[k].ev, C[k].ev_dir, C[k].obs_src};
     }
-    dst->map.n_map_kf = nk;
+    map_commit(*src, dst->map, done, 0, 1, lf->d, lf->lists);
     lf->nk = nk;
     lf->d.graph_delta = graph;
     lf->d.stream = (void*)s;
     lf->done = true;
-    lf->lists.valid = true;
     return PLSLAM_OK;
 }
 

@@ -1,15 +1,19 @@
 // lc_fuse_plan.hpp -- the pure host half of plslam_lc_fuse_run (lc_fuse.hip): the validation of the arguments, the growth bounds
-// the tuples alone give, and the packing of the call's tables into the one block that is staged to the device.  No HIP in here:
-// tests/cpp/test_lc_fuse_pack.cpp compiles it on its own and runs it under the sanitizers.
+// the tuples alone give, the layout of the handle's device buffer with its fill regions, and the packing of the call's tables into
+// the one block that is staged to the device.  No HIP in here: tests/cpp/test_lc_fuse_pack.cpp compiles it on its own and runs it
+// under the sanitizers.
 #pragma once
 
 #include <cstdint>
 #include <cstring>
 
 #include "map_image.hpp"
+#include "match_tables.hpp"   // Carver, align256
 #include "plslam_hip.h"
 
 namespace plslam {
+
+constexpr int LC_FUSE_COUNTER_WORDS = 20;        // the call counters: eight per kind, then the status word (lc_fuse.hip: W_WORDS)
 
 struct LcFuseKindPlan {
     const plslam_lc_fuse_kind* in = nullptr;     // nullptr: no tuple of this kind
@@ -17,12 +21,22 @@ struct LcFuseKindPlan {
     int32_t dl = 3, dv = 2;                      // doubles per feature position (3 / 6) and per observation (2 / 3)
     int64_t need_lm = 0, need_obs = 0;
     size_t o_tup = 0, o_eptr = 0, o_P0 = 0, o_o0 = 0, o_P1 = 0, o_o1 = 0;      // in the staged block
+    // the device buffer: zeroed (win, part: w_lm chain words) | 0x7f (head) | 0xff (killer) | behind the staged block the rest
+    unsigned w_lm = 1;                           // tiles of need_lm landmarks
+    size_t d_win = 0, d_part = 0, d_head = 0, d_killer = 0;
+    size_t d_len = 0, d_sc = 0, d_fw0 = 0, d_fw1 = 0, d_ev = 0, d_off = 0, d_pair = 0, d_nev = 0, d_dir = 0, d_osrc = 0;
 };
 struct LcFusePlan {
     int32_t n_lc = 0, nk = 0;
     LcFuseKindPlan k[2];
     size_t o_lc = 0, o_T = 0, stage_bytes = 0;
+    size_t d_cnt = 0, d_graph = 0;               // the device buffer: the counters, the dense nk x nk graph delta (zeroed)
+    FillRegion fill[3] = {};                     // zero, 0x7f (the heads: above every event number), 0xff (the killers: -1)
+    size_t stage_off = 0;                        // the staged block inside the device buffer
+    size_t total = 0;                            // the end of the last slice
     const char* why = "";                        // what was refused
+    // page-locked: the counters, the graph where the caller asked for it; the staged block follows
+    size_t res_bytes(bool with_graph) const { return align256((LC_FUSE_COUNTER_WORDS + (with_graph ? (size_t)nk * nk : 0)) * 4); }
 };
 
 inline size_t lc_fuse_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -105,6 +119,32 @@ inline int lc_fuse_plan(const plslam_map_index* src, const plslam_map_insert_dst
         K.o_o1 = take((size_t)K.m * K.dv * 8 + 8);
     }
     P->stage_bytes = off;
+    // ---- the device layout: [zeroed: counters, graph, per kind feat_win / part] [0x7f: head] [0xff: killer] [staged] [the rest] ----
+    Carver c;
+    P->d_cnt = c.take(LC_FUSE_COUNTER_WORDS * 4);
+    P->d_graph = c.take((size_t)nk * nk * 4);
+    for (int k = 0; k < 2; ++k) {
+        LcFuseKindPlan& K = P->k[k];
+        K.w_lm = map_tiles(K.need_lm);
+        K.d_win = c.take((size_t)S[k]->n_feat * 4 + 4);
+        K.d_part = c.take((size_t)K.w_lm * 4);
+    }
+    P->fill[0] = FillRegion{0, c.off, 0};
+    for (int k = 0; k < 2; ++k) P->k[k].d_head = c.take((size_t)S[k]->n * 4 + 4);
+    P->fill[1] = FillRegion{P->fill[0].bytes, c.off - P->fill[0].bytes, 0x7f};
+    for (int k = 0; k < 2; ++k) P->k[k].d_killer = c.take((size_t)S[k]->n * 4 + 4);
+    P->fill[2] = FillRegion{P->fill[1].off + P->fill[1].bytes, c.off - (P->fill[1].off + P->fill[1].bytes), 0xff};
+    P->stage_off = c.take(P->stage_bytes);
+    for (int k = 0; k < 2; ++k) {
+        LcFuseKindPlan& K = P->k[k];
+        const size_t m = (size_t)K.m;
+        K.d_len = c.take((size_t)K.need_lm * 4 + 4);
+        K.d_sc = c.take(m * 4 + 4); K.d_fw0 = c.take(m * 4 + 4); K.d_fw1 = c.take(m * 4 + 4);
+        K.d_ev = c.take(m * 24 + 24); K.d_off = c.take(m * 4 + 4); K.d_pair = c.take(m * 4 + 8);
+        K.d_nev = c.take((size_t)K.cC * 4 + 4); K.d_dir = c.take(m * 48 + 48);
+        K.d_osrc = c.take((size_t)obs_cap[k] * 4 + 4);       // (the destination's capacity: K71 clamps to it)
+    }
+    P->total = c.off;
     return PLSLAM_OK;
 }
 

@@ -9,22 +9,22 @@
 //   the gather of globalBundleAdjustment :1995-2092 K97 every flag set (form_all), then K59-K61 as they are
 //   the write-back of the global BA     :2681-2697  K84 with the moved test switched off, from a GBA plan's resident landmarks
 // Every output is an integer, a flag or a verbatim copy of a double: bit-exact against the sequential loops (tests/local_map_ref.py).
-// Each entry point: the context's lock, device and stream; one synchronisation; counts through page-locked memory written by the
-// call's last kernel.  Every index read from the image is range-checked before it is used as an address.
+// Each entry point: its check, the context's lock, device and stream, the launches, one synchronisation, the commit; counts through
+// page-locked memory written by the call's last kernel.  The host decisions -- the counter words, the image check, the layout of
+// the handle's buffer, the handle's state with its checks and transitions, the table of the buffers -- are local_map_plan.hpp (no
+// HIP in it; tests/cpp/test_local_map_plan.cpp).  Every index read from the image is range-checked before it is used as an address.
 #include <cstring>
 
 #include "common.hpp"
 #include "gba_plan.hpp"
 #include "lba_plan.hpp"
+#include "local_map_plan.hpp"
 #include "lookback_dev.hpp"
 #include "map_image_dev.hpp"
 #include "publish_dev.hpp"
 
 namespace plslam {
 namespace {
-
-// the call counters (device words, mirrored in the page-locked block): plslam_local_map_counts' order, then the tickets
-enum { C_KF_LOCAL = 0, C_PT_LOCAL, C_LS_LOCAL, C_NKF, C_NPT, C_NLS, C_PT_OBS, C_LS_OBS, C_PT_REM, C_LS_REM, C_CULL_DONE, C_FORM_DONE, C_PT_MOVED, C_LS_MOVED, C_APPLY_DONE, C_WORDS = 16 };
 
 // The counters of a call's LAST kernel (publish_dev.hpp): NC flags per lane counted into cnt[0 .. NC), then the ticket
 template <int NC>
@@ -314,12 +314,6 @@ k_lm_all_flags(int32_t nkf, const uint8_t* __restrict__ kf_valid, int32_t npt, c
     else if (t < (int64_t)nkf + npt + nls) ls_local[t - nkf - npt] = ls_valid[t - nkf - npt] != 0 ? 1 : 0;
 }
 
-bool map_ok(const plslam_map_index* m)
-{
-    return m && m->n_map_kf >= 1 && m->kf_valid && m->x_kf_w && map_src_kind_ok(m->points) && map_src_kind_ok(m->lines) &&
-           6 * (int64_t)m->n_map_kf + 3 * (int64_t)m->points.n + 6 * (int64_t)m->lines.n < (int64_t)1 << 31;
-}
-
 }  // namespace
 }  // namespace plslam
 
@@ -329,65 +323,49 @@ struct plslam_local_map {
     plslam_ctx* ctx = nullptr;
     DevBuf buf;
     HostBuf pin;                                 // C_WORDS counters, then the staged graph row
-    int32_t n_map_kf = 0, npt = 0, nls = 0, n_pt_obs = 0, n_ls_obs = 0;
-    bool formed = false, gathered = false, applied = false;
+    LocalMapState st;
+    LocalMapLayout lay;                          // of the last form's image
     plslam_local_map_buffers d = {};
-    int32_t *kf_inv = nullptr, *pt_off = nullptr, *ls_off = nullptr, *row = nullptr, *cnt = nullptr;
-    uint32_t* part = nullptr;                    // five chains: kf, pt, pt observations, ls, ls observations
-    size_t part_words = 0, zero_bytes = 0;       // zero_bytes: the flags and the counters, cleared by form in one go
-    int32_t h_cnt[C_WORDS] = {};                 // the counts of the last calls (download sizes)
+
+    template <class T> T* at(LocalMapSlot slot) { return slice_at<T>(buf.as<char>(), lay.off[slot]); }
+    int32_t* cnt() { return at<int32_t>(LM_CNT); }
+    uint32_t* chain(int c) { return at<uint32_t>(LM_PART) + lay.chain_off[c]; }
+    int32_t* pinned_dev() { return (int32_t*)pin.dev; }
 };
 
 namespace {
 
-// carve the handle's buffer for this map's totals (form); everything the other calls write has its slice here
-int lm_layout(plslam_local_map* lm, const plslam_map_index* m)
+// form and form_all: the layout for this image, the flags cleared, the graph row staged where the caller has one, the launches that
+// set the flags (set_flags(stream): the one step the two differ in), the three counts
+template <class SetFlags>
+int form(plslam_local_map* lm, const plslam_map_index* map, const int32_t* row, plslam_local_map_counts* counts, SetFlags set_flags)
 {
-    const size_t nk = (size_t)m->n_map_kf, np = (size_t)m->points.n, nl = (size_t)m->lines.n, op = (size_t)m->points.n_obs,
-                 ol = (size_t)m->lines.n_obs;
-    Carver c;
-    const size_t o_kfl = c.take(nk), o_ptl = c.take(np), o_lsl = c.take(nl), o_cnt = c.take(C_WORDS * 4);
-    const size_t zero_bytes = c.off;
-    const size_t o_ptc = c.take(np), o_lsc = c.take(nl), o_ptr_ = c.take(np), o_lsr = c.take(nl), o_ptm = c.take(np), o_lsm = c.take(nl);
-    const size_t o_kfi = c.take(nk * 4), o_kfv = c.take(nk * 4), o_row = c.take(nk * 4);
-    const size_t o_pti = c.take(np * 4), o_lsi = c.take(nl * 4), o_pto = c.take((np + 1) * 4), o_lso = c.take((nl + 1) * 4);
-    const size_t o_p6 = c.take(op * 24), o_l6 = c.take(ol * 24);
-    size_t o_col[6];
-    for (int k = 0; k < 3; ++k) o_col[k] = c.take(op * 4);
-    for (int k = 3; k < 6; ++k) o_col[k] = c.take(ol * 4);
-    const size_t o_puv = c.take(op * 16), o_llo = c.take(ol * 24), o_x = c.take((6 * nk + 3 * np + 6 * nl) * 8);
-    const size_t wk = map_tiles((int64_t)nk), wp = map_tiles((int64_t)np), wl = map_tiles((int64_t)nl);
-    const size_t part_words = wk + 2 * wp + 2 * wl, o_part = c.take(part_words * 4);
-    int rc = lm->buf.reserve(c.off + 256);
+    std::lock_guard<std::mutex> lk(lm->ctx->mu);
+    DeviceGuard dg_(lm->ctx->device);
+    hipStream_t s = lm->ctx->stream;
+    lm->st.begin_form(*map);
+    lm->lay = LocalMapLayout(lm->st.z);
+    int rc = lm->buf.reserve(lm->lay.total + 256);
     if (rc) return rc;
-    if ((rc = lm->pin.reserve((C_WORDS + nk) * 4))) return rc;
-    char* d = lm->buf.as<char>();
-    plslam_local_map_buffers& b = lm->d;
-    b.kf_local = (uint8_t*)(d + o_kfl); b.pt_local = (uint8_t*)(d + o_ptl); b.ls_local = (uint8_t*)(d + o_lsl);
-    lm->cnt = (int32_t*)(d + o_cnt);
-    b.pt_candidate = (uint8_t*)(d + o_ptc); b.ls_candidate = (uint8_t*)(d + o_lsc);
-    b.pt_removed = (uint8_t*)(d + o_ptr_); b.ls_removed = (uint8_t*)(d + o_lsr);
-    b.pt_moved = (uint8_t*)(d + o_ptm); b.ls_moved = (uint8_t*)(d + o_lsm);
-    b.kf_list = (int32_t*)(d + o_kfi); lm->kf_inv = (int32_t*)(d + o_kfv); lm->row = (int32_t*)(d + o_row);
-    b.pt_list = (int32_t*)(d + o_pti); b.ls_list = (int32_t*)(d + o_lsi);
-    lm->pt_off = (int32_t*)(d + o_pto); lm->ls_off = (int32_t*)(d + o_lso);
-    b.pt_obs = (int32_t*)(d + o_p6); b.ls_obs = (int32_t*)(d + o_l6);
-    b.pt_lm_loc = (int32_t*)(d + o_col[0]); b.pt_kf_loc = (int32_t*)(d + o_col[1]); b.pt_pose_slot = (int32_t*)(d + o_col[2]);
-    b.ls_lm_loc = (int32_t*)(d + o_col[3]); b.ls_kf_loc = (int32_t*)(d + o_col[4]); b.ls_pose_slot = (int32_t*)(d + o_col[5]);
-    b.pt_obs_uv = (double*)(d + o_puv); b.ls_l_obs = (double*)(d + o_llo); b.X_aux = (double*)(d + o_x);
-    b.stream = (void*)lm->ctx->stream;
-    lm->part = (uint32_t*)(d + o_part);
-    lm->part_words = part_words;
-    lm->zero_bytes = zero_bytes;
-    lm->n_map_kf = m->n_map_kf; lm->npt = m->points.n; lm->nls = m->lines.n;
-    lm->n_pt_obs = m->points.n_obs; lm->n_ls_obs = m->lines.n_obs;
+    if ((rc = lm->pin.reserve(lm->lay.pin_bytes))) return rc;
+    local_map_fill_buffers(lm->d, lm->lay, lm->buf.as<char>(), (void*)s);
+    PLSLAM_REQUIRE(lm->pin.dev, PLSLAM_ENOTSUP);               // the counters are written where the host reads them
+    StreamSyncOnError guard(s);
+    const int32_t nk = map->n_map_kf;
+    int32_t* h = lm->pin.as<int32_t>();
+    if (row) memcpy(h + C_WORDS, row, (size_t)nk * 4);
+    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->d.kf_local, 0, lm->lay.zero_bytes, s));
+    if (row) PLSLAM_HIP_CHECK(hipMemcpyAsync(lm->at<int32_t>(LM_ROW), h + C_WORDS, (size_t)nk * 4, hipMemcpyHostToDevice, s));
+    set_flags(s);
+    const Publish pub{lm->cnt() + C_FORM_DONE, lm->cnt(), lm->pinned_dev(), 3};
+    hipLaunchKernelGGL(k_lm_count_flags, dim3(map_tiles((int64_t)nk + map->points.n + map->lines.n)), dim3(MAP_TILE), 0, s,
+                       (const uint8_t*)lm->d.kf_local, nk, (const uint8_t*)lm->d.pt_local, map->points.n, (const uint8_t*)lm->d.ls_local,
+                       map->lines.n, lm->cnt(), pub);
+    PLSLAM_HIP_CHECK(hipGetLastError());
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    guard.dismiss();
+    lm->st.end_form(h, counts);
     return PLSLAM_OK;
-}
-
-bool same_map(const plslam_local_map* lm, const plslam_map_index* m)
-{
-    return lm->formed && lm->n_map_kf == m->n_map_kf && lm->npt == m->points.n && lm->nls == m->lines.n &&
-           lm->n_pt_obs == m->points.n_obs && lm->n_ls_obs == m->lines.n_obs;
 }
 
 }  // namespace
@@ -412,47 +390,36 @@ void plslam_local_map_destroy(plslam_local_map* lm)
 int plslam_local_map_form(plslam_local_map* lm, const plslam_map_index* map, int32_t anchor_kf, const int32_t* row,
                           int32_t min_lm_cov_graph, int32_t min_kf_local_map, plslam_local_map_counts* counts)
 {
-    PLSLAM_REQUIRE(lm && map_ok(map) && row && counts && anchor_kf >= 0 && anchor_kf < map->n_map_kf, PLSLAM_EINVAL);
-    std::lock_guard<std::mutex> lk(lm->ctx->mu);
-    DeviceGuard dg_(lm->ctx->device);
-    hipStream_t s = lm->ctx->stream;
-    lm->formed = lm->gathered = lm->applied = false;
-    int rc = lm_layout(lm, map);
-    if (rc) return rc;
-    PLSLAM_REQUIRE(lm->pin.dev, PLSLAM_ENOTSUP);               // the counters are written where the host reads them
-    StreamSyncOnError guard(s);
-    const int32_t nk = map->n_map_kf;
-    int32_t* h = lm->pin.as<int32_t>();
-    memcpy(h + C_WORDS, row, (size_t)nk * 4);
-    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->d.kf_local, 0, lm->zero_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(lm->row, h + C_WORDS, (size_t)nk * 4, hipMemcpyHostToDevice, s));
-    const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
-    hipLaunchKernelGGL(k_lm_kf_flags, dim3(map_tiles(nk)), dim3(MAP_TILE), 0, s, nk, anchor_kf, map->kf_valid, (const int32_t*)lm->row,
-                       min_lm_cov_graph, min_kf_local_map, lm->d.kf_local);
-    const int64_t nfeat = (int64_t)P.n_feat + L.n_feat;
-    if (nfeat > 0)
-        hipLaunchKernelGGL(k_lm_feat_flags, dim3(map_tiles(nfeat)), dim3(MAP_TILE), 0, s, nk, (const uint8_t*)lm->d.kf_local, P, L,
-                           lm->d.pt_local, lm->d.ls_local);
-    const Publish pub{lm->cnt + C_FORM_DONE, lm->cnt, (int32_t*)lm->pin.dev, 3};
-    hipLaunchKernelGGL(k_lm_count_flags, dim3(map_tiles((int64_t)nk + P.n + L.n)), dim3(MAP_TILE), 0, s, (const uint8_t*)lm->d.kf_local, nk,
-                       (const uint8_t*)lm->d.pt_local, P.n, (const uint8_t*)lm->d.ls_local, L.n, lm->cnt, pub);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    memset(lm->h_cnt, 0, sizeof lm->h_cnt);
-    for (int k = C_KF_LOCAL; k <= C_LS_LOCAL; ++k) lm->h_cnt[k] = h[k];
-    counts->n_kf_local = h[C_KF_LOCAL]; counts->n_pt_local = h[C_PT_LOCAL]; counts->n_ls_local = h[C_LS_LOCAL];
-    lm->formed = true;
-    return PLSLAM_OK;
+    PLSLAM_REQUIRE(lm && !LocalMapState::check_form(map, anchor_kf, row, counts), PLSLAM_EINVAL);
+    return form(lm, map, row, counts, [=](hipStream_t s) {
+        const int32_t nk = map->n_map_kf;
+        const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
+        hipLaunchKernelGGL(k_lm_kf_flags, dim3(map_tiles(nk)), dim3(MAP_TILE), 0, s, nk, anchor_kf, map->kf_valid,
+                           (const int32_t*)lm->at<int32_t>(LM_ROW), min_lm_cov_graph, min_kf_local_map, lm->d.kf_local);
+        const int64_t nfeat = (int64_t)P.n_feat + L.n_feat;
+        if (nfeat > 0)
+            hipLaunchKernelGGL(k_lm_feat_flags, dim3(map_tiles(nfeat)), dim3(MAP_TILE), 0, s, nk, (const uint8_t*)lm->d.kf_local, P, L,
+                               lm->d.pt_local, lm->d.ls_local);
+    });
+}
+
+int plslam_local_map_form_all(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts)
+{
+    PLSLAM_REQUIRE(lm && !LocalMapState::check_form_all(map, counts), PLSLAM_EINVAL);
+    return form(lm, map, nullptr, counts, [=](hipStream_t s) {
+        const int32_t nk = map->n_map_kf, npt = map->points.n, nls = map->lines.n;
+        hipLaunchKernelGGL(k_lm_all_flags, dim3(map_tiles((int64_t)nk + npt + nls)), dim3(MAP_TILE), 0, s, nk, map->kf_valid, npt,
+                           (const uint8_t*)map->points.valid, nls, (const uint8_t*)map->lines.valid, lm->d.kf_local, lm->d.pt_local,
+                           lm->d.ls_local);
+    });
 }
 
 int plslam_local_map_candidates(plslam_local_map* lm, const plslam_map_index* map, int32_t kf2_idx)
 {
-    PLSLAM_REQUIRE(lm && map_ok(map), PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && !lm->st.check_candidates(map), PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
     const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
     if ((int64_t)P.n + L.n == 0) return PLSLAM_OK;
     StreamSyncOnError guard(s);
@@ -466,145 +433,99 @@ int plslam_local_map_candidates(plslam_local_map* lm, const plslam_map_index* ma
 
 int plslam_local_map_gather(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts)
 {
-    PLSLAM_REQUIRE(lm && map_ok(map) && counts, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && !lm->st.check_gather(map, counts), PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
-    lm->gathered = lm->applied = false;
+    lm->st.begin_gather();
     StreamSyncOnError guard(s);
     const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
     const int32_t nk = map->n_map_kf;
-    const unsigned wk = map_tiles(nk), wp = map_tiles(P.n), wl = map_tiles(L.n);
-    uint32_t *part_k = lm->part, *part_pn = part_k + wk, *part_po = part_pn + wp, *part_ln = part_po + wp, *part_lo = part_ln + wl;
-    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->part, 0, lm->part_words * 4, s));
-    hipLaunchKernelGGL(k_lm_compact_kf, dim3(wk), dim3(MAP_TILE), 0, s, nk, map->kf_valid, (const uint8_t*)lm->d.kf_local, map->x_kf_w,
-                       lm->d.kf_list, lm->kf_inv, lm->d.X_aux, lm->cnt, part_k);
-    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wp), dim3(MAP_TILE), 0, s, P, 0, (const uint8_t*)lm->d.pt_local, lm->d.pt_list, lm->pt_off,
-                       lm->d.X_aux, lm->cnt, part_pn, part_po);
-    hipLaunchKernelGGL(k_lm_compact_lm, dim3(wl), dim3(MAP_TILE), 0, s, L, 1, (const uint8_t*)lm->d.ls_local, lm->d.ls_list, lm->ls_off,
-                       lm->d.X_aux, lm->cnt, part_ln, part_lo);
-    const ExpandOut op{lm->d.pt_obs, lm->d.pt_lm_loc, lm->d.pt_kf_loc, lm->d.pt_pose_slot, lm->d.pt_obs_uv, lm->d.pt_list, lm->pt_off};
-    const ExpandOut ol{lm->d.ls_obs, lm->d.ls_lm_loc, lm->d.ls_kf_loc, lm->d.ls_pose_slot, lm->d.ls_l_obs, lm->d.ls_list, lm->ls_off};
+    const LocalMapLayout& Y = lm->lay;
+    int32_t *kf_inv = lm->at<int32_t>(LM_KF_INV), *pt_off = lm->at<int32_t>(LM_PT_OFF), *ls_off = lm->at<int32_t>(LM_LS_OFF), *cnt = lm->cnt();
+    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->at<uint32_t>(LM_PART), 0, Y.part_words * 4, s));
+    hipLaunchKernelGGL(k_lm_compact_kf, dim3((unsigned)Y.chain_words[LM_CHAIN_KF]), dim3(MAP_TILE), 0, s, nk, map->kf_valid,
+                       (const uint8_t*)lm->d.kf_local, map->x_kf_w, lm->d.kf_list, kf_inv, lm->d.X_aux, cnt, lm->chain(LM_CHAIN_KF));
+    hipLaunchKernelGGL(k_lm_compact_lm, dim3((unsigned)Y.chain_words[LM_CHAIN_PT]), dim3(MAP_TILE), 0, s, P, 0, (const uint8_t*)lm->d.pt_local,
+                       lm->d.pt_list, pt_off, lm->d.X_aux, cnt, lm->chain(LM_CHAIN_PT), lm->chain(LM_CHAIN_PT_OBS));
+    hipLaunchKernelGGL(k_lm_compact_lm, dim3((unsigned)Y.chain_words[LM_CHAIN_LS]), dim3(MAP_TILE), 0, s, L, 1, (const uint8_t*)lm->d.ls_local,
+                       lm->d.ls_list, ls_off, lm->d.X_aux, cnt, lm->chain(LM_CHAIN_LS), lm->chain(LM_CHAIN_LS_OBS));
+    const ExpandOut op{lm->d.pt_obs, lm->d.pt_lm_loc, lm->d.pt_kf_loc, lm->d.pt_pose_slot, lm->d.pt_obs_uv, lm->d.pt_list, pt_off};
+    const ExpandOut ol{lm->d.ls_obs, lm->d.ls_lm_loc, lm->d.ls_kf_loc, lm->d.ls_pose_slot, lm->d.ls_l_obs, lm->d.ls_list, ls_off};
     hipLaunchKernelGGL(k_lm_expand, dim3(map_tiles((int64_t)P.n_obs + L.n_obs)), dim3(MAP_TILE), 0, s, P, L, op, ol, nk,
-                       (const int32_t*)lm->kf_inv, (const int32_t*)lm->cnt, (int32_t*)lm->pin.dev);
+                       (const int32_t*)kf_inv, (const int32_t*)cnt, lm->pinned_dev());
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
-    const int32_t* h = lm->pin.as<int32_t>();
-    for (int k = C_NKF; k <= C_LS_OBS; ++k) lm->h_cnt[k] = h[k];
-    counts->nkf = h[C_NKF]; counts->npt = h[C_NPT]; counts->nls = h[C_NLS];
-    counts->n_pt_obs = h[C_PT_OBS]; counts->n_ls_obs = h[C_LS_OBS];
-    counts->empty = (int64_t)h[C_PT_OBS] + h[C_LS_OBS] == 0;
-    lm->gathered = true;
+    lm->st.end_gather(lm->pin.as<int32_t>(), counts);
     return PLSLAM_OK;
 }
 
 int plslam_local_map_cull(plslam_local_map* lm, const plslam_map_index* map, int32_t max_kf_idx, int32_t min_lm_obs,
                           plslam_local_map_counts* counts)
 {
-    PLSLAM_REQUIRE(lm && map_ok(map) && counts, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && !lm->st.check_cull(map, counts), PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    PLSLAM_REQUIRE(same_map(lm, map), PLSLAM_EINVAL);
     const MapKindSrc P = map_kind_src(map->points, 0), L = map_kind_src(map->lines, 1);
-    counts->n_pt_removed = counts->n_ls_removed = 0;
-    lm->h_cnt[C_PT_REM] = lm->h_cnt[C_LS_REM] = 0;
+    lm->st.begin_cull(counts);
     if ((int64_t)P.n + L.n == 0) return PLSLAM_OK;
     StreamSyncOnError guard(s);
     // (the two counts and the ticket: C_PT_REM, C_LS_REM ... C_CULL_DONE are consecutive words)
-    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->cnt + C_PT_REM, 0, (C_CULL_DONE - C_PT_REM + 1) * 4, s));
-    const Publish pub{lm->cnt + C_CULL_DONE, lm->cnt + C_PT_REM, (int32_t*)lm->pin.dev + C_PT_REM, 2};
+    int32_t* cnt = lm->cnt();
+    PLSLAM_HIP_CHECK(hipMemsetAsync(cnt + C_PT_REM, 0, (C_CULL_DONE - C_PT_REM + 1) * 4, s));
+    const Publish pub{cnt + C_CULL_DONE, cnt + C_PT_REM, lm->pinned_dev() + C_PT_REM, 2};
     hipLaunchKernelGGL(k_lm_cull, dim3(map_tiles((int64_t)P.n + L.n)), dim3(MAP_TILE), 0, s, P, L,
                        CullKind{map->points.valid, map->points.feat_idx, lm->d.pt_removed},
                        CullKind{map->lines.valid, map->lines.feat_idx, lm->d.ls_removed}, map->n_map_kf, map->kf_valid,
-                       (const uint8_t*)lm->d.pt_local, (const uint8_t*)lm->d.ls_local, max_kf_idx, min_lm_obs, lm->cnt + C_PT_REM, pub);
+                       (const uint8_t*)lm->d.pt_local, (const uint8_t*)lm->d.ls_local, max_kf_idx, min_lm_obs, cnt + C_PT_REM, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
-    const int32_t* h = lm->pin.as<int32_t>();
-    counts->n_pt_removed = lm->h_cnt[C_PT_REM] = h[C_PT_REM];
-    counts->n_ls_removed = lm->h_cnt[C_LS_REM] = h[C_LS_REM];
+    lm->st.end_cull(lm->pin.as<int32_t>(), counts);
     return PLSLAM_OK;
 }
 
 int plslam_local_map_apply_lba(plslam_local_map* lm, plslam_lba_plan* plan, const plslam_local_map_lba_dst* dst, double moved_th,
                                plslam_local_map_counts* counts)
 {
-    PLSLAM_REQUIRE(lm && plan && dst && counts && plan->ctx == lm->ctx, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && plan && !lm->st.check_apply_lba(plan->ctx == lm->ctx, plan->npt, plan->nls, plan->state_valid, dst, counts),
+                   PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    PLSLAM_REQUIRE(lm->formed && lm->gathered, PLSLAM_EINVAL);
-    const int32_t npt_l = lm->h_cnt[C_NPT], nls_l = lm->h_cnt[C_NLS];
-    PLSLAM_REQUIRE(plan->npt == npt_l && plan->nls == nls_l && plan->state_valid, PLSLAM_EINVAL);
-    PLSLAM_REQUIRE((npt_l == 0 || (dst->pt_X && dst->pt_inlier)) && (nls_l == 0 || (dst->ls_X && dst->ls_inlier)), PLSLAM_EINVAL);
-    counts->n_pt_moved = counts->n_ls_moved = 0;
-    lm->h_cnt[C_PT_MOVED] = lm->h_cnt[C_LS_MOVED] = 0;
-    lm->applied = true;
+    const int32_t npt_l = lm->st.h_cnt[C_NPT], nls_l = lm->st.h_cnt[C_NLS];
+    lm->st.begin_apply_lba(counts);
     if ((int64_t)npt_l + nls_l == 0) return PLSLAM_OK;
     StreamSyncOnError guard(s);
     // (the two counts and the ticket: C_PT_MOVED, C_LS_MOVED, C_APPLY_DONE are consecutive words)
-    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->cnt + C_PT_MOVED, 0, (C_APPLY_DONE - C_PT_MOVED + 1) * 4, s));
-    const ApplyKind P{lm->d.pt_list, plan->x.Xw, dst->pt_X, dst->pt_inlier, lm->d.pt_moved, npt_l, lm->npt};
-    const ApplyKind L{lm->d.ls_list, plan->x.Lw, dst->ls_X, dst->ls_inlier, lm->d.ls_moved, nls_l, lm->nls};
-    const Publish pub{lm->cnt + C_APPLY_DONE, lm->cnt + C_PT_MOVED, (int32_t*)lm->pin.dev + C_PT_MOVED, 2};
-    hipLaunchKernelGGL(k_lm_apply_lba<true>, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, moved_th, lm->cnt + C_PT_MOVED, pub);
+    int32_t* cnt = lm->cnt();
+    PLSLAM_HIP_CHECK(hipMemsetAsync(cnt + C_PT_MOVED, 0, (C_APPLY_DONE - C_PT_MOVED + 1) * 4, s));
+    const ApplyKind P{lm->d.pt_list, plan->x.Xw, dst->pt_X, dst->pt_inlier, lm->d.pt_moved, npt_l, lm->st.z.npt};
+    const ApplyKind L{lm->d.ls_list, plan->x.Lw, dst->ls_X, dst->ls_inlier, lm->d.ls_moved, nls_l, lm->st.z.nls};
+    const Publish pub{cnt + C_APPLY_DONE, cnt + C_PT_MOVED, lm->pinned_dev() + C_PT_MOVED, 2};
+    hipLaunchKernelGGL(k_lm_apply_lba<true>, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, moved_th, cnt + C_PT_MOVED, pub);
     PLSLAM_HIP_CHECK(hipGetLastError());
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
-    const int32_t* h = lm->pin.as<int32_t>();
-    counts->n_pt_moved = lm->h_cnt[C_PT_MOVED] = h[C_PT_MOVED];
-    counts->n_ls_moved = lm->h_cnt[C_LS_MOVED] = h[C_LS_MOVED];
-    return PLSLAM_OK;
-}
-
-int plslam_local_map_form_all(plslam_local_map* lm, const plslam_map_index* map, plslam_local_map_counts* counts)
-{
-    PLSLAM_REQUIRE(lm && map_ok(map) && counts, PLSLAM_EINVAL);
-    std::lock_guard<std::mutex> lk(lm->ctx->mu);
-    DeviceGuard dg_(lm->ctx->device);
-    hipStream_t s = lm->ctx->stream;
-    lm->formed = lm->gathered = lm->applied = false;
-    int rc = lm_layout(lm, map);
-    if (rc) return rc;
-    PLSLAM_REQUIRE(lm->pin.dev, PLSLAM_ENOTSUP);               // the counters are written where the host reads them
-    StreamSyncOnError guard(s);
-    const int32_t nk = map->n_map_kf, npt = map->points.n, nls = map->lines.n;
-    PLSLAM_HIP_CHECK(hipMemsetAsync(lm->d.kf_local, 0, lm->zero_bytes, s));
-    const unsigned tiles = map_tiles((int64_t)nk + npt + nls);
-    hipLaunchKernelGGL(k_lm_all_flags, dim3(tiles), dim3(MAP_TILE), 0, s, nk, map->kf_valid, npt, (const uint8_t*)map->points.valid, nls,
-                       (const uint8_t*)map->lines.valid, lm->d.kf_local, lm->d.pt_local, lm->d.ls_local);
-    const Publish pub{lm->cnt + C_FORM_DONE, lm->cnt, (int32_t*)lm->pin.dev, 3};
-    hipLaunchKernelGGL(k_lm_count_flags, dim3(tiles), dim3(MAP_TILE), 0, s, (const uint8_t*)lm->d.kf_local, nk,
-                       (const uint8_t*)lm->d.pt_local, npt, (const uint8_t*)lm->d.ls_local, nls, lm->cnt, pub);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    guard.dismiss();
-    const int32_t* h = lm->pin.as<int32_t>();
-    memset(lm->h_cnt, 0, sizeof lm->h_cnt);
-    for (int k = C_KF_LOCAL; k <= C_LS_LOCAL; ++k) lm->h_cnt[k] = h[k];
-    counts->n_kf_local = h[C_KF_LOCAL]; counts->n_pt_local = h[C_PT_LOCAL]; counts->n_ls_local = h[C_LS_LOCAL];
-    lm->formed = true;
+    lm->st.end_apply_lba(lm->pin.as<int32_t>(), counts);
     return PLSLAM_OK;
 }
 
 int plslam_local_map_apply_gba(plslam_local_map* lm, plslam_gba_plan* plan, const plslam_local_map_lba_dst* dst)
 {
-    PLSLAM_REQUIRE(lm && plan && dst && plan->ctx == lm->ctx && plan->lba, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && plan && plan->lba && !lm->st.check_apply_gba(plan->ctx == lm->ctx, plan->npt, plan->nls, plan->optimized, dst),
+                   PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
     hipStream_t s = lm->ctx->stream;
-    PLSLAM_REQUIRE(lm->formed && lm->gathered, PLSLAM_EINVAL);
-    const int32_t npt_l = lm->h_cnt[C_NPT], nls_l = lm->h_cnt[C_NLS];
-    PLSLAM_REQUIRE(plan->npt == npt_l && plan->nls == nls_l && plan->optimized, PLSLAM_EINVAL);
-    PLSLAM_REQUIRE((npt_l == 0 || dst->pt_X) && (nls_l == 0 || dst->ls_X), PLSLAM_EINVAL);
+    const int32_t npt_l = lm->st.h_cnt[C_NPT], nls_l = lm->st.h_cnt[C_NLS];
     if ((int64_t)npt_l + nls_l == 0) return PLSLAM_OK;
     StreamSyncOnError guard(s);
     const plslam_lba_plan* P_ = plan->lba;
-    const ApplyKind P{lm->d.pt_list, P_->x.Xw, dst->pt_X, nullptr, nullptr, npt_l, lm->npt};
-    const ApplyKind L{lm->d.ls_list, P_->x.Lw, dst->ls_X, nullptr, nullptr, nls_l, lm->nls};
+    const ApplyKind P{lm->d.pt_list, P_->x.Xw, dst->pt_X, nullptr, nullptr, npt_l, lm->st.z.npt};
+    const ApplyKind L{lm->d.ls_list, P_->x.Lw, dst->ls_X, nullptr, nullptr, nls_l, lm->st.z.nls};
     hipLaunchKernelGGL(k_lm_apply_lba<false>, dim3(map_tiles((int64_t)npt_l + nls_l)), dim3(MAP_TILE), 0, s, P, L, 0.0, (int32_t*)nullptr,
                        Publish{nullptr, nullptr, nullptr, 0});
     PLSLAM_HIP_CHECK(hipGetLastError());
@@ -615,34 +536,21 @@ int plslam_local_map_apply_gba(plslam_local_map* lm, plslam_gba_plan* plan, cons
 
 int plslam_local_map_device_buffers(plslam_local_map* lm, plslam_local_map_buffers* out)
 {
-    PLSLAM_REQUIRE(lm && out && lm->formed, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && !lm->st.check_device_buffers(out), PLSLAM_EINVAL);
     *out = lm->d;
     return PLSLAM_OK;
 }
 
 int plslam_local_map_download(plslam_local_map* lm, const plslam_local_map_buffers* host)
 {
-    PLSLAM_REQUIRE(lm && host && lm->formed, PLSLAM_EINVAL);
-    const bool lists = host->kf_list || host->pt_list || host->ls_list || host->pt_obs || host->ls_obs || host->pt_lm_loc ||
-                       host->pt_kf_loc || host->pt_pose_slot || host->ls_lm_loc || host->ls_kf_loc || host->ls_pose_slot ||
-                       host->pt_obs_uv || host->ls_l_obs || host->X_aux;
-    PLSLAM_REQUIRE(!lists || lm->gathered, PLSLAM_EINVAL);
-    PLSLAM_REQUIRE((!host->pt_moved && !host->ls_moved) || lm->applied, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(lm && !lm->st.check_download(host), PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(lm->ctx->mu);
     DeviceGuard dg_(lm->ctx->device);
-    const plslam_local_map_buffers& d = lm->d;
-    const int32_t* c = lm->h_cnt;
-    const size_t nkf = (size_t)c[C_NKF], npt = (size_t)c[C_NPT], nls = (size_t)c[C_NLS], po = (size_t)c[C_PT_OBS], lo = (size_t)c[C_LS_OBS];
-    const DownloadItem items[] = {
-        {host->kf_local, d.kf_local, (size_t)lm->n_map_kf}, {host->pt_local, d.pt_local, (size_t)lm->npt},
-        {host->ls_local, d.ls_local, (size_t)lm->nls}, {host->pt_candidate, d.pt_candidate, (size_t)lm->npt},
-        {host->ls_candidate, d.ls_candidate, (size_t)lm->nls}, {host->pt_removed, d.pt_removed, (size_t)lm->npt},
-        {host->ls_removed, d.ls_removed, (size_t)lm->nls}, {host->kf_list, d.kf_list, nkf * 4}, {host->pt_list, d.pt_list, npt * 4},
-        {host->ls_list, d.ls_list, nls * 4}, {host->pt_obs, d.pt_obs, po * 24}, {host->ls_obs, d.ls_obs, lo * 24},
-        {host->pt_lm_loc, d.pt_lm_loc, po * 4}, {host->pt_kf_loc, d.pt_kf_loc, po * 4}, {host->pt_pose_slot, d.pt_pose_slot, po * 4},
-        {host->ls_lm_loc, d.ls_lm_loc, lo * 4}, {host->ls_kf_loc, d.ls_kf_loc, lo * 4}, {host->ls_pose_slot, d.ls_pose_slot, lo * 4},
-        {host->pt_obs_uv, d.pt_obs_uv, po * 16}, {host->ls_l_obs, d.ls_l_obs, lo * 24},
-        {host->X_aux, d.X_aux, (6 * nkf + 3 * npt + 6 * nls) * 8}, {host->pt_moved, d.pt_moved, npt}, {host->ls_moved, d.ls_moved, nls}};
+    DownloadItem items[LOCAL_MAP_N_BUFFERS];
+    for (int i = 0; i < LOCAL_MAP_N_BUFFERS; ++i) {
+        const LocalMapBuffer& e = LOCAL_MAP_BUFFERS[i];
+        items[i] = DownloadItem{local_map_buffer_get(*host, e), local_map_buffer_get(lm->d, e), lm->st.download_bytes(e)};
+    }
     return download_items(items, lm->ctx->stream);
 }
 

@@ -10,9 +10,7 @@
 
 namespace plslam {
 
-constexpr int MAP_TILE = 256;           // lanes per workgroup = items per look-back tile (plslam_amd/local_map.py: LOOKBACK_TILE)
-constexpr int MAP_NW = MAP_TILE / 64;
-inline unsigned map_tiles(int64_t n) { return (unsigned)(n > 0 ? (n + MAP_TILE - 1) / MAP_TILE : 1); }
+constexpr int MAP_NW = MAP_TILE / 64;   // waves per workgroup (MAP_TILE and map_tiles: map_image.hpp, shared with the host planners)
 
 struct MapKindSrc {                     // one landmark kind of an image a kernel READS
     int32_t n, n_obs, n_feat, dl, dv;   // dl: doubles per landmark / feature position (3 / 6), dv: doubles per observation (2 / 3)

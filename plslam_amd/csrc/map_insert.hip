@@ -15,11 +15,15 @@
 // Every output is an integer, a flag, a verbatim copy of a double or a fixed-order fp64 expression of correctly rounded
 // operations: bit-exact against the sequential restatement (tests/map_insert_ref.py).  Every index read from the image or a
 // table is range-checked before it is used as an address.
+// The host decisions -- the argument checks, the growth bounds, the launch geometry, the layout of the handle's buffer, the packing
+// of the staged block -- are map_insert_plan.hpp (no HIP in it; tests/cpp/test_map_insert_plan.cpp); the commit the insert shares
+// with the landmark fusion is map_image.hpp's.
 #include <cstring>
 
 #include "common.hpp"
 #include "lookback_dev.hpp"
 #include "map_image_dev.hpp"
+#include "map_insert_plan.hpp"
 #include "map_lists_plan.hpp"
 #include "se3_dev.hpp"
 
@@ -28,8 +32,8 @@ namespace {
 
 constexpr unsigned MI_MAX_GRID = 4096;  // K66 strides over its items
 // the call counters (device words, mirrored in the page-locked block): four per kind
-enum { W_EV = 0, W_NEW, W_PAIRS, W_OBS, W_KIND = 4, W_WORDS = 8 };
-enum { MODE_KF2KF = 0, MODE_MAP2KF = 1 };
+enum { W_EV = 0, W_NEW, W_PAIRS, W_OBS, W_KIND = 4, W_WORDS = MAP_INSERT_COUNTER_WORDS };
+enum { MODE_KF2KF = MAP_INSERT_KF2KF, MODE_MAP2KF = MAP_INSERT_MAP2KF };
 
 struct CallD {                          // one kind's tables and scratch (device), carved from the handle's buffer
     int32_t mode, lines, n_map_kf, kf1, kf2, n_tab, n_prev, n_curr, e_cap;
@@ -268,13 +272,6 @@ k_mi_publish(const int32_t* __restrict__ cnt, const int32_t* __restrict__ row_de
     for (int32_t i = (int32_t)threadIdx.x; i < W_WORDS + n_map_kf; i += MAP_TILE) pinned[i] = i < W_WORDS ? cnt[i] : row_delta[i - W_WORDS];
 }
 
-bool kind_args_ok(const plslam_map_insert_kind* k, int mode)
-{
-    if (!k || !k->table || k->n_table == 0) return !k || k->n_table >= 0;
-    if (k->n_table < 0 || k->n_curr < 0 || (k->n_curr > 0 && (!k->P2 || !k->obs2))) return false;
-    return mode == MODE_MAP2KF || (k->n_prev >= 0 && (k->n_prev == 0 || (k->P1 && k->obs1)));
-}
-
 }  // namespace
 }  // namespace plslam
 
@@ -292,141 +289,76 @@ struct plslam_map_insert {
 
 namespace {
 
-struct KindPlan {                                // one kind of one call, host side
-    const plslam_map_insert_kind* in = nullptr;  // nullptr: no table
-    int32_t n_tab = 0, n_prev = 0, n_curr = 0, m = 0, dl = 3, dv = 2;
-    size_t o_tab, o_P1, o_o1, o_P2, o_o2;        // in the staged block
-    size_t o_i1lm, o_ev, o_dir, o_pair, o_new, o_app, o_head, o_win, o_part, o_osrc;
-    unsigned w_tab = 1, w_lm = 1;
-};
+// one kind's tables and scratch: every slice of the plan's layout as the typed pointer the kernels take
+CallD call_of(const MapInsertPlan& P, int k, char* d)
+{
+    const MapInsertKindPlan& K = P.k[k];
+    CallD C{};
+    C.mode = P.mode; C.lines = k; C.n_map_kf = P.nk; C.kf1 = P.kf1; C.kf2 = P.kf2;
+    C.n_tab = K.n_tab; C.n_prev = K.n_prev; C.n_curr = K.n_curr; C.e_cap = K.m;
+    C.T = slice_at<double>(d, P.o_T); C.tab = slice_at<int32_t>(d, K.o_tab);
+    C.P1 = slice_at<double>(d, K.o_P1); C.o1 = slice_at<double>(d, K.o_o1);
+    C.P2 = slice_at<double>(d, K.o_P2); C.o2 = slice_at<double>(d, K.o_o2);
+    C.i1_lm = slice_at<int32_t>(d, K.o_i1lm); C.ev = slice_at<int32_t>(d, K.o_ev); C.pair_off = slice_at<int32_t>(d, K.o_pair);
+    C.new_ev = slice_at<int32_t>(d, K.o_new); C.app_cnt = slice_at<int32_t>(d, K.o_app); C.head = slice_at<int32_t>(d, K.o_head);
+    C.feat_win = slice_at<int32_t>(d, K.o_win); C.cnt = slice_at<int32_t>(d, P.o_cnt) + W_KIND * k; C.ev_dir = slice_at<double>(d, K.o_dir);
+    C.obs_src = slice_at<int32_t>(d, K.o_osrc);
+    return C;
+}
 
 int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_map_insert_dst* dst, int32_t kf1, int32_t kf2,
            const double* T1, const double* T2, const plslam_map_insert_kind* points, const plslam_map_insert_kind* lines,
            int32_t* row_delta, plslam_map_insert_counts* counts)
 {
-    // ---- validate everything, then commit once ----
-    PLSLAM_REQUIRE(mi && src && dst && T2 && row_delta && counts && (mode == MODE_MAP2KF || T1), PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(src->n_map_kf >= 1 && src->kf_valid && src->x_kf_w && map_src_kind_ok(src->points) && map_src_kind_ok(src->lines),
-                   PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(kf2 >= 0 && kf2 < src->n_map_kf && (mode == MODE_MAP2KF || (kf1 >= 0 && kf1 < src->n_map_kf && kf1 != kf2)),
-                   PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(dst->map.kf_valid && dst->map.x_kf_w && map_dst_kind_ok(dst->map.points, src->points) &&
-                       map_dst_kind_ok(dst->map.lines, src->lines) && kind_args_ok(points, mode) && kind_args_ok(lines, mode),
-                   PLSLAM_EINVAL);
+    // ---- validate everything (map_insert_plan.hpp), then commit once ----
+    PLSLAM_REQUIRE(mi && row_delta && counts, PLSLAM_EINVAL);
+    MapInsertPlan P;
+    int rc = map_insert_plan(mode, src, dst, kf1, kf2, T1, T2, points, lines, &P);
+    if (rc) {
+        set_last_error("plslam_map_insert: refused: %s", P.why);
+        return rc;
+    }
     const plslam_map_landmarks* S[2] = {&src->points, &src->lines};
+    plslam_map_landmarks* Dk[2] = {&dst->map.points, &dst->map.lines};
     const int32_t cap[2] = {dst->pt_cap, dst->ls_cap}, obs_cap[2] = {dst->pt_obs_cap, dst->ls_obs_cap};
-    KindPlan K[2];
-    K[0].in = points && points->table && points->n_table > 0 ? points : nullptr;
-    K[1].in = lines && lines->table && lines->n_table > 0 ? lines : nullptr;
-    K[1].dl = 6; K[1].dv = 3;
-    for (int k = 0; k < 2; ++k) {
-        KindPlan& P = K[k];
-        if (P.in) {
-            P.n_tab = P.in->n_table; P.n_prev = mode == MODE_KF2KF ? P.in->n_prev : 0; P.n_curr = P.in->n_curr;
-            PLSLAM_REQUIRE(mode == MODE_KF2KF || P.n_tab <= S[k]->n, PLSLAM_EINVAL);
-            PLSLAM_REQUIRE(mode == MODE_MAP2KF || P.n_tab <= PLSLAM_MAP_INSERT_MAX_TABLE, PLSLAM_ERANGE);
-            for (int32_t i = 0; i < P.n_tab; ++i) P.m += P.in->table[i] >= 0;
-        }
-        const int64_t need_lm = (int64_t)S[k]->n + (mode == MODE_KF2KF ? P.m : 0);
-        const int64_t need_obs = (int64_t)S[k]->n_obs + (mode == MODE_KF2KF ? 2 : 1) * (int64_t)P.m;
-        PLSLAM_REQUIRE(cap[k] >= need_lm && obs_cap[k] >= need_obs && need_obs < (1 << 30), PLSLAM_ERANGE);
-    }
-    const int32_t nk = src->n_map_kf;
-    // ---- the layout: [zeroed: counters, row_delta, per kind app_cnt / feat_win / part] [0x7f: head] [staged] [the rest] ----
-    Carver c;
-    const size_t o_cnt = c.take(W_WORDS * 4), o_row = c.take((size_t)nk * 4);
-    for (int k = 0; k < 2; ++k) {
-        KindPlan& P = K[k];
-        P.w_tab = map_tiles(P.n_tab); P.w_lm = map_tiles((int64_t)S[k]->n + P.m);
-        P.o_app = c.take((size_t)S[k]->n * 4 + 4); P.o_win = c.take((size_t)P.n_curr * 4 + 4);
-        P.o_part = c.take((3 * (size_t)P.w_tab + P.w_lm) * 4);
-    }
-    const size_t zero_bytes = c.off;
-    for (int k = 0; k < 2; ++k) K[k].o_head = c.take((size_t)S[k]->n * 4 + 4);
-    const size_t head_off = zero_bytes, head_bytes = c.off - zero_bytes;
-    const size_t stage_off = c.off, o_T = c.take(32 * 8);
-    for (int k = 0; k < 2; ++k) {
-        KindPlan& P = K[k];
-        P.o_tab = c.take((size_t)P.n_tab * 4 + 4);
-        P.o_P1 = c.take((size_t)P.n_prev * P.dl * 8 + 8); P.o_o1 = c.take((size_t)P.n_prev * P.dv * 8 + 8);
-        P.o_P2 = c.take((size_t)P.n_curr * P.dl * 8 + 8); P.o_o2 = c.take((size_t)P.n_curr * P.dv * 8 + 8);
-    }
-    const size_t stage_bytes = c.off - stage_off;
-    for (int k = 0; k < 2; ++k) {
-        KindPlan& P = K[k];
-        P.o_i1lm = c.take((size_t)P.n_tab * 4 + 4); P.o_ev = c.take((size_t)P.m * 16 + 16); P.o_dir = c.take((size_t)P.m * 48 + 48);
-        P.o_pair = c.take((size_t)P.m * 4 + 4); P.o_new = c.take((size_t)P.m * 4 + 4);
-    }
-    for (int k = 0; k < 2; ++k)                                  // (behind everything else: the layout in front is unchanged)
-        K[k].o_osrc = c.take(((size_t)S[k]->n_obs + (mode == MODE_KF2KF ? 2 : 1) * (size_t)K[k].m) * 4 + 4);
+    const int32_t nk = P.nk;
     std::lock_guard<std::mutex> lk(mi->ctx->mu);
     DeviceGuard dg_(mi->ctx->device);
     hipStream_t s = mi->ctx->stream;
     mi->done = false;
     mi->lists.valid = false;
-    int rc = mi->buf.reserve(c.off + 256);
-    if (rc) return rc;
-    const size_t res_bytes = align256((W_WORDS + (size_t)nk) * 4);
-    if ((rc = mi->pin.reserve(res_bytes + stage_bytes))) return rc;
+    if ((rc = mi->buf.reserve(P.total + 256))) return rc;
+    if ((rc = mi->pin.reserve(P.res_bytes + P.stage_bytes))) return rc;
     PLSLAM_REQUIRE(mi->pin.dev, PLSLAM_ENOTSUP);                 // the counters are written where the host reads them
     char* d = mi->buf.as<char>();
-    char* h = mi->pin.as<char>();
-    char* hs = h + res_bytes - stage_off;                        // (the staged block's offsets are the device layout's)
-    memset(h + res_bytes, 0, stage_bytes);
-    if (T1) memcpy(hs + o_T, T1, 128);
-    memcpy(hs + o_T + 128, T2, 128);
-    for (int k = 0; k < 2; ++k) {
-        const KindPlan& P = K[k];
-        if (!P.in) continue;
-        memcpy(hs + P.o_tab, P.in->table, (size_t)P.n_tab * 4);
-        if (P.n_prev) {
-            memcpy(hs + P.o_P1, P.in->P1, (size_t)P.n_prev * P.dl * 8);
-            memcpy(hs + P.o_o1, P.in->obs1, (size_t)P.n_prev * P.dv * 8);
-        }
-        if (P.n_curr) {
-            memcpy(hs + P.o_P2, P.in->P2, (size_t)P.n_curr * P.dl * 8);
-            memcpy(hs + P.o_o2, P.in->obs2, (size_t)P.n_curr * P.dv * 8);
-        }
-    }
+    char* staged = mi->pin.as<char>() + P.res_bytes;
+    map_insert_pack(P, T1, T2, staged);
     StreamSyncOnError guard(s);
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d, 0, zero_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemsetAsync(d + head_off, 0x7f, head_bytes, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + stage_off, h + res_bytes, stage_bytes, hipMemcpyHostToDevice, s));
+    for (const FillRegion& f : P.fill) PLSLAM_HIP_CHECK(hipMemsetAsync(d + f.off, f.byte, f.bytes, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + P.stage_off, staged, P.stage_bytes, hipMemcpyHostToDevice, s));
     if (dst->map.kf_valid != src->kf_valid)
         PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)dst->map.kf_valid, src->kf_valid, (size_t)nk, hipMemcpyDeviceToDevice, s));
     if (dst->map.x_kf_w != src->x_kf_w)
         PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)dst->map.x_kf_w, src->x_kf_w, (size_t)nk * 48, hipMemcpyDeviceToDevice, s));
-    plslam_map_landmarks* Dk[2] = {&dst->map.points, &dst->map.lines};
-    int32_t* cnt = (int32_t*)(d + o_cnt);
-    int32_t* row = (int32_t*)(d + o_row);
+    int32_t* cnt = slice_at<int32_t>(d, P.o_cnt);
+    int32_t* row = slice_at<int32_t>(d, P.o_row);
+    MapCommitKind done[2];
     for (int k = 0; k < 2; ++k) {
-        const KindPlan& P = K[k];
+        const MapInsertKindPlan& K = P.k[k];
         const plslam_map_landmarks& A = *S[k];
         plslam_map_landmarks& B = *Dk[k];
         if (A.n_feat > 0 && B.feat_ptr != A.feat_ptr)
             PLSLAM_HIP_CHECK(hipMemcpyAsync((void*)B.feat_ptr, A.feat_ptr, ((size_t)nk + 1) * 4, hipMemcpyDeviceToDevice, s));
         const MapKindSrc Sd = map_kind_src(A, k);
         const MapKindDst Dd = map_kind_dst(B, cap[k], obs_cap[k]);
-        CallD C{};
-        C.mode = mode; C.lines = k; C.n_map_kf = nk; C.kf1 = mode == MODE_KF2KF ? kf1 : -1; C.kf2 = kf2;
-        C.n_tab = P.n_tab; C.n_prev = P.n_prev; C.n_curr = P.n_curr; C.e_cap = P.m;
-        C.T = (const double*)(d + o_T); C.tab = (const int32_t*)(d + P.o_tab);
-        C.P1 = (const double*)(d + P.o_P1); C.o1 = (const double*)(d + P.o_o1);
-        C.P2 = (const double*)(d + P.o_P2); C.o2 = (const double*)(d + P.o_o2);
-        C.i1_lm = (int32_t*)(d + P.o_i1lm); C.ev = (int32_t*)(d + P.o_ev); C.pair_off = (int32_t*)(d + P.o_pair);
-        C.new_ev = (int32_t*)(d + P.o_new); C.app_cnt = (int32_t*)(d + P.o_app); C.head = (int32_t*)(d + P.o_head);
-        C.feat_win = (int32_t*)(d + P.o_win); C.cnt = cnt + W_KIND * k; C.ev_dir = (double*)(d + P.o_dir);
-        C.obs_src = (int32_t*)(d + P.o_osrc);
-        uint32_t* part = (uint32_t*)(d + P.o_part);
-        hipLaunchKernelGGL(k_mi_events, dim3(P.w_tab), dim3(MAP_TILE), 0, s, Sd, C, part, part + P.w_tab, part + 2 * P.w_tab);
-        hipLaunchKernelGGL(k_mi_ptr, dim3(P.w_lm), dim3(MAP_TILE), 0, s, Sd, Dd, C, part + 3 * P.w_tab);
-        const int64_t n_out = (int64_t)A.n_obs + (mode == MODE_KF2KF ? 2 : 1) * (int64_t)P.m;
-        if (n_out > 0) hipLaunchKernelGGL(k_mi_obs, dim3(map_tiles(n_out)), dim3(MAP_TILE), 0, s, Sd, Dd, C);
-        const unsigned g = map_tiles((int64_t)A.n_feat + A.n_obs + P.m);
+        const CallD C = call_of(P, k, d);
+        uint32_t* part = slice_at<uint32_t>(d, K.o_part);
+        hipLaunchKernelGGL(k_mi_events, dim3(K.w_tab), dim3(MAP_TILE), 0, s, Sd, C, part, part + K.w_tab, part + 2 * K.w_tab);
+        hipLaunchKernelGGL(k_mi_ptr, dim3(K.w_lm), dim3(MAP_TILE), 0, s, Sd, Dd, C, part + 3 * K.w_tab);
+        if (K.need_obs > 0) hipLaunchKernelGGL(k_mi_obs, dim3(map_tiles(K.need_obs)), dim3(MAP_TILE), 0, s, Sd, Dd, C);
+        const unsigned g = map_tiles((int64_t)A.n_feat + A.n_obs + K.m);
         hipLaunchKernelGGL(k_mi_feat_rows, dim3(g < MI_MAX_GRID ? g : MI_MAX_GRID), dim3(MAP_TILE), 0, s, Sd, Dd, C, row);
-        (k ? mi->d.ls_ev : mi->d.pt_ev) = C.ev;
-        (k ? mi->d.ls_dir : mi->d.pt_dir) = C.ev_dir;
-        (k ? mi->d.ls_obs_src : mi->d.pt_obs_src) = C.obs_src;
+        done[k] = MapCommitKind{0, 0, 0, {K.n_prev, K.n_curr}, C.ev, C.ev_dir, C.obs_src};
     }
     hipLaunchKernelGGL(k_mi_publish, dim3(1), dim3(MAP_TILE), 0, s, (const int32_t*)cnt, (const int32_t*)row, nk, (int32_t*)mi->pin.dev);
     PLSLAM_HIP_CHECK(hipGetLastError());
@@ -437,22 +369,14 @@ int insert(plslam_map_insert* mi, int mode, const plslam_map_index* src, plslam_
     plslam_map_insert_kind_counts* out[2] = {&counts->points, &counts->lines};
     for (int k = 0; k < 2; ++k) {
         const int32_t* w = r + W_KIND * k;
-        *out[k] = plslam_map_insert_kind_counts{w[W_EV], w[W_NEW], w[W_EV] + w[W_NEW], K[k].m - w[W_EV]};
-        mi->n_ev[k] = w[W_EV];
-        Dk[k]->n = S[k]->n + w[W_NEW];
-        Dk[k]->n_obs = w[W_OBS];
-        Dk[k]->n_feat = S[k]->n_feat;
-        ListsKindRecords& R = mi->lists.k[k];
-        R = ListsKindRecords{};
-        R.src_n = S[k]->n; R.src_obs = S[k]->n_obs; R.dst_n = Dk[k]->n; R.dst_obs = Dk[k]->n_obs;
-        R.n_ev = w[W_EV]; R.bound[0] = K[k].n_prev; R.bound[1] = K[k].n_curr; R.ev_stride = 4; R.need_side0 = mode == MODE_KF2KF;
-        R.ev = k ? mi->d.ls_ev : mi->d.pt_ev; R.dir = k ? mi->d.ls_dir : mi->d.pt_dir;
-        R.obs_src = k ? mi->d.ls_obs_src : mi->d.pt_obs_src;
+        *out[k] = plslam_map_insert_kind_counts{w[W_EV], w[W_NEW], w[W_EV] + w[W_NEW], P.k[k].m - w[W_EV]};
+        mi->n_ev[k] = done[k].n_ev = w[W_EV];
+        done[k].n_new = w[W_NEW];
+        done[k].n_obs = w[W_OBS];
     }
-    dst->map.n_map_kf = nk;
+    map_commit(*src, dst->map, done, 4, mode == MODE_KF2KF, mi->d, mi->lists);
     mi->d.stream = (void*)s;
     mi->done = true;
-    mi->lists.valid = true;
     return PLSLAM_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "map_image.hpp"      // MAP_TILE; ListsRecords: what the handle's last insert / run left for a carry
 #include "match_tables.hpp"   // Carver
 #include "plslam_hip.h"
 
@@ -15,25 +16,8 @@ struct plslam_lc_fuse;
 
 namespace plslam {
 
-constexpr int LISTS_TILE = 256;          // lanes per workgroup of K85-K88 (= MAP_TILE, map_image_dev.hpp: map_lists.hip asserts it)
+constexpr int LISTS_TILE = MAP_TILE;     // lanes per workgroup of K85-K88: the map kernels' one tile (map_image.hpp)
 constexpr int LISTS_LANES_PER_OBS = 8;   // K85: lanes 0-1 the descriptor (2 x 16 bytes), 2-4 the direction (3 x 8), 5-6 pts (2 x 16)
-
-// What the last successful insert / run of a handle left for a carry, per kind: the counts it read and produced, and its records
-// on the device.  Written by map_insert.hip / lc_fuse.hip, read by map_lists.hip.
-struct ListsKindRecords {
-    int32_t src_n = 0, src_obs = 0, dst_n = 0, dst_obs = 0;
-    int32_t n_ev = 0;                    // rows of ev / dir: the insert's events, the fuse's tuples
-    int32_t bound[2] = {0, 0};           // rows of the caller's arrays side w may name: n_prev, n_curr / m, m
-    int32_t ev_stride = 0;               // insert: 4, the row of side w is ev[4 e + 1 + w]; fuse: 0, the row is e
-    int32_t need_side0 = 0;              // insert: kf2kf (side 0 rows exist); fuse: 1
-    const int32_t* ev = nullptr;
-    const double* dir = nullptr;
-    const int32_t* obs_src = nullptr;
-};
-struct ListsRecords {
-    bool valid = false;
-    ListsKindRecords k[2];
-};
 
 // the rows of one kind, whichever call they belong to (plslam_map_insert_rows / plslam_lc_fuse_rows have this layout)
 struct ListsRows {

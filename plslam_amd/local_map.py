@@ -14,7 +14,7 @@ import numpy as np
 from ._lib import Handle, _check, _p, proto
 
 FEAT_NULL = -2            # include/plslam_hip.h: PLSLAM_FEAT_NULL
-LOOKBACK_TILE = 256       # plslam_amd/csrc/map_image_dev.hpp: MAP_TILE, the items one workgroup of a scan over the image takes
+LOOKBACK_TILE = 256       # plslam_amd/csrc/map_image.hpp: MAP_TILE, the items one workgroup of a scan over the image takes
 
 _vp, _i32 = C.c_void_p, C.c_int32
 

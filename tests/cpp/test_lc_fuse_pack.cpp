@@ -1,6 +1,8 @@
-// The pure host half of plslam_lc_fuse_run (plslam_amd/csrc/lc_fuse_plan.hpp): validation, the growth bounds and the packing of
-// the staged block, on heap arrays of exactly the documented sizes.  A stand-alone program: tests/test_lc_fuse_cpu.py builds it with
-// -fsanitize=address,undefined and runs it; it prints "lc_fuse_pack: ok" and returns 0, or says which check failed.
+// The pure host half of plslam_lc_fuse_run (plslam_amd/csrc/lc_fuse_plan.hpp): validation, the growth bounds, the packing of
+// the staged block on heap arrays of exactly the documented sizes, and the layout of the handle's device buffer at the tile's
+// edges.  A stand-alone program: tests/test_lc_fuse_cpu.py builds it with -fsanitize=address,undefined and runs it; it prints
+// "lc_fuse_layout: ok" and "lc_fuse_pack: ok" and returns 0, or says which check failed.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -57,6 +59,82 @@ struct Kind {                            // exactly m rows of everything, n_lc +
         k = plslam_lc_fuse_kind{tup.data(), eptr.data(), P0.data(), o0.data(), P1.data(), o1.data()};
     }
 };
+
+size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// What every device layout must satisfy.  The pieces in the order they are carved, with the bytes each holds:
+// [zeroed: counters, graph, per kind feat_win / part] [0x7f: head] [0xff: killer] [staged] [the rest, per kind]
+int device_layout_ok(const LcFusePlan& P, const plslam_map_index& src, const plslam_map_insert_dst& dst)
+{
+    const plslam_map_landmarks* S[2] = {&src.points, &src.lines};
+    const int32_t obs_cap[2] = {dst.pt_obs_cap, dst.ls_obs_cap};
+    struct Piece { size_t off, bytes; int region; };         // region: 0 zeroed, 1 0x7f, 2 0xff, 3 staged, 4 the rest
+    std::vector<Piece> v = {{P.d_cnt, 80, 0}, {P.d_graph, (size_t)P.nk * P.nk * 4, 0}};
+    for (int k = 0; k < 2; ++k) {
+        v.push_back({P.k[k].d_win, (size_t)S[k]->n_feat * 4 + 4, 0});
+        v.push_back({P.k[k].d_part, (size_t)P.k[k].w_lm * 4, 0});
+    }
+    for (int k = 0; k < 2; ++k) v.push_back({P.k[k].d_head, (size_t)S[k]->n * 4 + 4, 1});
+    for (int k = 0; k < 2; ++k) v.push_back({P.k[k].d_killer, (size_t)S[k]->n * 4 + 4, 2});
+    v.push_back({P.stage_off, P.stage_bytes, 3});
+    for (int k = 0; k < 2; ++k) {
+        const LcFuseKindPlan& K = P.k[k];
+        const size_t m = (size_t)K.m;
+        v.push_back({K.d_len, (size_t)K.need_lm * 4 + 4, 4});
+        v.push_back({K.d_sc, m * 4 + 4, 4});
+        v.push_back({K.d_fw0, m * 4 + 4, 4});
+        v.push_back({K.d_fw1, m * 4 + 4, 4});
+        v.push_back({K.d_ev, m * 24 + 24, 4});
+        v.push_back({K.d_off, m * 4 + 4, 4});
+        v.push_back({K.d_pair, m * 4 + 8, 4});
+        v.push_back({K.d_nev, (size_t)K.cC * 4 + 4, 4});
+        v.push_back({K.d_dir, m * 48 + 48, 4});
+        v.push_back({K.d_osrc, (size_t)obs_cap[k] * 4 + 4, 4});
+    }
+    // carved in this order, aligned as the carver aligns: each starts where the one before it ended, padded to 256
+    size_t end = 0;
+    for (const Piece& p : v) {
+        CHECK(p.off % 256 == 0 && p.off == end);
+        end = p.off + pad(p.bytes);
+    }
+    CHECK(P.total == end);                                    // the total is the last slice's end
+    // no two overlap: sorted by offset, each ends at or before the next one starts
+    std::vector<Piece> w = v;
+    std::sort(w.begin(), w.end(), [](const Piece& a, const Piece& b) { return a.off < b.off; });
+    for (size_t i = 0; i + 1 < w.size(); ++i) CHECK(w[i].off + w[i].bytes <= w[i + 1].off);
+    // the three fill regions and the staged block: contiguous, in that order, and each holds exactly its pieces
+    CHECK(P.fill[0].off == 0 && P.fill[0].byte == 0 && P.fill[1].byte == 0x7f && P.fill[2].byte == 0xff);
+    CHECK(P.fill[1].off == P.fill[0].bytes && P.fill[2].off == P.fill[1].off + P.fill[1].bytes);
+    CHECK(P.stage_off == P.fill[2].off + P.fill[2].bytes);
+    const size_t lo[4] = {0, P.fill[1].off, P.fill[2].off, P.stage_off};
+    const size_t hi[4] = {P.fill[1].off, P.fill[2].off, P.stage_off, P.stage_off + pad(P.stage_bytes)};
+    for (const Piece& p : v)
+        for (int r = 0; r < 4; ++r) CHECK((p.region == r) == (p.off >= lo[r] && p.off + p.bytes <= hi[r] && p.off < hi[r]));
+    // page-locked: 20 counter words, nk^2 more where the caller takes the graph
+    CHECK(P.res_bytes(false) == 256 && P.res_bytes(true) == pad((20 + (size_t)P.nk * P.nk) * 4));
+    return 0;
+}
+
+// the layout of a call on `n` point landmarks with `n_feat` features and `m` point tuples, `c` of them (-1, -1): one flagged entry
+int layout_case(int32_t n, int32_t n_feat, int32_t m, int32_t c)
+{
+    const int32_t nk = 7;
+    Image src(nk, n, 40, n ? 300 : 0, 90), dsti(nk, 0, 0, 0, 0);
+    src.ix.points.n_feat = n_feat;
+    plslam_map_insert_dst dst{dsti.ix, 1000, 2000, 100, 200};
+    std::vector<int32_t> lc = {1, 5, 1}, tup;
+    std::vector<double> T((size_t)nk * 16, 1.0);
+    for (int32_t i = 0; i < m; ++i) {
+        const int32_t t[4] = {i < c ? -1 : 0, i, i < c ? -1 : 1, i};
+        tup.insert(tup.end(), t, t + 4);
+    }
+    Kind pts({tup}, 3, 2), lns({{-1, 1, -1, 2}}, 6, 3);
+    LcFusePlan P;
+    CHECK(lc_fuse_plan(&src.ix, &dst, 1, lc.data(), T.data(), &pts.k, &lns.k, &P) == PLSLAM_OK);
+    CHECK(P.k[0].m == m && P.k[0].cC == c && P.k[0].need_lm == n + c && P.k[0].w_lm == (unsigned)(n + c > 256 ? 2 : 1));
+    CHECK(P.k[1].m == 1 && P.k[1].need_lm == 41 && P.k[1].w_lm == 1);
+    return device_layout_ok(P, src.ix, dst);
+}
 
 }  // namespace
 
@@ -150,6 +228,18 @@ int main()
         plslam_lc_fuse_kind huge{nullptr, ep.data(), nullptr, nullptr, nullptr, nullptr};
         CHECK(lc_fuse_plan(&src.ix, &dst, 3, lc.data(), T.data(), &huge, nullptr, &P) == PLSLAM_ERANGE);
     }
+    // ---- the device layout: the tuples, the landmarks it can end with and the features each at 0, 255, 256 and 257 ----
+    CHECK(lc_fuse_plan(&src.ix, &dst, 3, lc.data(), T.data(), &pts.k, &lns.k, &P) == PLSLAM_OK);
+    CHECK(device_layout_ok(P, src.ix, dst) == 0);
+    // 102 point landmarks at most: one tile, one chain word; the staged block sits behind the three fill regions
+    CHECK(P.k[0].w_lm == 1 && P.k[1].w_lm == 1 && P.k[0].d_part == P.k[0].d_win + 256 && P.k[1].d_win == P.k[0].d_part + 256);
+    const int32_t edge[4] = {0, 255, 256, 257};
+    for (int e = 0; e < 4; ++e) {
+        CHECK(layout_case(100, 10, edge[e], 0) == 0);                            // m
+        CHECK(layout_case(edge[e] ? edge[e] - 5 : 0, 10, edge[e] ? 9 : 0, edge[e] ? 5 : 0) == 0);   // need_lm = n + cC
+        CHECK(layout_case(100, edge[e], 9, 5) == 0);                             // n_feat
+    }
+    printf("lc_fuse_layout: ok\n");
     printf("lc_fuse_pack: ok\n");
     return 0;
 }

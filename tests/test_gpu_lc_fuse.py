@@ -53,16 +53,17 @@ def _blank(dst):
     assert dst.struct.points.n == 0 and dst.struct.lines.n_obs == 0
 
 
-def _run(ctx, name):
+def _run(ctx, name, handle=None):
     m, lc, (m2, out), _ = CS.run_ref(name)
-    lf = LF.LcFuse(ctx)
+    lf = handle or LF.LcFuse(ctx)
     src = MI.DeviceMapImage(m, device=ctx.device)
     dst = MI.DeviceMapImage(m, **LF.fuse_bounds(m, lc), device=ctx.device, blank=BLANK)
     got = lf.run(src, dst, lc)
     _same_out(got, lf.download(), out)
     _same_image(dst, m2)
     _same_image(src, m)                                          # the source is read, not written
-    lf.close()
+    if handle is None:
+        lf.close()
     return out
 
 
@@ -79,12 +80,21 @@ def test_cases_equal_the_restatement(ctx, name):
         assert not out["graph_delta"].any() and out["points"]["ev"].shape == (0, 6)
 
 
+def test_a_smaller_case_after_a_larger_one_on_one_handle(ctx):
+    """the handle's buffer is carved anew by every run: a case, then one without any tuple (every slice sized by the tuples
+    shrinks to its slack, everything behind moves), then the first again, each equal to the restatement"""
+    lf = LF.LcFuse(ctx)
+    for name in ("three_entries", "no_events", "three_entries"):
+        _run(ctx, name, lf)
+    lf.close()
+
+
 def test_the_tile_the_cases_are_built_around_is_the_kernels():
     import os
     import re
     import local_map_cases
     import map_insert_cases
-    src = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "csrc", "map_image_dev.hpp")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "csrc", "map_image.hpp")).read()
     tile = int(re.search(r"constexpr int MAP_TILE = (\d+);", src).group(1))
     assert tile == LM.LOOKBACK_TILE == MI.LOOKBACK_TILE == LF.LOOKBACK_TILE == CS.T == map_insert_cases.T == local_map_cases.T
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(LF.__file__)), "..", "include", "plslam_hip.h")).read()

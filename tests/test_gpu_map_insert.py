@@ -44,10 +44,11 @@ def _same_out(got, ev, want):
         assert np.array_equal(_bits(ev[kind]["dir"]), _bits(want[kind]["dir"])), kind
 
 
-def _both_passes(ctx, name):
-    """the two inserts of a case on the device, the second one on the image the first one left there"""
+def _both_passes(ctx, name, handle=None):
+    """the two inserts of a case on the device, the second one on the image the first one left there; on `handle` where one is
+    given, else on a handle of their own"""
     m, kf, (m_a, out_a), kf_b, (m_b, out_b), _ = CS.run_ref(name)
-    mi = MI.MapInsert(ctx)
+    mi = handle or MI.MapInsert(ctx)
     src = LM.DeviceMapIndex(m, ctx.device)
     dst = MI.DeviceMapImage(m, **MI.insert_bounds(m, kf, "kf2kf"), device=ctx.device, blank=BLANK)
     got = mi.kf2kf(src, dst, kf)
@@ -58,7 +59,8 @@ def _both_passes(ctx, name):
     _same_out(got, mi.download(), out_b)
     _same_image(dst2, m_b)
     _same_image(dst, m_a)                                        # the source of the second call is read, not written
-    mi.close()
+    if handle is None:
+        mi.close()
     return out_a, out_b
 
 
@@ -75,13 +77,22 @@ def test_cases_equal_the_restatement(ctx, name):
         assert a["points"]["counts"]["n_events"] == 0 and not a["row_delta"].any()
 
 
+def test_a_smaller_case_after_a_larger_one_on_one_handle(ctx):
+    """the handle's buffer is carved anew by every call: a case, then one without any event (every event slice shrinks to its
+    slack, everything behind moves), then the first again, each equal to the restatement"""
+    mi = MI.MapInsert(ctx)
+    for name in ("mixed", "no_events", "mixed"):
+        _both_passes(ctx, name, mi)
+    mi.close()
+
+
 def test_the_tile_the_cases_are_built_around_is_the_kernels():
     import os
     import re
     import lc_fuse_cases
     import local_map_cases
     from plslam_amd import lc_fuse as LF
-    src = open(os.path.join(os.path.dirname(os.path.abspath(MI.__file__)), "csrc", "map_image_dev.hpp")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(MI.__file__)), "csrc", "map_image.hpp")).read()
     tile = int(re.search(r"constexpr int MAP_TILE = (\d+);", src).group(1))
     assert tile == LM.LOOKBACK_TILE == MI.LOOKBACK_TILE == LF.LOOKBACK_TILE == CS.T == lc_fuse_cases.T == local_map_cases.T
 

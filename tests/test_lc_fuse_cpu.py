@@ -154,12 +154,12 @@ def test_generators_are_seeded():
 
 
 def test_the_host_half_under_the_sanitizers(tmp_path):
-    """tests/cpp/test_lc_fuse_pack.cpp: validation, bounds and packing (lc_fuse_plan.hpp) in a stand-alone program built with
-    -fsanitize=address,undefined"""
+    """tests/cpp/test_lc_fuse_pack.cpp: validation, bounds, packing and the device layout (lc_fuse_plan.hpp) in a stand-alone program
+    built with -fsanitize=address,undefined"""
     exe = str(tmp_path / "test_lc_fuse_pack")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
                         "-Werror", os.path.join(ROOT, "tests", "cpp", "test_lc_fuse_pack.cpp"), "-I" + os.path.join(ROOT, "include"),
                         "-I" + os.path.join(ROOT, "plslam_amd", "csrc"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and "lc_fuse_pack: ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.returncode == 0 and "lc_fuse_pack: ok" in r.stdout and "lc_fuse_layout: ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])

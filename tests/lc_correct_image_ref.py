@@ -49,13 +49,13 @@ def correct_kind(K, n_map_kf, T_corr, corrected, dirs=None, med_dir=None):
     return dict(X=X, dirs=dirs, med_dir=med, n=int((slot >= 0).sum()), n_dirs=n_dirs)
 
 
-def correct_image(m, T_corr, corrected, x_kf_w_new=None, lists=None, med_dir=None):
+def correct_image(m, T_corr, corrected, x_kf_w_new=None, lists=None, med_dir=None, kind_fn=correct_kind):
     """the whole call on an image dict -> dict(points, lines: correct_kind's dict, x_kf_w, counts)"""
     nk = int(m["n_map_kf"])
     out = {}
     for kind in KINDS:
         d = None if lists is None else lists[kind]["dir"]
-        out[kind] = correct_kind(m[kind], nk, T_corr, corrected, d, None if med_dir is None else med_dir.get(kind))
+        out[kind] = kind_fn(m[kind], nk, T_corr, corrected, d, None if med_dir is None else med_dir.get(kind))
     x = np.array(m["x_kf_w"], np.float64).reshape(nk, 6)
     if x_kf_w_new is not None:
         co = np.asarray(corrected).astype(bool)
@@ -63,6 +63,48 @@ def correct_image(m, T_corr, corrected, x_kf_w_new=None, lists=None, med_dir=Non
     out["x_kf_w"] = x
     out["counts"] = dict(n_pt=out["points"]["n"], n_ls=out["lines"]["n"], n_pt_dirs=out["points"]["n_dirs"], n_ls_dirs=out["lines"]["n_dirs"])
     return out
+
+
+# ---- the same in array operations: trusted only because test_lc_correct_image_cpu.py finds it equal to the loop, bit for bit -----
+def _rt_rows(T, p):
+    """_rt with one transform per row: T (m, 4, 4), p (m, 3) -> ((r0 p0 + r1 p1) + r2 p2) + t"""
+    R, t = T[:, :3, :3], T[:, :3, 3]
+    return ((R[:, :, 0] * p[:, 0:1] + R[:, :, 1] * p[:, 1:2]) + R[:, :, 2] * p[:, 2:3]) + t
+
+
+def correct_kind_fast(K, n_map_kf, T_corr, corrected, dirs=None, med_dir=None):
+    """correct_kind without a Python loop, for an obs_ptr that starts at 0 and never descends (anything else is refused: lists
+    that overlap are transformed twice by the loop, and a row then has no one landmark)"""
+    T_corr = np.asarray(T_corr, np.float64).reshape(-1, 4, 4)
+    valid, ptr = np.asarray(K["valid"]).reshape(-1), np.asarray(K["obs_ptr"], np.int64).reshape(-1)
+    obs_kf, corrected = np.asarray(K["obs_kf"], np.int64).reshape(-1), np.asarray(corrected).astype(bool)
+    n, lens = valid.size, np.diff(ptr)
+    assert ptr.size == n + 1 and ptr[0] == 0 and (lens >= 0).all(), "correct_kind_fast: obs_ptr must start at 0 and never descend"
+    X = np.array(K["X"], np.float64)
+    dirs = None if dirs is None else np.array(dirs, np.float64).reshape(-1, 3)
+    med = None if med_dir is None else np.array(med_dir, np.float64).reshape(-1, 3)
+    b, e = ptr[:n], ptr[1:]
+    ok = (valid != 0) & (e > b) & (e <= obs_kf.size)
+    slot = np.full(n, -1, np.int64)
+    first = obs_kf[b[ok]]
+    slot[ok] = np.where((first >= 0) & (first < n_map_kf) & corrected[np.clip(first, 0, corrected.size - 1)], first, -1)
+    j = np.flatnonzero(slot >= 0)
+    for h in range(0, X.shape[1], 3):
+        X[j, h:h + 3] = _rt_rows(T_corr[slot[j]], X[j, h:h + 3])
+    if med is not None:
+        med[j] = _rt_rows(T_corr[slot[j]], med[j])
+    n_dirs = 0
+    if dirs is not None:
+        row_slot = slot[np.repeat(np.arange(n), lens)]            # per row of [0, obs_ptr[n]) the slot of its landmark
+        o = np.flatnonzero(row_slot >= 0)
+        dirs[o] = _rt_rows(T_corr[row_slot[o]], dirs[o])
+        n_dirs = int(o.size)
+    return dict(X=X, dirs=dirs, med_dir=med, n=int(j.size), n_dirs=n_dirs)
+
+
+def correct_image_fast(m, T_corr, corrected, x_kf_w_new=None, lists=None, med_dir=None):
+    """correct_image through correct_kind_fast: the same signature, the same dict"""
+    return correct_image(m, T_corr, corrected, x_kf_w_new, lists, med_dir, kind_fn=correct_kind_fast)
 
 
 # ---- the reference's containers, replayed from the records -----------------------------------------------------------------------

@@ -9,6 +9,8 @@ import pytest
 import lc_correct_image_ref as R
 import lc_fuse_ref as FR
 import map_lists_ref as LR
+from lc_correct_image_cases import decision_map as _decision_map
+from lc_correct_image_cases import length_map as _length_map
 from plslam_amd import capi
 from plslam_amd import lc_fuse as LF
 from plslam_amd import local_map as LM
@@ -23,24 +25,6 @@ BLANK = 90
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float64).reshape(-1).view(np.uint64)
-
-
-def _hand_map(nk, points, lines, seed=1):
-    """an image from explicit landmarks: per kind a list of (valid, [obs_kf, ...]); no features"""
-    rng = np.random.Generator(np.random.PCG64(seed))
-
-    def kind(lms, dl, dv):
-        n = len(lms)
-        lens = [len(o) for _, o in lms]
-        ptr = np.zeros(n + 1, np.int32)
-        ptr[1:] = np.cumsum(lens)
-        okf = np.array([k for _, o in lms for k in o], np.int32)
-        return dict(n=n, valid=np.array([v for v, _ in lms], np.uint8), inlier=np.ones(n, np.uint8), X=rng.uniform(-20.0, 20.0, (n, dl)),
-                    obs_ptr=ptr, obs_kf=okf, obs_val=rng.uniform(0.0, 700.0, (okf.size, dv)), feat_ptr=np.zeros(nk + 1, np.int32),
-                    feat_idx=np.zeros(0, np.int32))
-
-    return dict(n_map_kf=nk, kf_valid=np.ones(nk, np.uint8), x_kf_w=rng.standard_normal((nk, 6)), row=np.zeros(nk, np.int32),
-                points=kind(points, 3, 2), lines=kind(lines, 6, 3))
 
 
 def _inputs(m, seed, corrected=None):
@@ -108,16 +92,6 @@ def test_landmark_counts_at_the_tile_edges(ctx, n):
         assert counts["n_pt"] > T // 4 and counts["n_ls"] > T // 4 and counts["n_pt_dirs"] > counts["n_pt"]
 
 
-def _length_map(nk, lines_too=True, seed=4):
-    """lists of 0, 1, 63, 64 and 65 rows, then one of 300 rows that lies across the first workgroup boundary of the direction pass
-    (rows 193 .. 492), then short ones; list i is first seen in slot i mod nk"""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lens = [0, 1, 63, 64, 65, 300, 0, 2, 5, 1, 0, 64, 3]
-    lms = [(1, [i % nk] * min(ln, 1) + [int(k) for k in rng.integers(0, nk, max(ln - 1, 0))]) for i, ln in enumerate(lens)]
-    lms[7] = (0, lms[7][1])                                       # an invalid landmark among them
-    return _hand_map(nk, lms, lms if lines_too else [], seed)
-
-
 @pytest.mark.parametrize("nk", [1, 2])
 @pytest.mark.parametrize("lines_too", [True, False])
 def test_list_lengths_and_a_list_across_a_workgroup_boundary(ctx, nk, lines_too):
@@ -138,14 +112,6 @@ def test_arrays_that_are_not_carried(ctx, with_dir, with_med):
 
 
 # ---- the decisions ----------------------------------------------------------------------------------------------------------------------
-def _decision_map():
-    """4 slots; slot 3 anchors nothing.  Points: 0 valid, first seen in 0; 1 INVALID, first seen in 0; 2 valid, first seen in 1;
-    3 valid, first observer -1; 4 valid, first observer n_map_kf; 5 valid without observations; 6 valid, first seen in 2, later
-    in 3.  The lines are the same."""
-    lms = [(1, [0, 1]), (0, [0, 2]), (1, [1, 3]), (1, [-1, 0]), (1, [4, 0]), (1, []), (1, [2, 3])]
-    return _hand_map(4, lms, lms, seed=9)
-
-
 def test_nothing_corrected_changes_nothing(ctx):
     m = _decision_map()
     T_corr, _, lists, med, x_new = _inputs(m, 3)

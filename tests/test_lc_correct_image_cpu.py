@@ -1,13 +1,15 @@
 """The loop-closure correction on the map image, without a GPU: the invariant that lets it do without anchor lists (the reference's
 map_*_kf_idx containers, replayed from the records of the image calls by the reference's own push / erase rules, always equal the
-lists derived from the image), the numpy restatement of the image rule against the anchor-list restatement, and the host half of
-the call under the sanitizers."""
+lists derived from the image), the numpy restatement of the image rule against the anchor-list restatement, its vectorised form against
+the loop, the reach of the maps the GPU tests run at scale, and the host half of the call under the sanitizers."""
 import copy
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
+import lc_correct_image_cases as CS
 import lc_correct_image_ref as R
 import lc_fuse_ref as FR
 import local_map_ref as LR
@@ -132,6 +134,89 @@ def test_anchor_lists_leave_out_what_the_image_rule_leaves_out():
             assert idx[ptr[k]:ptr[k + 1]].tolist() == want, (kind, k)
         assert (first == -1).any() and (first == nk).any() and (first == -9).any() and (K["valid"] == 0).any()
         assert ptr[3] > ptr[2] and ptr[8] > ptr[7]                # a NULL keyframe slot still anchors what it first observed
+
+
+# ---- the vectorised restatement is the loop ----------------------------------------------------------------------------------------
+def _same_restatement(m, T_corr, corrected, x_new, lists, med, what):
+    want = R.correct_image(m, T_corr, corrected, x_new, lists, med)
+    got = R.correct_image_fast(m, T_corr, corrected, x_new, lists, med)
+    assert got["counts"] == want["counts"], (what, got["counts"], want["counts"])
+    assert np.array_equal(_bits(got["x_kf_w"]), _bits(want["x_kf_w"])), (what, "x_kf_w")
+    for kind in R.KINDS:
+        for f in ("X", "dirs", "med_dir"):
+            g, w = got[kind][f], want[kind][f]
+            assert (g is None) == (w is None), (what, kind, f)
+            assert g is None or (g.shape == w.shape and np.array_equal(_bits(g), _bits(w))), (what, kind, f)
+    return want["counts"]
+
+
+def _fast_cases():
+    yield "decision map", CS.decision_map(), ([1, 1, 1, 1], [1, 0, 0, 0], [0, 0, 0, 1], [0, 0, 0, 0])
+    for nk in (1, 2):
+        for lines_too in (True, False):
+            yield f"length map {nk} {lines_too}", CS.length_map(nk, lines_too), ([1] * nk, [1] + [0] * (nk - 1), [0] * (nk - 1) + [1])
+    for n in (0, 1, CS.T - 1, CS.T, CS.T + 1):                    # test_landmark_counts_at_the_tile_edges
+        yield f"tile edge {n}", LM.synthetic_map(n_kf=6, n_pt=n, n_ls=n, seed=300 + n, no_obs_frac=0.1), ([1, 0, 1, 1, 0, 1],)
+    yield "edge map", _edge_map(), (None,)
+    yield "inside map", CS.inside_map(), ([1, 1, 1], [1, 0, 0], [0, 0, 1])
+    for ends_empty in (False, True):
+        yield f"depth map {ends_empty}", CS.depth_map(CS.T + 1, ends_empty), ([1, 1, 1, 1, 1], [1, 0, 1, 0, 1])
+
+
+def test_the_vectorised_restatement_equals_the_loop_bit_for_bit():
+    moved = 0
+    for what, m, patterns in _fast_cases():
+        T_corr, lists, med, x_new = CS.inputs(m, 70)
+        for co in patterns:
+            co = np.random.Generator(np.random.PCG64(71)).random(m["n_map_kf"]) < 0.6 if co is None else np.asarray(co, bool)
+            moved += _same_restatement(m, T_corr, co, x_new, lists, med, (what, co.tolist()))["n_pt_dirs"]
+    assert moved > 5000
+    m = LM.synthetic_map()                                        # ... with and without the arrays that need not be carried
+    T_corr, lists, med, x_new = CS.inputs(m, 72)
+    co = np.arange(m["n_map_kf"]) % 3 > 0
+    for with_dir in (True, False):
+        for with_med in (True, False):
+            for with_x in (True, False):
+                c = _same_restatement(m, T_corr, co, x_new if with_x else None, lists if with_dir else None, med if with_med else None,
+                                      ("synthetic_map", with_dir, with_med, with_x))
+                assert c["n_pt"] > 300 and (c["n_pt_dirs"] > c["n_pt"]) == with_dir
+
+
+def test_the_vectorised_restatement_refuses_what_it_is_not_defined_for():
+    m = CS.length_map(2)
+    T_corr, lists, med, x_new = CS.inputs(m, 73)
+    for j, by in ((5, -70), (0, 1)):                              # obs_ptr descends; obs_ptr does not start at 0
+        mb = dict(m, points=dict(m["points"], obs_ptr=m["points"]["obs_ptr"].copy()))
+        mb["points"]["obs_ptr"][j] += by
+        with pytest.raises(AssertionError, match="obs_ptr must start at 0 and never descend"):
+            R.correct_image_fast(mb, T_corr, [1, 1], x_new, lists, med)
+
+
+# ---- the maps of test_gpu_lc_correct_image_scale.py reach what they are named for -------------------------------------------------
+def test_the_constants_the_cases_are_built_around():
+    assert CS.T == LM.LOOKBACK_TILE and CS.G >= 2 and CS.DEPTH_SIZES == (255, 256, 257, 65535, 65536, 65537)
+    assert [len(CS.search_rounds(n, 0)[0]) for n in CS.DEPTH_SIZES] == list(CS.DEPTH_ROUNDS) == [1, 1, 2, 2, 2, 3]
+    assert CS.search_rounds(CS.T * CS.T + 1, CS.T * CS.T) == ([(0, 65537, 257), (65535, 2, 1)], True)
+
+
+@pytest.mark.parametrize("ends_empty", [False, True])
+@pytest.mark.parametrize("n", CS.DEPTH_SIZES)
+def test_the_depth_maps_reach_their_rounds(n, ends_empty):
+    m = CS.depth_map(n, ends_empty)
+    CS.depth_reach(m, n)
+    lens = np.diff(m["points"]["obs_ptr"])
+    assert (lens[0] == 0) == (lens[-1] == 0) == ends_empty and set(lens[2:-2].tolist()) == {0, 1, 2, 3}
+
+
+def test_the_inside_map_has_tiles_inside_one_list():
+    assert CS.inside_reach(CS.inside_map()) == 12
+
+
+def test_the_walk_map_has_more_tiles_than_workgroups():
+    m = CS.walk_map()
+    assert CS.walk_reach(m) == (CS.G + 5, 2 * CS.G + 874)
+    nk = m["n_map_kf"]
+    assert [int(CS.walk_corrected(p, nk)[[CS.WALK_A, CS.WALK_B, CS.WALK_C]] @ [1, 2, 4]) for p in CS.WALK_PATTERNS] == [7, 5, 2, 6, 0]
 
 
 def test_the_host_half_under_the_sanitizers(tmp_path):

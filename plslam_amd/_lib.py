@@ -50,9 +50,23 @@ def proto(name, argtypes, restype=C.c_int) -> None:
         _apply(_lib, name)
 
 
+# name -> (header, argtypes, restype) of the entry points that OTHER headers of include/ declare (plslam_track.h): stated with
+# proto_in() beside their wrappers and applied by load() in the same way.  PROTOTYPES stays the surface of plslam_hip.h alone.
+HEADER_PROTOTYPES = {}
+
+
+def proto_in(header, name, argtypes, restype=C.c_int) -> None:
+    """proto() for an entry point that include/<header> declares."""
+    if name in PROTOTYPES:
+        raise ValueError(f"{name} is declared by include/plslam_hip.h")
+    HEADER_PROTOTYPES[name] = (header, argtypes, restype)
+    if _lib is not None:
+        _apply(_lib, name)
+
+
 def _apply(L, name) -> None:
     f = getattr(L, name)
-    f.argtypes, f.restype = PROTOTYPES[name]
+    f.argtypes, f.restype = PROTOTYPES[name] if name in PROTOTYPES else HEADER_PROTOTYPES[name][1:]
 
 
 proto("plslam_strerror", [C.c_int], C.c_char_p)
@@ -101,7 +115,7 @@ def load() -> C.CDLL:
     if L.plslam_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libplslam_hip.so has ABI version {L.plslam_abi_version()}, these bindings were written for {ABI_VERSION} "
                            "(struct layouts differ: rebuild with plslam_amd/build.py)")
-    for name in PROTOTYPES:
+    for name in (*PROTOTYPES, *HEADER_PROTOTYPES):
         _apply(L, name)
     _lib = L
     return L

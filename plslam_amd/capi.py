@@ -11,7 +11,7 @@ import os  # noqa: F401
 
 import numpy as np  # noqa: F401
 
-from . import _lib, lc_fuse, local_map, map_insert, map_lists  # noqa: F401 (the last four: their prototypes)
+from . import _lib, lc_fuse, local_map, map_insert, map_lists, track  # noqa: F401 (the last five: their prototypes; track's are include/plslam_track.h's, in _lib.HEADER_PROTOTYPES)
 from ._lib import (ABI_VERSION, EHIP, EINVAL, ENODEV, ENOMEM, ENOTSUP, ERANGE, LIB_PATH, OK, PROTOTYPES, Handle,  # noqa: F401
                    PlslamError, _HERE, _addressof, _arr, _check, _from_buffer, _hip_memcpy_dtod, _p,
                    _preload_shared_hip_runtime, load, proto)

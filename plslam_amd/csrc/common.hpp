@@ -339,6 +339,13 @@ int check_stereo_gate_problem(const plslam_stereo_gate_problem& q);
 int launch_median_desc(const uint8_t* desc, const int32_t* off, int32_t n_lm, int32_t total,
                        int32_t* med_idx, uint8_t* med_desc, hipStream_t s);
 
+// --- K54 from inside the library (loop_closure.hip; the tracker, track.hip) --------------------
+// plslam_relpose_robust_gn_batched_dev behind its checks and its lock: K54 on the context's stream, behind what `us` holds on
+// entry and in front of what it is given next.  The caller holds ctx->mu and has selected the context's device.
+int lc_relpose_batched_unlocked(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
+                                const int32_t* pt_off, const double* sPeP, const double* le_obs, const int32_t* ls_off, int32_t B,
+                                plslam_lc_result* results, uint8_t* pt_inlier, uint8_t* ls_inlier, hipStream_t us);
+
 // --- LBD float -> binary line descriptor (lbd.hip) ---------------------------------------------
 // lbd: n x 72 f32, codes: n x 32 u8 (both 16-byte aligned)
 int launch_lbd_binarise(const float* lbd, int32_t n, uint8_t* codes, hipStream_t s);

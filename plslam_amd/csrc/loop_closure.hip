@@ -552,6 +552,29 @@ GnImage gn_image(char* base, size_t np, size_t nl)
 }
 
 }  // namespace
+
+// plslam_relpose_robust_gn_batched_dev behind its checks and its lock (common.hpp; the tracker, track.hip, runs K54 through
+// it): the B records, K54 behind `us`.  The caller holds ctx->mu and has selected the context's device.
+int lc_relpose_batched_unlocked(plslam_ctx* ctx, const plslam_lc_params* params, const double* P, const double* pl_obs,
+                                const int32_t* pt_off, const double* sPeP, const double* le_obs, const int32_t* ls_off, int32_t B,
+                                plslam_lc_result* results, uint8_t* pt_inlier, uint8_t* ls_inlier, hipStream_t us)
+{
+    int rc;
+    const size_t bytes = (size_t)B * sizeof(LcArgs);
+    if ((rc = ctx->lc_args.reserve(bytes))) return rc;
+    ctx->lc_args_h.resize(bytes);
+    LcArgs* h = reinterpret_cast<LcArgs*>(ctx->lc_args_h.data());
+    LcArgs a;                   // K54 takes the counts from pt_off / ls_off; no correspondence rows: row k is (k, k)
+    lc_identity_args(a, params, P, pl_obs, 0, sPeP, le_obs, 0, LcOut{nullptr, nullptr, pt_inlier, nullptr, ls_inlier});
+    for (int32_t b = 0; b < B; ++b) {
+        h[b] = a;
+        h[b].res = results + b;
+    }
+    if ((rc = fence_enter(ctx, us))) return rc;
+    if ((rc = launch_k54(ctx, ctx->lc_args.as<LcArgs>(), h, B, pt_off, ls_off))) return rc;
+    return fence_leave(ctx, us);
+}
+
 }  // namespace plslam
 
 extern "C" {
@@ -712,20 +735,8 @@ int plslam_relpose_robust_gn_batched_dev(plslam_ctx* ctx, const plslam_lc_params
     PLSLAM_REQUIRE(P || sPeP, PLSLAM_EINVAL);
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard(ctx->device);
-    hipStream_t us = static_cast<hipStream_t>(stream);
-    const size_t bytes = (size_t)B * sizeof(LcArgs);
-    if ((rc = ctx->lc_args.reserve(bytes))) return rc;
-    ctx->lc_args_h.resize(bytes);
-    LcArgs* h = reinterpret_cast<LcArgs*>(ctx->lc_args_h.data());
-    LcArgs a;                   // K54 takes the counts from pt_off / ls_off; no correspondence rows: row k is (k, k)
-    lc_identity_args(a, params, P, pl_obs, 0, sPeP, le_obs, 0, LcOut{nullptr, nullptr, pt_inlier, nullptr, ls_inlier});
-    for (int32_t b = 0; b < B; ++b) {
-        h[b] = a;
-        h[b].res = results + b;
-    }
-    if ((rc = fence_enter(ctx, us))) return rc;
-    if ((rc = launch_k54(ctx, ctx->lc_args.as<LcArgs>(), h, B, pt_off, ls_off))) return rc;
-    return fence_leave(ctx, us);
+    return lc_relpose_batched_unlocked(ctx, params, P, pl_obs, pt_off, sPeP, le_obs, ls_off, B, results, pt_inlier, ls_inlier,
+                                       static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -959,7 +959,7 @@ typedef struct plslam_gather_step {
 int plslam_match_plan_step_gather(plslam_match_plan* plan, const plslam_gather_step* step);
 int plslam_match_plan_gather_sync(plslam_match_plan* plan);
 
-/* ---- Bag of words: DBoW2 vocabulary transform and the keyframe confusion matrix (bow.hip) ----------------------------------
+/* ---- Bag of words: DBoW2 vocabulary transform and the keyframe confusion matrix (bow.hip, bow_plan.hpp) --------------------
  * Replaces the bag-of-words step of MapHandler::addKeyFrame (src/mapHandler.cpp:196-201 -> insertKFBowVector{P,L,PL},
  * :3007-3128): TemplatedVocabulary<FORB>::transform (3rdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1046-1100,
  * :1198-1240) and L1Scoring::score (src/DBoW2/ScoringObject.cpp:23-67) against every earlier keyframe.

@@ -34,7 +34,7 @@ SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_m
 LEGACY_SOURCES = ["hamming_mfma.hip", "hamming_mfma_d.hip"]
 LEGACY_AWARE = ("context.hip", "hamming_mfma_h.hip")
 HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "match_tables.hpp", "match_planner.hpp", "match_plan.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp", "lba_lists.hpp", "lba_blocks_dev.hpp", "lba_plan.hpp", "lba_lm_ctl.hpp", "pose_step_dev.hpp", "match_grid.hpp", "match_grid_layout.hpp", "match_grid_dev.hpp",
-                                            "stereo_gates_dev.hpp", "pose_gn_dev.hpp", "gn_cam.hpp", "dense6_dev.hpp", "lc_plan.hpp", "se3_dev.hpp", "g2o_dev.hpp", "ldlt_dense.hpp", "env_ldlt.hpp", "pgo_graph.hpp", "gba_lists.hpp", "gba_plan.hpp", "lookback_dev.hpp", "distribute_dev.hpp", "lc_fuse_plan.hpp", "lc_image_plan.hpp", "map_image.hpp", "map_image_dev.hpp", "publish_dev.hpp", "map2kf_dev.hpp", "map2kf_plan.hpp", "median_desc_dev.hpp", "map_lists_plan.hpp", "local_map_plan.hpp", "map_insert_plan.hpp", "track_plan.hpp")] + [os.path.join(_ROOT, "include", h) for h in ("plslam_hip.h", "plslam_track.h")]
+                                            "stereo_gates_dev.hpp", "pose_gn_dev.hpp", "gn_cam.hpp", "dense6_dev.hpp", "lc_plan.hpp", "se3_dev.hpp", "g2o_dev.hpp", "ldlt_dense.hpp", "env_ldlt.hpp", "pgo_graph.hpp", "gba_lists.hpp", "gba_plan.hpp", "lookback_dev.hpp", "distribute_dev.hpp", "lc_fuse_plan.hpp", "lc_image_plan.hpp", "map_image.hpp", "map_image_dev.hpp", "publish_dev.hpp", "map2kf_dev.hpp", "map2kf_plan.hpp", "median_desc_dev.hpp", "map_lists_plan.hpp", "local_map_plan.hpp", "map_insert_plan.hpp", "track_plan.hpp", "bow_plan.hpp")] + [os.path.join(_ROOT, "include", h) for h in ("plslam_hip.h", "plslam_track.h")]
 # -ffp-contract=off: the fp64 row kernels must execute the reference's operation order
 # (no FMA contraction) so that thresholded masks reproduce the CPU restatement bit for bit.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -26,20 +26,18 @@
 //                     ascending word id) through ballot + shuffles.  All three folds run in the reference's order: the
 //                     results are bit-identical to it (-ffp-contract=off).
 // One keyframe insert = 1 H2D copy, K19, K20, K21, 1 D2H copy, 1 synchronisation (DESIGN.md section "Bag of words").
+//
+// The kernels, the handles with their buffers and the launches are here.  Every check, the flattening of the vocabulary tree,
+// the database's bookkeeping, the staged layouts and the LDS sizes are in bow_plan.hpp (pure host): an entry point reads
+// check (planner) -> lock and guard -> reserve and stage by the plan -> launch -> commit.
 #include "common.hpp"
 
-#include <algorithm>
 #include <cstring>
+
+#include "bow_plan.hpp"   // STAGE_NODES, DESCEND_THREADS, SET_THREADS, NO_WORD, the LDS sizes; the planner
 
 namespace plslam {
 namespace {
-
-constexpr int STAGE_NODES = 1228;          // 1228 x (32 + 8) B = 48 KB of LDS: no dynamic-LDS attribute needed for K19
-constexpr int DESCEND_THREADS = 256;
-constexpr int SET_THREADS = 1024;
-constexpr uint32_t NO_WORD = 0xFFFFFFFFu;  // sorts behind every word id (< 2^31)
-constexpr size_t SET_LDS_MAX = (size_t)PLSLAM_BOW_MAX_SET * 4 + SET_THREADS * 4 + 16;
-constexpr size_t SCORE_LDS_MAX = (size_t)2 * PLSLAM_BOW_MAX_SET * 4;
 
 struct VocabDev {                          // what the kernels read of one vocabulary
     const int32_t* links;                  // n x {first, count}
@@ -310,54 +308,72 @@ struct plslam_bow_vocab {
     {
         return VocabDev{links.as<int32_t>(), desc.as<uint32_t>(), node_w.as<double>(), word_w.as<double>(), n_stage};
     }
-    size_t stage_bytes() const { return (size_t)n_stage * 40; }
 };
 
 struct plslam_bow_db {
     plslam_ctx* ctx = nullptr;
     plslam_bow_vocab* vp = nullptr;
     plslam_bow_vocab* vl = nullptr;
-    int mode = 0;                                    // 1 P, 2 L, 3 PL
-    int32_t cap_kf = 0, size = 0;
-    int64_t cap_p = 0, used_p = 0, cap_l = 0, used_l = 0;
+    BowDbState st;                                   // sizes, capacities, reservations: written by bow_db_commit alone
     DevBuf tab, pw, pv, lw, lv;                      // keyframe table; the pools of stored vectors (entries)
     DevBuf scratch;                                  // insert: descriptors, alive, words, the row
     HostBuf pin_in, pin_out;
-    std::vector<int32_t> res_p, res_l;               // entries reserved per keyframe
-    std::vector<uint8_t> inserted;
-    std::vector<plslam_bow_pl_stats> stats;
 };
 
 namespace {
 
-int fail(int code, const char* msg, long a = 0, long b = 0)
+int refuse(int code, const BowWhy& why)
 {
-    set_last_error(msg, a, b);
+    set_last_error(why.fmt, why.a, why.b);
     return code;
 }
 
-// grows a device array of `elem`-byte entries from `have` to at least `need` entries, keeping the first `keep` entries
-// (copied on `s`); new space filled with `fill` bytes
-int grow(DevBuf& b, size_t elem, int64_t& have, int64_t need, int64_t keep, int fill, hipStream_t s)
-{
-    if (need <= have) return PLSLAM_OK;
-    const int64_t want = std::max(need, have * 2);
+struct FreshBlock {                                  // a new device block until a DevBuf takes it
     void* p = nullptr;
-    PLSLAM_HIP_CHECK(hipMalloc(&p, (size_t)want * elem));
-    if (keep > 0) PLSLAM_HIP_CHECK(hipMemcpyAsync(p, b.p, (size_t)keep * elem, hipMemcpyDeviceToDevice, s));
-    if (fill >= 0) PLSLAM_HIP_CHECK(hipMemsetAsync((char*)p + keep * elem, fill, (size_t)(want - keep) * elem, s));
-    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));      // the old block may still be read by enqueued work
-    b.release();
-    b.p = p;
-    b.cap = (size_t)want * elem;
-    have = want;
+    ~FreshBlock()
+    {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// Carries out the planned growth of one set of arrays with ONE capacity (now `have` entries): a pool's word ids and weights
+// (`ea` / `eb` bytes per entry), or the keyframe table alone (b == nullptr).  Every new array is allocated first, the g.keep
+// entries in use are copied and the rest filled with `fill` bytes (< 0: left as is) on `s`, one synchronisation, then every old
+// array is released and replaced: a failure leaves all of them as they were, and the caller's capacity with them.
+int grow_pool(int64_t have, const BowGrow& g, DevBuf& a, size_t ea, DevBuf* b, size_t eb, int fill, hipStream_t s)
+{
+    if (g.cap == have) return PLSLAM_OK;
+    DevBuf* const buf[2] = {&a, b};
+    const size_t elem[2] = {ea, eb};
+    FreshBlock fresh[2];
+    for (int i = 0; i < 2 && buf[i]; ++i) PLSLAM_HIP_CHECK(hipMalloc(&fresh[i].p, (size_t)g.cap * elem[i]));
+    for (int i = 0; i < 2 && buf[i]; ++i) {
+        const size_t kept = (size_t)g.keep * elem[i];
+        if (kept) PLSLAM_HIP_CHECK(hipMemcpyAsync(fresh[i].p, buf[i]->p, kept, hipMemcpyDeviceToDevice, s));
+        if (fill >= 0) PLSLAM_HIP_CHECK(hipMemsetAsync((char*)fresh[i].p + kept, fill, (size_t)g.cap * elem[i] - kept, s));
+    }
+    PLSLAM_HIP_CHECK(hipStreamSynchronize(s));      // the old blocks may still be read by enqueued work
+    for (int i = 0; i < 2 && buf[i]; ++i) {
+        buf[i]->release();
+        buf[i]->p = fresh[i].p;
+        buf[i]->cap = (size_t)g.cap * elem[i];
+        fresh[i].p = nullptr;
+    }
     return PLSLAM_OK;
+}
+
+// the growth of a plan: the table, then each pool; the capacities are recorded by bow_db_commit once all of it is through
+int db_grow(plslam_bow_db* db, const BowInsertPlan& P, hipStream_t s)
+{
+    int rc;
+    if ((rc = grow_pool(db->st.cap_kf, P.tab, db->tab, 16, nullptr, 0, 0xFF, s))) return rc;
+    if ((rc = grow_pool(db->st.p.cap, P.p, db->pw, 4, &db->pv, 8, -1, s))) return rc;
+    return grow_pool(db->st.l.cap, P.l, db->lw, 4, &db->lv, 8, -1, s);
 }
 
 DescendJob descend_job(const plslam_bow_vocab* v, const uint8_t* q, int32_t n, int32_t* word, double* weight)
 {
-    return DescendJob{v->dev(), reinterpret_cast<const uint32_t*>(q), n, (n + DESCEND_THREADS - 1) / DESCEND_THREADS, word,
-                      weight};
+    return DescendJob{v->dev(), reinterpret_cast<const uint32_t*>(q), n, bow_descend_blocks(n), word, weight};
 }
 
 int launch_descend(const DescendJob& j0, const DescendJob& j1, size_t lds, hipStream_t s)
@@ -369,13 +385,6 @@ int launch_descend(const DescendJob& j0, const DescendJob& j1, size_t lds, hipSt
     return PLSLAM_OK;
 }
 
-size_t set_lds(int32_t max_set)
-{
-    int P = 1;
-    while (P < max_set) P <<= 1;
-    return (size_t)P * 4 + SET_THREADS * 4;
-}
-
 int launch_sets(const SetJob& j0, const SetJob& j1, size_t lds, hipStream_t s)
 {
     const int nb = j0.nsets + j1.nsets;
@@ -385,13 +394,25 @@ int launch_sets(const SetJob& j0, const SetJob& j1, size_t lds, hipStream_t s)
     return PLSLAM_OK;
 }
 
-int launch_score(const ScoreArgs& a, int32_t nq, hipStream_t s)
+int launch_score(const ScoreArgs& a, int32_t nq, size_t lds, hipStream_t s)
 {
     if (nq == 0 || a.ntarget == 0) return PLSLAM_OK;
-    const size_t lds = std::max<size_t>(16, (size_t)(a.cap_p + a.cap_l) * 4);
-    hipLaunchKernelGGL(k_bow_score, dim3((a.ntarget + 3) / 4, nq), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(k_bow_score, dim3(bow_score_grid_x(a.ntarget), nq), dim3(256), lds, s, a);
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
+}
+
+// what K21 reads of a database whichever call launches it
+ScoreArgs score_args(const plslam_bow_db* db)
+{
+    ScoreArgs a{};
+    a.tab = db->tab.as<int32_t>();
+    a.pw = db->pw.as<int32_t>();
+    a.pv = db->pv.as<double>();
+    a.lw = db->lw.as<int32_t>();
+    a.lv = db->lv.as<double>();
+    a.mode = db->st.mode;
+    return a;
 }
 
 // the dynamic-LDS limits of K20 / K21 on the CURRENT device (asked for every vocabulary / database: a process-wide once would
@@ -405,6 +426,17 @@ int raise_lds_limits()
     return PLSLAM_OK;
 }
 
+int upload(DevBuf& b, const void* src, size_t bytes)
+{
+    int rc;
+    if ((rc = b.reserve(bytes))) return rc;
+    if (hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        set_last_error("bow vocabulary: upload failed");
+        return PLSLAM_EHIP;
+    }
+    return PLSLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -413,92 +445,25 @@ int plslam_bow_vocab_create(plslam_ctx* ctx, const plslam_bow_vocab_desc* d, pls
 {
     PLSLAM_REQUIRE(ctx && d && out, PLSLAM_EINVAL);
     *out = nullptr;
-    const int32_t N = d->n_nodes, W = d->n_words;
-    if (N <= 0 || W <= 0) return fail(PLSLAM_EINVAL, "bow vocabulary: empty (%ld nodes, %ld words)", N, W);
-    PLSLAM_REQUIRE(d->nodes && d->words, PLSLAM_EINVAL);
-    if (d->scoring_type != PLSLAM_BOW_L1_NORM)
-        return fail(PLSLAM_ENOTSUP, "bow vocabulary: scoring type %ld is not supported (only L1_NORM = 0)", d->scoring_type);
-    if (d->weighting_type < PLSLAM_BOW_TF_IDF || d->weighting_type > PLSLAM_BOW_BINARY)
-        return fail(PLSLAM_EINVAL, "bow vocabulary: weighting type %ld out of range", d->weighting_type);
-    // children lists in file order (TemplatedVocabulary.h:1470 m_nodes[pid].children.push_back(nid)), as CSR
-    std::vector<int32_t> rec_of((size_t)N + 1, -1), nchild((size_t)N + 2, 0);
-    for (int32_t r = 0; r < N; ++r) {
-        const int32_t id = d->nodes[r].node_id, pid = d->nodes[r].parent_id;
-        if (id < 1 || id > N) return fail(PLSLAM_EINVAL, "bow vocabulary: node id %ld out of range 1..%ld", id, N);
-        if (rec_of[id] >= 0) return fail(PLSLAM_EINVAL, "bow vocabulary: duplicate node id %ld", id);
-        if (pid < 0 || pid > N) return fail(PLSLAM_EINVAL, "bow vocabulary: parent %ld of node %ld is not a node", pid, id);
-        if (pid == id) return fail(PLSLAM_EINVAL, "bow vocabulary: node %ld is its own parent (cycle)", id);
-        rec_of[id] = r;
-        ++nchild[pid + 1];
-    }
-    std::vector<int32_t> first((size_t)N + 2, 0);
-    for (int32_t i = 0; i <= N; ++i) first[i + 1] = first[i] + nchild[i + 1];
-    std::vector<int32_t> kids((size_t)N), fill(first.begin(), first.end() - 1);
-    for (int32_t r = 0; r < N; ++r) kids[fill[d->nodes[r].parent_id]++] = d->nodes[r].node_id;
-    // words
-    std::vector<int32_t> word_of((size_t)N + 1, -1), node_of_word((size_t)W, -1);
-    for (int32_t r = 0; r < W; ++r) {
-        const int32_t wid = d->words[r].word_id, nid = d->words[r].node_id;
-        if (wid < 0 || wid >= W) return fail(PLSLAM_EINVAL, "bow vocabulary: word id %ld out of range 0..%ld", wid, W - 1);
-        if (nid < 1 || nid > N) return fail(PLSLAM_EINVAL, "bow vocabulary: word %ld names node %ld, not a node", wid, nid);
-        if (node_of_word[wid] >= 0) return fail(PLSLAM_EINVAL, "bow vocabulary: duplicate word id %ld", wid);
-        if (word_of[nid] >= 0) return fail(PLSLAM_EINVAL, "bow vocabulary: node %ld carries two words", nid);
-        node_of_word[wid] = nid;
-        word_of[nid] = wid;
-    }
-    // breadth-first order from the root: every parent's children contiguous, in list order
-    std::vector<int32_t> order;
-    order.reserve((size_t)N + 1);
-    order.push_back(0);
-    for (size_t h = 0; h < order.size(); ++h) {
-        const int32_t u = order[h];
-        for (int32_t c = first[u]; c < first[u + 1]; ++c) order.push_back(kids[c]);
-        if (order.size() > (size_t)N + 1) break;
-    }
-    if (order.size() != (size_t)N + 1)
-        return fail(PLSLAM_EINVAL, "bow vocabulary: %ld of %ld nodes are not reachable from the root (a cycle)",
-                    (long)N + 1 - (long)order.size(), N);
-    std::vector<int32_t> pos((size_t)N + 1);
-    for (int32_t i = 0; i <= N; ++i) pos[order[i]] = i;
-    std::vector<int32_t> links((size_t)2 * (N + 1));
-    std::vector<uint8_t> desc((size_t)32 * (N + 1), 0);
-    std::vector<double> node_w((size_t)N + 1, 0.0), word_w((size_t)W, 0.0);
-    for (int32_t i = 0; i <= N; ++i) {
-        const int32_t u = order[i], nc = first[u + 1] - first[u];
-        if (nc == 0 && word_of[u] < 0) return fail(PLSLAM_EINVAL, "bow vocabulary: leaf node %ld has no word", u);
-        links[2 * (size_t)i] = nc ? pos[kids[first[u]]] : word_of[u];
-        links[2 * (size_t)i + 1] = nc;
-        if (u > 0) {
-            std::memcpy(&desc[32 * (size_t)i], d->nodes[rec_of[u]].descriptor, 32);
-            node_w[i] = d->nodes[rec_of[u]].weight;
-        }
-    }
-    for (int32_t w = 0; w < W; ++w) word_w[w] = d->nodes[rec_of[node_of_word[w]]].weight;
-
+    BowVocabFlat F;
+    int rc;
+    if ((rc = bow_vocab_flatten(d, &F))) return refuse(rc, F.why);
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    int rc;
     if ((rc = raise_lds_limits())) return rc;
     plslam_bow_vocab* v = new plslam_bow_vocab();
     v->ctx = ctx;
     v->k = d->k;
     v->L = d->L;
     v->weighting = d->weighting_type;
-    v->n = N + 1;
-    v->n_words = W;
-    v->n_stage = std::min(N + 1, STAGE_NODES);
-    if ((rc = v->links.reserve(links.size() * 4)) || (rc = v->desc.reserve(desc.size())) ||
-        (rc = v->node_w.reserve(node_w.size() * 8)) || (rc = v->word_w.reserve(word_w.size() * 8))) {
+    v->n = F.n;
+    v->n_words = F.n_words;
+    v->n_stage = F.n_stage;
+    if ((rc = upload(v->links, F.links.data(), F.links.size() * 4)) || (rc = upload(v->desc, F.desc.data(), F.desc.size())) ||
+        (rc = upload(v->node_w, F.node_w.data(), F.node_w.size() * 8)) ||
+        (rc = upload(v->word_w, F.word_w.data(), F.word_w.size() * 8))) {
         plslam_bow_vocab_destroy(v);
         return rc;
-    }
-    if (hipMemcpy(v->links.p, links.data(), links.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->desc.p, desc.data(), desc.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->node_w.p, node_w.data(), node_w.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(v->word_w.p, word_w.data(), word_w.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        set_last_error("bow vocabulary: upload failed");
-        plslam_bow_vocab_destroy(v);
-        return PLSLAM_EHIP;
     }
     *out = v;
     return PLSLAM_OK;
@@ -517,75 +482,62 @@ void plslam_bow_vocab_destroy(plslam_bow_vocab* v)
     delete v;
 }
 
-static int transform_enqueue(plslam_bow_vocab* v, const uint8_t* desc, const int32_t* off, int32_t nsets, int32_t total,
-                             int32_t max_set, int32_t* word, double* weight, int32_t* bow_word, double* bow_w, int32_t* bow_len,
-                             hipStream_t s)
+static int transform_enqueue(plslam_bow_vocab* v, const uint8_t* desc, const int32_t* off, const BowTransformCheck& C,
+                             int32_t* word, double* weight, int32_t* bow_word, double* bow_w, int32_t* bow_len, hipStream_t s)
 {
     DescendJob none{};
-    if (total > 0) {
-        const DescendJob j = descend_job(v, desc, total, word, weight);
-        int rc = launch_descend(j, none, v->stage_bytes(), s);
+    if (C.total > 0) {
+        const DescendJob j = descend_job(v, desc, C.total, word, weight);
+        int rc = launch_descend(j, none, bow_stage_bytes(v->n_stage), s);
         if (rc) return rc;
     }
-    SetJob sj{off, 0, nsets, max_set, v->weighting, word, v->word_w.as<double>(), bow_word, bow_w, bow_len, nullptr, 0};
+    SetJob sj{off, 0, C.nsets, C.max_set, v->weighting, word, v->word_w.as<double>(), bow_word, bow_w, bow_len, nullptr, 0};
     SetJob sn{};
-    return launch_sets(sj, sn, set_lds(max_set), s);
+    return launch_sets(sj, sn, bow_set_lds(C.max_set), s);
 }
 
 int plslam_bow_transform_dev(plslam_bow_vocab* v, const uint8_t* desc, const int32_t* offsets, int32_t nsets, int32_t total,
                              int32_t max_set, int32_t* word_id, double* word_weight, int32_t* bow_word, double* bow_weight,
                              int32_t* bow_len, void* stream)
 {
-    PLSLAM_REQUIRE(v && nsets >= 0 && total >= 0 && max_set >= 0, PLSLAM_EINVAL);
-    if (max_set > PLSLAM_BOW_MAX_SET) return fail(PLSLAM_ERANGE, "bow transform: max_set %ld > PLSLAM_BOW_MAX_SET (%ld)", max_set,
-                                                  PLSLAM_BOW_MAX_SET);
-    if (nsets == 0) return PLSLAM_OK;
-    PLSLAM_REQUIRE(offsets && word_id && bow_word && bow_weight && bow_len && (total == 0 || desc), PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(((uintptr_t)desc & 15) == 0, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(v, PLSLAM_EINVAL);
+    BowTransformCheck C;
+    int rc;
+    if ((rc = bow_transform_check_dev(desc, offsets, nsets, total, max_set, word_id, bow_word, bow_weight, bow_len, &C)))
+        return refuse(rc, C.why);
+    if (C.nsets == 0) return PLSLAM_OK;
     DeviceGuard g(v->ctx->device);
-    return transform_enqueue(v, desc, offsets, nsets, total, max_set, word_id, word_weight, bow_word, bow_weight, bow_len,
+    return transform_enqueue(v, desc, offsets, C, word_id, word_weight, bow_word, bow_weight, bow_len,
                              stream ? static_cast<hipStream_t>(stream) : v->ctx->stream);
 }
 
 int plslam_bow_transform(plslam_bow_vocab* v, const uint8_t* desc, const int32_t* offsets, int32_t nsets, int32_t* word_id,
                          double* word_weight, int32_t* bow_word, double* bow_weight, int32_t* bow_len)
 {
-    PLSLAM_REQUIRE(v && nsets >= 0, PLSLAM_EINVAL);
-    if (nsets == 0) return PLSLAM_OK;
-    PLSLAM_REQUIRE(offsets && bow_len && offsets[0] == 0, PLSLAM_EINVAL);
-    int32_t max_set = 0;
-    for (int32_t s = 0; s < nsets; ++s) {
-        const int64_t n = (int64_t)offsets[s + 1] - offsets[s];
-        PLSLAM_REQUIRE(n >= 0, PLSLAM_EINVAL);
-        if (n > PLSLAM_BOW_MAX_SET)
-            return fail(PLSLAM_ERANGE, "bow transform: set of %ld descriptors > PLSLAM_BOW_MAX_SET (%ld)", (long)n,
-                        PLSLAM_BOW_MAX_SET);
-        max_set = std::max<int32_t>(max_set, (int32_t)n);
-    }
-    const int32_t total = offsets[nsets];
-    PLSLAM_REQUIRE(total == 0 || desc, PLSLAM_EINVAL);
+    PLSLAM_REQUIRE(v, PLSLAM_EINVAL);
+    BowTransformCheck C;
+    int rc;
+    if ((rc = bow_transform_check_host(desc, offsets, nsets, bow_len, &C))) return refuse(rc, C.why);
+    if (C.nsets == 0) return PLSLAM_OK;
+    const BowTransformLayout L = bow_transform_layout(C.nsets, C.total);
+    const size_t total = (size_t)C.total;
     plslam_ctx* ctx = v->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    Carver c;
-    const size_t oD = c.take((size_t)total * 32), oO = c.take((size_t)(nsets + 1) * 4), oW = c.take((size_t)total * 4),
-                 oV = c.take((size_t)total * 8), oBW = c.take((size_t)total * 4), oBV = c.take((size_t)total * 8),
-                 oL = c.take((size_t)nsets * 4);
-    int rc;
-    if ((rc = ctx->in_a.reserve(c.off))) return rc;
+    if ((rc = ctx->in_a.reserve(L.bytes))) return rc;
     char* d = ctx->in_a.as<char>();
     hipStream_t s = ctx->stream;
     StreamSyncOnError guard(s);
-    if (total) PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oD, desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oO, offsets, (size_t)(nsets + 1) * 4, hipMemcpyHostToDevice, s));
-    if ((rc = transform_enqueue(v, (const uint8_t*)(d + oD), (const int32_t*)(d + oO), nsets, total, max_set, (int32_t*)(d + oW),
-                                (double*)(d + oV), (int32_t*)(d + oBW), (double*)(d + oBV), (int32_t*)(d + oL), s)))
+    if (total) PLSLAM_HIP_CHECK(hipMemcpyAsync(d + L.oD, desc, total * 32, hipMemcpyHostToDevice, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + L.oO, offsets, ((size_t)C.nsets + 1) * 4, hipMemcpyHostToDevice, s));
+    if ((rc = transform_enqueue(v, (const uint8_t*)(d + L.oD), (const int32_t*)(d + L.oO), C, (int32_t*)(d + L.oW),
+                                (double*)(d + L.oV), (int32_t*)(d + L.oBW), (double*)(d + L.oBV), (int32_t*)(d + L.oL), s)))
         return rc;
-    if (total && word_id) PLSLAM_HIP_CHECK(hipMemcpyAsync(word_id, d + oW, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-    if (total && word_weight) PLSLAM_HIP_CHECK(hipMemcpyAsync(word_weight, d + oV, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    if (total && bow_word) PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_word, d + oBW, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-    if (total && bow_weight) PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_weight, d + oBV, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_len, d + oL, (size_t)nsets * 4, hipMemcpyDeviceToHost, s));
+    if (total && word_id) PLSLAM_HIP_CHECK(hipMemcpyAsync(word_id, d + L.oW, total * 4, hipMemcpyDeviceToHost, s));
+    if (total && word_weight) PLSLAM_HIP_CHECK(hipMemcpyAsync(word_weight, d + L.oV, total * 8, hipMemcpyDeviceToHost, s));
+    if (total && bow_word) PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_word, d + L.oBW, total * 4, hipMemcpyDeviceToHost, s));
+    if (total && bow_weight) PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_weight, d + L.oBV, total * 8, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(bow_len, d + L.oL, (size_t)C.nsets * 4, hipMemcpyDeviceToHost, s));
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
     return PLSLAM_OK;
@@ -605,19 +557,13 @@ int plslam_bow_db_create(plslam_ctx* ctx, plslam_bow_vocab* vocab_p, plslam_bow_
     db->ctx = ctx;
     db->vp = vocab_p;
     db->vl = vocab_l;
-    db->mode = (vocab_p ? 1 : 0) | (vocab_l ? 2 : 0);
-    const int64_t cap = std::max<int32_t>(capacity_hint, 16);
-    int64_t c0 = 0;
-    rc = grow(db->tab, 16, c0, cap, 0, 0xFF, ctx->stream);
-    db->cap_kf = (int32_t)c0;
-    if (!rc && vocab_p) rc = grow(db->pw, 4, db->cap_p, cap * 256, 0, -1, ctx->stream);
-    if (!rc && vocab_p) { int64_t c = 0; rc = grow(db->pv, 8, c, db->cap_p, 0, -1, ctx->stream); }
-    if (!rc && vocab_l) rc = grow(db->lw, 4, db->cap_l, cap * 64, 0, -1, ctx->stream);
-    if (!rc && vocab_l) { int64_t c = 0; rc = grow(db->lv, 8, c, db->cap_l, 0, -1, ctx->stream); }
-    if (rc) {
+    db->st.mode = (vocab_p ? 1 : 0) | (vocab_l ? 2 : 0);
+    const BowInsertPlan P = bow_db_initial(capacity_hint, db->st.mode);
+    if ((rc = db_grow(db, P, ctx->stream))) {
         plslam_bow_db_destroy(db);
         return rc;
     }
+    bow_db_commit(db->st, P, nullptr);
     *out = db;
     return PLSLAM_OK;
 }
@@ -638,137 +584,73 @@ void plslam_bow_db_destroy(plslam_bow_db* db)
 int plslam_bow_db_size(plslam_bow_db* db, int32_t* n)
 {
     PLSLAM_REQUIRE(db && n, PLSLAM_EINVAL);
-    *n = db->size;
+    *n = db->st.size;
     return PLSLAM_OK;
 }
 
-// host-side bookkeeping and growth in front of an insert; the caller holds the context lock (host path) or owns the db (dev)
-static int db_prepare(plslam_bow_db* db, int32_t kf_idx, int32_t n_p, int32_t n_l, int64_t& off_p, int64_t& off_l)
-{
-    hipStream_t s = db->ctx->stream;
-    int rc;
-    int64_t cap_kf = db->cap_kf;
-    if ((rc = grow(db->tab, 16, cap_kf, (int64_t)kf_idx + 1, db->size, 0xFF, s))) return rc;
-    db->cap_kf = (int32_t)cap_kf;
-    off_p = db->used_p;
-    off_l = db->used_l;
-    if (db->mode & 1) {
-        int64_t c = db->cap_p;
-        if ((rc = grow(db->pw, 4, db->cap_p, db->used_p + n_p, db->used_p, -1, s))) return rc;
-        if ((rc = grow(db->pv, 8, c, db->cap_p, db->used_p, -1, s))) return rc;
-    }
-    if (db->mode & 2) {
-        int64_t c = db->cap_l;
-        if ((rc = grow(db->lw, 4, db->cap_l, db->used_l + n_l, db->used_l, -1, s))) return rc;
-        if ((rc = grow(db->lv, 8, c, db->cap_l, db->used_l, -1, s))) return rc;
-    }
-    if ((int32_t)db->res_p.size() <= kf_idx) {
-        db->res_p.resize((size_t)kf_idx + 1, 0);
-        db->res_l.resize((size_t)kf_idx + 1, 0);
-        db->inserted.resize((size_t)kf_idx + 1, 0);
-        db->stats.resize((size_t)kf_idx + 1, plslam_bow_pl_stats{0, 0, 0.0, 0.0});
-    }
-    if ((off_p + n_p) > INT32_MAX || (off_l + n_l) > INT32_MAX)
-        return fail(PLSLAM_ERANGE, "bow database: more than 2^31 stored entries");
-    return PLSLAM_OK;
-}
-
-static void db_commit(plslam_bow_db* db, int32_t kf_idx, int32_t n_p, int32_t n_l, const plslam_bow_pl_stats* stats)
-{
-    if (db->mode & 1) { db->res_p[kf_idx] = n_p; db->used_p += n_p; }
-    if (db->mode & 2) { db->res_l[kf_idx] = n_l; db->used_l += n_l; }
-    db->inserted[kf_idx] = 1;
-    db->stats[kf_idx] = stats ? *stats : plslam_bow_pl_stats{0, 0, 0.0, 0.0};
-    db->size = std::max(db->size, kf_idx + 1);
-}
-
-// K19 + K20 + K21 of one insert on `s`; pdesc / ldesc / alive / row are device pointers
-static int db_enqueue_insert(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t n_p, const uint8_t* ldesc,
-                             int32_t n_l, const plslam_bow_pl_stats* stats, const uint8_t* alive, double* row, int32_t* words,
-                             int64_t off_p, int64_t off_l, hipStream_t s)
+// K19 + K20 + K21 of one planned insert on `s`; pdesc / ldesc / alive / row / words are device pointers
+static int db_enqueue_insert(plslam_bow_db* db, const BowInsertPlan& P, const uint8_t* pdesc, const uint8_t* ldesc,
+                             const plslam_bow_pl_stats* stats, const uint8_t* alive, double* row, int32_t* words, hipStream_t s)
 {
     DescendJob jp{}, jl{};
     SetJob sp{}, sl{};
-    int32_t* tab = db->tab.as<int32_t>() + 4 * (size_t)kf_idx;
-    if (db->mode & 1) {
-        jp = descend_job(db->vp, pdesc, n_p, words, nullptr);
-        sp = SetJob{nullptr, n_p, 1, n_p, db->vp->weighting, words, db->vp->word_w.as<double>(), db->pw.as<int32_t>() + off_p,
-                    db->pv.as<double>() + off_p, nullptr, tab, (int32_t)off_p};
+    int32_t* tab = db->tab.as<int32_t>() + 4 * (size_t)P.kf_idx;
+    if (db->st.mode & 1) {
+        jp = descend_job(db->vp, pdesc, P.n_p, words, nullptr);
+        sp = SetJob{nullptr, P.n_p, 1, P.n_p, db->vp->weighting, words, db->vp->word_w.as<double>(),
+                    db->pw.as<int32_t>() + P.off_p, db->pv.as<double>() + P.off_p, nullptr, tab, (int32_t)P.off_p};
     }
-    if (db->mode & 2) {
-        jl = descend_job(db->vl, ldesc, n_l, words + n_p, nullptr);
-        sl = SetJob{nullptr, n_l, 1, n_l, db->vl->weighting, words + n_p, db->vl->word_w.as<double>(),
-                    db->lw.as<int32_t>() + off_l, db->lv.as<double>() + off_l, nullptr, tab + 2, (int32_t)off_l};
+    if (db->st.mode & 2) {
+        jl = descend_job(db->vl, ldesc, P.n_l, words + P.n_p, nullptr);
+        sl = SetJob{nullptr, P.n_l, 1, P.n_l, db->vl->weighting, words + P.n_p, db->vl->word_w.as<double>(),
+                    db->lw.as<int32_t>() + P.off_l, db->lv.as<double>() + P.off_l, nullptr, tab + 2, (int32_t)P.off_l};
     }
     int rc;
-    size_t lds = std::max(db->vp ? db->vp->stage_bytes() : 0, db->vl ? db->vl->stage_bytes() : 0);
+    const size_t lds = std::max(db->vp ? bow_stage_bytes(db->vp->n_stage) : 0, db->vl ? bow_stage_bytes(db->vl->n_stage) : 0);
     if ((rc = launch_descend(jp.n ? jp : DescendJob{}, jl.n ? jl : DescendJob{}, lds, s))) return rc;
-    if ((rc = launch_sets(sp, sl, set_lds(std::max(n_p, n_l)), s))) return rc;
-    ScoreArgs a{};
-    a.tab = db->tab.as<int32_t>();
-    a.pw = db->pw.as<int32_t>();
-    a.pv = db->pv.as<double>();
-    a.lw = db->lw.as<int32_t>();
-    a.lv = db->lv.as<double>();
-    a.mode = db->mode;
-    a.ntarget = kf_idx + 1;
-    a.cap_p = (db->mode & 1) ? n_p : 0;
-    a.cap_l = (db->mode & 2) ? n_l : 0;
-    a.query0 = kf_idx;
+    if ((rc = launch_sets(sp, sl, P.sets_lds, s))) return rc;
+    ScoreArgs a = score_args(db);
+    a.ntarget = P.kf_idx + 1;
+    a.cap_p = P.n_p;
+    a.cap_l = P.n_l;
+    a.query0 = P.kf_idx;
     a.stats0 = stats ? *stats : plslam_bow_pl_stats{0, 0, 0.0, 0.0};
     a.alive = alive;
     a.out = row;
     a.out_stride = 0;
-    return launch_score(a, 1, s);
-}
-
-static int check_insert(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t& n_p, const uint8_t* ldesc,
-                        int32_t& n_l, const plslam_bow_pl_stats* stats, const uint8_t* alive, const double* row)
-{
-    PLSLAM_REQUIRE(db && kf_idx >= 0 && kf_idx < INT32_MAX && row && (kf_idx == 0 || alive), PLSLAM_EINVAL);
-    if (!(db->mode & 1)) n_p = 0;
-    if (!(db->mode & 2)) n_l = 0;
-    PLSLAM_REQUIRE(n_p >= 0 && n_l >= 0 && (n_p == 0 || pdesc) && (n_l == 0 || ldesc), PLSLAM_EINVAL);
-    PLSLAM_REQUIRE(db->mode != 3 || stats, PLSLAM_EINVAL);
-    if (n_p > PLSLAM_BOW_MAX_SET || n_l > PLSLAM_BOW_MAX_SET)
-        return fail(PLSLAM_ERANGE, "bow insert: %ld point / %ld line descriptors; at most PLSLAM_BOW_MAX_SET each", n_p, n_l);
-    return PLSLAM_OK;
+    return launch_score(a, 1, P.score_lds, s);
 }
 
 int plslam_bow_db_insert(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t n_pdesc, const uint8_t* ldesc,
                          int32_t n_ldesc, const plslam_bow_pl_stats* stats, const uint8_t* alive, double* conf_row)
 {
+    PLSLAM_REQUIRE(db, PLSLAM_EINVAL);
+    BowInsertPlan P;
     int rc;
-    if ((rc = check_insert(db, kf_idx, pdesc, n_pdesc, ldesc, n_ldesc, stats, alive, conf_row))) return rc;
-    for (int32_t i = 0; i < kf_idx; ++i)
-        if (alive[i] && (i >= (int32_t)db->inserted.size() || !db->inserted[i]))
-            return fail(PLSLAM_EINVAL, "bow insert: keyframe %ld is alive but was never inserted", i);
+    if ((rc = bow_insert_check(db->st, kf_idx, pdesc, n_pdesc, ldesc, n_ldesc, stats, alive, conf_row, true, &P)))
+        return refuse(rc, P.why);
     plslam_ctx* ctx = db->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
     StreamSyncOnError guard(s);
-    int64_t off_p, off_l;
-    if ((rc = db_prepare(db, kf_idx, n_pdesc, n_ldesc, off_p, off_l))) return rc;
-    Carver c;
-    const size_t oP = c.take((size_t)n_pdesc * 32), oL = c.take((size_t)n_ldesc * 32), oA = c.take((size_t)kf_idx + 1);
-    const size_t up = c.off;
-    const size_t oW = c.take((size_t)(n_pdesc + n_ldesc) * 4), oR = c.take((size_t)(kf_idx + 1) * 8);
-    if ((rc = db->scratch.reserve(c.off)) || (rc = db->pin_in.reserve(up)) || (rc = db->pin_out.reserve((size_t)(kf_idx + 1) * 8)))
+    if ((rc = bow_db_plan_insert(db->st, kf_idx, n_pdesc, n_ldesc, true, &P))) return refuse(rc, P.why);
+    if ((rc = db_grow(db, P, s)) || (rc = db->scratch.reserve(P.scratch_bytes)) || (rc = db->pin_in.reserve(P.pin_in_bytes)) ||
+        (rc = db->pin_out.reserve(P.pin_out_bytes)))
         return rc;
     char* h = db->pin_in.as<char>();
-    if (n_pdesc) std::memcpy(h + oP, pdesc, (size_t)n_pdesc * 32);
-    if (n_ldesc) std::memcpy(h + oL, ldesc, (size_t)n_ldesc * 32);
-    if (kf_idx) std::memcpy(h + oA, alive, (size_t)kf_idx);
+    if (P.n_p) std::memcpy(h + P.oP, pdesc, (size_t)P.n_p * 32);
+    if (P.n_l) std::memcpy(h + P.oL, ldesc, (size_t)P.n_l * 32);
+    if (kf_idx) std::memcpy(h + P.oA, alive, (size_t)kf_idx);
     char* d = db->scratch.as<char>();
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, s));
-    if ((rc = db_enqueue_insert(db, kf_idx, (const uint8_t*)(d + oP), n_pdesc, (const uint8_t*)(d + oL), n_ldesc, stats,
-                                (const uint8_t*)(d + oA), (double*)(d + oR), (int32_t*)(d + oW), off_p, off_l, s)))
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d, h, P.up, hipMemcpyHostToDevice, s));
+    if ((rc = db_enqueue_insert(db, P, (const uint8_t*)(d + P.oP), (const uint8_t*)(d + P.oL), stats, (const uint8_t*)(d + P.oA),
+                                (double*)(d + P.oR), (int32_t*)(d + P.oW), s)))
         return rc;
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(db->pin_out.p, d + oR, (size_t)(kf_idx + 1) * 8, hipMemcpyDeviceToHost, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(db->pin_out.p, d + P.oR, P.pin_out_bytes, hipMemcpyDeviceToHost, s));
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
-    db_commit(db, kf_idx, n_pdesc, n_ldesc, stats);
+    bow_db_commit(db->st, P, stats);
     const double* r = db->pin_out.as<double>();
     for (int32_t i = 0; i < kf_idx; ++i)
         if (alive[i]) conf_row[i] = r[i];
@@ -779,67 +661,47 @@ int plslam_bow_db_insert(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc
 int plslam_bow_db_insert_dev(plslam_bow_db* db, int32_t kf_idx, const uint8_t* pdesc, int32_t n_pdesc, const uint8_t* ldesc,
                              int32_t n_ldesc, const plslam_bow_pl_stats* stats, const uint8_t* alive, double* conf_row)
 {
+    PLSLAM_REQUIRE(db, PLSLAM_EINVAL);
+    BowInsertPlan P;
     int rc;
-    if ((rc = check_insert(db, kf_idx, pdesc, n_pdesc, ldesc, n_ldesc, stats, alive, conf_row))) return rc;
-    PLSLAM_REQUIRE(((uintptr_t)pdesc & 15) == 0 && ((uintptr_t)ldesc & 15) == 0 && ((uintptr_t)conf_row & 7) == 0, PLSLAM_EINVAL);
+    if ((rc = bow_insert_check(db->st, kf_idx, pdesc, n_pdesc, ldesc, n_ldesc, stats, alive, conf_row, false, &P)) ||
+        (rc = bow_db_plan_insert(db->st, kf_idx, n_pdesc, n_ldesc, false, &P)))
+        return refuse(rc, P.why);
     DeviceGuard g(db->ctx->device);
     hipStream_t s = db->ctx->stream;
-    int64_t off_p, off_l;
-    if ((rc = db_prepare(db, kf_idx, n_pdesc, n_ldesc, off_p, off_l))) return rc;
-    if ((rc = db->scratch.reserve((size_t)(n_pdesc + n_ldesc) * 4 + 16))) return rc;
-    if ((rc = db_enqueue_insert(db, kf_idx, pdesc, n_pdesc, ldesc, n_ldesc, stats, alive, conf_row, db->scratch.as<int32_t>(),
-                                off_p, off_l, s)))
-        return rc;
-    db_commit(db, kf_idx, n_pdesc, n_ldesc, stats);
+    if ((rc = db_grow(db, P, s)) || (rc = db->scratch.reserve(P.scratch_bytes))) return rc;
+    if ((rc = db_enqueue_insert(db, P, pdesc, ldesc, stats, alive, conf_row, db->scratch.as<int32_t>(), s))) return rc;
+    bow_db_commit(db->st, P, stats);
     return PLSLAM_OK;
 }
 
 int plslam_bow_db_score(plslam_bow_db* db, const int32_t* queries, int32_t nq, double* out)
 {
-    PLSLAM_REQUIRE(db && nq >= 0, PLSLAM_EINVAL);
-    if (nq == 0 || db->size == 0) return PLSLAM_OK;
-    PLSLAM_REQUIRE(queries && out, PLSLAM_EINVAL);
-    int32_t cap_p = 0, cap_l = 0;
-    std::vector<plslam_bow_pl_stats> st((size_t)nq);
-    for (int32_t q = 0; q < nq; ++q) {
-        const int32_t k = queries[q];
-        if (k < 0 || k >= db->size || !db->inserted[k])
-            return fail(PLSLAM_EINVAL, "bow score: query %ld (keyframe %ld) was never inserted", q, k);
-        cap_p = std::max(cap_p, (db->mode & 1) ? db->res_p[k] : 0);
-        cap_l = std::max(cap_l, (db->mode & 2) ? db->res_l[k] : 0);
-        st[q] = db->stats[k];
-    }
-    const int32_t n = db->size;
+    PLSLAM_REQUIRE(db, PLSLAM_EINVAL);
+    BowScorePlan P;
+    int rc;
+    if ((rc = bow_score_plan(db->st, queries, nq, out, &P))) return refuse(rc, P.why);
+    if (P.nq == 0 || P.n == 0) return PLSLAM_OK;
     plslam_ctx* ctx = db->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
     hipStream_t s = ctx->stream;
     StreamSyncOnError guard(s);
-    Carver c;
-    const size_t oQ = c.take((size_t)nq * 4), oS = c.take((size_t)nq * sizeof(plslam_bow_pl_stats));
-    const size_t oO = c.take((size_t)nq * n * 8);
-    int rc;
-    if ((rc = db->scratch.reserve(c.off))) return rc;
+    if ((rc = db->scratch.reserve(P.bytes))) return rc;
     char* d = db->scratch.as<char>();
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oQ, queries, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + oS, st.data(), (size_t)nq * sizeof(plslam_bow_pl_stats), hipMemcpyHostToDevice, s));
-    ScoreArgs a{};
-    a.tab = db->tab.as<int32_t>();
-    a.pw = db->pw.as<int32_t>();
-    a.pv = db->pv.as<double>();
-    a.lw = db->lw.as<int32_t>();
-    a.lv = db->lv.as<double>();
-    a.mode = db->mode;
-    a.ntarget = n;
-    a.cap_p = cap_p;
-    a.cap_l = cap_l;
-    a.queries = (const int32_t*)(d + oQ);
-    a.stats = (const plslam_bow_pl_stats*)(d + oS);
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + P.oQ, queries, (size_t)P.nq * 4, hipMemcpyHostToDevice, s));
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(d + P.oS, P.st.data(), (size_t)P.nq * sizeof(plslam_bow_pl_stats), hipMemcpyHostToDevice, s));
+    ScoreArgs a = score_args(db);
+    a.ntarget = P.n;
+    a.cap_p = P.cap_p;
+    a.cap_l = P.cap_l;
+    a.queries = (const int32_t*)(d + P.oQ);
+    a.stats = (const plslam_bow_pl_stats*)(d + P.oS);
     a.alive = nullptr;
-    a.out = (double*)(d + oO);
-    a.out_stride = n;
-    if ((rc = launch_score(a, nq, s))) return rc;
-    PLSLAM_HIP_CHECK(hipMemcpyAsync(out, d + oO, (size_t)nq * n * 8, hipMemcpyDeviceToHost, s));
+    a.out = (double*)(d + P.oO);
+    a.out_stride = P.n;
+    if ((rc = launch_score(a, P.nq, P.score_lds, s))) return rc;
+    PLSLAM_HIP_CHECK(hipMemcpyAsync(out, d + P.oO, (size_t)P.nq * P.n * 8, hipMemcpyDeviceToHost, s));
     PLSLAM_HIP_CHECK(hipStreamSynchronize(s));
     guard.dismiss();
     return PLSLAM_OK;

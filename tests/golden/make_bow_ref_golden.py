@@ -26,7 +26,7 @@ from plslam_amd.capi import BOW_MAX_SET  # noqa: E402
 from tests import dbow_ref as R  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bow_ref_golden.npz")
-STAGE_NODES = 1228          # bow.hip: K19 stages the first 1228 breadth-first nodes in LDS
+STAGE_NODES = 1228          # bow_plan.hpp: K19 stages the first 1228 breadth-first nodes in LDS
 SENTINEL = -3.0             # not a score: conf_matrix cells the reference leaves alone keep it
 SPECIAL = [-0.0, -1.5, float("nan"), float("inf"), 1e-310, float(np.finfo(np.float64).max)]
 

@@ -439,6 +439,15 @@ int upload(DevBuf& b, const void* src, size_t bytes)
 
 }  // namespace
 
+namespace plslam {
+// K19 alone over n device rows, for the vocabulary training (bow_train.hip): word[i] = the word of row i
+int bow_descend_enqueue(plslam_bow_vocab* v, const uint8_t* q, int32_t n, int32_t* word, hipStream_t s)
+{
+    if (n <= 0) return PLSLAM_OK;
+    return launch_descend(descend_job(v, q, n, word, nullptr), DescendJob{}, bow_stage_bytes(v->n_stage), s);
+}
+}  // namespace plslam
+
 extern "C" {
 
 int plslam_bow_vocab_create(plslam_ctx* ctx, const plslam_bow_vocab_desc* d, plslam_bow_vocab** out)

@@ -5,6 +5,8 @@
 //        3rdparty/DBoW2/include/DBoW2/TemplatedVocabulary.h:1046-1100
 //   double Vocabulary::score(const BowVector& v1, const BowVector& v2) const   -> L1Scoring::score, ScoringObject.cpp:23-67
 //   MapHandler::insertKFBowVector{P,L,PL}(KeyFrame*)   src/mapHandler.cpp:3007-3128 (conf_matrix filled symmetrically)
+//   void Vocabulary::create(const std::vector<std::vector<cv::Mat>>& training_features, int k, int L, WeightingType, ScoringType)
+//        TemplatedVocabulary.h:536-976 -> PlslamBow::train (include/plslam_bow_train.h: the three departures from create)
 // The BowVector is a template argument: DBoW2::BowVector (a std::map<WordId, WordValue>) or any map with clear() and
 // operator[] works unchanged.  Descriptor blocks are templates too (cv::Mat or StVO::DescMat: rows, ptr<uchar>(), continuous
 // N x 32 rows).  Header-only; link with libplslam_hip.so.  Errors throw std::runtime_error.
@@ -18,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "plslam_bow_train.h"
 #include "plslam_hip.h"
 
 namespace PlslamBow {
@@ -91,6 +94,56 @@ private:
     mutable std::vector<int32_t> words_;
     mutable std::vector<double> weights_;
 };
+
+// A trained vocabulary: the records of TemplatedVocabulary::save in ascending node id.  desc() is what Vocabulary is
+// constructed from (valid as long as this object is).
+struct Trained {
+    int32_t k = 0, L = 0, weighting = 0;
+    std::vector<plslam_bow_node> nodes;
+    std::vector<plslam_bow_word> words;
+    plslam_bow_train_stats stats{};
+    plslam_bow_vocab_desc desc() const
+    {
+        return plslam_bow_vocab_desc{k, L, PLSLAM_BOW_L1_NORM, weighting, (int32_t)nodes.size(), (int32_t)words.size(), nodes.data(), words.data()};
+    }
+};
+
+// TemplatedVocabulary::create(training_features, k, L, weighting, L1_NORM) on the device.  rows: the documents' descriptors
+// one after the other (N x 32 bytes); doc_offsets: n_docs + 1 row offsets from 0.  max_iters = 0: the default cap.
+inline Trained train(plslam_ctx* ctx, const uint8_t* rows, const int32_t* doc_offsets, int32_t n_docs, int32_t k, int32_t L,
+                     int32_t weighting, uint64_t seed, int32_t max_iters = 0)
+{
+    const plslam_bow_train_params prm{k, L, weighting, PLSLAM_BOW_L1_NORM, seed, max_iters, 0};
+    plslam_bow_trainer* t = nullptr;
+    check(plslam_bow_train_create(ctx, &prm, rows, doc_offsets, n_docs, &t), "plslam_bow_train_create");
+    Trained out;
+    out.k = k;
+    out.L = L;
+    out.weighting = weighting;
+    int rc = plslam_bow_train_run(t, &out.stats);
+    if (rc == PLSLAM_OK) {
+        out.nodes.resize((size_t)out.stats.n_nodes);
+        out.words.resize((size_t)out.stats.n_words);
+        rc = plslam_bow_train_export(t, out.nodes.data(), out.words.data());
+    }
+    plslam_bow_train_destroy(t);
+    check(rc, "plslam_bow_train_run");
+    return out;
+}
+
+// the same over one vector of descriptor rows per document (cv::Mat or any type with ptr<uint8_t>())
+template <class Mat>
+inline Trained train(plslam_ctx* ctx, const std::vector<std::vector<Mat>>& training_features, int32_t k, int32_t L, int32_t weighting,
+                     uint64_t seed, int32_t max_iters = 0)
+{
+    std::vector<uint8_t> rows;
+    std::vector<int32_t> off(1, 0);
+    for (const auto& doc : training_features) {
+        for (const Mat& f : doc) rows.insert(rows.end(), f.template ptr<uint8_t>(), f.template ptr<uint8_t>() + PLSLAM_DESC_BYTES);
+        off.push_back((int32_t)(rows.size() / PLSLAM_DESC_BYTES));
+    }
+    return train(ctx, rows.data(), off.data(), (int32_t)training_features.size(), k, L, weighting, seed, max_iters);
+}
 
 // MapHandler's keyframe BowVectors + conf_matrix rows (src/mapHandler.cpp:3007-3128) on the device.  vocab_p or vocab_l may
 // be null: the mode of mapHandler.cpp:196-201.  The vocabularies must outlive the database.

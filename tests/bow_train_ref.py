@@ -187,10 +187,38 @@ def descend(children, ndesc, feature):
     return node
 
 
+def descend_all(children, ndesc, desc):
+    """descend() for every row of desc at once, level by level: the first minimum over a node's children by strict '<'.  The
+    children of a node are consecutive ids (HKmeansStep makes them in one go), which is asserted."""
+    first = np.array([c[0] if c else 0 for c in children], np.int64)
+    count = np.array([len(c) for c in children], np.int64)
+    for c, f in zip(children, first):
+        assert c == list(range(int(f), int(f) + len(c))), "the children of a node are not consecutive ids"
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    q = desc.view(np.uint64)                                       # (N, 4)
+    nd = np.ascontiguousarray(np.stack(ndesc), np.uint8).view(np.uint64)
+    node = np.zeros(desc.shape[0], np.int64)
+    live = np.flatnonzero(count[node] > 0)
+    while live.size:
+        at, m = first[node[live]], count[node[live]]
+        best = at.copy()
+        best_d = np.bitwise_count(q[live] ^ nd[at]).sum(axis=1, dtype=np.int64)
+        for c in range(1, int(m.max())):
+            has = np.flatnonzero(c < m)
+            d = np.bitwise_count(q[live[has]] ^ nd[at[has] + c]).sum(axis=1, dtype=np.int64)
+            less = d < best_d[has]
+            best_d[has[less]] = d[less]
+            best[has[less]] = at[has[less]] + c
+        node[live] = best
+        live = live[count[best] > 0]
+    return node
+
+
 def train(docs, k, L, weighting, draws, max_iters=1000):
     """create(training_features) for TemplatedVocabulary(k, L, weighting, L1_NORM).  docs: a list of (n_i, 32) uint8 arrays.
     Returns a dict: nodes (NODE_DTYPE, ascending node id, no root), words (WORD_DTYPE), stats, leaf (per descriptor: the node
-    of the training partition), word (per descriptor: the word of the descent), key0."""
+    of the training partition), word (per descriptor: the word of the descent), children and ndesc (the tree that descend and
+    descend_all walk)."""
     docs = [np.asarray(d, np.uint8).reshape(-1, 32) for d in docs]
     desc = np.concatenate(docs) if docs else np.zeros((0, 32), np.uint8)
     N = desc.shape[0]
@@ -203,7 +231,10 @@ def train(docs, k, L, weighting, draws, max_iters=1000):
         if not T.children[nid]:
             word_of[nid] = len(word_of)
     weight = np.zeros(nn + 1)
-    word = np.array([word_of[descend(T.children, T.ndesc, f)] for f in desc], np.int64).reshape(N)
+    word_at = np.full(nn + 1, -1, np.int64)
+    word_at[list(word_of.keys())] = list(word_of.values())
+    word = word_at[descend_all(T.children, T.ndesc, desc)] if N else np.zeros(0, np.int64)
+    assert (word >= 0).all()
     if weighting in (TF, BINARY):                                 # setNodeWeights, :923-976
         for nid in word_of:
             weight[nid] = 1.0
@@ -228,7 +259,7 @@ def train(docs, k, L, weighting, draws, max_iters=1000):
     words["node_id"] = list(word_of.keys())
     stats = dict(nodes=nn, words=len(word_of), rounds_total=T.rounds_total, rounds_max=T.rounds_max, empty_groups=T.empty,
                  capped_nodes=T.capped)
-    return dict(nodes=nodes, words=words, stats=stats, leaf=T.leaf, word=word)
+    return dict(nodes=nodes, words=words, stats=stats, leaf=T.leaf, word=word, children=T.children, ndesc=T.ndesc)
 
 
 def uniform_docs(rng, n_docs=5, lo=50, hi=400):
@@ -257,6 +288,35 @@ def duplicate_docs(rng, n_docs=4, n_distinct=30, max_rep=12):
     rows = rows[rng.permutation(rows.shape[0])]
     cuts = np.sort(rng.integers(0, rows.shape[0] + 1, n_docs - 1))
     return [rows[a:b] for a, b in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [rows.shape[0]]]))]
+
+
+# The inputs on which tests/test_bow_train_cpu.py holds this module to the reference's compiled create: stated here once, for
+# that file and for the tests that walk the same inputs again (tests/test_bow_train_cases_cpu.py).
+WEIGHTINGS = [TF_IDF, TF, IDF, BINARY]
+UNIFORM_K, UNIFORM_L = [2, 3, 10], [1, 2, 4]
+DUPLICATE_KL = [(10, 2), (3, 4), (2, 4)]
+DEPARTURE_CLUSTERED = (33, 4, 3, TF_IDF, 50)                       # (rng seed, k, L, weighting, draw seed): groups run empty
+DEPARTURE_CAPPED = (1, 4, 2, TF, 1, (1, 2))                        # (rng seed, k, L, weighting, draw seed, the caps)
+
+
+def uniform_seed0(k, L, weighting):
+    return 300 + 16 * k + 4 * L + weighting
+
+
+def duplicate_seed0(k, L, weighting):
+    return 500 + 16 * k + 4 * L + weighting
+
+
+def clean_input(make_docs, k, L, weighting, seed0):
+    """-> (docs, seed, train(docs, ..., LibcDraws(seed))) for the first seed of seed0 .. seed0 + 7 on which the restatement sees
+    no empty group and no capped node, or None: only such an input may reach the reference (which would read a released
+    matrix on any other and take the process down)."""
+    for seed in range(seed0, seed0 + 8):
+        docs = make_docs(np.random.default_rng(seed))
+        mine = train(docs, k, L, weighting, LibcDraws(seed))
+        if mine["stats"]["empty_groups"] == 0 and mine["stats"]["capped_nodes"] == 0:
+            return docs, seed, mine
+    return None
 
 
 def reference_records(O, docs, k, L, weighting, seed):

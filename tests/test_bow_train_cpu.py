@@ -31,33 +31,30 @@ def _ref(oracle):
 def _against_the_reference(O, make_docs, k, L, weighting, seed0):
     """The restatement first: an input on which it sees an empty group or a capped node is replaced by another seed and never
     reaches the reference (which would read a released matrix and take the process down)."""
-    for seed in range(seed0, seed0 + 8):
-        docs = make_docs(np.random.default_rng(seed))
-        mine = T.train(docs, k, L, weighting, T.LibcDraws(seed))
-        if mine["stats"]["empty_groups"] == 0 and mine["stats"]["capped_nodes"] == 0:
-            break
-    else:
+    found = T.clean_input(make_docs, k, L, weighting, seed0)
+    if found is None:
         pytest.fail("no input without an empty group in 8 seeds")
+    docs, seed, mine = found
     assert mine["stats"]["empty_groups"] == 0 and mine["stats"]["capped_nodes"] == 0
     nodes, words = T.reference_records(O, docs, k, L, weighting, seed)
     assert T.same_records(mine["nodes"], mine["words"], nodes, words), (k, L, weighting, seed)
     return mine
 
 
-@pytest.mark.parametrize("weighting", [T.TF_IDF, T.TF, T.IDF, T.BINARY])
-@pytest.mark.parametrize("L", [1, 2, 4])
-@pytest.mark.parametrize("k", [2, 3, 10])
+@pytest.mark.parametrize("weighting", T.WEIGHTINGS)
+@pytest.mark.parametrize("L", T.UNIFORM_L)
+@pytest.mark.parametrize("k", T.UNIFORM_K)
 def test_restatement_is_the_references_create_on_uniform_documents(oracle, k, L, weighting):
     """five documents of 50-400 uniform random descriptors, docs[0][:20] appended to each; records and weights as uint64"""
-    _against_the_reference(_ref(oracle), T.uniform_docs, k, L, weighting, 300 + 16 * k + 4 * L + weighting)
+    _against_the_reference(_ref(oracle), T.uniform_docs, k, L, weighting, T.uniform_seed0(k, L, weighting))
 
 
-@pytest.mark.parametrize("weighting", [T.TF_IDF, T.TF, T.IDF, T.BINARY])
-@pytest.mark.parametrize("k,L", [(10, 2), (3, 4), (2, 4)])
+@pytest.mark.parametrize("weighting", T.WEIGHTINGS)
+@pytest.mark.parametrize("k,L", T.DUPLICATE_KL)
 def test_restatement_is_the_references_create_on_heavy_duplicates(oracle, k, L, weighting):
     """30 distinct descriptors repeated up to 12 times: nodes with fewer distinct rows than k stop seeding early (dist_sum == 0),
     and trivial nodes hold duplicates, where the descent's word is not the training partition's leaf"""
-    mine = _against_the_reference(_ref(oracle), T.duplicate_docs, k, L, weighting, 500 + 16 * k + 4 * L + weighting)
+    mine = _against_the_reference(_ref(oracle), T.duplicate_docs, k, L, weighting, T.duplicate_seed0(k, L, weighting))
     leaf_word = {int(n): int(w) for w, n in zip(mine["words"]["word_id"], mine["words"]["node_id"])}
     if k == 10:
         assert any(leaf_word[int(l)] != int(w) for l, w in zip(mine["leaf"], mine["word"]))     # the two do differ here
@@ -81,14 +78,16 @@ def test_restatement_reproduces_the_recorded_reference_outputs():
 
 def test_departures_are_counted_by_the_restatement():
     """clustered inputs run groups empty; max_iters 1 and 2 cap nodes; the counter draws do not depend on the walk's order"""
-    docs = T.clustered_docs(np.random.default_rng(33), 4, 150, 6, 15)
-    a = T.train(docs, 4, 3, T.TF_IDF, T.CounterDraws(50))
+    rs, k, L, weighting, seed = T.DEPARTURE_CLUSTERED
+    docs = T.clustered_docs(np.random.default_rng(rs), 4, 150, 6, 15)
+    a = T.train(docs, k, L, weighting, T.CounterDraws(seed))
     assert a["stats"]["empty_groups"] > 0 and a["stats"]["capped_nodes"] == 0
-    u = T.uniform_docs(np.random.default_rng(1))
-    for cap in (1, 2):
-        s = T.train(u, 4, 2, T.TF, T.CounterDraws(1), cap)["stats"]
+    rs, ck, cL, cw, cseed, caps = T.DEPARTURE_CAPPED
+    u = T.uniform_docs(np.random.default_rng(rs))
+    for cap in caps:
+        s = T.train(u, ck, cL, cw, T.CounterDraws(cseed), cap)["stats"]
         assert s["capped_nodes"] > 0 and s["rounds_max"] == cap
-    b = T.train(docs, 4, 3, T.TF_IDF, T.CounterDraws(50))
+    b = T.train(docs, k, L, weighting, T.CounterDraws(seed))
     assert a["nodes"].tobytes() == b["nodes"].tobytes() and a["stats"] == b["stats"]
 
 

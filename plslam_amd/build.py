@@ -19,22 +19,23 @@ OUT = os.path.join(_HERE, "lib", "libplslam_hip.so")
 # in a subprocess (tests/test_gpu_match.py::test_earlier_scan_generations_cross_check_in_a_legacy_build)
 LEGACY_OUT = os.path.join(_HERE, "lib", "libplslam_hip_legacy.so")
 OBJ_DIR = os.path.join(_ROOT, "build", "obj")
-# the product: what AUTO can pick (K1i and its merge kernel, K1f for column-split plans, the popcount kernels) and every
-# other row of SURVEY section 8
-SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_h.hip", "hamming_mfma_i.hip", "lba.hip", "lba_assemble_rows.hip", "lba_plan.hip", "lba_schur.hip", "lba_plan_dev.hip", "lba_lm_dev.hip", "distribute.hip",
+# the product: what AUTO can pick (K1i, K1f for column-split plans, the popcount kernels, and the stages behind a scan:
+# match_post.hip) and every other row of SURVEY section 8
+SOURCES = ["hamming.hip", "hamming_mfma_g.hip", "hamming_mfma_i.hip", "match_post.hip", "lba.hip", "lba_assemble_rows.hip", "lba_plan.hip", "lba_schur.hip", "lba_plan_dev.hip", "lba_lm_dev.hip", "distribute.hip",
            "map2kf.hip", "map2kf_kernels.hip", "lbd.hip", "median_desc.hip", "match_grid.hip", "match_grid_listers.hip", "match_grid_dense.hip", "match_grid_api.hip", "stereo_gates.hip", "pose_gn.hip", "lbd_float.hip", "bow.hip", "bow_train.hip",
            "loop_closure.hip", "gba.hip", "gba_plan_dev.hip", "ldlt_dense.hip", "pgo.hip", "env_ldlt.hip", "lc_correct.hip", "lc_correct_image.hip", "local_map.hip", "map_insert.hip", "lc_fuse.hip", "map_lists.hip",
            "context.hip", "match_plan.hip", "host_calls.hip", "match_pipeline.hip", "gather.hip", "track.hip"]
 # earlier generations of the matrix-core scan, reachable only through the context option "mfma_form" (1 = K1e, 3 = K1g,
-# 4 = K1h -- whose scan kernel sits behind the same macro in hamming_mfma_h.hip): cross-checks for the tests and A/B baselines
-# for the tools.  OPT-IN: build_hip(legacy=True) / PLSLAM_BUILD_LEGACY_SCANS=1 python -m plslam_amd.build -> LEGACY_OUT.
-# Without them (the product) the option values are refused with PLSLAM_ENOTSUP and the test cases that use them skip in the
-# main test process.  Only the translation units that see the macro are compiled twice (LEGACY_AWARE: the context,
-# which answers what the build carries, and K1h's scan kernel): the legacy library shares every other object with the product.
-LEGACY_SOURCES = ["hamming_mfma.hip", "hamming_mfma_d.hip"]
-LEGACY_AWARE = ("context.hip", "hamming_mfma_h.hip")
-HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "match_tables.hpp", "match_planner.hpp", "match_plan.hpp", "gfx950_only.hpp", "mfma_h_common.hpp", "lba_rows_dev.hpp", "lba_lists.hpp", "lba_blocks_dev.hpp", "lba_plan.hpp", "lba_lm_ctl.hpp", "pose_step_dev.hpp", "match_grid.hpp", "match_grid_layout.hpp", "match_grid_dev.hpp",
-                                            "stereo_gates_dev.hpp", "pose_gn_dev.hpp", "gn_cam.hpp", "dense6_dev.hpp", "lc_plan.hpp", "se3_dev.hpp", "g2o_dev.hpp", "ldlt_dense.hpp", "env_ldlt.hpp", "pgo_graph.hpp", "gba_lists.hpp", "gba_plan.hpp", "lookback_dev.hpp", "distribute_dev.hpp", "lc_fuse_plan.hpp", "lc_image_plan.hpp", "map_image.hpp", "map_image_dev.hpp", "publish_dev.hpp", "map2kf_dev.hpp", "map2kf_plan.hpp", "median_desc_dev.hpp", "map_lists_plan.hpp", "local_map_plan.hpp", "map_insert_plan.hpp", "track_plan.hpp", "bow_plan.hpp", "bow_train_plan.hpp", "bow_train_draw.h")] + [os.path.join(_ROOT, "include", h) for h in ("plslam_hip.h", "plslam_track.h", "plslam_bow_train.h")]
+# 4 = K1h): cross-checks for the tests and A/B baselines for the tools.  OPT-IN: build_hip(legacy=True) /
+# PLSLAM_BUILD_LEGACY_SCANS=1 python -m plslam_amd.build -> LEGACY_OUT.  Without them (the product) the option values are
+# refused with PLSLAM_ENOTSUP and the test cases that use them skip in the main test process.  Only the context, which
+# answers what the build carries, sees the macro and is compiled twice (LEGACY_AWARE): the legacy library shares every other
+# object with the product.
+LEGACY_SOURCES = ["hamming_mfma.hip", "hamming_mfma_d.hip", "hamming_mfma_h.hip"]
+LEGACY_AWARE = ("context.hip",)
+# every header: an edit to any of them rebuilds every object
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith((".hpp", ".h"))) + \
+    [os.path.join(_ROOT, "include", h) for h in ("plslam_hip.h", "plslam_track.h", "plslam_bow_train.h")]
 # -ffp-contract=off: the fp64 row kernels must execute the reference's operation order
 # (no FMA contraction) so that thresholded masks reproduce the CPU restatement bit for bit.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

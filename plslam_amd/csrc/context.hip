@@ -1,5 +1,5 @@
 // context.hip -- the context of libplslam_hip.so (see include/plslam_hip.h): the last-error text, the grow-only device and
-// pinned buffers, plslam_ctx_create / destroy and the option table.  The one translation unit beside the scan kernels that
+// pinned buffers, plslam_ctx_create / destroy and the option table.  The one translation unit that
 // sees PLSLAM_BUILD_LEGACY_SCANS: what the build carries is answered here (option "legacy_scans", launch_scan_mfma_form).
 #include <stdarg.h>
 #include <string.h>
@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "match_grid.hpp"   // g_grid_dense
+#include "match_kernels.hpp"   // launch_scan_mfma_form and the scans it picks among
 #include "match_plan.hpp"   // match_plan_release: the context owns two plans
 
 namespace plslam {

@@ -1,18 +1,18 @@
-// hamming.hip -- K1 (256-bit Hamming kNN-2 scans) and K2 (ratio + mutual finalize) for gfx950.
+// hamming.hip -- the popcount forms of K1 (256-bit Hamming kNN-2 scans) for gfx950: K1a, K1d, K1b, K1b'.
 //
-// Replaces cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) + stvo-pl matchNNR()/match()
+// Replaces cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) of stvo-pl matchNNR()/match()
 // (reached from src/mapHandler.cpp:277,424,597,712,3223,3249 of the reference).
 //
 // The XOR + popcount forms of the scan: a 256-bit distance costs 8 v_xor_b32 + 8 v_bcnt_u32_b32 (the
 // bcnt accumulates for free); these kernels are VALU-issue bound, HBM sees each descriptor once.
-// (The default scan for mutual problems is the matrix-core form K1e in hamming_mfma.hip; the kernels
-// here serve directed problems, single small problems, n2 > 2048, and forced scan variants.)
+// (The default scan is the matrix-core form K1i in hamming_mfma_i.hip; the kernels here serve single
+// small problems -- K1d, one StVO::match call -- and forced scan variants.  The stages behind a scan --
+// column merges, ratio test + mutual check -- are in match_post.hip.)
 //
 // Result order == OpenCV batchDistance(K=2): lexicographic (distance, trainIdx).  It is encoded
 // as an unsigned min over composite keys  key = (distance << 23) | trainIdx  so that every
 // merge (per lane, across lanes, across workgroups) is associative and tie-exact.
 #include "mfma_h_common.hpp"
-#include "stereo_gates_dev.hpp"
 
 namespace plslam {
 
@@ -477,277 +477,6 @@ k_scan_symmetric_r4(const SymDesc* __restrict__ syms, const BlockDesc* __restric
     }
 }
 
-// K1c  merge the per-block column partials of K1b: keys21[j] = best-2 over iblk of part21[iblk][j]
-__global__ void __launch_bounds__(256)
-k_merge_partials(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ blocks)
-{
-    const BlockDesc bd = blocks[blockIdx.x];
-    const SymDesc sd = syms[bd.item];
-    const int j = bd.row0 + (int)threadIdx.x;
-    if (j >= sd.n2) return;
-    const auto part = g_(reinterpret_cast<const gvec2_t*>(sd.part21));
-    uint32_t b0 = KEY_NONE, b1 = KEY_NONE;
-    for (int ib = 0; ib < sd.n_iblk; ++ib) {
-        const gvec2_t p = part[(size_t)ib * sd.n2 + j];
-        merge2(b0, b1, p.x, p.y);
-    }
-    g_(reinterpret_cast<gvec2_t*>(sd.keys21))[j] = gvec2_t{b0, b1};
-}
-
-// ---------------------------------------------------------------------------------------------
-// K2  finalize: ratio test (fp32, one multiply) + mutual consistency -> matches_12, #matches.
-// stvo-pl matchNNR: accept iff (float)d0 < (float)d1 * nnr; match(): keep i1->i2 iff m21[i2]==i1.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ratio_pick(uint32_t k0, uint32_t k1, float nnr)
-{
-    if (k1 == KEY_NONE) return -1;  // fewer than two neighbours: defined as "no match"
-    const float d0 = (float)(k0 >> KEY_IDX_BITS);
-    const float d1n = __fmul_rn((float)(k1 >> KEY_IDX_BITS), nnr);
-    return d0 < d1n ? (int)(k0 & KEY_IDX_MASK) : -1;
-}
-
-// One row of a problem: ratio test on its scan result, the mutual check against the candidate column's pair kb = fetch_kb(m)
-// (K1h / K1i plans: completed lazily, see below), the table entry, the count and the stereo gate.  EVERY lane of the workgroup
-// calls it (DPP row rotations inside); the workgroup's 256 lanes are 256 consecutive rows starting at a multiple of 16.
-// `pre`: the row's pair of keys12 if the caller has loaded it already (problems that are not column-split), else nullptr.
-template <class FetchKb>
-__device__ __forceinline__ void finalize_row(const ProblemDesc& p, const int i1, const plslam_stereo_gate_problem* __restrict__ gates,
-                                             FetchKb fetch_kb, const gvec2_t* pre = nullptr)
-{
-    int m = -1;
-    bool accepted = false, cleared = false;
-    uint2 k = make_uint2(KEY_NONE, KEY_NONE);            // this row's scan result (rows past n1: none)
-    uint2 kb = make_uint2(KEY_NONE, KEY_NONE);           // the candidate column's keys21 pair
-    bool check = false;                                  // this row has a candidate whose consistency must be checked
-    if (i1 < p.n1) {
-        if (p.nsplit > 1) {
-            // column-split problem: best-2 over the ranges' row results; keys are (d << 23 | j) with j relative to the
-            // range, so its first column is added first -- (d, j) order holds within and across ranges
-            const auto tmp = g_(reinterpret_cast<const gvec2_t*>(p.split_tmp));
-            uint32_t b0 = KEY_NONE, b1 = KEY_NONE;
-            for (int s = 0; s < p.nsplit; ++s) {
-                const gvec2_t q = tmp[(size_t)s * p.n1 + i1];
-                const uint32_t off = (uint32_t)(s * p.cstep);
-                merge2(b0, b1, q.x == KEY_NONE ? KEY_NONE : q.x + off, q.y == KEY_NONE ? KEY_NONE : q.y + off);
-            }
-            k = make_uint2(b0, b1);
-            g_(reinterpret_cast<gvec2_t*>(p.keys12_out))[i1] = gvec2_t{k.x, k.y};          // diagnostics (plslam_match_plan_dump)
-        } else if (pre) {
-            k = make_uint2(pre->x, pre->y);
-        } else {
-            // (read once: non-temporal, like the table written below -- they must not push the scan's rows out of L2)
-            const gvec2_t kv = __builtin_nontemporal_load(g_(reinterpret_cast<const gvec2_t*>(p.keys12)) + i1);
-            k = make_uint2(kv.x, kv.y);
-        }
-        m = ratio_pick(k.x, k.y, p.nnr);
-        accepted = m >= 0;
-        // [RECALL] stvo-pl matchNNR resize()s the table it is given: an entry already there survives a rejected row, then
-        // goes through the consistency loop like any other (an entry outside [0, n2) -- an out-of-bounds read upstream --
-        // is defined as failing it)
-        if (!accepted && p.keep_prior) m = g_(p.matches_12)[i1];
-        if (m >= 0 && p.mutual) {
-            check = m < p.n2;
-            if (check) kb = fetch_kb(m);
-            else { m = -1; cleared = true; }
-        }
-    }
-    bool ok = true;
-    if (!p.lazy21) {
-        if (check) ok = ratio_pick(kb.x, kb.y, p.nnr) == i1;
-    } else {
-        // K1h plans.  kb.x = column m's best row (exact); kb.y = its best row OUTSIDE kb.x's aligned group of 16 rows of d1: an
-        // upper bound of the true second best.  The consistency check can only hold if the best row is THIS row; then the
-        // other 15 rows of this row's group are what kb.y has not seen.  Row r's own scan result bounds its distance to
-        // column m from below: it IS r's best distance if m is r's best column, and it is at least r's second-best distance
-        // otherwise.  Those results sit in the neighbouring lanes (a group = 16 aligned lanes: DPP row rotation).  With the
-        // lower bound lo = min(kb.y's distance, the 15 bounds) and the upper bound hi = kb.y's distance on the same side of
-        // the ratio threshold the test is decided; only between them are the 15 distances recomputed (XOR + popcount).
-        const uint32_t mm = check ? (uint32_t)m : 0xFFFFFFFFu;
-        uint32_t lb = 0xFFFFFFFFu;                       // min over the other rows of the group of their bound (a distance)
-#define PLSLAM_FIN_ROT(S)                                                                           \
-        {                                                                                          \
-            const uint32_t px = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k.x, 0x120 + (S), 0xf, 0xf, false); \
-            const uint32_t py = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k.y, 0x120 + (S), 0xf, 0xf, false); \
-            const uint32_t b = (px != KEY_NONE && (px & KEY_IDX_MASK) == mm) ? (px >> KEY_IDX_BITS)  \
-                                                                           : (py == KEY_NONE ? 0xFFFFFFFFu : (py >> KEY_IDX_BITS)); \
-            lb = lb < b ? lb : b;                                                                  \
-        }
-        PLSLAM_FIN_ROT(1) PLSLAM_FIN_ROT(2) PLSLAM_FIN_ROT(3) PLSLAM_FIN_ROT(4) PLSLAM_FIN_ROT(5)
-        PLSLAM_FIN_ROT(6) PLSLAM_FIN_ROT(7) PLSLAM_FIN_ROT(8) PLSLAM_FIN_ROT(9) PLSLAM_FIN_ROT(10)
-        PLSLAM_FIN_ROT(11) PLSLAM_FIN_ROT(12) PLSLAM_FIN_ROT(13) PLSLAM_FIN_ROT(14) PLSLAM_FIN_ROT(15)
-#undef PLSLAM_FIN_ROT
-        if (check) {
-            ok = kb.x != KEY_NONE && (int)(kb.x & KEY_IDX_MASK) == i1;
-            if (ok) {
-                const float d0 = (float)(kb.x >> KEY_IDX_BITS);
-                const uint32_t hi = kb.y == KEY_NONE ? 0xFFFFFFFFu : (kb.y >> KEY_IDX_BITS);
-                const uint32_t lo = hi < lb ? hi : lb;
-                if (hi != 0xFFFFFFFFu && !(d0 < __fmul_rn((float)hi, p.nnr))) {
-                    ok = false;                                      // fails even against the upper bound
-                } else if (lo != 0xFFFFFFFFu && d0 < __fmul_rn((float)lo, p.nnr)) {
-                    ok = true;                                       // holds even against the lower bound (a second row exists)
-                } else {
-                    uint32_t second = kb.y;
-                    const auto b = g_(reinterpret_cast<const u32x4*>(p.d2 + (size_t)m * 32));
-                    const u32x4 b_lo = b[0], b_hi = b[1];
-                    const int base = i1 & ~15;
-                    for (int q = 0; q < 16; ++q) {
-                        const int i = base + q;
-                        const bool use = i != i1 && i < p.n1;
-                        const auto a = g_(reinterpret_cast<const u32x4*>(p.d1 + (size_t)(use ? i : i1) * 32));
-                        const u32x4 a_lo = a[0], a_hi = a[1];
-                        const uint32_t d = __popc(a_lo.x ^ b_lo.x) + __popc(a_lo.y ^ b_lo.y) + __popc(a_lo.z ^ b_lo.z) +
-                                           __popc(a_lo.w ^ b_lo.w) + __popc(a_hi.x ^ b_hi.x) + __popc(a_hi.y ^ b_hi.y) +
-                                           __popc(a_hi.z ^ b_hi.z) + __popc(a_hi.w ^ b_hi.w);
-                        const uint32_t cand = use ? ((d << KEY_IDX_BITS) | (uint32_t)i) : KEY_NONE;
-                        second = second < cand ? second : cand;
-                    }
-                    ok = ratio_pick(kb.x, second, p.nnr) == i1;
-                }
-            }
-        }
-    }
-    if (check && !ok) { m = -1; cleared = true; }
-    if (i1 < p.n1) {
-        __builtin_nontemporal_store(m, g_(p.matches_12) + i1);
-        // the gather's wire table (plslam_match_plan_set_wire16): the same entry as int16 (m < n2 <= 32768)
-        if (p.matches_16) g_(p.matches_16)[i1] = (int16_t)m;
-    }
-    if (p.n_matches) {
-        // the reference's arithmetic: +1 per row the ratio test accepts, -1 per entry the consistency loop clears (equal
-        // to the number of entries >= 0 unless kept entries are involved)
-        const int delta = (int)__popcll(__ballot(accepted)) - (int)__popcll(__ballot(cleared));
-        if ((threadIdx.x & 63) == 0 && delta) (void)atomic_add_global(p.n_matches, delta);
-    }
-    if (gates && p.gate >= 0) {           // (a plan without a gate stage passes no table: never read through a stale index)
-        // StereoFrame's gate over this L<->R table (stereo_gates_dev.hpp), on the entry just decided.  (Requesting the gate's
-        // descriptor and the row's left feature ahead of the keys -- two links off the chain of dependent accesses -- measured
-        // 2.5 % SLOWER for the stages behind the scan, 0.298 against 0.290 ms per 4096-pair step.)
-        const plslam_stereo_gate_problem q = gates[p.gate];
-        const int kept = i1 < p.n1 ? stereo_gate_row(q, i1, m) : 0;
-        const unsigned long long bal = __ballot(kept);
-        if (q.n_stereo && (threadIdx.x & 63) == 0 && bal) (void)atomic_add_global(q.n_stereo, (int)__popcll(bal));
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_finalize(const ProblemDesc* __restrict__ probs, const BlockDesc* __restrict__ blocks,
-           const plslam_stereo_gate_problem* __restrict__ gates, int nblocks, int per_xcd)
-{
-  // per_xcd > 0: workgroup b runs on XCD b % 8 and takes table entry (b % 8) * per_xcd + b / 8, so that the (<= 6) row blocks of
-  // one problem gather their column pairs keys21[m] through ONE L2 -- in table order they sit on six XCDs and each fetches
-  // the problem's whole column table (round-4 counters: FETCH_SIZE 488 k KiB per 4096-pair step against 174 k; tools/
-  // fetch_gather_calib.hip reproduces the pattern and the factor).  Option "post_xcd" 2 (default): plan_build deals the table
-  // to the XCDs problem by problem (rows of per_xcd entries, padding item = -1) -- consecutive problems on different XCDs, the
-  // eight sweep memory together: step time equal to 1 % better, the stage alone 2 % slower.  Option 1: per_xcd = ceil(nblocks /
-  // 8) over the table in problem order, i.e. a contiguous eighth per XCD: the same bytes but 8 % SLOWER for the stage (0.302
-  // against 0.280 ms per step) -- eight distant regions of memory at a time.
-  // (a capped grid walks the block table: plslam_ctx option "post_workgroups")
-  const int nslots = per_xcd > 0 ? 8 * per_xcd : nblocks;
-  for (int b = blockIdx.x; b < nslots; b += gridDim.x) {
-    const int blk = per_xcd > 0 ? (b & 7) * per_xcd + (b >> 3) : b;
-    if (blk >= nblocks) continue;                      // (the whole workgroup: finalize_row's DPP rotations see all lanes or none)
-    const BlockDesc bd = blocks[blk];
-    if (bd.item < 0) continue;                         // padding entry of a table dealt to the XCDs (option "post_xcd" 2)
-    const ProblemDesc p = probs[bd.item];
-    finalize_row(p, bd.row0 + (int)threadIdx.x, gates, [&](int m) {
-        const gvec2_t kv = g_(reinterpret_cast<const gvec2_t*>(p.keys21))[m];
-        return make_uint2(kv.x, kv.y);
-    });
-  }
-}
-
-// K2'  everything behind a K1h / K1i scan in ONE kernel, one workgroup per problem: the column partials of the problem's <= 16
-// row blocks are merged into LDS (what k_merge_fix16<1, false> writes to keys21: best row, distance of the best row outside
-// its group of 16), then the problem's rows are finalized from there (+ gates).  No merged column table in HBM: the separate
-// kernels write it once (8 B per column) and gather it back through up to six L2s with 8-byte reads (round 3 PMC: 1.0 GB
-// fetched to write 0.16 GB).  Throughput plans only (plan_build: every problem mutual, on K1h / K1i, n2 <= POST_FUSED_MAX_N2,
-// lazy keys): a plan of a few large problems has too few workgroups for this.
-template <int NT>
-__global__ void __launch_bounds__(NT)
-k_post_fused(const ProblemDesc* __restrict__ probs, const plslam_stereo_gate_problem* __restrict__ gates, int nprob)
-{
-    extern __shared__ __attribute__((aligned(16))) uint2 kb_lds[];           // [n2]: the merged pair of every column
-    for (int pi = blockIdx.x; pi < nprob; pi += gridDim.x) {
-        const ProblemDesc p = probs[pi];
-        const MhLayout L(p.n2);
-        const int nwb = (p.n1 + 255) >> 8, n2p = L.slots_padded(), nslots = 32 * L.ntiles;
-        const auto part = g_(p.part21);
-        if (pi != (int)blockIdx.x) __syncthreads();        // the problem before: every lane is past its reads of kb_lds
-        // the first 256 rows of keys12 now: their latency passes under the merge
-        const auto k12 = g_(reinterpret_cast<const gvec2_t*>(p.keys12));
-        gvec2_t kcur = gvec2_t{KEY_NONE, KEY_NONE};
-        if ((int)threadIdx.x < p.n1) kcur = __builtin_nontemporal_load(k12 + threadIdx.x);
-        // merge: a lane takes slots 256 apart, PF at a time (their nwb words each are requested together: one round trip)
-        constexpr int PF = NT >= 1024 ? 2 : 4;
-        for (int s0_ = (int)threadIdx.x; s0_ < nslots; s0_ += NT * PF) {
-            uint32_t b0[PF], b1[PF], sx[PF];
-            int j[PF];
-#pragma unroll
-            for (int q = 0; q < PF; ++q) {
-                const int slot = s0_ + NT * q;
-                j[q] = slot < nslots ? L.row_of(slot >> 5, slot & 31) : p.n2;
-                b0[q] = b1[q] = KEY_NONE;
-                sx[q] = 0xFFFFFFFFu;
-            }
-            for (int wb = 0; wb < nwb; ++wb) {
-                uint32_t e[PF];
-#pragma unroll
-                for (int q = 0; q < PF; ++q) e[q] = j[q] < p.n2 ? __builtin_nontemporal_load(&part[(size_t)wb * n2p + s0_ + NT * q]) : 0xFFFFFFFFu;
-#pragma unroll
-                for (int q = 0; q < PF; ++q) {
-                    const uint32_t e0 = e[q] >> 9, e1 = ((e[q] & 511u) << 8) | 255u;     // (d0 << 8 | row0), the second entry's distance
-                    const uint32_t k = ((e0 >> 8) << KEY_IDX_BITS) | ((e0 & 255u) + 256u * (uint32_t)wb);
-                    sx[q] = k < b0[q] ? e1 : sx[q];
-                    b1[q] = umin_(b1[q], umax_(b0[q], k));
-                    b0[q] = umin_(b0[q], k);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < PF; ++q) {
-                if (j[q] >= p.n2) continue;                // the slot holds no column
-                if (b0[q] < (257u << KEY_IDX_BITS)) {
-                    b1[q] = umin_(b1[q], ((sx[q] >> 8) << KEY_IDX_BITS) | KEY_IDX_MASK);
-                    if (b1[q] >= (257u << KEY_IDX_BITS)) b1[q] = KEY_NONE;
-                } else {
-                    b0[q] = b1[q] = KEY_NONE;
-                }
-                kb_lds[j[q]] = make_uint2(b0[q], b1[q]);
-            }
-        }
-        __syncthreads();
-        // rows: the next block's keys are requested before this block's are consumed
-#pragma unroll 1
-        for (int r0 = 0; r0 < p.n1; r0 += NT) {
-            const int inext = r0 + NT + (int)threadIdx.x;
-            gvec2_t knext = gvec2_t{KEY_NONE, KEY_NONE};
-            if (inext < p.n1) knext = __builtin_nontemporal_load(k12 + inext);
-            finalize_row(p, r0 + (int)threadIdx.x, gates, [&](int m) { return kb_lds[m]; }, &kcur);
-            kcur = knext;
-        }
-    }
-}
-
-// copies the per-problem counters to caller pointers that are not one contiguous array
-__global__ void __launch_bounds__(256)
-k_scatter_counts(const int32_t* __restrict__ src, int32_t* const* __restrict__ dst, int32_t n)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n && g_(dst)[i]) *g_(g_(dst)[i]) = g_(src)[i];
-}
-
-// keys -> (idx, dist) pairs of the knnMatch ABI
-__global__ void __launch_bounds__(256)
-k_unpack_keys(const uint32_t* __restrict__ keys, int32_t n, int32_t* __restrict__ idx,
-              int32_t* __restrict__ dist)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = g_(keys)[i];
-    idx[i] = k == KEY_NONE ? -1 : (int32_t)(k & KEY_IDX_MASK);
-    dist[i] = k == KEY_NONE ? INT32_MAX : (int32_t)(k >> KEY_IDX_BITS);
-}
-
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
@@ -802,59 +531,6 @@ int launch_scan_sym(int rows_per_lane, const SymDesc* d_sym, const BlockDesc* d_
         hipLaunchKernelGGL(k_scan_symmetric_r4, dim3(nblocks), dim3(64), 0, s, d_sym, d_blocks, d_zero, nzero);
     else
         hipLaunchKernelGGL(k_scan_symmetric, dim3(nblocks), dim3(256), 0, s, d_sym, d_blocks, d_zero, nzero);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-int launch_merge_partials(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, hipStream_t s)
-{
-    if (nblocks <= 0) return PLSLAM_OK;
-    hipLaunchKernelGGL(k_merge_partials, dim3(nblocks), dim3(256), 0, s, d_sym, d_blocks);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-constexpr int POST_FUSED_THREADS = 256;
-int launch_post_fused(const ProblemDesc* d_probs, int nprob, const plslam_stereo_gate_problem* d_gates, size_t lds_bytes,
-                      hipStream_t s)
-{
-    if (nprob <= 0) return PLSLAM_OK;
-    // (measured per 16 384-problem step at C2, exclusive: this kernel with 256 lanes per problem 0.335 ms, with 1024 lanes
-    // 0.65 ms, the separate merge + finalize kernels 0.276 ms -- see match_planner.hpp plan_decide, option "post_fuse")
-    hipLaunchKernelGGL(k_post_fused<POST_FUSED_THREADS>, dim3(nprob), dim3(POST_FUSED_THREADS), lds_bytes, s, d_probs, d_gates, nprob);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-int launch_finalize(const ProblemDesc* d_probs, const BlockDesc* d_blocks, int nblocks,
-                    const plslam_stereo_gate_problem* d_gates, hipStream_t s, int grid_cap, bool xcd_chunks, int dealt_row)
-{
-    if (nblocks <= 0) return PLSLAM_OK;
-    // xcd_chunks: contiguous table entries per XCD (k_finalize; option post_xcd 1, measured slower); pointless below a few entries
-    // per XCD.  dealt_row > 0: the table is already dealt to the XCDs in 8 rows of that length (plan_build, option post_xcd 2).
-    const int per_xcd = dealt_row > 0 ? dealt_row : (xcd_chunks && nblocks >= 64 ? (nblocks + 7) / 8 : 0);
-    const int nslots = per_xcd > 0 ? 8 * per_xcd : nblocks;
-    int grid = grid_cap > 0 && grid_cap < nslots ? grid_cap : nslots;
-    if (per_xcd > 0 && grid < nslots) grid = grid >= 8 ? grid & ~7 : 8;   // a walking workgroup stays on its XCD's chunk
-    hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, s, d_probs, d_blocks, d_gates, nblocks, per_xcd);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-int launch_scatter_counts(const int32_t* d_src, int32_t* const* d_dst, int32_t n, hipStream_t s)
-{
-    if (n <= 0) return PLSLAM_OK;
-    hipLaunchKernelGGL(k_scatter_counts, dim3((n + 255) / 256), dim3(256), 0, s, d_src, d_dst, n);
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-int launch_unpack_keys(const uint32_t* d_keys, int32_t n, int32_t* d_idx, int32_t* d_dist,
-                       hipStream_t s)
-{
-    if (n <= 0) return PLSLAM_OK;
-    hipLaunchKernelGGL(k_unpack_keys, dim3((n + 255) / 256), dim3(256), 0, s, d_keys, n, d_idx,
-                       d_dist);
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }

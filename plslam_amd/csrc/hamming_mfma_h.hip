@@ -1,5 +1,7 @@
 // hamming_mfma_h.hip -- K1h: the matrix-core symmetric Hamming kNN-2 scan with MINIMUM-ONLY bookkeeping in BOTH
-// directions (gfx950).  Round 3; the default.
+// directions (gfx950).  Round 3's default (mfma_form 4), kept as a cross-check: a LEGACY source, compiled only into the library
+// with the earlier scan generations (plslam_amd/build.py, PLSLAM_BUILD_LEGACY_SCANS).  The default scan K1i
+// (hamming_mfma_i.hip) keeps this kernel's tables and its merge kernel, k_merge_fix16 (match_post.hip).
 //
 // Contract, work decomposition, block tables: those of K1f (hamming_mfma_g.hip) -- keys12[i] = best-2 over j; the column
 // partials are per WORKGROUP (256 rows of a; K1f: per wave): part21[256-row block of a][column slot] = one word
@@ -43,12 +45,10 @@ namespace plslam {
 
 // (typedefs, constants and device helpers: mfma_h_common.hpp)
 
-int mh_slot_of_column(int n2, int j) { return MhLayout(n2).slot_of(j); }     // for tests / tools (plslam_match_plan_dump readers)
 // row within the workgroup's 256 rows of a held by wave w, M-tile mt, MFMA row m: 128 mt + 32 w + 16 g + r with
 // m = (r & 3) + 8 (r >> 2) + 4 g
 __host__ __device__ inline int mh_block_row(int w, int mt, int m) { return 128 * mt + 32 * w + 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3); }
 
-#if PLSLAM_BUILD_LEGACY_SCANS      // K1h's scan kernel (mfma_form 4): round 3's default, kept as a cross-check; its merge kernel below serves K1i
 // DIRECTED = true: only keys12 (row direction) is produced.
 template <bool DIRECTED>
 __global__ void __launch_bounds__(256, 3)      // 3 waves per SIMD: <= 168 unified VGPRs
@@ -514,164 +514,7 @@ k_scan_sym_mfma_h(const SymDesc* __restrict__ syms, const BlockDesc* __restrict_
         wt1 = ntiles < wt0 + MH_WINDOW ? ntiles : wt0 + MH_WINDOW;
     }
 }
-#endif  // PLSLAM_BUILD_LEGACY_SCANS
 
-// K1c''  merge of K1h's column partials + the second-best recomputation: keys21[j] = best-2 over all rows of a.
-// part[256-row block][slot] = (d0 << 17 | row0 << 9 | d1): the block's best row and the distance of its best row OUTSIDE
-// row0's aligned group of 16 rows (FIX: the pair of words (d0 << 8 | row0, d1 << 8 | row1)).  Over the blocks: K0 = the best
-// row, K1 = the best of (every other block's best row, the winner block's second entry) = the best row outside K0's group of 16.
-// FIX = false: keys21[j] = (K0, K1) as they are -- K1's index is not a row then (all ones) -- and the finalize kernel completes
-// the second best for the columns it needs (ProblemDesc::lazy21); FIX = true (exact key tables asked for): the 15 other
-// rows of K0's group are recomputed here for every column (512 contiguous bytes of a).  PARTS lanes share a column (tall
-// problems: see K1f).
-template <int PARTS, bool FIX>
-__global__ void __launch_bounds__(256)
-k_merge_fix16(const SymDesc* __restrict__ syms, const BlockDesc* __restrict__ blocks, int nblocks)
-{
-  // (a capped grid walks the block table: plslam_ctx option "post_workgroups")
-  for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
-    constexpr int COLS = 256 / PARTS;
-    // PARTS == 1: a lane takes SPT slots, 256 apart (one block-table entry per 1024 slots): the kernel is a chain of dependent
-    // round trips (block entry -> descriptor -> partials -> store) with a few loads at its end, and four slots' loads
-    // share the chain
-    constexpr int SPT = PARTS == 1 ? MH_MERGE_SPT : 1;
-    __shared__ uint32_t red[PARTS > 1 ? 512 : 2];
-    const BlockDesc bd = blocks[blk];
-    const SymDesc sd = syms[bd.item];
-    // lanes walk the partial table in SLOT order (coalesced reads of every block's row); the slot's column is where the result goes
-    const int jl = (int)threadIdx.x % COLS, part_id = (int)threadIdx.x / COLS;
-    const MhLayout L(sd.n2);
-    const gcu32_t part = (gcu32_t) sd.part21;
-    const int nwb = (sd.n1 + 255) >> 8;
-    const int n2p = (MH_TILE_N * L.ntiles + 255) & ~255;
-    int slot[SPT], j[SPT];
-    uint32_t b0[SPT], b1[SPT], s0[SPT];     // s0: the winner block's second entry, kept raw: it joins at the end
-#pragma unroll
-    for (int q = 0; q < SPT; ++q) {
-        slot[q] = bd.row0 + jl + 256 * q;
-        j[q] = slot[q] < MH_TILE_N * L.ntiles ? L.row_of(slot[q] >> 5, slot[q] & 31) : sd.n2;     // >= n2: the slot holds no column
-        if (j[q] >= sd.n2) slot[q] = 0;       // (reads a valid word, drops the result)
-        b0[q] = b1[q] = KEY_NONE;
-        s0[q] = 0xFFFFFFFFu;
-    }
-    auto wide = [](uint32_t k17, uint32_t wb) -> uint32_t {         // (d << 8 | row in block) -> (d << 23 | row)
-        return ((k17 >> 8) << KEY_IDX_BITS) | ((k17 & 255u) + 256u * wb);
-    };
-    // only a block's BEST key is widened and merged per entry
-    // the default form (one word per entry, a lane per slot): the words of MH_MERGE_WB row blocks are requested together
-    if (PARTS == 1 && !FIX) {
-        constexpr int WB = MH_MERGE_WB;
-        for (int wb0 = 0; wb0 < nwb; wb0 += WB) {
-            uint32_t e[WB][SPT];
-#pragma unroll
-            for (int u = 0; u < WB; ++u) {
-                if (wb0 + u < nwb) {                  // (uniform)
-#pragma unroll
-                    for (int q = 0; q < SPT; ++q)
-                        e[u][q] = __builtin_nontemporal_load(&part[(size_t)(wb0 + u) * n2p + slot[q]]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < WB; ++u) {
-                if (wb0 + u < nwb) {
-#pragma unroll
-                    for (int q = 0; q < SPT; ++q) {
-                        const uint32_t k = wide(e[u][q] >> 9, (uint32_t)(wb0 + u)), e1 = ((e[u][q] & 511u) << 8) | 255u;
-                        s0[q] = k < b0[q] ? e1 : s0[q];
-                        b1[q] = umin_(b1[q], umax_(b0[q], k));
-                        b0[q] = umin_(b0[q], k);
-                    }
-                }
-            }
-        }
-    } else
-#pragma unroll 2
-    for (int wb = part_id; wb < nwb; wb += PARTS) {
-        uint32_t e0[SPT], e1[SPT];
-#pragma unroll
-        for (int q = 0; q < SPT; ++q) {
-            if (FIX) {
-                const gu2c_t pp = (gu2c_t) part + ((size_t)wb * n2p + slot[q]);
-                const u32x2_t e = __builtin_nontemporal_load(pp);
-                e0[q] = e.x; e1[q] = e.y;
-            } else {
-                const uint32_t e = __builtin_nontemporal_load(&part[(size_t)wb * n2p + slot[q]]);
-                e0[q] = e >> 9; e1[q] = ((e & 511u) << 8) | 255u;     // the second entry's row is not in the word
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < SPT; ++q) {
-            const uint32_t k = wide(e0[q], (uint32_t)wb);
-            s0[q] = k < b0[q] ? e1[q] : s0[q];
-            b1[q] = umin_(b1[q], umax_(b0[q], k));
-            b0[q] = umin_(b0[q], k);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < SPT; ++q) {
-        if (j[q] < sd.n2 && b0[q] < (257u << KEY_IDX_BITS)) {
-            const uint32_t k1 = FIX ? wide(s0[q], (b0[q] & KEY_IDX_MASK) >> 8) : (((s0[q] >> 8) << KEY_IDX_BITS) | KEY_IDX_MASK);
-            b1[q] = umin_(b1[q], k1);
-            if (b1[q] >= (257u << KEY_IDX_BITS)) b1[q] = KEY_NONE;
-        } else {
-            b0[q] = b1[q] = KEY_NONE;
-        }
-    }
-    if (PARTS > 1) {
-        // the parts' pairs: each is (best of its blocks, best outside THAT best's group): the overall best's pair partner is
-        // still "outside its group", and any other part's best is outside it too (another block, or the same block's
-        // other group only if it came as a second entry -- which is also outside) -- merge2 keeps exactly that
-        if (blk != (int)blockIdx.x) __syncthreads();          // the entry before: every lane is past its reads of red[]
-        red[2 * threadIdx.x] = b0[0];
-        red[2 * threadIdx.x + 1] = b1[0];
-        __syncthreads();
-        if (part_id == 0) {
-#pragma unroll
-            for (int q = 1; q < PARTS; ++q) merge2(b0[0], b1[0], red[2 * (q * COLS + jl)], red[2 * (q * COLS + jl) + 1]);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < SPT; ++q) {
-        if (part_id == 0 && j[q] < sd.n2) {
-            if (FIX && b0[q] != KEY_NONE) {
-                const gcu32_t araw = (gcu32_t) reinterpret_cast<const uint32_t*>(sd.a);
-                const gcu32x4_t bp = (gcu32x4_t)((gcu32_t) reinterpret_cast<const uint32_t*>(sd.b) + (size_t)j[q] * 8);
-                const u32x4_t b_lo = bp[0], b_hi = bp[1];
-                const uint32_t i0 = b0[q] & KEY_IDX_MASK, ibase = i0 & ~15u;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const uint32_t i = ibase + (uint32_t)k;
-                    const bool ok = i != i0 && i < (uint32_t)sd.n1;
-                    const gcu32x4_t ap = (gcu32x4_t)(araw + (size_t)(ok ? i : i0) * 8);
-                    const u32x4_t a_lo = ap[0], a_hi = ap[1];
-                    const uint32_t d = hamming256(a_lo, a_hi, b_lo, b_hi);
-                    b1[q] = umin_(b1[q], ok ? ((d << KEY_IDX_BITS) | i) : KEY_NONE);
-                }
-            }
-            ((gu2_t) reinterpret_cast<u32x2_t*>(sd.keys21))[j[q]] = u32x2_t{b0[q], b1[q]};
-        }
-    }
-  }
-}
-
-int merge_fix16_cols(int parts) { return parts >= 16 ? 16 : parts >= 4 ? 64 : 256 * MH_MERGE_SPT; }
-
-// d_blocks: one entry per (problem, merge_fix16_cols(parts) column slots)
-int launch_merge_fix16(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int parts, bool fix, hipStream_t s, int grid_cap)
-{
-    if (nblocks <= 0) return PLSLAM_OK;
-    const int grid = grid_cap > 0 && grid_cap < nblocks ? grid_cap : nblocks;
-#define PLSLAM_MH_MERGE(P) { if (fix) hipLaunchKernelGGL((k_merge_fix16<P, true>), dim3(grid), dim3(256), 0, s, d_sym, d_blocks, nblocks); \
-                             else hipLaunchKernelGGL((k_merge_fix16<P, false>), dim3(grid), dim3(256), 0, s, d_sym, d_blocks, nblocks); }
-    if (parts >= 16) PLSLAM_MH_MERGE(16)
-    else if (parts >= 4) PLSLAM_MH_MERGE(4)
-    else PLSLAM_MH_MERGE(1)
-#undef PLSLAM_MH_MERGE
-    PLSLAM_HIP_CHECK(hipGetLastError());
-    return PLSLAM_OK;
-}
-
-#if PLSLAM_BUILD_LEGACY_SCANS
 int launch_scan_sym_mfma_h(const SymDesc* d_sym, const BlockDesc* d_blocks, int nblocks, int32_t* d_zero, int nzero,
                            bool directed, hipStream_t s)
 {
@@ -681,6 +524,5 @@ int launch_scan_sym_mfma_h(const SymDesc* d_sym, const BlockDesc* d_blocks, int 
     PLSLAM_HIP_CHECK(hipGetLastError());
     return PLSLAM_OK;
 }
-#endif  // PLSLAM_BUILD_LEGACY_SCANS
 
 }  // namespace plslam

@@ -7,6 +7,7 @@
 #include <new>
 
 #include "map2kf_dev.hpp"   // the gates and the visibility pre-filter
+#include "match_kernels.hpp"   // plslam_knn2_hamming256: the scans and the key unpack
 #include "match_plan.hpp"
 
 using namespace plslam;

@@ -5,6 +5,7 @@
 
 #include <new>
 
+#include "match_kernels.hpp"   // what plan_run launches; the table shapes the planner is told
 #include "match_plan.hpp"
 
 using namespace plslam;

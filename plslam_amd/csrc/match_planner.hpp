@@ -194,7 +194,7 @@ inline int plan_decide(const PlanOptions& o, const plslam_match_problem* probs, 
     const int64_t want = c.col_split ? ((o.split_target > 0 ? o.split_target : 3) * (int64_t)o.cu_count + mf_row_blocks - 1) / mf_row_blocks : 1;
     const int32_t min_tiles = o.split_min_tiles > 0 ? o.split_min_tiles : 4;
     // A column-split plan of mutual K1f problems runs in TWO launches: k_split_post merges the column partials and decides the
-    // matches from the column side (hamming_mfma_g.hip); rows without a match keep the -1 the scan's first column range
+    // matches from the column side (match_post.hip); rows without a match keep the -1 the scan's first column range
     // writes.  Not with kept entries (keep_prior: a rejected row's old entry goes through the consistency loop) and not with a
     // stereo gate behind the table (add_stereo_gates switches back to merge + finalize).  Option "split_post": 0 = auto, 1 = never.
     c.split_post = c.col_split && !c.h_tables() && !c.fused && o.split_post != 1 && nprob > 0;
@@ -342,7 +342,7 @@ inline void plan_tables(const PlanChoice& c, const plslam_match_problem* probs, 
         const int64_t nn = (int64_t)p.n1 * p.n2;
         const bool on_mfma = q.path == ProblemPath::split || (c.sym_mfma && (q.path == ProblemPath::sym || q.path == ProblemPath::directed));
         // (finalize blocks start at multiples of 256 rows and run all 256 lanes: the lazy completion of K1h's / K1i's column keys
-        // rotates the neighbouring rows' keys through DPP within aligned groups of 16 lanes -- hamming.hip, finalize_row)
+        // rotates the neighbouring rows' keys through DPP within aligned groups of 16 lanes -- match_post.hip, finalize_row)
         if (!(c.fused && on_mfma)) blocks_of(t.fin_blocks, (size_t)i, p.n1, 256);
         SymDesc y{};
         y.flags = c.exact_second ? 1 : 0;

@@ -86,7 +86,7 @@ static_assert(sizeof(SymDesc) == 88, "SymDesc layout");
 static_assert(sizeof(ProblemDesc) == 120, "ProblemDesc layout");
 static_assert(sizeof(BlockDesc) == 8, "BlockDesc layout");
 
-// K2' (hamming.hip, k_post_fused): merge of K1h's / K1i's column partials + finalize + gates, one workgroup per problem
+// K2' (match_post.hip, k_post_fused): merge of K1h's / K1i's column partials + finalize + gates, one workgroup per problem
 constexpr int POST_FUSED_MAX_N2 = 4096;
 constexpr int POST_FUSED_MAX_ROW_BLOCKS = 16;
 // K1f fused (hamming_mfma_g.hip): a mutual problem keeps its merged column keys in LDS
@@ -95,7 +95,8 @@ constexpr int PLSLAM_K1F_FUSED_MAX_N2 = 4096;
 // K1h's tables (one column partial per 256-row block, launch_merge_fix16 behind the scan): K1h and K1i; 0 = auto (= 5)
 inline bool mfma_form_is_h(int form) { return form == 0 || form == 4 || form == 5; }
 // PLSLAM_BUILD_LEGACY_SCANS (plslam_amd/build.py; default 0): the earlier generations of the matrix-core scan -- K1e
-// (hamming_mfma.hip, mfma_form 1), K1g (hamming_mfma_d.hip, 3) and K1h's scan kernel (hamming_mfma_h.hip, 4) -- are compiled in.
+// (hamming_mfma.hip, mfma_form 1), K1g (hamming_mfma_d.hip, 3) and K1h (hamming_mfma_h.hip, 4) -- are compiled in, each a source
+// of the legacy library alone; the one translation unit that sees the macro is context.hip.
 // AUTO never picks them; without them plslam_ctx_set_option("mfma_form", 1 | 3 | 4) returns PLSLAM_ENOTSUP.
 #ifndef PLSLAM_BUILD_LEGACY_SCANS
 #define PLSLAM_BUILD_LEGACY_SCANS 0

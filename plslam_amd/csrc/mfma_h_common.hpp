@@ -1,12 +1,13 @@
 // mfma_h_common.hpp -- the one home of what the matrix-core scans share (K1e hamming_mfma.hip, K1f hamming_mfma_g.hip,
 // K1g hamming_mfma_d.hip, K1h hamming_mfma_h.hip, K1i hamming_mfma_i.hip), and of the key / popcount helpers the XOR + popcount
-// scans (hamming.hip) share with them.  Two parts: (1) what every scan uses -- vector and address-space typedefs, fp4 operand
-// codes, packed 16-bit key operations, the raw-row Hamming distance; (2) the MH_* layout constants of K1h / K1i alone.
+// scans (hamming.hip) and the stages behind a scan (match_post.hip) share with them.  Two parts: (1) what every scan uses --
+// vector and address-space typedefs, fp4 operand codes, packed 16-bit key operations, the raw-row Hamming distance; (2) the
+// MH_* layout constants of K1h / K1i (and of their merge) alone.
 // Every helper is __forceinline__ and carries the one comment that says why it is written as it is.
 // Internal to libplslam_hip.so.
 #pragma once
 
-#include "common.hpp"
+#include "match_kernels.hpp"   // the launch interface of the scans and of the stages behind them (+ common.hpp)
 
 namespace plslam {
 // ---- part 1: every matrix-core scan ---------------------------------------------------------------------------------------

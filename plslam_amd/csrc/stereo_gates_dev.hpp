@@ -1,5 +1,5 @@
 // stereo_gates_dev.hpp -- the per-feature gates of StVO::StereoFrame (matchStereoPoints / matchStereoLines, [RECALL])
-// as device functions: used by the stand-alone gate kernels (stereo_gates.hip) and by the finalize kernel (hamming.hip), which
+// as device functions: used by the stand-alone gate kernels (stereo_gates.hip) and by the finalize kernel (match_post.hip), which
 // applies them to a row's match the moment it is decided (plans with a gate stage: no second pass over the tables).
 #pragma once
 #include "common.hpp"

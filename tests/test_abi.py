@@ -98,6 +98,16 @@ def test_no_device_scope_fence_and_no_flat_access_in_any_kernel():
         assert not flat, (src, len(flat), flat[:3])
 
 
+def test_every_kernel_source_is_in_exactly_one_source_list():
+    """A .hip file under plslam_amd/csrc that neither build compiles is dead text, one in both lists is linked twice: every one is
+    in exactly one of build.SOURCES (the product) and build.LEGACY_SOURCES, and both lists name only files that exist."""
+    from plslam_amd import build as B
+    on_disk = sorted(f for f in os.listdir(B.CSRC) if f.endswith(".hip"))
+    listed = list(B.SOURCES) + list(B.LEGACY_SOURCES)
+    assert sorted(listed) == on_disk, (sorted(set(on_disk) - set(listed)), sorted(set(listed) - set(on_disk)),
+                                       sorted(f for f in set(listed) if listed.count(f) > 1))
+
+
 def test_header_is_plain_c(tmp_path):
     """The drop-in boundary is a C ABI: include/plslam_hip.h compiles on its own as C99 (and as C++11), pedantic, no warnings."""
     import subprocess

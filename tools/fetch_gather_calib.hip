@@ -1,6 +1,6 @@
 // What does rocprofv3's FETCH_SIZE report for GATHERS?  MI355X_MICROARCH.md: this rocprofv3 reports HALF the bytes of a wide
 // coalesced streaming read and calls other access patterns uncalibrated; round 3 calibrated dword-per-lane streaming (factor 2).
-// The finalize kernel's column-key reads are 8-byte gathers (k_finalize, hamming.hip): this launches kernels whose fetched LINES
+// The finalize kernel's column-key reads are 8-byte gathers (k_finalize, match_post.hip): this launches kernels whose fetched LINES
 // are known by construction, one launch each, over a table no cache has seen --
 //   stream16   16 B per lane, contiguous                     bytes = n x 16, every byte used
 //   stream8     8 B per lane, contiguous                     bytes = n x 8
